@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — VQA train-step throughput on MI355X (BASELINE.json metric: VQA samples/sec).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,12 @@ A step = forward + soft-target CE + backward + gradient all-reduce (N > 1) + Ada
 batch that is already resident in HBM: BASELINE.json configs[1] (batch 256 per GPU, 224x224 images,
 14-token questions, 1000-way answer head, fp32), train mode with all dropout sites active, random-init
 weights of the reference architecture (config.yaml:51-74).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline.  --full adds the measurements that take
+runs or event brackets of their own: the CPU baseline, the fp32x3 step beside an fp32 headline, the per-kernel
+`kernels` / `roofline` / `streaming` tables and, under data parallelism, the overlap and alternative-schedule runs.
+--dump-outputs DIR writes what the last timed step handed its caller (see dump_outputs) for output-by-output
+comparisons of two builds: the inputs and weights are seeded, so they are identical from run to run.
 """
 from __future__ import annotations
 
@@ -120,6 +126,30 @@ def cpu_baseline(cfg, V, A, T, steps=1):
                       f"run before the GPU leg ({time.time() - t_all:.1f} s)"}
 
 
+DUMP_SAMPLE = 1 << 18      # elements kept per tensor: 24 parameters x (value + gradient) x 1 MB stays under 64 MB
+
+
+def dump_outputs(model, loss, score, out_dir):
+    """Write what one train step hands its caller as out_dir/<name>.npy (float32): `loss` and `score` (run_batch's
+    return values) and, after the step's Adam update, every parameter (`param.<name>`) and its gradient
+    (`grad.<name>`).  A tensor of more than DUMP_SAMPLE elements is written as a fixed sample of DUMP_SAMPLE of its
+    flattened elements (seeded, so the same positions on every run)."""
+    import numpy as np
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "score": score.detach().float().reshape(1).cpu().numpy()}
+    for name, p in model.named_parameters():
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            a = t.detach().float().reshape(-1).cpu().numpy()
+            if a.size > DUMP_SAMPLE:
+                a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+            arrays[f"{kind}.{name}"] = a
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -134,19 +164,25 @@ def main():
                     help="fp32 = the headline / parity path (BASELINE configs[1]); bf16 = the bf16 MFMA conv/FC path "
                          "(configs[3]: use with --batch 512 --size 448); never the headline; fp32x3 = fp32 tensors and fp32 "
                          "accuracy with the conv blocks' contractions on the bf16 matrix cores (exact 3 x bf16 operand split)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the fp32x3 step, the per-kernel tables and the data-parallel overlap runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's loss, score, parameters and gradients as DIR/<name>.npy")
     ap.add_argument("--stream-steps", type=int, default=3,
-                    help="extra steps after the timed region in which the HBM-bound kernel families are bracketed "
+                    help="--full: extra steps after the timed region in which the HBM-bound kernel families are bracketed "
                          "with HIP events (the `streaming` table); 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-x3", action="store_true",
-                    help="skip the extra fp32x3 measurement that a --dtype fp32 run appends as the `fp32x3` object")
+                    help="--full: skip the extra fp32x3 measurement that a --dtype fp32 run appends as the `fp32x3` object")
     ap.add_argument("--eval-mode", action="store_true", help="diagnostic only: dropout off")
     ap.add_argument("--force-dist", action="store_true",
                     help="diagnostic: take the RCCL data-parallel path even with one rank (under torchrun)")
     ap.add_argument("--roofline-kernel", default="auto",
-                    help="kernel reported as `roofline`: auto = the kernel family with the most device time; or "
+                    help="--full: kernel reported as `roofline`: auto = the kernel family with the most device time; or "
                          "conv_fwd|conv_dgrad|conv_wgrad[:layer]")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -176,7 +212,8 @@ def main():
     cfg = reference_cfg(args.answers)
     B, S, T, V, A = args.batch, args.size, args.tokens, args.vocab, args.answers
     # the CPU baseline runs FIRST (rank 0, N = 1 only): the GPU leg is then the contiguous tail of the run
-    cpu_info = cpu_baseline(cfg, V, A, T, steps=2) if (world == 1 and rank == 0 and not args.no_cpu_baseline) else None
+    cpu_info = (cpu_baseline(cfg, V, A, T, steps=2)
+                if (args.full and world == 1 and rank == 0 and not args.no_cpu_baseline) else None)
     torch.manual_seed(1)                                   # config.yaml:9 seed
     model = VqaNet(cfg, V, compute_dtype=args.dtype).to(dev)
     model.train(not args.eval_mode)
@@ -193,7 +230,7 @@ def main():
         loss.backward()
         opt.step()
         it[0] += 1
-        return loss
+        return loss, score
 
     for _ in range(args.warmup):
         step()
@@ -201,24 +238,29 @@ def main():
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
-    lib.vqa_prof_arm_mask(0b1111, -1)            # bracket the MFMA kernel families (GEMM, conv fwd / dgrad / wgrad) with HIP events
-    torch.cuda.synchronize()
+    if args.full:
+        lib.vqa_prof_arm_mask(0b1111, -1)        # bracket the MFMA kernel families (GEMM, conv fwd / dgrad / wgrad) with HIP events
+        torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, score = step()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # before any step outside the timed region changes the parameters
+        dump_outputs(model, loss, score, args.dump_outputs)
     import ctypes
     cap = 64
     g_id, g_tag, g_n = (ctypes.c_int * cap)(), (ctypes.c_int * cap)(), (ctypes.c_int * cap)()
     g_ms = (ctypes.c_float * cap)()
-    n_groups = lib.vqa_prof_read_groups(g_id, g_tag, g_n, g_ms, cap)
-    lib.vqa_prof_arm(-1, -1)
+    n_groups = 0
+    if args.full:
+        n_groups = lib.vqa_prof_read_groups(g_id, g_tag, g_n, g_ms, cap)
+        lib.vqa_prof_arm(-1, -1)
     # HBM-bound stages: a few extra steps OUTSIDE the timed region with their families bracketed as well
     stream_rows = []
-    if args.stream_steps > 0 and not use_dist:      # single GPU only: under DP every rank would have to step
+    if args.full and args.stream_steps > 0 and not use_dist:      # single GPU only: under DP every rank would have to step
         lib.vqa_prof_arm_mask(((1 << _lib.K_COUNT) - 1) & ~0b1111, -1)
         for _ in range(args.stream_steps):
             step()
@@ -240,6 +282,7 @@ def main():
                    "bucketed_direct_path": bool(model._last_backward_direct),
                    "collectives_per_backward": list(dp.issued[-4:]),
                    "streams_bwd": os.environ.get("VQA_STREAMS_BWD", os.environ.get("VQA_STREAMS", "2"))}
+    if use_dist and args.full:
 
         def timed_dp(nsteps):
             """nsteps more steps with every bucket's issue point and the end of backward marked by HIP events."""
@@ -283,7 +326,7 @@ def main():
     # bf16 matrix cores through exact 3 x bf16 operand splits), measured the same way and reported BESIDE the headline as
     # the `fp32x3` object: `value` stays the native fp32 MFMA path (BASELINE configs[1]).
     x3_info = None
-    if args.dtype == "fp32" and not args.no_x3:
+    if args.full and args.dtype == "fp32" and not args.no_x3:
         try:
             torch.manual_seed(1)
             model_x = VqaNet(cfg, V, compute_dtype="fp32x3").to(dev)
@@ -346,12 +389,13 @@ def main():
         # correction per MI355X_MICROARCH.md): tools/pmc_conv_run.py launches every conv kernel of one layer in isolation
         # under rocprofv3, tools/pmc_traffic_summary.py writes profiles/r03_conv_traffic_<dtype>_<size>_<batch>.json keyed
         # "<family>:<layer>" with the kernel names it saw
-        traffic_db, traffic_file = {}, f"r03_conv_traffic_{args.dtype}_{S}_{B}.json"
-        try:
-            with open(os.path.join(ROOT, "profiles", traffic_file)) as f:
-                traffic_db = json.load(f)
-        except (OSError, ValueError):
-            traffic_file = None
+        traffic_db, traffic_file = {}, f"r03_conv_traffic_{args.dtype}_{S}_{B}.json" if args.full else None
+        if traffic_file:
+            try:
+                with open(os.path.join(ROOT, "profiles", traffic_file)) as f:
+                    traffic_db = json.load(f)
+            except (OSError, ValueError):
+                traffic_file = None
         esz = 2 if args.dtype == "bf16" else 4           # bytes per activation element between the conv blocks
 
         def conv_alg_bytes(fam, tag):
@@ -462,10 +506,9 @@ def main():
             "step_mfma_frac": round(value * gflop_sample / 1e3 / (peak * world), 4),
             "step_mfma_peak_tflops": peak,
             "final_loss": round(final_loss, 5),
-            "roofline": roofline,
-            "kernels": kernels,
-            "streaming": streaming,
         }
+        if args.full:
+            out.update(roofline=roofline, kernels=kernels, streaming=streaming)
         if x3_info is not None:
             out["fp32x3"] = x3_info
         if dp_info is not None:

@@ -3,48 +3,22 @@
 Round-2 ADVICE: an `import run_batch` at the top of the reference's train.py is a no-op, because that file
 defines its own module-level `def run_batch` further down (train.py:172) and `train()` / `evaluate()` look the
 name up at call time (train.py:70,159).  The documented patch therefore appends the import at the END of the file.
-Three checks:
-  1. against the reference's own file, when it is present (this container only; read as text through `ast`,
-     nothing is imported or executed from it): the structure the argument relies on;
-  2. the name-binding rule itself, on a synthetic module of the same shape;
-  3. the patched loop shape end to end on the CPU stand-in engine: run_batch -> zero_grad -> update_learning_rate
+Two checks:
+  1. the name-binding rule itself, on a synthetic module of the same shape;
+  2. the patched loop shape end to end on the CPU stand-in engine: run_batch -> zero_grad -> update_learning_rate
      -> backward -> step (train.py:70-80), with FusedAdam, and under data parallelism (gloo, world_size 2) with
      NO explicit divisor -- the global-batch divisor must come from the attached synchroniser.
 """
-import ast
 import os
 import types
 
-import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests.test_autograd_glue_cpu import _free_port, close, make_model, oracle_grads
 
-REF_TRAIN = "/root/reference/train.py"
-
 PATCH_TAIL = "from dl_vqa_amd.train import run_batch, FusedAdam   # noqa: E402,F811\n"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_TRAIN), reason="the reference tree is only present in the build container")
-def test_reference_train_py_has_the_shape_the_patch_relies_on():
-    tree = ast.parse(open(REF_TRAIN).read())
-    top = {n.name: n for n in tree.body if isinstance(n, ast.FunctionDef)}
-    assert {"train", "evaluate", "run_batch", "update_learning_rate"} <= set(top)
-    # run_batch is defined at module level BELOW train / evaluate: a top-of-file import would be rebound by it
-    assert top["run_batch"].lineno > top["evaluate"].lineno > top["train"].lineno
-    for fn in ("train", "evaluate"):
-        calls = [c for c in ast.walk(top[fn]) if isinstance(c, ast.Call) and isinstance(c.func, ast.Name)
-                 and c.func.id == "run_batch"]
-        assert calls, f"{fn}() does not call run_batch by its global name"
-        for c in calls:                      # (model, log_softmax, batch_data, max_answers): no divisor argument
-            assert len(c.args) == 4 and not c.keywords
-    # the optimiser line the patch replaces
-    src = open(REF_TRAIN).read().splitlines()
-    assert "torch.optim.Adam(model.parameters(), lr=train_params.lr)" in src[54]
-    imports_after = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom)) and n.lineno > top["run_batch"].lineno]
-    assert not imports_after                 # nothing below the def yet: the appended import is the last binding
 
 
 def test_an_import_at_the_end_of_the_module_wins_and_one_at_the_top_does_not():

@@ -4,10 +4,10 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 T="timeout -k 10"
 $T 900 python -m pytest tests -m gpu -q > $O/r03_gputests.log 2>&1; echo "pytest rc=$?" >> $O/r03_gputests.log; tail -3 $O/r03_gputests.log
-$T 400 python bench.py --steps 20 --warmup 3 > $O/r03_bench_fp32.json 2> $O/r03_bench_fp32.err; head -c 300 $O/r03_bench_fp32.json; echo
-$T 300 python bench.py --dtype bf16 --batch 512 --size 448 --steps 5 --warmup 2 --no-cpu-baseline > $O/r03_bench_bf16_448.json 2> $O/r03_bench_bf16_448.err; head -c 300 $O/r03_bench_bf16_448.json; echo
-$T 300 python bench.py --batch 1024 --tokens 30 --answers 3000 --steps 4 --warmup 2 --no-cpu-baseline > $O/r03_bench_stress.json 2> $O/r03_bench_stress.err; head -c 300 $O/r03_bench_stress.json; echo
-$T 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --force-dist --no-cpu-baseline > $O/r03_bench_rccl_ws1.json 2> $O/r03_bench_rccl_ws1.err; head -c 300 $O/r03_bench_rccl_ws1.json; echo
+$T 400 python bench.py --full --steps 20 --warmup 3 > $O/r03_bench_fp32.json 2> $O/r03_bench_fp32.err; head -c 300 $O/r03_bench_fp32.json; echo
+$T 300 python bench.py --full --dtype bf16 --batch 512 --size 448 --steps 5 --warmup 2 --no-cpu-baseline > $O/r03_bench_bf16_448.json 2> $O/r03_bench_bf16_448.err; head -c 300 $O/r03_bench_bf16_448.json; echo
+$T 300 python bench.py --full --batch 1024 --tokens 30 --answers 3000 --steps 4 --warmup 2 --no-cpu-baseline > $O/r03_bench_stress.json 2> $O/r03_bench_stress.err; head -c 300 $O/r03_bench_stress.json; echo
+$T 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 3 --force-dist --no-cpu-baseline > $O/r03_bench_rccl_ws1.json 2> $O/r03_bench_rccl_ws1.err; head -c 300 $O/r03_bench_rccl_ws1.json; echo
 cd /tmp; export TMPDIR=/tmp
 rm -rf $O/r03_prof_* $O/r03_pm_* $O/r03_pmcc_*
 VQA_STREAMS=1 $T 300 rocprofv3 --kernel-trace --stats -d $O/r03_prof_serial -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-x3 --stream-steps 0 > $O/r03_prof_serial.log 2>&1
