@@ -71,6 +71,9 @@ PROTOTYPES = {
     "vqa_conv0_wgrad_workspace_bytes": (i64, [i32]),
     "vqa_conv0_wgrad": (i32, [vp, i32, f32p, u8p, f32p, f32p, i32, i32, i32, i32, i32, f32p, i64, vp]),
     "vqa_conv0_wgrad_bf16": (i32, [vp, i32, vp, u8p, f32p, f32p, i32, i32, i32, i32, i32, f32p, i64, vp]),
+    "vqa_conv0_dgrad_supported": (i32, [i32, i32, i32, i32, i32]),
+    "vqa_conv0_dgrad": (i32, [vp, i32, u8p, f32p, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "vqa_nhwc_to_nchw": (i32, [f32p, vp, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_dropout": (i32, [f32p, f32p, i64, f32, u64, vp]),
     "vqa_dropout_add": (i32, [f32p, f32p, i64, f32, u64, vp]),
     "vqa_l2norm_fwd": (i32, [f32p, f32p, f32p, i64, i32, f32, u64, vp, i32, f32, u64, vp]),

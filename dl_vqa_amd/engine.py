@@ -186,20 +186,23 @@ class Engine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, training: bool, seed: int,
-                keep: bool, bad_tokens: Optional[Tensor] = None):
+                keep: bool, bad_tokens: Optional[Tensor] = None, need_dx: bool = False):
         """Returns (logits [B,A], ctx or None). `keep` = save what backward needs.
-        bad_tokens: optional device int32 [1] that counts token ids outside the vocabulary."""
+        bad_tokens: optional device int32 [1] that counts token ids outside the vocabulary.
+        need_dx (with keep): backward also returns the gradient w.r.t. the image v."""
         # kernels launch on HIP's CURRENT device and torch's current stream of that device: make the tensors'
         # device current for the whole schedule (a model on cuda:1 while cuda:0 is current would otherwise
         # launch on GPU 0 with GPU-1 pointers)
         with torch.cuda.device(v.device):
-            return self._forward(P, v, q, q_len, training, seed, keep, bad_tokens)
+            return self._forward(P, v, q, q_len, training, seed, keep, bad_tokens, need_dx)
 
     def _forward(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, training: bool, seed: int,
-                 keep: bool, bad_tokens: Optional[Tensor] = None):
+                 keep: bool, bad_tokens: Optional[Tensor] = None, need_dx: bool = False):
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [B,C,S,S]"
         v = v.contiguous()
+        need_dx = bool(keep and need_dx)
+        v_dtype, v_shape = v.dtype, tuple(v.shape)
         q = q.to(device=v.device, dtype=torch.int64).contiguous()
         q_len = q_len.to(device=v.device, dtype=torch.int64).contiguous()
         dev = v.device
@@ -340,7 +343,8 @@ class Engine:
             pdg = (keep and l > 0 and not x3 and self.stride == 1 and acts[-1].dim() == 4 and pdg_mode != "0"
                    and (x_shape[3] % 128 != 0 or pdg_mode == "2")
                    and ops.pconvf_supported(x_shape[1], x_shape[2], x_shape[3], w.shape[0]))
-            wf, wd = ops.conv_pack_weights(w, x_shape[3], need_wd=(keep and l > 0 and not pdg))
+            # block 0 packs its backward-data weights only when the input gradient is wanted
+            wf, wd = ops.conv_pack_weights(w, x_shape[3], need_wd=(keep and (l > 0 or need_dx) and not pdg))
             if pdg:
                 wd = ("pconvf", ops.pconvf_pack_weights(w))
             if x3:
@@ -440,19 +444,21 @@ class Engine:
         ctx = SimpleNamespace(B=B, T=T, Pn=Pn, q=q, q_len=q_len, acts=acts, idxs=idxs, wds=wds, vn=vn, norm=norm,
                               x_emb=x_emb, x16=x16[0], lstm=lstm, v_in=v_in, v16=v16, wv16=wv16, q_in=q_in, ld_q=ld_q, xs=xs, probs=probs,
                               c_in=c_in, h1=h1, h1d=h1d, fast0=fast0, use_pc=use_pc, fc=fc, vprime=vprime, qp=qp, p_img=p_img, p_txt=p_txt, p_att=p_att, p_cls=p_cls,
-                              seed=seed, stages=dict(pooled=pooled, score=score, combined=combined))
+                              seed=seed, stages=dict(pooled=pooled, score=score, combined=combined),
+                              need_dx=need_dx, v_dtype=v_dtype, v_shape=v_shape)
         return logits, ctx
 
     # ------------------------------------------------------------------ backward
     def backward(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
-                 on_ready: Optional[Callable[[str], None]] = None) -> None:
-        """Writes the gradient of every parameter into Gr[name] (caller-owned, same shapes as P).
+                 on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:
+        """Writes the gradient of every parameter into Gr[name] (caller-owned, same shapes as P).  Returns the gradient
+        w.r.t. the image (NCHW, the dtype the forward received) when the forward ran with need_dx, else None.
 
         `on_ready(group)` is called after the kernels producing a parameter group have been enqueued
         ('classifier', 'attention', 'text', 'image'): the data-parallel wrapper starts that bucket's
         all-reduce there, overlapping the rest of backward."""
         with torch.cuda.device(dlogits.device):
-            self._backward(P, ctx, dlogits, Gr, on_ready)
+            return self._backward(P, ctx, dlogits, Gr, on_ready)
 
     def _backward(self, P, ctx, dlogits, Gr, on_ready):
         B, T, Pn = ctx.B, ctx.T, ctx.Pn
@@ -660,6 +666,7 @@ class Engine:
             main.wait_event(ev0)
 
         # ---- image: L2-norm (+dropout) backward, then conv blocks from the last to the first
+        dv = None
         c16_hw = tuple(ctx.idxs[-1].shape[2:4]) if self.bf16 and ctx.use_pc else None   # channel-blocked for the routed patches
         if join:
             dP = ops.l2norm_bwd_joined(dcomb, Dc, ctx.probs, dv_in, ctx.p_att, sd(SITE_ATT_V), ctx.vn, ctx.norm, ctx.p_img,
@@ -674,13 +681,18 @@ class Engine:
         for l in range(self.L - 1, -1, -1):
             if self.ks != 3:
                 dP = ops.convk_bwd(ctx.acts[l], dP, ctx.idxs[l], ctx.wds[l], Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"],
-                                   self.ks, self.stride, need_dx=l > 0, tag=l)
+                                   self.ks, self.stride, need_dx=l > 0 or ctx.need_dx, tag=l)
                 continue
             if l == 0 and ctx.fast0:
                 if self.bf16:
                     ops.conv0_wgrad_bf16(ctx.acts[0], dP, ctx.idxs[0], Gr["image.conv0.weight"], Gr["image.conv0.bias"])
                 else:
                     ops.conv0_wgrad(ctx.acts[0], dP, ctx.idxs[0], Gr["image.conv0.weight"], Gr["image.conv0.bias"])
+                if ctx.need_dx:
+                    # the image gradient straight from the pooled gradient, in the caller's NCHW layout and dtype (csrc/conv0_dgrad.hip);
+                    # the bf16 path's forward multiplies by the bf16-rounded weights, so its backward-data does as well
+                    dv = ops.conv0_dgrad(dP, ctx.idxs[0], P["image.conv0.weight"], ctx.v_shape, out_dtype=ctx.v_dtype,
+                                         round_w_bf16=self.bf16)
                 continue
             if self.bf16 and ctx.use_pc:
                 # both kernels route the pre-pool gradient themselves (pooled gradient + arg-max bytes, C16); the block below
@@ -703,7 +715,11 @@ class Engine:
                            None if x3 else Gr[f"image.conv{l}.bias"], self.stride, tag=l, x3=x3, dpooled_packed=dPp)
             if l > 0 and isinstance(ctx.wds[l], tuple):
                 dP = ops.pconvf_dgrad(dP, ctx.idxs[l], ctx.wds[l][1], x_shape, tag=l)
-            elif l > 0:
+            elif l > 0 or ctx.need_dx:
                 dP = ops.conv_dgrad(dPp if x3 else dP, ctx.idxs[l], ctx.wds[l], x_shape, self.stride, tag=l, x3=x3)
+        if ctx.need_dx and dv is None:
+            # generic first block (NHWC4 input): drop the pad channel, back to the caller's NCHW layout and dtype
+            dv = ops.nhwc_to_nchw(dP, ctx.v_shape[1], out_dtype=ctx.v_dtype)
         ready("image")
         main.wait_event(ev0)
+        return dv

@@ -129,8 +129,10 @@ class _VqaFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, v, q, q_len, seed, *params):
         P = model._param_dict()
+        # v.requires_grad: the forward keeps what the first block's backward-data needs
+        extra = {"need_dx": True} if ctx.needs_input_grad[1] else {}
         logits, saved = model._engine.forward(P, v, q, q_len, model.training, seed, keep=True,
-                                              bad_tokens=model._bad_tokens)
+                                              bad_tokens=model._bad_tokens, **extra)
         ctx.model = model
         ctx.saved = saved
         model._last_ctx = saved
@@ -144,6 +146,14 @@ class _VqaFunction(torch.autograd.Function):
             raise RuntimeError("dl_vqa_amd.VqaNet: backward through the same forward twice (the saved "
                                "activations are released after the first backward; retain_graph is not supported)")
         names = model._names
+        if not any(ctx.needs_input_grad[5:]):
+            # every parameter frozen, only the image gradient is wanted: the parameter gradients go to a scratch buffer
+            # (the model's flat gradient buffer, p.grad and the data-parallel buckets are left alone)
+            _flat, Gr = model._grad_buffer(fresh=True)
+            dv = model._engine.backward(model._param_dict(), ctx.saved, dlogits, Gr, None)
+            ctx.saved = None
+            model._pending.discard(ctx)
+            return (None, dv, None, None, None) + (None,) * len(names)
         others = [c for c in model._pending if c is not ctx]
         direct = not others and all(p.grad is None for p in model._params)
         if not direct and others and not model._warned_stale:
@@ -159,12 +169,12 @@ class _VqaFunction(torch.autograd.Function):
         # ranks' four)
         on_ready = (lambda group: sync.bucket_ready(model, group, flat)) if sync is not None else None
         model._last_backward_direct = direct
-        model._engine.backward(model._param_dict(), ctx.saved, dlogits, Gr, on_ready)
+        dv = model._engine.backward(model._param_dict(), ctx.saved, dlogits, Gr, on_ready)
         if sync is not None:
             sync.finish(model)
         ctx.saved = None
         model._pending.discard(ctx)
-        return (None, None, None, None, None) + tuple(Gr[n] for n in names)
+        return (None, dv, None, None, None) + tuple(Gr[n] for n in names)
 
 
 class VqaNet(nn.Module):
@@ -333,7 +343,8 @@ class VqaNet(nn.Module):
         if v.dtype not in (torch.float32, torch.float16):
             v = v.float()
         seed = self._next_seed() if self.training else 0
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._params)
+        # the autograd node also when only the image wants a gradient (saliency / attribution on a frozen model)
+        need_grad = torch.is_grad_enabled() and (v.requires_grad or any(p.requires_grad for p in self._params))
         if need_grad:
             logits = _VqaFunction.apply(self, v, q, q_len, seed, *self._params)
         else:

@@ -288,6 +288,36 @@ def conv0_wgrad_bf16(x_nchw, dpooled16, amax, dw: torch.Tensor, dbias: torch.Ten
          ws.numel() * 4, stream())
 
 
+def conv0_dgrad_supported(Ci: int, H: int, W: int, Co: int, stride: int) -> bool:
+    return bool(_lib.load().vqa_conv0_dgrad_supported(Ci, H, W, Co, stride))
+
+
+def conv0_dgrad(dpooled: torch.Tensor, amax: torch.Tensor, w: torch.Tensor, x_shape, out_dtype=torch.float32,
+                round_w_bf16: bool = False) -> torch.Tensor:
+    """Input-image gradient of the dedicated first block: dpooled NHWC [B,Hp,Wp,Co] (fp32 or bf16) routed through the
+    arg-max bytes and w [Co,Ci,3,3] -> dv NCHW x_shape (fp32 or fp16).  round_w_bf16: the weights as the bf16-path forward
+    uses them."""
+    B, Ci, H, W = x_shape
+    Co = w.shape[0]
+    Hp, Wp = conv_out_hw(H, W, 1)
+    assert dpooled.dtype in (torch.float32, torch.bfloat16) and dpooled.is_contiguous() and dpooled.shape == (B, Hp, Wp, Co)
+    assert amax.dtype == torch.uint8 and amax.shape == dpooled.shape and w.dtype == torch.float32 and w.is_contiguous()
+    assert out_dtype in (torch.float32, torch.float16)
+    dv = torch.empty(B, Ci, H, W, dtype=out_dtype, device=dpooled.device)
+    call("vqa_conv0_dgrad", ptr(dpooled), int(dpooled.dtype == torch.bfloat16), ptr(amax), ptr(w), ptr(dv),
+         int(out_dtype == torch.float16), int(round_w_bf16), B, Ci, H, W, Co, stream())
+    return dv
+
+
+def nhwc_to_nchw(x: torch.Tensor, C: int, out_dtype=torch.float32) -> torch.Tensor:
+    """fp32 NHWC [B,H,W,CP] -> NCHW [B,C,H,W] (fp32 or fp16), the pad channels dropped: the inverse of nchw_to_nhwc4."""
+    B, H, W, CP = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and out_dtype in (torch.float32, torch.float16)
+    y = torch.empty(B, C, H, W, dtype=out_dtype, device=x.device)
+    call("vqa_nhwc_to_nchw", ptr(x), ptr(y), int(out_dtype == torch.float16), B, C, CP, H, W, stream())
+    return y
+
+
 def dropout(x: torch.Tensor, p: float, seed: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     y = out if out is not None else torch.empty_like(x)
     call("vqa_dropout", ptr(x), ptr(y), x.numel(), p, seed, stream())

@@ -28,7 +28,7 @@ extern "C" {
 
 /* Bumped whenever an exported entry point changes its argument list or disappears (round 1: 1, round 2: 2, round 3: 3).
  * dl_vqa_amd/_lib.py parses this line and refuses a library that answers differently. */
-#define VQA_ABI_VERSION 7
+#define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
 #define VQA_ERR_INVALID 1 /* bad argument (shape, alignment, null pointer) */
@@ -150,6 +150,19 @@ int vqa_conv0_wgrad(const void* x_nchw, int x_is_fp16, const float* dpooled, con
 int vqa_conv0_wgrad_bf16(const void* x_nchw, int x_is_fp16, const void* dpooled_bf16, const uint8_t* argmax, float* dw,
                          float* dbias, int B, int Ci, int H, int W, int Co, float* workspace,
                          int64_t workspace_bytes, vqa_stream_t stream);
+
+/* ---- input-image gradient (v.requires_grad: saliency, attribution; csrc/conv0_dgrad.hip) ----------------------------
+ * The first block's backward-data on the dedicated path (Ci <= 3, stride 1, Co in {32, 64}, W % 4 == 0):
+ *   dv[b][c][y][x] = sum_{co,ky,kx} w[co][c][ky][kx] * dY[b][co][y-ky][x-kx], dY routed from the pooled gradient
+ *   dpooled [B][Hp][Wp][Co] (fp32, or bf16 when dpooled_is_bf16) through the arg-max bytes (0..3, 4 = dead).
+ * w in torch layout [Co][Ci][3][3] (round_w_bf16: rounded to bf16 as the bf16-path forward uses them).  dv is the
+ * caller's NCHW layout, fp32 or (dv_is_fp16) fp16; every element is written, no atomics (bit-reproducible). */
+int vqa_conv0_dgrad_supported(int Ci, int H, int W, int Co, int stride);
+int vqa_conv0_dgrad(const void* dpooled, int dpooled_is_bf16, const uint8_t* argmax, const float* w, void* dv, int dv_is_fp16,
+                    int round_w_bf16, int B, int Ci, int H, int W, int Co, vqa_stream_t stream);
+/* NHWC [B][H][W][CP] fp32 -> NCHW [B][C][H][W] fp32 or (y_is_fp16) fp16, channels C..CP-1 dropped: the inverse of
+ * vqa_nchw_to_nhwc4, for the input gradient of the generic first-block paths. */
+int vqa_nhwc_to_nchw(const float* x_nhwc, void* y_nchw, int y_is_fp16, int B, int C, int CP, int H, int W, vqa_stream_t stream);
 
 /* ---- dropout (nn.Dropout, 7 sites: models/model.py:84,156,185,186,194,201,204) ---------------
  * y = x * keep(seed, i) / (1-p); keep() is a counter-based hash, so backward calls the same
