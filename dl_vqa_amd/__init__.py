@@ -5,6 +5,6 @@ backward run on hand-written HIP kernels (csrc/, bound through the C ABI in incl
 ``train`` mirrors the reference training procedure (train.py) with a fused device-side loss and
 Adam; ``distributed.DataParallel`` shards the minibatch over the GPUs of one node with RCCL.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image  # noqa: F401
 
-__all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier"]
+__all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image"]

@@ -858,14 +858,15 @@ __device__ __forceinline__ void att_softmax_to_lds(const float* score, float* pr
 // (the scalar form below runs at 26 % of the HBM rate: one 4-byte load per FMA pair, 169 dependent iterations).
 // grid (B, ceil(C/64)); dynamic LDS: G*P + 16 + 16*G*64 floats.  Sum order per channel: positions pg, pg+16, ... within
 // a group, then the 16 groups in order.
+// b = the sample (score / probs / out row), n = the image whose vn rows it weights: n == b in vqa_att_apply_fwd,
+// n = img[b] in vqa_att_apply_gather_fwd (several questions per image)
 template <int G>
-__global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, float* probs, float* out, int64_t out_ld,
-                                        int P, int C) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
+__device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* score, const float* vn, float* probs, float* out,
+                                                      int64_t out_ld, int P, int C, int b, int n) {
   float* pr = sm;            // [G][P]
   float* red = sm + G * P;   // [16]
   float* part = red + 16;    // [16][G][64]
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   att_softmax_to_lds<G>(score, probs, pr, red, b, P, blockIdx.y == 0);
   __syncthreads();
   const int cq = tid & 15, pg = tid >> 4;
@@ -874,7 +875,7 @@ __global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, flo
 #pragma unroll
   for (int g = 0; g < G; ++g) acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (c < C) {
-    const float* vb = vn + (int64_t)b * P * C + c;
+    const float* vb = vn + (int64_t)n * P * C + c;
     int i = pg;
     for (; i + 48 < P; i += 64) {
       float4 v[4];
@@ -910,15 +911,31 @@ __global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, flo
   }
 }
 
+template <int G>
+__global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, float* probs, float* out, int64_t out_ld,
+                                        int P, int C) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, blockIdx.x);
+}
+
+// the same with an image index; a sample whose index is outside [0, N) is left unwritten (block-uniform exit)
+template <int G>
+__global__ void att_apply_gather_fwd_v4_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
+                                               int64_t out_ld, int P, int C, int N) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int n = img[blockIdx.x];
+  if ((unsigned)n >= (unsigned)N) return;
+  att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
+}
+
 // grid (B, ceil(C/64)), 256 threads = 4 position groups x 64 channels; dynamic LDS: G*P + 16 + 4*G*64 floats
 template <int G>
-__global__ void att_apply_fwd_kernel(const float* score, const float* vn, float* probs, float* out,
-                                     int64_t out_ld, int P, int C) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
+__device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score, const float* vn, float* probs, float* out,
+                                                   int64_t out_ld, int P, int C, int b, int n) {
   float* pr = sm;            // [G][P]
   float* red = sm + G * P;   // [16]
   float* part = red + 16;    // [4][G][64]
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   for (int g = 0; g < G; ++g) {
     const float* s = score + ((int64_t)b * G + g) * P;
     float mx = -INFINITY;
@@ -941,7 +958,7 @@ __global__ void att_apply_fwd_kernel(const float* score, const float* vn, float*
 #pragma unroll
   for (int g = 0; g < G; ++g) acc[g] = 0.f;
   if (c < C) {
-    const float* vb = vn + (int64_t)b * P * C + c;
+    const float* vb = vn + (int64_t)n * P * C + c;
     for (int i = pg; i < P; i += 4) {
       const float v = vb[(int64_t)i * C];
 #pragma unroll
@@ -958,6 +975,22 @@ __global__ void att_apply_fwd_kernel(const float* score, const float* vn, float*
       out[(int64_t)b * out_ld + g * C + c] = v;
     }
   }
+}
+
+template <int G>
+__global__ void att_apply_fwd_kernel(const float* score, const float* vn, float* probs, float* out,
+                                     int64_t out_ld, int P, int C) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, blockIdx.x);
+}
+
+template <int G>
+__global__ void att_apply_gather_fwd_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
+                                            int64_t out_ld, int P, int C, int N) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int n = img[blockIdx.x];
+  if ((unsigned)n >= (unsigned)N) return;
+  att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
 }
 
 // pass 1: one wave per (b,p): dprob -> dscore buffer, dvn row written
@@ -1417,6 +1450,26 @@ int vqa_att_apply_fwd(const float* score, const float* vn, float* probs, float* 
   DISPATCH_G(G, hipLaunchKernelGGL(att_apply_fwd_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score, vn,
                                    probs, out, out_ld, P, C));
   return check_hip(hipGetLastError(), "att_apply_fwd launch");
+}
+
+int vqa_att_apply_gather_fwd(const float* score, const float* vn, const int32_t* img, float* probs, float* out,
+                             int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
+  VQA_REQUIRE(score && vn && img && probs && out, "vqa_att_apply_gather_fwd: null pointer");
+  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && C >= 1 && out_ld >= (int64_t)G * C,
+              "vqa_att_apply_gather_fwd: N=%d, B=%d, P=%d, C=%d, out_ld=%lld out of range", N, B, P, C, (long long)out_ld);
+  const size_t lds = ((size_t)G * P + 16 + 16 * G * 64) * 4;
+  VQA_REQUIRE(lds <= 64 * 1024, "vqa_att_apply_gather_fwd: G*P=%d too large for LDS", G * P);
+  if (B == 0) return VQA_OK;
+  if (C % 4 == 0) {
+    DISPATCH_G(G, hipLaunchKernelGGL(att_apply_gather_fwd_v4_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score,
+                                     vn, img, probs, out, out_ld, P, C, N));
+    return check_hip(hipGetLastError(), "att_apply_gather_fwd launch");
+  }
+  DISPATCH_G(G, hipLaunchKernelGGL(att_apply_gather_fwd_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score, vn,
+                                   img, probs, out, out_ld, P, C, N));
+  return check_hip(hipGetLastError(), "att_apply_gather_fwd launch");
 }
 
 int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, float* dscore,

@@ -448,6 +448,105 @@ class Engine:
                               need_dx=need_dx, v_dtype=v_dtype, v_shape=v_shape)
         return logits, ctx
 
+    # ------------------------------------------------------------------ many questions per image (inference)
+    # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder and the question branch repeat the launches
+    # of _forward (which stays exactly as it is); the attention stage runs on ONE v' per image (csrc/att_grouped.hip).
+    def encode_images(self, P: Dict[str, Tensor], v: Tensor):
+        """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid], (gh, gw))."""
+        assert not self.bf16, "encode_images: fp32 / fp32x3 only"
+        with torch.cuda.device(v.device):
+            return self._encode_images(P, v)
+
+    def _encode_images(self, P, v):
+        assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
+            "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
+        v = v.contiguous()
+        fast0 = self.ks == 3 and ops.conv0_supported(v.shape[1], v.shape[2], v.shape[3], self.channels[1], self.stride)
+        if v.dtype == torch.float16 and not fast0:
+            v = ops.half_to_float(v)
+        x = v if fast0 else ops.nchw_to_nhwc4(v)
+        for l in range(self.L):
+            w, bias = P[f"image.conv{l}.weight"], P[f"image.conv{l}.bias"]
+            if self.ks != 3:
+                x, _ = ops.convk_fwd(x, ops.convk_pack_weights(w, x.shape[3]), bias, self.ks, self.stride, tag=l)
+                continue
+            nxt_x3 = l + 1 < self.L and self._x3_layer(self._out_shape(x, l, fast0), self.channels[l + 2])
+            if l == 0 and fast0:
+                x, _ = ops.conv0_fwd(v, w, bias, out_packed=nxt_x3)
+                continue
+            x_shape = ops.nhwc_shape(x)
+            x3 = self._x3_layer(x_shape, w.shape[0])
+            wf, _ = ops.conv_pack_weights(w, x_shape[3], need_wd=False)
+            if x3:
+                wf = ops.x3_split(wf)
+                if x.dim() == 4:
+                    x = ops.x3_pack(x)
+            x, _ = ops.conv_fwd(x, wf, bias, self.stride, tag=l, x3=x3, out_packed=x3 and nxt_x3)
+        N, gh, gw, C = x.shape
+        Pn = gh * gw
+        vn, _ = ops.l2norm_fwd(x, 0.0, 0)
+        vprime = torch.empty(N * Pn, self.mid, dtype=torch.float32, device=v.device)
+        ops.gemm(vn, P["attention.v_conv.weight"], vprime, N * Pn, self.mid, C, tag=21, x3=self._x3_gemm(N * Pn))
+        return vn.view(N, Pn, C), vprime, (gh, gw)
+
+    def answer(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
+               bad_tokens: Optional[Tensor] = None):
+        """B questions against the N encoded images of `feats` (vn, vprime): question b looks at image img[b]; order /
+        offsets (device int32) group the questions by image.  Returns (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
+        assert not self.bf16, "answer: fp32 / fp32x3 only"
+        with torch.cuda.device(feats.vn.device):
+            return self._answer(P, feats, q, q_len, order, offsets, img, bad_tokens)
+
+    def _answer(self, P, feats, q, q_len, order, offsets, img, bad_tokens):
+        dev = feats.vn.device
+        q = q.to(device=dev, dtype=torch.int64).contiguous()
+        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
+        B, T = q.shape
+        N, Pn, C = feats.vn.shape
+        E, H, G, mid, hid, A, Dc, GC, Q = self.E, self.H, self.G, self.mid, self.hid, self.A, self.Dc, self.GC, self.Q
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+
+        # ---- question encoder: the launches of _forward's question branch, eval mode, on the current stream (there are
+        # no convolutions to hide it under)
+        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], 0.0, 0, bad_tokens)                     # [T,B,E]
+        combined = new(B, Dc)
+        sfx = lambda d: "_reverse" if d else ""
+        dirs = []
+        for d in range(self.ndir):
+            xg = new(T * B, 4 * H)
+            ops.gemm(x_emb, P["text.lstm.weight_ih_l0" + sfx(d)], xg, T * B, 4 * H, E,
+                     bias1=P["text.lstm.bias_ih_l0" + sfx(d)], bias2=P["text.lstm.bias_hh_l0" + sfx(d)], tag=10)
+            st = dict(w_hh=P["text.lstm.weight_hh_l0" + sfx(d)], xg=xg, gates=new(T, B, 4 * H), Hs=new(T + 1, B, H),
+                      Cs=new(T + 1, B, H), c_final=combined[:, GC + d * H:], reverse=bool(d))
+            st["Hs"][T if d else 0].zero_()
+            st["Cs"][T if d else 0].zero_()
+            dirs.append(st)
+        if ops.lstm_step_supported(H) and os.environ.get("VQA_FUSED_LSTM", "1") == "1":
+            ops.lstm_seq_fwd(dirs, q_len, B, T, H, cf_ld=Dc, use_graph=os.environ.get("VQA_GRAPH", "1") == "1")
+        else:
+            for d, st in enumerate(dirs):
+                hg = new(B, 4 * H)
+                steps = range(T) if d == 0 else range(T - 1, -1, -1)
+                for k, t in enumerate(steps):
+                    si, so = (t, t + 1) if d == 0 else (t + 1, t)
+                    ops.gemm(st["Hs"][si], st["w_hh"], hg, B, 4 * H, H, tag=11)
+                    ops.lstm_cell_fwd(st["xg"][t * B:(t + 1) * B], hg, st["Cs"][si], st["Hs"][si], q_len, t, st["gates"][t],
+                                      st["Cs"][so], st["Hs"][so], st["c_final"] if k == T - 1 else None, Dc)
+        qp = new(B, mid)
+        ops.gemm(combined[:, GC:], P["attention.q_lin.weight"], qp, B, mid, Q, lda=Dc, bias1=P["attention.q_lin.bias"], tag=20)
+
+        # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
+        score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"],
+                                          order, offsets, N, B, Pn, self.att_mode)
+        probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, Dc)
+
+        # ---- classifier
+        h1 = new(B, hid)
+        logits = new(B, A)
+        ops.gemm(combined, P["classifier.lin1.weight"], h1, B, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True, tag=30)
+        ops.gemm(h1, P["classifier.lin2.weight"], logits, B, A, hid, bias1=P["classifier.lin2.bias"], tag=31)
+        return logits, probs, score
+
     # ------------------------------------------------------------------ backward
     def backward(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
                  on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:

@@ -111,6 +111,33 @@ def validate_question_lengths(q_len, T: int) -> None:
                            "(pack_padded_sequence would raise: models/model.py:159-162)")
 
 
+def group_by_image(image_index, N: int):
+    """Group questions by the image they ask about: image_index[b] in [0, N) -> (order int32 [B], offsets int32 [N+1]) on
+    the host; the questions of image n are order[offsets[n]:offsets[n+1]], in their original order (a stable counting
+    sort).  IndexError for an entry outside [0, N)."""
+    idx = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+        bad = int(idx.min()) if int(idx.min()) < 0 else int(idx.max())
+        raise IndexError(f"image_index entry {bad} out of range [0, {N})")
+    offsets = torch.zeros(N + 1, dtype=torch.int64)
+    if idx.numel():
+        offsets[1:] = torch.cumsum(torch.bincount(idx, minlength=N), 0)
+    order = torch.argsort(idx, stable=True)
+    return order.to(torch.int32), offsets.to(torch.int32)
+
+
+class ImageFeatures:
+    """What VqaNet.encode_images returns and VqaNet.answer reads: the L2-normalised image features `vn` [N, P, C], their
+    attention projection `vprime` = v_conv(vn) [N*P, mid], the grid (gh, gw) with P = gh * gw, and N.  A plain holder of
+    CUDA tensors; it can be kept across many answer() calls, as long as the weights it was computed from stay the same."""
+    __slots__ = ("vn", "vprime", "grid", "N", "_model", "_flat_ptr")
+
+    def __init__(self, vn, vprime, grid, model):
+        self.vn, self.vprime, self.grid, self.N = vn, vprime, tuple(grid), vn.shape[0]
+        self._model = weakref.ref(model)
+        self._flat_ptr = model._flat_param.data_ptr()     # a re-flattened model (moved, new storage) no longer matches
+
+
 class _VqaFunction(torch.autograd.Function):
     """Autograd node of one VqaNet.forward call.
 
@@ -351,4 +378,75 @@ class VqaNet(nn.Module):
             logits, _ = self._engine.forward(self._param_dict(), v, q, q_len, self.training, seed, keep=False,
                                              bad_tokens=self._bad_tokens)
         self._after_forward_tokens(q)
+        return logits
+
+    # ------------------------------------------------------------------ many questions per image (inference)
+    def _check_inference(self, what: str):
+        if self.compute_dtype == "bf16":
+            raise NotImplementedError(f"VqaNet.{what}: compute_dtype='bf16' is not supported (fp32 and fp32x3 are); the bf16 "
+                                      "path rounds x = relu(v' (+|*) q') to bf16, a tensor this path never forms")
+        if self.training:
+            raise RuntimeError(f"VqaNet.{what} is an inference call and the model is in training mode: the image, attention "
+                               "and classifier dropout sites (models/model.py:84,185,186,194) draw a new mask per forward, so "
+                               "image features cached across questions would be meaningless; call model.eval() first")
+
+    @torch.no_grad()
+    def encode_images(self, v) -> ImageFeatures:
+        """The image-only part of the forward, once per image: conv blocks, L2 normalisation and v' = v_conv(vn).
+        v [N,3,S,S] fp32 or fp16, CUDA.  Eval mode, compute_dtype fp32 or fp32x3; no autograd graph.
+
+        The result belongs to this model and to its current weights.  answer() refuses features of another model instance
+        or of a model whose parameters have moved to new storage, but it cannot see weights that changed IN PLACE (FusedAdam
+        steps the flat parameter buffer through raw pointers; load_state_dict copies into it): re-encode after an
+        optimiser step or load_state_dict."""
+        self._check_inference("encode_images")
+        self._ensure_flat()
+        if not v.is_cuda:
+            raise RuntimeError("dl_vqa_amd.VqaNet.encode_images needs CUDA (HIP) tensors; there is no CPU fallback")
+        if v.dtype not in (torch.float32, torch.float16):
+            v = v.float()
+        vn, vprime, grid = self._engine.encode_images(self._param_dict(), v.detach())
+        return ImageFeatures(vn, vprime, grid, self)
+
+    @torch.no_grad()
+    def answer(self, feats: ImageFeatures, q, q_len, image_index, return_attention: bool = False):
+        """Logits [B, A] of B questions about the N encoded images: question b (q[b], q_len[b]) looks at image
+        image_index[b].  B and N are independent; any order of image_index, repeats and images nobody asks about
+        included; rows come back in the caller's question order.  return_attention: also att [B, G, gh, gw] =
+        softmax over positions of the attention scores, the weights the image features are summed with
+        (models/model.py:217), on the feature grid (no upsampling).
+
+        image_index is host data (a list or a CPU integer tensor); a CUDA tensor is copied to the host first, which
+        synchronises once.  Nothing is kept for a backward: _last_ctx, the gradient buffer and the dropout seed stream are
+        left alone.  See encode_images for when `feats` has to be recomputed."""
+        self._check_inference("answer")
+        self._ensure_flat()
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError("VqaNet.answer: feats must come from VqaNet.encode_images")
+        if feats._model() is not self or feats._flat_ptr != self._flat_param.data_ptr():
+            raise RuntimeError("VqaNet.answer: these image features belong elsewhere -- they were encoded by another model "
+                               "instance, or this model's parameters have moved to new storage since (.to(), a re-flatten); "
+                               "call encode_images again on this model")
+        q = torch.as_tensor(q)
+        q_len = torch.as_tensor(q_len)
+        if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
+            raise ValueError(f"VqaNet.answer: q [B,T] and q_len [B] expected, got {tuple(q.shape)} and {tuple(q_len.shape)}")
+        self._validate_tokens(q)
+        validate_question_lengths(q_len, q.shape[1])
+        B, N = q.shape[0], feats.N
+        order, offsets = group_by_image(image_index, N)
+        if order.numel() != B:
+            raise ValueError(f"VqaNet.answer: {order.numel()} image_index entries for {B} questions")
+        dev = feats.vn.device
+        eng = self._engine
+        if B == 0:
+            logits = torch.empty(0, eng.A, dtype=torch.float32, device=dev)
+            return (logits, torch.empty(0, eng.G, *feats.grid, dtype=torch.float32, device=dev)) if return_attention else logits
+        img = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int32).reshape(-1)
+        idx = torch.cat([order, offsets, img]).to(dev)               # one upload: order [B] | offsets [N+1] | img [B]
+        logits, probs, _score = eng.answer(self._param_dict(), feats, q, q_len, idx[:B], idx[B:B + N + 1], idx[B + N + 1:],
+                                           bad_tokens=self._bad_tokens if q.is_cuda else None)
+        self._after_forward_tokens(q)
+        if return_attention:
+            return logits, probs.view(B, eng.G, *feats.grid)
         return logits

@@ -485,6 +485,31 @@ def att_apply_fwd(score, vn, out, out_ld):
     return probs
 
 
+def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
+    """Scores [B, G, P] of B questions against N images from ONE v' [N*P, mid] per image: order / offsets (device int32,
+    model.group_by_image) list the questions of image n as order[offsets[n]:offsets[n+1]].  mode 0 '+', 1 '*', 2 '|'
+    (wx [G, 2*mid])."""
+    G, xld = wx.shape[0], wx.shape[1]
+    mid = xld // 2 if mode == 2 else xld
+    _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
+    score = torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+    call("vqa_att_score_grouped_fwd", ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
+         N, B, P, mid, G, mode, stream())
+    return score
+
+
+def att_apply_gather_fwd(score, vn, img, out, out_ld):
+    """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C]."""
+    B, G, P = score.shape
+    N, C = vn.shape[0], vn.shape[-1]
+    _chk(img, torch.int32)
+    assert img.numel() == B and vn.numel() == N * P * C
+    probs = torch.empty_like(score)
+    call("vqa_att_apply_gather_fwd", ptr(score), ptr(vn), ptr(img), ptr(probs), ptr(out), out_ld, N, B, P, C, G, stream())
+    return probs
+
+
 def att_apply_bwd(dout, dout_ld, probs, vn, dvn_out=None, rowsum=None, want_dvn=True):
     """rowsum: optional [B, G] output, sum over positions of dscore (per-sample x_conv bias gradient).
     want_dvn=False: the weighted-sum branch of d loss / d vn is not written (l2norm_bwd_joined recomputes it)."""

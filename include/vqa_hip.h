@@ -271,6 +271,23 @@ int vqa_att_score_bwd(const float* dscore, const float* wx, int wx_ld, void* xs_
 /* probs = softmax_p(score); out[b*out_ld + g*C + c] = sum_p probs[b][g][p] * vn[b][p][c] */
 int vqa_att_apply_fwd(const float* score, const float* vn, float* probs, float* out, int64_t out_ld,
                       int B, int P, int C, int G, vqa_stream_t stream);
+/* Many questions per image (inference; VqaNet.encode_images / answer).  One v' = v_conv(vn) [N*P][mid] per IMAGE, the
+ * questions grouped by image: order[offsets[n] .. offsets[n+1]) are the questions of image n (device int32; order [B] a
+ * permutation of 0..B-1, offsets [N+1] non-decreasing from 0 to B).  x = relu(v' (+|*) q') is never written:
+ *   mode 0 '+', 1 '*':  score[b][g][p] = bx[g] + sum_m wx[g*wx_ld + m] * relu(v'[n*P+p][m] (+|*) qp[b][m])
+ *   mode 2 '|':         score[b][g][p] = bx[g] + sum_m wx[g*wx_ld + m] * relu(v'[n*P+p][m])
+ *                                              + sum_m wx[g*wx_ld + mid + m] * relu(qp[b][m])
+ * A workgroup keeps a tile of positions of one image in LDS and walks that image's questions over it: v' is read once
+ * per image, an image without questions costs nothing.  No atomics: every element has one summation order whatever the
+ * grouping.  mid % 4 == 0, mid <= 4096, wx_ld % 4 == 0, G in 1..4, N <= 65535; vprime, qp, wx 16-byte aligned. */
+int vqa_att_score_grouped_fwd(const float* vprime, const float* qp, const float* wx, int wx_ld, const float* bx,
+                              const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P, int mid,
+                              int G, int mode, vqa_stream_t stream);
+/* vqa_att_apply_fwd with an image index (device int32 [B], entries in [0, N)): vn is [N][P][C],
+ * probs = softmax_p(score[b][g][:]); out[b*out_ld + g*C + c] = sum_p probs[b][g][p] * vn[img[b]][p][c].
+ * With img = 0..B-1 the results equal vqa_att_apply_fwd's bit for bit (same device code). */
+int vqa_att_apply_gather_fwd(const float* score, const float* vn, const int32_t* img, float* probs, float* out,
+                             int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream);
 /* dscore[b][g][p] and dvn[b][p][c] (written; NULL: skipped, see vqa_l2norm_bwd_joined) from dout[b*dout_ld + g*C + c]; dscore_rowsum (optional)
  * [b][g] = sum_p dscore[b][g][p], the per-sample part of the x_conv bias gradient. */
 int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn,

@@ -1,0 +1,117 @@
+"""CPU: many questions per image (VqaNet.encode_images / answer) -- the two new entry points in the header, the ctypes
+prototypes and the built library, their host-side argument validation, the grouping of questions by image, and the
+errors the public calls raise before any device work."""
+import re
+
+import pytest
+import torch
+
+from dl_vqa_amd import ImageFeatures, VqaNet, group_by_image      # noqa: F401  (the new public names)
+from tests.golden_util import Golden, full_cfg, tiny_cfg
+
+NEW_ENTRY_POINTS = ("vqa_att_score_grouped_fwd", "vqa_att_apply_gather_fwd")
+
+
+def test_new_entry_points_in_header_prototypes_and_library():
+    from dl_vqa_amd import _lib, build
+    build.build_library(verbose=False)
+    with open(_lib.HEADER_PATH) as f:
+        header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    assert _lib.header_abi_version() == 8
+    for name in NEW_ENTRY_POINTS:
+        assert re.search(r"\b" + name + r"\s*\(", header), name
+        assert name in _lib.PROTOTYPES, name
+    lib = _lib.load()
+    assert lib.vqa_abi_version() == 8
+    for name in NEW_ENTRY_POINTS:
+        assert hasattr(lib, name), name
+
+
+def test_grouped_score_argument_validation_without_gpu():
+    """Every check runs on the host before any HIP call.  Arguments: vprime, qp, wx, wx_ld, bx, order, offsets, score,
+    N, B, P, mid, G, mode, stream (pointers are made-up 16-byte-aligned integers: nothing dereferences them)."""
+    from dl_vqa_amd import _lib
+    lib = _lib.load()
+    f = lib.vqa_att_score_grouped_fwd
+    assert f(16, 16, 16, 8, 16, 16, 16, 16, 2, 3, 4, 8, 9, 0, None) == 1 and b"glimpses" in lib.vqa_last_error()   # G = 9
+    assert f(16, 16, 16, 8, 16, 16, 16, 16, 2, 3, 4, 6, 2, 0, None) == 1 and b"mid=6" in lib.vqa_last_error()      # mid = 6
+    assert f(16, 16, 16, 8, 16, None, 16, 16, 2, 3, 4, 8, 2, 0, None) == 1 and b"order" in lib.vqa_last_error()    # null order
+    assert f(16, 16, 16, 8, 16, 16, None, 16, 2, 3, 4, 8, 2, 0, None) == 1 and b"offsets" in lib.vqa_last_error()
+    assert f(16, 16, 16, 8, 16, 16, 16, 16, 2, 3, 4, 8, 2, 3, None) == 1 and b"mode 3" in lib.vqa_last_error()     # mode = 3
+    assert f(None, 16, 16, 8, 16, 16, 16, 16, 2, 3, 4, 8, 2, 0, None) == 1 and b"null pointer" in lib.vqa_last_error()
+    assert f(16, 16, 16, 8, 16, 16, 16, 16, 0, 3, 4, 8, 2, 0, None) == 1 and b"out of range" in lib.vqa_last_error()   # N = 0
+    assert f(16, 16, 16, 8, 16, 16, 16, 16, 2, 3, 4, 8, 2, 2, None) == 1 and b"wx_ld" in lib.vqa_last_error()   # '|': wx_ld < 2 mid
+    assert f(16, 16, 16, 6, 16, 16, 16, 16, 2, 3, 4, 4, 2, 0, None) == 1 and b"wx_ld" in lib.vqa_last_error()   # wx_ld % 4
+    assert f(16, 16, 16, 8192, 16, 16, 16, 16, 2, 3, 4, 8192, 2, 0, None) == 1 and b"LDS" in lib.vqa_last_error()
+    assert f(20, 16, 16, 8, 16, 16, 16, 16, 2, 3, 4, 8, 2, 0, None) == 1 and b"aligned" in lib.vqa_last_error()
+    assert f(16, 16, 16, 8, 16, 16, 16, 16, 2, 0, 4, 8, 2, 0, None) == 0                                        # B = 0: no launch
+
+
+def test_apply_gather_argument_validation_without_gpu():
+    """score, vn, img, probs, out, out_ld, N, B, P, C, G, stream."""
+    from dl_vqa_amd import _lib
+    lib = _lib.load()
+    f = lib.vqa_att_apply_gather_fwd
+    assert f(16, 16, None, 16, 16, 1024, 2, 3, 4, 8, 2, None) == 1 and b"null pointer" in lib.vqa_last_error()
+    assert f(16, 16, 16, 16, 16, 1024, 2, 3, 4, 8, 9, None) == 1 and b"glimpses" in lib.vqa_last_error()
+    assert f(16, 16, 16, 16, 16, 1024, 2, 3, 20000, 8, 2, None) == 1 and b"too large for LDS" in lib.vqa_last_error()
+    assert f(16, 16, 16, 16, 16, 8, 2, 3, 4, 8, 2, None) == 1 and b"out_ld" in lib.vqa_last_error()             # out_ld < G*C
+    assert f(16, 16, 16, 16, 16, 64, 0, 3, 4, 8, 2, None) == 1 and b"out of range" in lib.vqa_last_error()
+    assert f(16, 16, 16, 16, 16, 64, 2, 0, 4, 8, 2, None) == 0
+
+
+def test_group_by_image_is_a_stable_counting_sort():
+    N = 6
+    idx = [4, 0, 2, 4, 4, 0, 5, 2, 0, 4, 1, 1]                  # shuffled, repeats, image 3 has no question
+    order, offsets = group_by_image(idx, N)
+    assert order.dtype == torch.int32 and offsets.dtype == torch.int32 and not order.is_cuda
+    counts = [idx.count(n) for n in range(N)]
+    assert counts[3] == 0
+    assert offsets.tolist() == [0] + [sum(counts[:n + 1]) for n in range(N)]
+    assert sorted(order.tolist()) == list(range(len(idx)))                     # a permutation
+    for n in range(N):
+        grp = order[offsets[n]:offsets[n + 1]].tolist()
+        assert [idx[b] for b in grp] == [n] * counts[n]
+        assert grp == sorted(grp)                                               # original order inside a group
+    # the same from a tensor, any integer dtype
+    o2, f2 = group_by_image(torch.tensor(idx, dtype=torch.int32), N)
+    assert torch.equal(o2, order) and torch.equal(f2, offsets)
+    # no questions at all; a single image holding every question
+    o0, f0 = group_by_image([], 3)
+    assert o0.numel() == 0 and f0.tolist() == [0, 0, 0, 0]
+    o1, f1 = group_by_image([0, 0, 0], 1)
+    assert o1.tolist() == [0, 1, 2] and f1.tolist() == [0, 3]
+
+
+@pytest.mark.parametrize("bad", [-1, 6])
+def test_group_by_image_rejects_out_of_range(bad):
+    with pytest.raises(IndexError, match="out of range"):
+        group_by_image([0, 5, bad, 1], 6)
+
+
+def test_bf16_is_not_implemented_and_is_checked_first():
+    """compute mode, then training, then device: all before any device work, so a CPU-only box sees them."""
+    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
+    v = torch.zeros(1, 3, 32, 32)
+    with pytest.raises(NotImplementedError, match="compute_dtype"):
+        m.encode_images(v)
+    with pytest.raises(NotImplementedError, match="compute_dtype"):
+        m.answer(None, torch.ones(1, 3, dtype=torch.int64), torch.tensor([3]), [0])
+    m.eval()
+    with pytest.raises(NotImplementedError, match="compute_dtype"):
+        m.encode_images(v)
+
+
+def test_training_mode_is_refused_before_the_device_check():
+    g = Golden("tiny_plus")
+    m = VqaNet(tiny_cfg(g.meta), g.meta["V"])
+    m.load_state_dict(g.sd)
+    m.train()
+    with pytest.raises(RuntimeError, match="training mode"):
+        m.encode_images(g.t["v"])
+    with pytest.raises(RuntimeError, match="training mode"):
+        m.answer(None, g.t["q"], g.t["q_len"], [0, 1, 2])
+    m.eval()                                                        # eval mode on the CPU: the device check speaks
+    with pytest.raises(RuntimeError, match="cuda"):
+        m.encode_images(g.t["v"])
+    assert m._last_ctx is None and m._flat_param is None
