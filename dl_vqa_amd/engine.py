@@ -26,6 +26,19 @@ def _site_seed(base: int, site: int) -> int:
     return (base * 0x9E3779B97F4A7C15 + site * 0xD1B54A32D192ED03 + 0x632BE59BD9B4E019) & _MASK64
 
 
+_SFX = ("", "_reverse")     # parameter-name suffix of LSTM direction d
+
+
+def _gemm(A, B, C, M, N, K, x3=False, **kw):
+    """One dense product C[M,N] = op(A) op(B), by the form its operands are in: bf16 A and B take the bf16 MFMA GEMM
+    (fp32 accumulation), fp32 operands the fp32 GEMM (x3: the split GEMM).  Arguments as ops.gemm."""
+    if A.dtype == torch.bfloat16:
+        assert not x3
+        return ops.gemm_bf16(A, B, C, M, N, K, **kw)
+    return ops.gemm(A, B, C, M, N, K, x3=x3, **kw)
+
+
+
 class Engine:
     def __init__(self, cfg: dict, embedding_tokens: int, compute_dtype: str = "fp32"):
         t, i, a, c = cfg["text"], cfg["image"], cfg["attention"], cfg["classifier"]
@@ -87,6 +100,7 @@ class Engine:
             if self.L < 2 or any(ch % 64 for ch in self.channels[1:]) or self.mid % 8 or self.stride != 1:
                 raise ValueError("the bf16 path needs >= 2 conv blocks, stride 1 and channel counts that are multiples "
                                  f"of 64 after the first block (num_channels={self.channels}, stride={self.stride})")
+        self._sides = {}        # the side stream of each device (_on_side_stream)
 
     def _pconv_ok(self, H: int, W: int) -> bool:
         """bf16 path: do the patch convolutions cover every block after the first for an H x W image?"""
@@ -137,7 +151,10 @@ class Engine:
         Hp, Wp = ops.conv_out_hw(H, W, self.stride)
         return (B, Hp, Wp, self.channels[l + 1])
 
-    def _side_streams(self, dev):
+    # ------------------------------------------------------------------ stream fork / join
+    def _on_side_stream(self, dev, job, backward=False):
+        """Run job() on the side stream, after everything enqueued so far.  Returns (what job returned, the event that
+        marks its end); the caller joins with current_stream.wait_event(event)."""
         # VQA_STREAMS: 0 = one stream; 1 = the question branch on a side stream, joined before the image branch;
         # 2 (default) = the question branch runs UNDER the convolutions (forward: joined before the attention stage,
         # backward: joined at the end).  VQA_STREAMS_BWD (default: VQA_STREAMS) picks the BACKWARD schedule on its
@@ -147,42 +164,41 @@ class Engine:
         # LSTM step launches leave bubbles (prologue / cell epilogue / launch seams of a 44 us kernel) that
         # convolution workgroups fill.
         mode = os.environ.get("VQA_STREAMS", "2")
-        if mode == "0":
-            cur = torch.cuda.current_stream(dev)
-            return [cur, cur]
-        if not hasattr(self, "_sides"):
-            self._sides = {}
-        key = str(dev)
-        if key not in self._sides:
-            # (a high-priority side stream measured no difference: 27.03 / 27.05 ms per step, 115.4 / 115.6 at the
-            # stress shape)
-            self._sides[key] = [torch.cuda.Stream(device=dev) for _ in range(2)]
-        return self._sides[key]
-
-    # ------------------------------------------------------------------ stream fork / join
-    def _fork_join(self, dev, jobs):
-        """Run independent launch sequences concurrently: job 0 on the current stream, the others on side
-        streams that first wait for everything enqueued so far; the current stream then waits for them."""
-        if len(jobs) == 1:
-            jobs[0]()
-            return
         main = torch.cuda.current_stream(dev)
-        if not hasattr(self, "_side"):
-            self._side = {}
+        if mode == "0":
+            side = main
+        else:
+            if str(dev) not in self._sides:
+                # (a high-priority side stream measured no difference: 27.03 / 27.05 ms per step, 115.4 / 115.6 at the
+                # stress shape)
+                self._sides[str(dev)] = torch.cuda.Stream(device=dev)
+            side = self._sides[str(dev)]
         fork = torch.cuda.Event()
         fork.record(main)
-        joins = []
-        for k, job in enumerate(jobs[1:]):
-            side = self._side.setdefault((str(dev), k), torch.cuda.Stream(device=dev))
-            side.wait_event(fork)
-            with torch.cuda.stream(side):
-                job()
-                ev = torch.cuda.Event()
-                ev.record(side)
-                joins.append(ev)
-        jobs[0]()
-        for ev in joins:
-            main.wait_event(ev)
+        side.wait_event(fork)
+        with torch.cuda.stream(side):
+            out = job()
+            done = torch.cuda.Event()
+            done.record(side)
+        if (os.environ.get("VQA_STREAMS_BWD", mode) if backward else mode) == "1":
+            main.wait_event(done)
+        return out, done
+
+    def _lstm_schedule(self):
+        """(fused, use_graph): the recurrence as ONE call per pass, every direction per launch (a cached hipGraph of T
+        launches when use_graph), or -- H % 32 != 0, VQA_FUSED_LSTM=0 -- a recurrent GEMM + cell kernel per step."""
+        return (ops.lstm_step_supported(self.H) and os.environ.get("VQA_FUSED_LSTM", "1") == "1",
+                os.environ.get("VQA_GRAPH", "1") == "1")
+
+    @staticmethod
+    def _lstm_steps(T, reverse):
+        """(t, state slot read, state slot written) of every step of one direction, in the forward's order."""
+        return [(t, t + 1, t) for t in range(T - 1, -1, -1)] if reverse else [(t, t, t + 1) for t in range(T)]
+
+    def _fc_operand(self, fc, x: Tensor, ld: int, cols: int) -> Tensor:
+        """The activation x [B, cols] (leading dimension ld) as the FC products take it: as it is, or (bf16 FC) a bf16 copy
+        whose rows are padded to a multiple of 8 with zeros: they become the K dimension of the weight-gradient products."""
+        return x if fc is None else self._rows16(x, ld, fc.B, cols, fc.B8)
 
     # ------------------------------------------------------------------ forward
     def forward(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, training: bool, seed: int,
@@ -202,169 +218,30 @@ class Engine:
             "v must be a float32 (or the dataset's float16) CUDA tensor [B,C,S,S]"
         v = v.contiguous()
         need_dx = bool(keep and need_dx)
-        v_dtype, v_shape = v.dtype, tuple(v.shape)
-        q = q.to(device=v.device, dtype=torch.int64).contiguous()
-        q_len = q_len.to(device=v.device, dtype=torch.int64).contiguous()
         dev = v.device
+        q = q.to(device=dev, dtype=torch.int64).contiguous()
+        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
         B, T = q.shape
-        E, H, G, C, mid, hid, A, Dc, GC, Q = self.E, self.H, self.G, self.C, self.mid, self.hid, self.A, self.Dc, self.GC, self.Q
+        C, mid, Dc, GC = self.C, self.mid, self.Dc, self.GC
         tr = bool(training)
+        p_txt, p_img, p_att, p_cls = (self.p_text, self.p_image, self.p_att, self.p_cls) if tr else (0.0, 0.0, 0.0, 0.0)
         sd = lambda site: _site_seed(seed, site)
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
 
         # ---- question encoder (model.py:155-166)
-        p_txt = self.p_text if tr else 0.0
         x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, sd(SITE_TEXT), bad_tokens)       # [T,B,E]
-        combined = new(B, Dc)
-        lstm = [None] * self.ndir
-        fused = ops.lstm_step_supported(H) and os.environ.get("VQA_FUSED_LSTM", "1") == "1"
-        use_graph = os.environ.get("VQA_GRAPH", "1") == "1"
-
-        def sfx(d):
-            return "_reverse" if d else ""
-
-        # bf16 path: the LSTM's non-recurrent products on bf16 MFMA (fp32 accumulation): xg = x . W_ih^T here, dW_hh, dW_ih
-        # and dx in backward; x and W_ih staged as bf16 with the embedding width padded to a multiple of 8 (16-byte rows).
-        # The recurrence h . W_hh^T, the cells and their gradients stay fp32.  VQA_LSTM16=0: everything fp32.
-        l16 = self.lstm16 and (T * B) % 8 == 0
-        E8 = (E + 7) // 8 * 8
-        x16 = [None]
-
-        def run_question_branch():
-            if l16:
-                x16[0] = self._cols16(x_emb, T * B, E, E8)
-            for d in range(self.ndir):
-                xg = new(T * B, 4 * H)
-                wih16 = None
-                if l16:
-                    wih16 = self._cols16(P["text.lstm.weight_ih_l0" + sfx(d)], 4 * H, E, E8)
-                    ops.gemm_bf16(x16[0], wih16, xg, T * B, 4 * H, E8, bias1=P["text.lstm.bias_ih_l0" + sfx(d)],
-                                  bias2=P["text.lstm.bias_hh_l0" + sfx(d)], tag=10)
-                else:
-                    ops.gemm(x_emb, P["text.lstm.weight_ih_l0" + sfx(d)], xg, T * B, 4 * H, E,
-                             bias1=P["text.lstm.bias_ih_l0" + sfx(d)], bias2=P["text.lstm.bias_hh_l0" + sfx(d)], tag=10)
-                lstm[d] = SimpleNamespace(gates=new(T, B, 4 * H), xg=xg, Hs=new(T + 1, B, H), Cs=new(T + 1, B, H), wih16=wih16)
-                lstm[d].Hs[T if d else 0].zero_()         # h_0 = c_0 = 0: only the initial slot is read before
-                lstm[d].Cs[T if d else 0].zero_()         # it is written
-            if fused:
-                # the whole recurrence, both directions per launch, as ONE call (a cached hipGraph of T launches)
-                dirs = [dict(w_hh=P["text.lstm.weight_hh_l0" + sfx(d)], xg=lstm[d].xg, gates=lstm[d].gates,
-                             Hs=lstm[d].Hs, Cs=lstm[d].Cs, c_final=combined[:, GC + d * H:], reverse=bool(d))
-                        for d in range(self.ndir)]
-                ops.lstm_seq_fwd(dirs, q_len, B, T, H, cf_ld=Dc, use_graph=use_graph)
-                return
-            for d in range(self.ndir):          # H % 32 != 0: recurrent GEMM + cell kernel per step
-                st, w_hh = lstm[d], P["text.lstm.weight_hh_l0" + sfx(d)]
-                hg = new(B, 4 * H)
-                order = range(T) if d == 0 else range(T - 1, -1, -1)
-                for n, t in enumerate(order):
-                    si, so = (t, t + 1) if d == 0 else (t + 1, t)
-                    cf = combined[:, GC + d * H:] if n == T - 1 else None
-                    ops.gemm(st.Hs[si], w_hh, hg, B, 4 * H, H, tag=11)
-                    ops.lstm_cell_fwd(st.xg[t * B:(t + 1) * B], hg, st.Cs[si], st.Hs[si], q_len, t, st.gates[t],
-                                      st.Cs[so], st.Hs[so], cf, Dc)
-
+        combined = torch.empty(B, Dc, dtype=torch.float32, device=dev)
         # The question branch is a chain of small (M = B) launches, independent of the image branch until the
         # attention stage; it runs on a side stream, under the convolutions (VQA_STREAMS=2, the default; 1: the main
         # stream waits for it before the convolutions start; 0: everything on one stream).
-        main = torch.cuda.current_stream(dev)
-        sides = self._side_streams(dev)
-        fork = torch.cuda.Event()
-        fork.record(main)
-        sides[0].wait_event(fork)
-        with torch.cuda.stream(sides[0]):
-            run_question_branch()
-            text_done = torch.cuda.Event()
-            text_done.record(sides[0])
-        if os.environ.get("VQA_STREAMS", "2") == "1":
-            main.wait_event(text_done)
-        # ---- image encoder: conv+relu+pool x L (models/model.py:79-84)
-        # the first block has a dedicated kernel that reads the NCHW image as is (K = 27 is too thin for the
-        # generic implicit GEMM); otherwise the image is converted to NHWC4 once
-        fast0 = self.ks == 3 and ops.conv0_supported(v.shape[1], v.shape[2], v.shape[3], self.channels[1], self.stride)
-        if v.dtype == torch.float16 and not fast0:
-            # the dedicated first-block kernels read the dataset's fp16 features as they are (widened where the LDS patch is
-            # staged); only shapes they do not cover take a widened copy through the generic NHWC path
-            v = ops.half_to_float(v)
-        acts = [v if fast0 else ops.nchw_to_nhwc4(v)]
-        idxs, wds = [], []
-        # bf16 path: blocks 1.. on the patch convolutions (csrc/conv_patch_bf16.hip: LDS-resident input patch, activations
-        # between the blocks channel-blocked "C16") when every block's shape has them; VQA_PCONV=0 keeps the implicit-GEMM
-        # kernels (A/B runs, parity tests of both)
-        use_pc = self.bf16 and fast0 and self._pconv_ok(v.shape[2], v.shape[3])
-        for l in range(self.L):
-            w = P[f"image.conv{l}.weight"]
-            assert w.shape[0] == self.channels[l + 1]
-            # fp32x3: a block whose successor runs on the split kernels writes its output x3-packed (split once per
-            # tensor by the producer's epilogue; forward and wgrad of the successor read that form)
-            if self.ks != 3:
-                wk = ops.convk_pack_weights(w, acts[-1].shape[3])
-                pooled, am = ops.convk_fwd(acts[-1], wk, P[f"image.conv{l}.bias"], self.ks, self.stride, tag=l)
-                acts.append(pooled)
-                idxs.append(am)
-                wds.append(wk)
-                continue
-            nxt_x3 = l + 1 < self.L and self._x3_layer(self._out_shape(acts[-1], l, fast0), self.channels[l + 2])
-            if l == 0 and fast0:
-                pooled, am = ops.conv0_fwd(v, w, P["image.conv0.bias"],
-                                           out_dtype=torch.bfloat16 if self.bf16 else torch.float32, bf16_mfma=self.bf16,
-                                           out_packed=nxt_x3, out_c16=use_pc)
-                acts.append(pooled)
-                idxs.append(am)
-                wds.append(None)
-                continue
-            if self.bf16:
-                if l == 0:
-                    raise ValueError("the bf16 path needs the dedicated first-block kernel (3-channel NCHW image, "
-                                     "W % 4 == 0, 32 or 64 output channels)")
-                # bf16 activations in, bf16 out (fp32 out of the last block: the L2 normalisation consumes it)
-                if use_pc:
-                    wf_img, wd_img = ops.pconv_pack_weights(w, need_wd=keep)
-                    pooled, am = ops.pconv_fwd(acts[-1], wf_img, P[f"image.conv{l}.bias"], w.shape[0],
-                                               out_dtype=torch.float32 if l == self.L - 1 else torch.bfloat16, tag=l)
-                    acts.append(pooled)
-                    idxs.append(am)
-                    wds.append(wd_img)
-                    continue
-                wfT, wdT = ops.conv_pack_weights_bf16(w, acts[-1].shape[3], need_wd=keep)
-                pooled, am = ops.conv_fwd_bf16(acts[-1], wfT, P[f"image.conv{l}.bias"], self.stride,
-                                               out_dtype=torch.float32 if l == self.L - 1 else torch.bfloat16, tag=l)
-                acts.append(pooled)
-                idxs.append(am)
-                wds.append(wdT)
-                continue
-            x_shape = ops.nhwc_shape(acts[-1])
-            x3 = self._x3_layer(x_shape, w.shape[0])
-            # fp32 backward-data of blocks 1.. on the patch kernel (csrc/conv_patch_f32.hip: the pre-pool gradient built in LDS once
-            # per K-slice instead of routed once per tap by the loaders); VQA_PDGRAD=0 keeps the implicit-GEMM kernel
-            # (measured at B = 256, 224 x 224: 64-channel input 3.96 -> 3.69 ms; 128-channel input 3.20 -> 3.32 ms, so blocks whose
-            # input has a multiple of 128 channels stay on the implicit-GEMM kernel unless VQA_PDGRAD=2 forces the patch kernel)
-            pdg_mode = os.environ.get("VQA_PDGRAD", "1")
-            pdg = (keep and l > 0 and not x3 and self.stride == 1 and acts[-1].dim() == 4 and pdg_mode != "0"
-                   and (x_shape[3] % 128 != 0 or pdg_mode == "2")
-                   and ops.pconvf_supported(x_shape[1], x_shape[2], x_shape[3], w.shape[0]))
-            # block 0 packs its backward-data weights only when the input gradient is wanted
-            wf, wd = ops.conv_pack_weights(w, x_shape[3], need_wd=(keep and (l > 0 or need_dx) and not pdg))
-            if pdg:
-                wd = ("pconvf", ops.pconvf_pack_weights(w))
-            if x3:
-                # operands are split once per tensor, not by every workgroup in every K-step: the weights here, the
-                # input activation by its producer (or here, when the producer could not: it replaces the fp32 tensor)
-                wf, wd = ops.x3_split(wf), (ops.x3_split(wd) if wd is not None else None)
-                if acts[-1].dim() == 4:
-                    acts[-1] = ops.x3_pack(acts[-1])
-            pooled, am = ops.conv_fwd(acts[-1], wf, P[f"image.conv{l}.bias"], self.stride, tag=l, x3=x3,
-                                      out_packed=x3 and nxt_x3)
-            acts.append(pooled)
-            idxs.append(am)
-            wds.append(wd)
-        pooled = acts[-1]
+        l16 = self.lstm16 and (T * B) % 8 == 0
+        (lstm, x16), text_done = self._on_side_stream(dev, lambda: self._question_encoder(P, x_emb, q_len, combined, l16))
+
+        # ---- image encoder, image dropout + L2 normalisation over channels (model.py:84,56)
+        img = self._image_encoder(P, v, keep, need_dx)
+        pooled = img.out
         Pn = pooled.shape[1] * pooled.shape[2]
-        # ---- image dropout + L2 normalisation over channels (model.py:84,56)
-        p_img = self.p_image if tr else 0.0
         # attention.drop(v) (model.py:185) is written by the same pass as a second output: the v_conv operand, as
         # bf16 on the bf16 path
-        p_att = self.p_att if tr else 0.0
         v_in = v16 = None
         if self.bf16:
             vn, norm, v16 = ops.l2norm_fwd(pooled, p_img, sd(SITE_IMAGE), drop2=(p_att, sd(SITE_ATT_V), torch.bfloat16))
@@ -373,84 +250,202 @@ class Engine:
         else:
             vn, norm = ops.l2norm_fwd(pooled, p_img, sd(SITE_IMAGE))
             v_in = vn
-        main.wait_event(text_done)
-
-        qf = combined[:, GC:]
+        torch.cuda.current_stream(dev).wait_event(text_done)
 
         # ---- attention (model.py:183-195): v' = v_conv(drop(v)), q' = q_lin(drop(q)), x = relu(v' + q')
         wv16 = ops.to_bf16(P["attention.v_conv.weight"].view(mid, C)) if self.bf16 else None
-        if p_att > 0:
-            q_in = new(B, Q)
-            ops.add2d(qf, Dc, None, 0, q_in, Q, B, Q)
-            ops.dropout(q_in, p_att, sd(SITE_ATT_Q), out=q_in)
-            ld_q = Q
-        else:
-            q_in, ld_q = qf, Dc
-        qp = new(B, mid)
-        fc = None
-        if self.fc16:
-            # bf16 FC: activations and weights rounded to bf16 where the GEMM stages them (rows padded to a multiple of 8 with
-            # zeros: they become the K dimension of the weight-gradient products), fp32 accumulation, fp32 outputs
-            B8 = (B + 7) // 8 * 8
-            fc = SimpleNamespace(B8=B8,
-                                 wq=ops.to_bf16(P["attention.q_lin.weight"]), w1=ops.to_bf16(P["classifier.lin1.weight"]),
-                                 w2=ops.to_bf16(P["classifier.lin2.weight"]))
-            fc.q16 = self._rows16(q_in, ld_q, B, Q, B8)
-            ops.gemm_bf16(fc.q16, fc.wq, qp, B, mid, Q, bias1=P["attention.q_lin.bias"], tag=20)
-        else:
-            ops.gemm(q_in, P["attention.q_lin.weight"], qp, B, mid, Q, lda=ld_q, bias1=P["attention.q_lin.bias"], tag=20)
-        # x = relu(v' + q') | relu(v' * q') | relu(cat[v', q'])  (model.py:188-193); v' itself is only kept for
-        # '*' (its backward needs it), as the aux output of the same GEMM
-        # (bf16 path: x is stored as bf16 -- it is streamed three more times and becomes, overwritten in place by
-        # d loss / d v', the bf16 operand of both v_conv gradient products)
-        xs = torch.empty(B * Pn, mid, dtype=torch.bfloat16 if self.bf16 else torch.float32, device=dev)
-        mode = self.att_mode
-        vprime = new(B * Pn, mid) if (mode == 1 and keep) else None
-        if self.bf16 and vprime is None and os.environ.get("VQA_TALL_GEMM", "1") != "0" and \
-                ops.gemm_tall_bf16_supported(B * Pn, mid, C, Pn, mode != 2):
-            # tall GEMM with K = C only: persistent 256 x 128 tiles (csrc/gemm_tall_bf16.hip)
-            ops.gemm_tall_bf16(v16.view(B * Pn, C), wv16, xs, B * Pn, mid, C, rowgroup=(qp if mode != 2 else None),
-                               rg_div=Pn, rg_op=(1 if mode == 1 else 0), relu=True, tag=21)
-        elif self.bf16:
-            ops.gemm_bf16(v16.view(B * Pn, C), wv16, xs, B * Pn, mid, C, rowgroup=(qp if mode != 2 else None),
-                          rg_div=Pn, rg_op=(1 if mode == 1 else 0), relu=True, aux=vprime, tag=21)
-        else:
-            ops.gemm(v_in, P["attention.v_conv.weight"], xs, B * Pn, mid, C, rowgroup=(qp if mode != 2 else None),
-                     rg_div=Pn, rg_op=(1 if mode == 1 else 0), relu=True, aux=vprime, tag=21, x3=self._x3_gemm(B * Pn))
-        wx = P["attention.x_conv.weight"]
-        score = ops.att_score_fwd(xs, wx.view(G, -1), P["attention.x_conv.bias"], B, Pn, p_att, sd(SITE_ATT_X),
-                                  qcat=(qp if mode == 2 else None))
-        # ---- softmax over positions + weighted sum (model.py:208-221) -> combined[:, :G*C]
-        probs = ops.att_apply_fwd(score, vn, combined, Dc)
+        qp, q_in, ld_q, fc = self._q_lin_fwd(P, combined[:, GC:], p_att, seed)
+        v_op, wv_op = (v16.view(B * Pn, C), wv16) if self.bf16 else (v_in, P["attention.v_conv.weight"])
+        xs, vprime, score, probs = self._attention_fwd(P, v_op, wv_op, vn, qp, combined, B, Pn, p_att, seed, keep)
 
         # ---- classifier (model.py:198-205)
-        p_cls = self.p_cls if tr else 0.0
-        c_in = ops.dropout(combined, p_cls, sd(SITE_CLS1)) if p_cls > 0 else combined
-        h1 = new(B, hid)
-        logits = new(B, A)
-        if fc is not None:
-            fc.c16 = self._rows16(c_in, Dc, B, Dc, fc.B8)
-            ops.gemm_bf16(fc.c16, fc.w1, h1, B, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True, tag=30)
-            h1d = ops.dropout(h1, p_cls, sd(SITE_CLS2)) if p_cls > 0 else h1
-            fc.h16 = self._rows16(h1d, hid, B, hid, fc.B8)
-            ops.gemm_bf16(fc.h16, fc.w2, logits, B, A, hid, bias1=P["classifier.lin2.bias"], tag=31)
-        else:
-            ops.gemm(c_in, P["classifier.lin1.weight"], h1, B, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True, tag=30)
-            h1d = ops.dropout(h1, p_cls, sd(SITE_CLS2)) if p_cls > 0 else h1
-            ops.gemm(h1d, P["classifier.lin2.weight"], logits, B, A, hid, bias1=P["classifier.lin2.bias"], tag=31)
+        logits, c_in, h1, h1d = self._classifier_fwd(P, combined, p_cls, seed, fc)
 
         if not keep:
             return logits, None
-        ctx = SimpleNamespace(B=B, T=T, Pn=Pn, q=q, q_len=q_len, acts=acts, idxs=idxs, wds=wds, vn=vn, norm=norm,
-                              x_emb=x_emb, x16=x16[0], lstm=lstm, v_in=v_in, v16=v16, wv16=wv16, q_in=q_in, ld_q=ld_q, xs=xs, probs=probs,
-                              c_in=c_in, h1=h1, h1d=h1d, fast0=fast0, use_pc=use_pc, fc=fc, vprime=vprime, qp=qp, p_img=p_img, p_txt=p_txt, p_att=p_att, p_cls=p_cls,
+        ctx = SimpleNamespace(B=B, T=T, Pn=Pn, q=q, q_len=q_len, acts=img.acts, idxs=img.idxs, wds=img.wds, vn=vn, norm=norm,
+                              x_emb=x_emb, x16=x16, lstm=lstm, v_in=v_in, v16=v16, wv16=wv16, q_in=q_in, ld_q=ld_q, xs=xs, probs=probs,
+                              c_in=c_in, h1=h1, h1d=h1d, fast0=img.fast0, use_pc=img.use_pc, fc=fc, vprime=vprime, qp=qp, p_img=p_img, p_txt=p_txt, p_att=p_att, p_cls=p_cls,
                               seed=seed, stages=dict(pooled=pooled, score=score, combined=combined),
-                              need_dx=need_dx, v_dtype=v_dtype, v_shape=v_shape)
+                              need_dx=need_dx, v_dtype=v.dtype, v_shape=tuple(v.shape))
         return logits, ctx
 
+    def _question_encoder(self, P, x_emb, q_len, combined, l16):
+        """LSTM over the embedded question x_emb [T,B,E] on the current stream; the final cell states land in combined[:, GC:].
+        Returns (per-direction state: the dicts ops.lstm_seq_fwd takes, plus wih16; x16).
+        l16 (bf16 path): the LSTM's non-recurrent products on bf16 MFMA (fp32 accumulation): xg = x . W_ih^T here, dW_hh, dW_ih
+        and dx in backward; x and W_ih staged as bf16 (x16, wih16) with the embedding width padded to a multiple of 8
+        (16-byte rows).  The recurrence h . W_hh^T, the cells and their gradients stay fp32.  VQA_LSTM16=0: everything fp32."""
+        T, B, E = x_emb.shape
+        H, Dc, GC = self.H, self.Dc, self.GC
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x_emb.device)
+        Ek = (E + 7) // 8 * 8 if l16 else E
+        x16 = self._cols16(x_emb, T * B, E, Ek) if l16 else None
+        lstm = []
+        for d in range(self.ndir):
+            xg = new(T * B, 4 * H)
+            w_ih = P["text.lstm.weight_ih_l0" + _SFX[d]]
+            wih16 = self._cols16(w_ih, 4 * H, E, Ek) if l16 else None
+            _gemm(x16 if l16 else x_emb, wih16 if l16 else w_ih, xg, T * B, 4 * H, Ek,
+                  bias1=P["text.lstm.bias_ih_l0" + _SFX[d]], bias2=P["text.lstm.bias_hh_l0" + _SFX[d]], tag=10)
+            st = dict(w_hh=P["text.lstm.weight_hh_l0" + _SFX[d]], xg=xg, gates=new(T, B, 4 * H), Hs=new(T + 1, B, H),
+                      Cs=new(T + 1, B, H), c_final=combined[:, GC + d * H:], reverse=bool(d), wih16=wih16)
+            st["Hs"][T if d else 0].zero_()         # h_0 = c_0 = 0: only the initial slot is read before
+            st["Cs"][T if d else 0].zero_()         # it is written
+            lstm.append(st)
+        fused, use_graph = self._lstm_schedule()
+        if fused:
+            ops.lstm_seq_fwd(lstm, q_len, B, T, H, cf_ld=Dc, use_graph=use_graph)
+            return lstm, x16
+        for st in lstm:
+            hg = new(B, 4 * H)
+            for n, (t, si, so) in enumerate(self._lstm_steps(T, st["reverse"])):
+                ops.gemm(st["Hs"][si], st["w_hh"], hg, B, 4 * H, H, tag=11)
+                ops.lstm_cell_fwd(st["xg"][t * B:(t + 1) * B], hg, st["Cs"][si], st["Hs"][si], q_len, t, st["gates"][t],
+                                  st["Cs"][so], st["Hs"][so], st["c_final"] if n == T - 1 else None, Dc)
+        return lstm, x16
+
+    def _image_encoder(self, P, v, keep, need_dx=False):
+        """conv + relu + pool x L (models/model.py:79-84) over the image v [B,C,S,S].  Returns a namespace: out (the last
+        pooled activation), fast0, use_pc and -- when `keep` -- what backward reads: acts (every block's input, then out),
+        idxs (arg-max bytes) and wds (backward-data weights) per block.  Nothing kept: an activation is dropped as soon
+        as the next block has consumed it."""
+        # the first block has a dedicated kernel that reads the NCHW image as is (K = 27 is too thin for the
+        # generic implicit GEMM); otherwise the image is converted to NHWC4 once
+        fast0 = self.ks == 3 and ops.conv0_supported(v.shape[1], v.shape[2], v.shape[3], self.channels[1], self.stride)
+        if v.dtype == torch.float16 and not fast0:
+            # the dedicated first-block kernels read the dataset's fp16 features as they are (widened where the LDS patch is
+            # staged); only shapes they do not cover take a widened copy through the generic NHWC path
+            v = ops.half_to_float(v)
+        x = v if fast0 else ops.nchw_to_nhwc4(v)
+        if self.bf16 and not fast0:
+            raise ValueError("the bf16 path needs the dedicated first-block kernel (3-channel NCHW image, "
+                             "W % 4 == 0, 32 or 64 output channels)")
+        # bf16 path: blocks 1.. on the patch convolutions (csrc/conv_patch_bf16.hip: LDS-resident input patch, activations
+        # between the blocks channel-blocked "C16") when every block's shape has them; VQA_PCONV=0 keeps the implicit-GEMM
+        # kernels (A/B runs, parity tests of both)
+        use_pc = self.bf16 and fast0 and self._pconv_ok(v.shape[2], v.shape[3])
+        # fp32 backward-data of blocks 1.. on the patch kernel (csrc/conv_patch_f32.hip: the pre-pool gradient built in LDS once
+        # per K-slice instead of routed once per tap by the loaders); VQA_PDGRAD=0 keeps the implicit-GEMM kernel
+        # (measured at B = 256, 224 x 224: 64-channel input 3.96 -> 3.69 ms; 128-channel input 3.20 -> 3.32 ms, so blocks whose
+        # input has a multiple of 128 channels stay on the implicit-GEMM kernel unless VQA_PDGRAD=2 forces the patch kernel)
+        pdg_mode = os.environ.get("VQA_PDGRAD", "1")
+        acts, idxs, wds = [], [], []
+        for l in range(self.L):
+            w, bias = P[f"image.conv{l}.weight"], P[f"image.conv{l}.bias"]
+            Co = w.shape[0]
+            assert Co == self.channels[l + 1]
+            # fp32x3: a block whose successor runs on the split kernels writes its output x3-packed (split once per
+            # tensor by the producer's epilogue; forward and wgrad of the successor read that form)
+            nxt_x3 = self.x3 and l + 1 < self.L and self._x3_layer(self._out_shape(x, l, fast0), self.channels[l + 2])
+            wd = None
+            if self.ks != 3:
+                wd = ops.convk_pack_weights(w, x.shape[3])
+                y, am = ops.convk_fwd(x, wd, bias, self.ks, self.stride, tag=l)
+            elif l == 0 and fast0:
+                y, am = ops.conv0_fwd(x, w, bias, out_dtype=torch.bfloat16 if self.bf16 else torch.float32,
+                                      bf16_mfma=self.bf16, out_packed=nxt_x3, out_c16=use_pc)
+            elif self.bf16:
+                # bf16 activations in, bf16 out (fp32 out of the last block: the L2 normalisation consumes it)
+                out_dtype = torch.float32 if l == self.L - 1 else torch.bfloat16
+                if use_pc:
+                    wf, wd = ops.pconv_pack_weights(w, need_wd=keep)
+                    y, am = ops.pconv_fwd(x, wf, bias, Co, out_dtype=out_dtype, tag=l)
+                else:
+                    wf, wd = ops.conv_pack_weights_bf16(w, x.shape[3], need_wd=keep)
+                    y, am = ops.conv_fwd_bf16(x, wf, bias, self.stride, out_dtype=out_dtype, tag=l)
+            else:
+                x_shape = ops.nhwc_shape(x)
+                x3 = self._x3_layer(x_shape, Co)
+                pdg = (keep and l > 0 and not x3 and self.stride == 1 and x.dim() == 4 and pdg_mode != "0"
+                       and (x_shape[3] % 128 != 0 or pdg_mode == "2")
+                       and ops.pconvf_supported(x_shape[1], x_shape[2], x_shape[3], Co))
+                # block 0 packs its backward-data weights only when the input gradient is wanted
+                wf, wd = ops.conv_pack_weights(w, x_shape[3], need_wd=(keep and (l > 0 or need_dx) and not pdg))
+                if pdg:
+                    wd = ("pconvf", ops.pconvf_pack_weights(w))
+                if x3:
+                    # operands are split once per tensor, not by every workgroup in every K-step: the weights here, the
+                    # input activation by its producer (or here, when the producer could not: it replaces the fp32 tensor)
+                    wf, wd = ops.x3_split(wf), (ops.x3_split(wd) if wd is not None else None)
+                    if x.dim() == 4:
+                        x = ops.x3_pack(x)
+                y, am = ops.conv_fwd(x, wf, bias, self.stride, tag=l, x3=x3, out_packed=x3 and nxt_x3)
+            if keep:
+                acts.append(x)
+                idxs.append(am)
+                wds.append(wd)
+            x = y
+            del y, am, wd       # nothing kept: only the block's output is alive while the next block runs
+        if keep:
+            acts.append(x)
+        return SimpleNamespace(out=x, acts=acts, idxs=idxs, wds=wds, fast0=fast0, use_pc=use_pc)
+
+    def _q_lin_fwd(self, P, qf, p_att, seed):
+        """q' = q_lin(drop(qf)) for the question features qf [B,Q] (leading dimension Dc).  Returns (q' [B,mid], the
+        product's input q_in with its leading dimension, fc).  fc: None, or on the bf16 FC path the bf16 weights of q_lin /
+        lin1 / lin2 and the bf16 activations that backward reads again: activations and weights are rounded to bf16 where
+        the GEMM stages them, fp32 accumulation, fp32 outputs."""
+        B, Q, mid, Dc = qf.shape[0], self.Q, self.mid, self.Dc
+        if p_att > 0:
+            q_in, ld_q = torch.empty(B, Q, dtype=torch.float32, device=qf.device), Q
+            ops.add2d(qf, Dc, None, 0, q_in, Q, B, Q)
+            ops.dropout(q_in, p_att, _site_seed(seed, SITE_ATT_Q), out=q_in)
+        else:
+            q_in, ld_q = qf, Dc
+        qp = torch.empty(B, mid, dtype=torch.float32, device=qf.device)
+        fc = None
+        if self.fc16:
+            fc = SimpleNamespace(B=B, B8=(B + 7) // 8 * 8,
+                                 wq=ops.to_bf16(P["attention.q_lin.weight"]), w1=ops.to_bf16(P["classifier.lin1.weight"]),
+                                 w2=ops.to_bf16(P["classifier.lin2.weight"]))
+            fc.q16 = self._fc_operand(fc, q_in, ld_q, Q)
+        a, wq, lda = (fc.q16, fc.wq, Q) if fc is not None else (q_in, P["attention.q_lin.weight"], ld_q)
+        _gemm(a, wq, qp, B, mid, Q, lda=lda, bias1=P["attention.q_lin.bias"], tag=20)
+        return qp, q_in, ld_q, fc
+
+    def _attention_fwd(self, P, v_op, wv_op, vn, qp, combined, B, Pn, p_att, seed, keep):
+        """x = relu(v' + q') | relu(v' * q') | relu(cat[v', q']) (model.py:188-193) with v' = v_op . wv_op^T (both fp32 or
+        both bf16), the scores, and softmax over positions + weighted sum of vn (model.py:208-221) -> combined[:, :G*C].
+        Returns (x, v' or None, score, probs)."""
+        C, mid, G, Dc, mode = self.C, self.mid, self.G, self.Dc, self.att_mode
+        # v' itself is only kept for '*' (its backward needs it), as the aux output of the same GEMM
+        # (bf16 path: x is stored as bf16 -- it is streamed three more times and becomes, overwritten in place by
+        # d loss / d v', the bf16 operand of both v_conv gradient products)
+        xs = torch.empty(B * Pn, mid, dtype=torch.bfloat16 if self.bf16 else torch.float32, device=vn.device)
+        vprime = torch.empty(B * Pn, mid, dtype=torch.float32, device=vn.device) if (mode == 1 and keep) else None
+        epi = dict(rowgroup=(qp if mode != 2 else None), rg_div=Pn, rg_op=(1 if mode == 1 else 0), relu=True, tag=21)
+        if self.bf16 and vprime is None and os.environ.get("VQA_TALL_GEMM", "1") != "0" and \
+                ops.gemm_tall_bf16_supported(B * Pn, mid, C, Pn, mode != 2):
+            # tall GEMM with K = C only: persistent 256 x 128 tiles (csrc/gemm_tall_bf16.hip)
+            ops.gemm_tall_bf16(v_op, wv_op, xs, B * Pn, mid, C, **epi)
+        else:
+            _gemm(v_op, wv_op, xs, B * Pn, mid, C, aux=vprime, x3=self._x3_gemm(B * Pn), **epi)
+        score = ops.att_score_fwd(xs, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"], B, Pn, p_att,
+                                  _site_seed(seed, SITE_ATT_X), qcat=(qp if mode == 2 else None))
+        probs = ops.att_apply_fwd(score, vn, combined, Dc)
+        return xs, vprime, score, probs
+
+    def _classifier_fwd(self, P, combined, p_cls, seed, fc):
+        """logits = lin2(drop(relu(lin1(drop(combined))))) (model.py:198-205).  Returns (logits, c_in, h1, h1d); on the
+        bf16 FC path the bf16 operands stay in fc.c16 / fc.h16 for backward."""
+        B, Dc, hid, A = combined.shape[0], self.Dc, self.hid, self.A
+        w1, w2 = (fc.w1, fc.w2) if fc is not None else (P["classifier.lin1.weight"], P["classifier.lin2.weight"])
+        c_in = ops.dropout(combined, p_cls, _site_seed(seed, SITE_CLS1)) if p_cls > 0 else combined
+        h1 = torch.empty(B, hid, dtype=torch.float32, device=combined.device)
+        logits = torch.empty(B, A, dtype=torch.float32, device=combined.device)
+        c_op = self._fc_operand(fc, c_in, Dc, Dc)
+        _gemm(c_op, w1, h1, B, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True, tag=30)
+        h1d = ops.dropout(h1, p_cls, _site_seed(seed, SITE_CLS2)) if p_cls > 0 else h1
+        h_op = self._fc_operand(fc, h1d, hid, hid)
+        _gemm(h_op, w2, logits, B, A, hid, bias1=P["classifier.lin2.bias"], tag=31)
+        if fc is not None:
+            fc.c16, fc.h16 = c_op, h_op
+        return logits, c_in, h1, h1d
+
     # ------------------------------------------------------------------ many questions per image (inference)
-    # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder and the question branch repeat the launches
-    # of _forward (which stays exactly as it is); the attention stage runs on ONE v' per image (csrc/att_grouped.hip).
+    # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder, the question encoder, q_lin and the
+    # classifier are the forward's own stages; the attention stage runs on ONE v' per image (csrc/att_grouped.hip).
     def encode_images(self, P: Dict[str, Tensor], v: Tensor):
         """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid], (gh, gw))."""
         assert not self.bf16, "encode_images: fp32 / fp32x3 only"
@@ -460,28 +455,7 @@ class Engine:
     def _encode_images(self, P, v):
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
-        v = v.contiguous()
-        fast0 = self.ks == 3 and ops.conv0_supported(v.shape[1], v.shape[2], v.shape[3], self.channels[1], self.stride)
-        if v.dtype == torch.float16 and not fast0:
-            v = ops.half_to_float(v)
-        x = v if fast0 else ops.nchw_to_nhwc4(v)
-        for l in range(self.L):
-            w, bias = P[f"image.conv{l}.weight"], P[f"image.conv{l}.bias"]
-            if self.ks != 3:
-                x, _ = ops.convk_fwd(x, ops.convk_pack_weights(w, x.shape[3]), bias, self.ks, self.stride, tag=l)
-                continue
-            nxt_x3 = l + 1 < self.L and self._x3_layer(self._out_shape(x, l, fast0), self.channels[l + 2])
-            if l == 0 and fast0:
-                x, _ = ops.conv0_fwd(v, w, bias, out_packed=nxt_x3)
-                continue
-            x_shape = ops.nhwc_shape(x)
-            x3 = self._x3_layer(x_shape, w.shape[0])
-            wf, _ = ops.conv_pack_weights(w, x_shape[3], need_wd=False)
-            if x3:
-                wf = ops.x3_split(wf)
-                if x.dim() == 4:
-                    x = ops.x3_pack(x)
-            x, _ = ops.conv_fwd(x, wf, bias, self.stride, tag=l, x3=x3, out_packed=x3 and nxt_x3)
+        x = self._image_encoder(P, v.contiguous(), keep=False).out
         N, gh, gw, C = x.shape
         Pn = gh * gw
         vn, _ = ops.l2norm_fwd(x, 0.0, 0)
@@ -501,50 +475,19 @@ class Engine:
         dev = feats.vn.device
         q = q.to(device=dev, dtype=torch.int64).contiguous()
         q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
-        B, T = q.shape
-        N, Pn, C = feats.vn.shape
-        E, H, G, mid, hid, A, Dc, GC, Q = self.E, self.H, self.G, self.mid, self.hid, self.A, self.Dc, self.GC, self.Q
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-
-        # ---- question encoder: the launches of _forward's question branch, eval mode, on the current stream (there are
-        # no convolutions to hide it under)
+        B = q.shape[0]
+        N, Pn, _ = feats.vn.shape
+        # ---- question encoder and q_lin, eval mode, on the current stream (there are no convolutions to hide them under)
         x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], 0.0, 0, bad_tokens)                     # [T,B,E]
-        combined = new(B, Dc)
-        sfx = lambda d: "_reverse" if d else ""
-        dirs = []
-        for d in range(self.ndir):
-            xg = new(T * B, 4 * H)
-            ops.gemm(x_emb, P["text.lstm.weight_ih_l0" + sfx(d)], xg, T * B, 4 * H, E,
-                     bias1=P["text.lstm.bias_ih_l0" + sfx(d)], bias2=P["text.lstm.bias_hh_l0" + sfx(d)], tag=10)
-            st = dict(w_hh=P["text.lstm.weight_hh_l0" + sfx(d)], xg=xg, gates=new(T, B, 4 * H), Hs=new(T + 1, B, H),
-                      Cs=new(T + 1, B, H), c_final=combined[:, GC + d * H:], reverse=bool(d))
-            st["Hs"][T if d else 0].zero_()
-            st["Cs"][T if d else 0].zero_()
-            dirs.append(st)
-        if ops.lstm_step_supported(H) and os.environ.get("VQA_FUSED_LSTM", "1") == "1":
-            ops.lstm_seq_fwd(dirs, q_len, B, T, H, cf_ld=Dc, use_graph=os.environ.get("VQA_GRAPH", "1") == "1")
-        else:
-            for d, st in enumerate(dirs):
-                hg = new(B, 4 * H)
-                steps = range(T) if d == 0 else range(T - 1, -1, -1)
-                for k, t in enumerate(steps):
-                    si, so = (t, t + 1) if d == 0 else (t + 1, t)
-                    ops.gemm(st["Hs"][si], st["w_hh"], hg, B, 4 * H, H, tag=11)
-                    ops.lstm_cell_fwd(st["xg"][t * B:(t + 1) * B], hg, st["Cs"][si], st["Hs"][si], q_len, t, st["gates"][t],
-                                      st["Cs"][so], st["Hs"][so], st["c_final"] if k == T - 1 else None, Dc)
-        qp = new(B, mid)
-        ops.gemm(combined[:, GC:], P["attention.q_lin.weight"], qp, B, mid, Q, lda=Dc, bias1=P["attention.q_lin.bias"], tag=20)
-
+        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=dev)
+        self._question_encoder(P, x_emb, q_len, combined, l16=False)
+        qp = self._q_lin_fwd(P, combined[:, self.GC:], 0.0, 0)[0]
         # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
-        score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"],
-                                          order, offsets, N, B, Pn, self.att_mode)
-        probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, Dc)
-
+        score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
+                                          P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode)
+        probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, self.Dc)
         # ---- classifier
-        h1 = new(B, hid)
-        logits = new(B, A)
-        ops.gemm(combined, P["classifier.lin1.weight"], h1, B, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True, tag=30)
-        ops.gemm(h1, P["classifier.lin2.weight"], logits, B, A, hid, bias1=P["classifier.lin2.bias"], tag=31)
+        logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
         return logits, probs, score
 
     # ------------------------------------------------------------------ backward
@@ -560,57 +503,71 @@ class Engine:
             return self._backward(P, ctx, dlogits, Gr, on_ready)
 
     def _backward(self, P, ctx, dlogits, Gr, on_ready):
-        B, T, Pn = ctx.B, ctx.T, ctx.Pn
-        E, H, G, C, mid, hid, A, Dc, GC, Q = self.E, self.H, self.G, self.C, self.mid, self.hid, self.A, self.Dc, self.GC, self.Q
+        dev = dlogits.device
+        ready = on_ready if on_ready is not None else (lambda group: None)
+        dcomb = self._classifier_bwd(P, ctx, dlogits, Gr)
+        ready("classifier")
+        dv_in = self._attention_bwd(P, ctx, dcomb, Gr)
+        ready("attention")
+
+        # The question branch's backward runs on a side stream: BPTT, the weight gradients of every direction, the
+        # embedding gradient, and from there the 'text' bucket goes to the data-parallel hook, so its all-reduce
+        # overlaps the convolution backward.  Default schedule (VQA_STREAMS=2): the branch runs under the convolution
+        # backward and is joined at the end; VQA_STREAMS=1: the main stream waits for it before the convolutions.
+        def question_branch():
+            self._question_bwd(P, ctx, dcomb, Gr)
+            ready("text")
+
+        _, text_done = self._on_side_stream(dev, question_branch, backward=True)
+        dv = self._image_bwd(P, ctx, dcomb, dv_in, Gr)
+        ready("image")
+        torch.cuda.current_stream(dev).wait_event(text_done)
+        return dv
+
+    def _classifier_bwd(self, P, ctx, dlogits, Gr):
+        """Gradients of lin2 / lin1; returns d loss / d combined [B, Dc]."""
+        B, Dc, hid, A = ctx.B, self.Dc, self.hid, self.A
         dev = dlogits.device
         sd = lambda site: _site_seed(ctx.seed, site)
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        ready = on_ready if on_ready is not None else (lambda group: None)
-
         # dlogits as a GEMM operand needs a leading dimension that is a multiple of 4
         ldA = (A + 3) // 4 * 4
         if ldA != A or not dlogits.is_contiguous() or dlogits.data_ptr() % 16:
             dl = torch.zeros(B, ldA, dtype=torch.float32, device=dev)
             ops.add2d(dlogits, dlogits.stride(0), None, 0, dl, ldA, B, A)
             dlogits = dl
-
-        # ---- classifier
+        # bf16 FC: output gradients staged as bf16 (zero rows up to B8: the K of the dW products), compact rows
         fc = ctx.fc
-        dh1 = new(B, hid)
-        dcomb = new(B, Dc)
-        if fc is not None:      # bf16 FC: output gradients staged as bf16 (zero rows up to B8: the K of the dW products)
-            dl16 = self._rows16(dlogits, ldA, B, A, fc.B8)
-            ops.gemm_bf16(dl16, fc.h16, Gr["classifier.lin2.weight"], A, hid, fc.B8, transA=True, transB=False, lda=A,
-                          ldb=hid, tag=40)
-            ops.colsum(dlogits, B, A, Gr["classifier.lin2.bias"], ld=ldA)
-            ops.gemm_bf16(dl16, fc.w2, dh1, B, hid, A, transB=False, lda=A, ldb=hid, tag=41)
-            ops.relu_drop_bwd(ctx.h1, dh1, dh1, ctx.p_cls, sd(SITE_CLS2))
-            dh16 = self._rows16(dh1, hid, B, hid, fc.B8)
-            ops.gemm_bf16(dh16, fc.c16, Gr["classifier.lin1.weight"], hid, Dc, fc.B8, transA=True, transB=False, lda=hid,
-                          ldb=Dc, tag=42)
-            ops.colsum(dh1, B, hid, Gr["classifier.lin1.bias"])
-            ops.gemm_bf16(dh16, fc.w1, dcomb, B, Dc, hid, transB=False, lda=hid, ldb=Dc, tag=43)
+        if fc is not None:
+            Bk, ld_dl, h_op, c_op, w2, w1 = fc.B8, A, fc.h16, fc.c16, fc.w2, fc.w1
         else:
-            ops.gemm(dlogits, ctx.h1d, Gr["classifier.lin2.weight"], A, hid, B, transA=True, transB=False, lda=ldA,
-                     ldb=hid, tag=40)
-            ops.colsum(dlogits, B, A, Gr["classifier.lin2.bias"], ld=ldA)
-            ops.gemm(dlogits, P["classifier.lin2.weight"], dh1, B, hid, A, transB=False, lda=ldA, ldb=hid, tag=41)
-            ops.relu_drop_bwd(ctx.h1, dh1, dh1, ctx.p_cls, sd(SITE_CLS2))
-            ops.gemm(dh1, ctx.c_in, Gr["classifier.lin1.weight"], hid, Dc, B, transA=True, transB=False, lda=hid, ldb=Dc,
-                     tag=42)
-            ops.colsum(dh1, B, hid, Gr["classifier.lin1.bias"])
-            ops.gemm(dh1, P["classifier.lin1.weight"], dcomb, B, Dc, hid, transB=False, lda=hid, ldb=Dc, tag=43)
+            Bk, ld_dl, h_op, c_op, w2, w1 = B, ldA, ctx.h1d, ctx.c_in, P["classifier.lin2.weight"], P["classifier.lin1.weight"]
+        dh1 = torch.empty(B, hid, dtype=torch.float32, device=dev)
+        dcomb = torch.empty(B, Dc, dtype=torch.float32, device=dev)
+        dl_op = self._fc_operand(fc, dlogits, ldA, A)
+        _gemm(dl_op, h_op, Gr["classifier.lin2.weight"], A, hid, Bk, transA=True, transB=False, lda=ld_dl, ldb=hid, tag=40)
+        ops.colsum(dlogits, B, A, Gr["classifier.lin2.bias"], ld=ldA)
+        _gemm(dl_op, w2, dh1, B, hid, A, transB=False, lda=ld_dl, ldb=hid, tag=41)
+        ops.relu_drop_bwd(ctx.h1, dh1, dh1, ctx.p_cls, sd(SITE_CLS2))
+        dh_op = self._fc_operand(fc, dh1, hid, hid)
+        _gemm(dh_op, c_op, Gr["classifier.lin1.weight"], hid, Dc, Bk, transA=True, transB=False, lda=hid, ldb=Dc, tag=42)
+        ops.colsum(dh1, B, hid, Gr["classifier.lin1.bias"])
+        _gemm(dh_op, w1, dcomb, B, Dc, hid, transB=False, lda=hid, ldb=Dc, tag=43)
         if ctx.p_cls > 0:
             ops.dropout(dcomb, ctx.p_cls, sd(SITE_CLS1), out=dcomb)
-        ready("classifier")
+        return dcomb
 
+    def _attention_bwd(self, P, ctx, dcomb, Gr):
+        """Gradients of x_conv, v_conv and q_lin; adds d loss / d (question features) into dcomb[:, GC:].  Returns
+        dv_in = d loss / d (v_conv's input) [B*Pn, C]."""
+        B, Pn = ctx.B, ctx.Pn
+        G, C, mid, Dc, GC, Q = self.G, self.C, self.mid, self.Dc, self.GC, self.Q
+        sd = lambda site: _site_seed(ctx.seed, site)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dcomb.device)
         # ---- attention apply + scores
         ds_rows = new(B, G, 1)
         # d loss / d vn has two branches -- the weighted sum (probs x dcomb) and attention.drop(v) -> v_conv -- and one reader,
-        # the L2-norm backward: it joins them itself (VQA_JOIN_DVN=0: the three-kernel form att_apply_bwd -> dropout_add ->
-        # l2norm_bwd through a [B*P][C] fp32 tensor)
-        join = os.environ.get("VQA_JOIN_DVN", "1") != "0"
-        dscore, dvn = ops.att_apply_bwd(dcomb, Dc, ctx.probs, ctx.vn, rowsum=ds_rows, want_dvn=not join)
+        # the L2-norm backward: it joins them itself (_image_bwd), so the weighted-sum branch is not written here
+        dscore, _ = ops.att_apply_bwd(dcomb, Dc, ctx.probs, ctx.vn, rowsum=ds_rows, want_dvn=False)
         ops.sum_bgp(ds_rows, Gr["attention.x_conv.bias"])       # x_conv bias gradient: sum over samples of the row sums
         wx = P["attention.x_conv.weight"].view(G, -1)
         dwx_part, dq_part, RS = ops.att_score_bwd(dscore, wx, ctx.xs, B, Pn, ctx.p_att, sd(SITE_ATT_X),
@@ -619,164 +576,106 @@ class Engine:
         ops.colsum(dwx_part, B * RS, wx.numel(), Gr["attention.x_conv.weight"])
         dqp = new(B, mid)
         ops.sum_parts(dq_part, dqp, B, RS, mid)
-        wv = P["attention.v_conv.weight"]
-        if self.bf16:
-            # both v_conv gradient products on bf16 MFMA: dW = dx'^T . v_in (both operands reduction-major),
-            # dv_in = dx' . Wv (Wv [mid][C] as the [K][N] operand); dx' already is bf16 (written in place over x)
-            dx16 = dxpre
-            ops.gemm_bf16(dx16, ctx.v16.view(B * Pn, C), Gr["attention.v_conv.weight"].view(mid, C), mid, C, B * Pn,
-                          transA=True, transB=False, lda=mid, ldb=C, tag=44)
-            if join:
-                dv_in = new(B * Pn, C)
-                ops.gemm_bf16(dx16, ctx.wv16, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45)
-            elif ctx.p_att > 0:     # dvn += dropout-mask * (dx' . Wv): one pass joins the two branches
-                dv_in = new(B * Pn, C)
-                ops.gemm_bf16(dx16, ctx.wv16, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45)
-                ops.dropout_add(dv_in, dvn, ctx.p_att, sd(SITE_ATT_V))
-            else:
-                ops.gemm_bf16(dx16, ctx.wv16, dvn.view(B * Pn, C), B * Pn, C, mid, transB=False, lda=mid, ldb=C,
-                              accumulate=True, tag=45)
-        else:
-            gx3 = self._x3_gemm(B * Pn)
-            ops.gemm(dxpre, ctx.v_in, Gr["attention.v_conv.weight"], mid, C, B * Pn, transA=True, transB=False, lda=mid,
-                     ldb=C, tag=44, x3=gx3)
-            if join:
-                dv_in = new(B * Pn, C)
-                ops.gemm(dxpre, wv, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
-            elif ctx.p_att > 0:     # dvn += dropout-mask * (dx' . Wv): one pass joins the two branches
-                dv_in = new(B * Pn, C)
-                ops.gemm(dxpre, wv, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
-                ops.dropout_add(dv_in, dvn, ctx.p_att, sd(SITE_ATT_V))
-            else:
-                ops.gemm(dxpre, wv, dvn, B * Pn, C, mid, transB=False, lda=mid, ldb=C, accumulate=True, tag=45, x3=gx3)
+        # ---- v_conv: dW = dx'^T . v_in (both operands reduction-major), dv_in = dx' . Wv (Wv [mid][C] as the [K][N] operand);
+        # bf16 path: both on bf16 MFMA, dx' already is bf16 (written in place over x)
+        v_op, wv_op = (ctx.v16.view(B * Pn, C), ctx.wv16) if self.bf16 else (ctx.v_in, P["attention.v_conv.weight"])
+        gx3 = self._x3_gemm(B * Pn)
+        _gemm(dxpre, v_op, Gr["attention.v_conv.weight"], mid, C, B * Pn, transA=True, transB=False, lda=mid, ldb=C, tag=44,
+              x3=gx3)
+        dv_in = new(B * Pn, C)
+        _gemm(dxpre, wv_op, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
+        # ---- q_lin
         ops.colsum(dqp, B, mid, Gr["attention.q_lin.bias"])
-        wq = P["attention.q_lin.weight"]
+        fc = ctx.fc
         if fc is not None:
-            dqp16 = self._rows16(dqp, mid, B, mid, fc.B8)
-            ops.gemm_bf16(dqp16, fc.q16, Gr["attention.q_lin.weight"], mid, Q, fc.B8, transA=True, transB=False, lda=mid,
-                          ldb=Q, tag=46)
-            dq_in = new(B, Q)
-            ops.gemm_bf16(dqp16, fc.wq, dq_in, B, Q, mid, transB=False, lda=mid, ldb=Q, tag=47)
+            Bk, q_op, ld_qop, wq = fc.B8, fc.q16, Q, fc.wq
+        else:
+            Bk, q_op, ld_qop, wq = B, ctx.q_in, ctx.ld_q, P["attention.q_lin.weight"]
+        dqp_op = self._fc_operand(fc, dqp, mid, mid)
+        _gemm(dqp_op, q_op, Gr["attention.q_lin.weight"], mid, Q, Bk, transA=True, transB=False, lda=mid, ldb=ld_qop, tag=46)
+        # fp32 FC without attention dropout: the GEMM accumulates straight into dcomb's question columns; otherwise the
+        # product goes through dq_in, where the dropout mask is applied, and is added from there
+        direct = fc is None and ctx.p_att == 0
+        dq_in, ld_dq = (dcomb[:, GC:], Dc) if direct else (new(B, Q), Q)
+        _gemm(dqp_op, wq, dq_in, B, Q, mid, transB=False, lda=mid, ldb=Q, ldc=ld_dq, accumulate=direct, tag=47)
+        if not direct:
             if ctx.p_att > 0:
                 ops.dropout(dq_in, ctx.p_att, sd(SITE_ATT_Q), out=dq_in)
             ops.add2d(dcomb[:, GC:], Dc, dq_in, Q, dcomb[:, GC:], Dc, B, Q)
+        return dv_in
+
+    def _question_bwd(self, P, ctx, dcomb, Gr):
+        """BPTT over the masked steps, the LSTM weight gradients of every direction and the embedding gradient, on the
+        current stream."""
+        B, T = ctx.B, ctx.T
+        E, H, Dc, GC = self.E, self.H, self.Dc, self.GC
+        dev = dcomb.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        # ---- the recurrence: dgates [T][B][4H] of every direction
+        dirs = []
+        for d, st in enumerate(ctx.lstm):
+            dc = new(B, H)
+            ops.add2d(dcomb[:, GC + d * H:], Dc, None, 0, dc, H, B, H)
+            dh = torch.zeros(B, H, dtype=torch.float32, device=dev)
+            st["dgates"] = new(T, B, 4 * H)                   # kept alive until the streams have joined
+            dirs.append(dict(w_hh=P["text.lstm.weight_hh_l0" + _SFX[d]], gates=st["gates"], Hs=st["Hs"], Cs=st["Cs"],
+                             dgates=st["dgates"], dh=dh, dc=dc, reverse=bool(d)))
+        fused, use_graph = self._lstm_schedule()
+        if fused:
+            # one call: the first cell backward + T-1 fused (dgates . W_hh -> next cell backward) launches,
+            # every direction per launch, replayed as a cached hipGraph
+            ops.lstm_seq_bwd(dirs, ctx.q_len, B, T, H, use_graph=use_graph)
         else:
-            ops.gemm(dqp, ctx.q_in, Gr["attention.q_lin.weight"], mid, Q, B, transA=True, transB=False, lda=mid,
-                     ldb=ctx.ld_q, tag=46)
-            if ctx.p_att > 0:
-                dq_in = new(B, Q)
-                ops.gemm(dqp, wq, dq_in, B, Q, mid, transB=False, lda=mid, ldb=Q, tag=47)
-                ops.dropout(dq_in, ctx.p_att, sd(SITE_ATT_Q), out=dq_in)
-                ops.add2d(dcomb[:, GC:], Dc, dq_in, Q, dcomb[:, GC:], Dc, B, Q)
-            else:
-                ops.gemm(dqp, wq, dcomb[:, GC:], B, Q, mid, transB=False, lda=mid, ldb=Q, ldc=Dc, accumulate=True, tag=47)
-        ready("attention")
-
-        # ---- LSTM (BPTT over the masked steps), embedding
-        dx_parts = [new(T * B, E) for _ in range(self.ndir)]
-        fused = ops.lstm_step_supported(H) and os.environ.get("VQA_FUSED_LSTM", "1") == "1"
-        use_graph = os.environ.get("VQA_GRAPH", "1") == "1"
-
-        def sfx(d):
-            return "_reverse" if d else ""
-
-        def bptt_recurrence():
-            """dgates [T][B][4H] of every direction."""
-            dcs, dhs = [], []
-            for d in range(self.ndir):
-                dc = new(B, H)
-                ops.add2d(dcomb[:, GC + d * H:], Dc, None, 0, dc, H, B, H)
-                dcs.append(dc)
-                dhs.append(torch.zeros(B, H, dtype=torch.float32, device=dev))
-                ctx.lstm[d].dgates = new(T, B, 4 * H)          # kept alive until the streams have joined
-            if fused:
-                # one call: the first cell backward + T-1 fused (dgates . W_hh -> next cell backward) launches,
-                # every direction per launch, replayed as a cached hipGraph
-                dirs = [dict(w_hh=P["text.lstm.weight_hh_l0" + sfx(d)], gates=ctx.lstm[d].gates, Hs=ctx.lstm[d].Hs,
-                             Cs=ctx.lstm[d].Cs, dgates=ctx.lstm[d].dgates, dh=dhs[d], dc=dcs[d], reverse=bool(d))
-                        for d in range(self.ndir)]
-                ops.lstm_seq_bwd(dirs, ctx.q_len, B, T, H, use_graph=use_graph)
-                return
-            for d in range(self.ndir):
-                st, w_hh = ctx.lstm[d], P["text.lstm.weight_hh_l0" + sfx(d)]
-                order = range(T - 1, -1, -1) if d == 0 else range(T)
-                for n, t in enumerate(order):
-                    si, so = (t, t + 1) if d == 0 else (t + 1, t)
-                    ops.lstm_cell_bwd(st.gates[t], st.Cs[si], st.Cs[so], ctx.q_len, t, dhs[d], dcs[d], st.dgates[t])
+            for st in dirs:
+                for n, (t, si, so) in enumerate(reversed(self._lstm_steps(T, st["reverse"]))):
+                    ops.lstm_cell_bwd(st["gates"][t], st["Cs"][si], st["Cs"][so], ctx.q_len, t, st["dh"], st["dc"],
+                                      st["dgates"][t])
                     if n != T - 1:
-                        ops.gemm(st.dgates[t], w_hh, dhs[d], B, H, 4 * H, transB=False, lda=4 * H, ldb=H,
+                        ops.gemm(st["dgates"][t], st["w_hh"], st["dh"], B, H, 4 * H, transB=False, lda=4 * H, ldb=H,
                                  accumulate=True, tag=50)
-
-        def weight_grads(d):
-            st = ctx.lstm[d]
-            dgates = st.dgates
-            h_in = st.Hs[0:T] if d == 0 else st.Hs[1:T + 1]
-            l16 = ctx.x16 is not None                # the forward's decision (bf16 path, T * B a multiple of 8)
+        # ---- weight gradients and dx per direction.  The forward's decision (ctx.x16: bf16 path, T * B a multiple of 8):
+        # one bf16 copy of dgates feeds the three products; dW_ih and dx come out Ek wide (the padded embedding width) and
+        # their first E columns are copied to where the fp32 products write them
+        l16 = ctx.x16 is not None
+        x_op, Ek = (ctx.x16, ctx.x16.shape[1]) if l16 else (ctx.x_emb, E)
+        dx_parts = []
+        for d, st in enumerate(ctx.lstm):
+            dgates = st["dgates"]
+            h_in = st["Hs"][0:T] if d == 0 else st["Hs"][1:T + 1]
+            dw_hh, dw_ih, dx = Gr["text.lstm.weight_hh_l0" + _SFX[d]], Gr["text.lstm.weight_ih_l0" + _SFX[d]], new(T * B, E)
             if l16:
-                # one bf16 copy of dgates feeds the three products; dW_ih and dx come out E8 wide (the padded embedding
-                # width) and their first E columns are copied to where the fp32 products would have written them
-                E8 = ctx.x16.shape[1]
-                dg16 = ops.to_bf16(dgates.view(T * B, 4 * H))
-                h16 = ops.to_bf16(h_in.reshape(T * B, H))
-                ops.gemm_bf16(dg16, h16, Gr["text.lstm.weight_hh_l0" + sfx(d)], 4 * H, H, T * B, transA=True, transB=False,
-                              lda=4 * H, ldb=H, tag=51)
-                dwp = Gr["text.lstm.weight_ih_l0" + sfx(d)] if E8 == E else new(4 * H, E8)
-                ops.gemm_bf16(dg16, ctx.x16, dwp, 4 * H, E8, T * B, transA=True, transB=False, lda=4 * H, ldb=E8, tag=52)
-                if E8 != E:
-                    ops.add2d(dwp, E8, None, 0, Gr["text.lstm.weight_ih_l0" + sfx(d)], E, 4 * H, E)
+                dg_op, h_op, wih_op = ops.to_bf16(dgates.view(T * B, 4 * H)), ops.to_bf16(h_in.reshape(T * B, H)), st["wih16"]
             else:
-                ops.gemm(dgates, h_in, Gr["text.lstm.weight_hh_l0" + sfx(d)], 4 * H, H, T * B, transA=True, transB=False,
-                         lda=4 * H, ldb=H, tag=51)
-                ops.gemm(dgates, ctx.x_emb, Gr["text.lstm.weight_ih_l0" + sfx(d)], 4 * H, E, T * B, transA=True,
-                         transB=False, lda=4 * H, ldb=E, tag=52)
-            ops.colsum(dgates, T * B, 4 * H, Gr["text.lstm.bias_ih_l0" + sfx(d)])
-            ops.add2d(Gr["text.lstm.bias_ih_l0" + sfx(d)], 4 * H, None, 0, Gr["text.lstm.bias_hh_l0" + sfx(d)], 4 * H, 1, 4 * H)
-            if l16:
-                dxp = dx_parts[d] if E8 == E else new(T * B, E8)
-                ops.gemm_bf16(dg16, st.wih16, dxp, T * B, E8, 4 * H, transB=False, lda=4 * H, ldb=E8, tag=53)
-                if E8 != E:
-                    ops.add2d(dxp, E8, None, 0, dx_parts[d], E, T * B, E)
-            else:
-                ops.gemm(dgates, P["text.lstm.weight_ih_l0" + sfx(d)], dx_parts[d], T * B, E, 4 * H, transB=False,
-                         lda=4 * H, ldb=E, tag=53)
+                dg_op, h_op, wih_op = dgates, h_in, P["text.lstm.weight_ih_l0" + _SFX[d]]
+            _gemm(dg_op, h_op, dw_hh, 4 * H, H, T * B, transA=True, transB=False, lda=4 * H, ldb=H, tag=51)
+            dwp = dw_ih if Ek == E else new(4 * H, Ek)
+            _gemm(dg_op, x_op, dwp, 4 * H, Ek, T * B, transA=True, transB=False, lda=4 * H, ldb=Ek, tag=52)
+            if Ek != E:
+                ops.add2d(dwp, Ek, None, 0, dw_ih, E, 4 * H, E)
+            ops.colsum(dgates, T * B, 4 * H, Gr["text.lstm.bias_ih_l0" + _SFX[d]])
+            ops.add2d(Gr["text.lstm.bias_ih_l0" + _SFX[d]], 4 * H, None, 0, Gr["text.lstm.bias_hh_l0" + _SFX[d]], 4 * H, 1, 4 * H)
+            dxp = dx if Ek == E else new(T * B, Ek)
+            _gemm(dg_op, wih_op, dxp, T * B, Ek, 4 * H, transB=False, lda=4 * H, ldb=Ek, tag=53)
+            if Ek != E:
+                ops.add2d(dxp, Ek, None, 0, dx, E, T * B, E)
+            dx_parts.append(dx)
+        # ---- embedding
+        dx_emb = dx_parts[0]
+        if self.ndir > 1:
+            ops.add(dx_parts[0], dx_parts[1], dx_emb)
+        # every row of the embedding gradient is written (deterministic per-row sums)
+        ops.embed_tanh_bwd(ctx.q, ctx.x_emb, dx_emb, Gr["text.embedding.weight"], ctx.p_txt, _site_seed(ctx.seed, SITE_TEXT))
 
-        # The question branch's backward runs on a side stream: BPTT, the weight gradients of every direction, the
-        # embedding gradient, and from there the 'text' bucket goes to the data-parallel hook, so its all-reduce
-        # overlaps the convolution backward.  Default schedule (VQA_STREAMS=2): the branch runs under the convolution
-        # backward and is joined at the end; VQA_STREAMS=1: the main stream waits for it before the convolutions.
-        main = torch.cuda.current_stream(dev)
-        sides = self._side_streams(dev)
-        fork = torch.cuda.Event()
-        fork.record(main)
-        sides[0].wait_event(fork)
-        with torch.cuda.stream(sides[0]):
-            bptt_recurrence()
-            for d in range(self.ndir):
-                weight_grads(d)
-            dx_emb = dx_parts[0]
-            if self.ndir > 1:
-                ops.add(dx_parts[0], dx_parts[1], dx_emb)
-            demb = Gr["text.embedding.weight"]       # every row is written (deterministic per-row sums)
-            ops.embed_tanh_bwd(ctx.q, ctx.x_emb, dx_emb, demb, ctx.p_txt, sd(SITE_TEXT))
-            ready("text")
-            ev0 = torch.cuda.Event()
-            ev0.record(sides[0])
-        if os.environ.get("VQA_STREAMS_BWD", os.environ.get("VQA_STREAMS", "2")) == "1":
-            main.wait_event(ev0)
-
-        # ---- image: L2-norm (+dropout) backward, then conv blocks from the last to the first
+    def _image_bwd(self, P, ctx, dcomb, dv_in, Gr):
+        """L2-norm (+ dropout) backward, then the conv blocks from the last to the first.  Returns the image gradient
+        (ctx.need_dx) or None."""
+        sd = lambda site: _site_seed(ctx.seed, site)
         dv = None
         c16_hw = tuple(ctx.idxs[-1].shape[2:4]) if self.bf16 and ctx.use_pc else None   # channel-blocked for the routed patches
-        if join:
-            dP = ops.l2norm_bwd_joined(dcomb, Dc, ctx.probs, dv_in, ctx.p_att, sd(SITE_ATT_V), ctx.vn, ctx.norm, ctx.p_img,
-                                       sd(SITE_IMAGE), out_dtype=torch.bfloat16 if self.bf16 else torch.float32, c16_hw=c16_hw)
-            if c16_hw is None:
-                dP = dP.view_as(ctx.acts[-1])
-        elif c16_hw is not None:
-            dP = ops.l2norm_bwd(dvn, ctx.vn, ctx.norm, ctx.p_img, sd(SITE_IMAGE), c16_hw=c16_hw)
-        else:
-            dP = ops.l2norm_bwd(dvn, ctx.vn, ctx.norm, ctx.p_img, sd(SITE_IMAGE),
-                                out_dtype=torch.bfloat16 if self.bf16 else torch.float32).view_as(ctx.acts[-1])
+        dP = ops.l2norm_bwd_joined(dcomb, self.Dc, ctx.probs, dv_in, ctx.p_att, sd(SITE_ATT_V), ctx.vn, ctx.norm, ctx.p_img,
+                                   sd(SITE_IMAGE), out_dtype=torch.bfloat16 if self.bf16 else torch.float32, c16_hw=c16_hw)
+        if c16_hw is None:
+            dP = dP.view_as(ctx.acts[-1])
         for l in range(self.L - 1, -1, -1):
             if self.ks != 3:
                 dP = ops.convk_bwd(ctx.acts[l], dP, ctx.idxs[l], ctx.wds[l], Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"],
@@ -819,6 +718,4 @@ class Engine:
         if ctx.need_dx and dv is None:
             # generic first block (NHWC4 input): drop the pad channel, back to the caller's NCHW layout and dtype
             dv = ops.nhwc_to_nchw(dP, ctx.v_shape[1], out_dtype=ctx.v_dtype)
-        ready("image")
-        main.wait_event(ev0)
         return dv

@@ -33,7 +33,6 @@ class questionNet(nn.Module):
         self.embedding = nn.Embedding(num_embeddings=embedding_tokens, embedding_dim=embedding_features, padding_idx=0)
         self.drop = nn.Dropout(drop)
         self.tanh = nn.Tanh()
-        import warnings
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")   # torch warns that dropout is a no-op with one layer (as in the reference)
             self.lstm = nn.LSTM(input_size=embedding_features, hidden_size=lstm_features, num_layers=num_lstm_layers,
