@@ -442,9 +442,12 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::THREADS / 256) void conv_wgrad_x
   store_acc_tiles<Cfg>(acc, slab + (int64_t)tc.split * pa.KI * Co, Co, pa.KI, Co, m0, n0, wm, wn, lane);
 }
 
-template <class Cfg, class AL, bool OP>
+// XP / DP: the activation / pooled-gradient operand is x3-packed (the *x loaders) or fp32 (the conv.hip loaders, split in
+// the kernel); OP: the pooled output is written packed
+template <class Cfg, bool XP, bool OP>
 static int launch_fwd_x3(const void* x, const void* wf, const float* bias, void* pooled, uint8_t* amax,
                          const ConvGeom& g, hipStream_t s) {
+  using AL = std::conditional_t<XP, ConvFwdAx<Cfg::NVA, Cfg::LT>, ConvFwdA<Cfg::NVA, Cfg::LT, true>>;
   using SL = SmemLayoutX<Cfg, true, false>;
   const int nWin = g.B * g.Hp * g.Wp, K = 9 * g.CiP;
   typename AL::Params pa{static_cast<decltype(AL::Params::x)>(x), g.H, g.W, g.CiP, g.Hp, g.Wp, g.stride, nWin, K};
@@ -453,57 +456,44 @@ static int launch_fwd_x3(const void* x, const void* wf, const float* bias, void*
   // one workgroup per CU: nothing else covers a tile's prologue and epilogue, so the tiles are walked persistently
   // (VQA_PERSISTENT=0 selects one workgroup per tile)
   const int tiles = tiles_m * tiles_n;
-  if (knobs().persistent != 0 && tiles > 256) {
-    auto pk = conv_fwd_x3_persistent_kernel<Cfg, AL, OP>;
-    { int rc = set_smem(pk, SL::BYTES, "attr(conv_fwd_x3_p)"); if (rc) return rc; }
-    hipLaunchKernelGGL(pk, dim3(256), dim3(Cfg::THREADS), SL::BYTES, s, pa, pb, bias, pooled, amax, g.Co, tiles_m, tiles_n,
-                       K / BK);
-    return check_hip(hipGetLastError(), "conv_fwd_x3_persistent launch");
-  }
-  auto kern = conv_fwd_x3_kernel<Cfg, AL, OP>;
-  { int rc = set_smem(kern, SL::BYTES, "attr(conv_fwd_x3)"); if (rc) return rc; }
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(Cfg::THREADS), SL::BYTES, s, pa, pb, bias, pooled, amax, g.Co,
-                     tiles_m, tiles_n, K / BK);
-  return check_hip(hipGetLastError(), "conv_fwd_x3 launch");
+  return launch_tiles(knobs().persistent != 0 && tiles > 256, conv_fwd_x3_persistent_kernel<Cfg, AL, OP>,
+                      {"attr(conv_fwd_x3_p)", "conv_fwd_x3_persistent launch"}, 256, conv_fwd_x3_kernel<Cfg, AL, OP>,
+                      {"attr(conv_fwd_x3)", "conv_fwd_x3 launch"}, tiles, Cfg::THREADS, SL::BYTES, s, pa, pb, bias, pooled,
+                      amax, g.Co, tiles_m, tiles_n, K / BK);
 }
 
-template <class Cfg, class AL>
+template <class Cfg, bool DP>
 static int launch_dgrad_x3(const void* dp, const uint8_t* am, const void* wd, float* dx, const ConvGeom& g,
                            hipStream_t s) {
+  using AL = std::conditional_t<DP, ConvDgradAx<Cfg::NVA, Cfg::LT>, ConvDgradA<Cfg::NVA, Cfg::LT, true>>;
   using SL = SmemLayoutX<Cfg, true, false>;
   const int rows = g.B * g.H * g.W, K = 9 * g.Co;
   typename AL::Params pa{static_cast<decltype(AL::Params::dp)>(dp), am, g.H, g.W, g.Hp, g.Wp, g.Co, g.stride, rows, K};
   typename PlainCx<Cfg::NVB, Cfg::LT>::Params pb{wd, g.CiP, g.CiP, K, (int64_t)K * g.CiP};
   const int tiles_m = (rows + Cfg::BM - 1) / Cfg::BM, tiles_n = (g.CiP + Cfg::BN - 1) / Cfg::BN;
   const int tiles = tiles_m * tiles_n;
-  if (knobs().persistent != 0 && tiles > 256) {      // see launch_fwd_x3
-    auto pk = conv_dgrad_x3_persistent_kernel<Cfg, AL>;
-    { int rc = set_smem(pk, SL::BYTES, "attr(conv_dgrad_x3_p)"); if (rc) return rc; }
-    hipLaunchKernelGGL(pk, dim3(256), dim3(Cfg::THREADS), SL::BYTES, s, pa, pb, dx, g.CiP, tiles_m, tiles_n, K / BK);
-    return check_hip(hipGetLastError(), "conv_dgrad_x3_persistent launch");
-  }
-  auto kern = conv_dgrad_x3_kernel<Cfg, AL>;
-  { int rc = set_smem(kern, SL::BYTES, "attr(conv_dgrad_x3)"); if (rc) return rc; }
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(Cfg::THREADS), SL::BYTES, s, pa, pb, dx, g.CiP, tiles_m,
-                     tiles_n, K / BK);
-  return check_hip(hipGetLastError(), "conv_dgrad_x3 launch");
+  return launch_tiles(knobs().persistent != 0 && tiles > 256 /* see launch_fwd_x3 */,
+                      conv_dgrad_x3_persistent_kernel<Cfg, AL>, {"attr(conv_dgrad_x3_p)", "conv_dgrad_x3_persistent launch"},
+                      256, conv_dgrad_x3_kernel<Cfg, AL>, {"attr(conv_dgrad_x3)", "conv_dgrad_x3 launch"}, tiles,
+                      Cfg::THREADS, SL::BYTES, s, pa, pb, dx, g.CiP, tiles_m, tiles_n, K / BK);
 }
 
-struct WgradPlanX { int tiles_m, tiles_n, nk, splits, ks_per_split, Mtot, KI; };
-static WgradPlanX plan_wgrad_x3(const ConvGeom& g) {
-  WgradPlanX p;
-  p.KI = 9 * g.CiP;
-  p.Mtot = g.B * 2 * g.Hp * 2 * g.Wp;
-  p.tiles_m = (p.KI + CfgX::BM - 1) / CfgX::BM;
-  p.tiles_n = (g.Co + CfgX::BN - 1) / CfgX::BN;
-  p.nk = (p.Mtot + BK - 1) / BK;
-  int splits = 256 / (p.tiles_m * p.tiles_n);       // one workgroup per CU: at most 256 resident
-  if (splits < 1) splits = 1;
-  const int max_splits = p.nk / 8 > 1 ? p.nk / 8 : 1;
-  if (splits > max_splits) splits = max_splits;
-  p.ks_per_split = (p.nk + splits - 1) / splits;
-  p.splits = (p.nk + p.ks_per_split - 1) / p.ks_per_split;
-  return p;
+static WgradPlan plan_wgrad_x3(const ConvGeom& g) {
+  return plan_splits(g, CfgXw::BM, CfgXw::BN, BK, 256);       // one workgroup per CU: at most 256 resident
+}
+
+template <bool XP, bool DP>
+static int launch_wgrad_x3(const void* x, const void* dp, const uint8_t* am, float* slab, const ConvGeom& g,
+                           const WgradPlan& p, hipStream_t s) {
+  using AL = std::conditional_t<XP, WgradAx<CfgXw::NVA, CfgXw::LT>, WgradA<CfgXw::NVA, CfgXw::LT, true>>;
+  using BL = std::conditional_t<DP, WgradBx<CfgXw::NVB, CfgXw::LT>, WgradB<CfgXw::NVB, CfgXw::LT, true>>;
+  using SL = SmemLayoutX<CfgXw, false, false>;
+  WgradGeom wg{g.H, g.W, g.CiP, g.Hp, g.Wp, g.Co, g.stride, p.Mtot};
+  typename AL::Params pa{static_cast<decltype(AL::Params::x)>(x), wg, p.KI};
+  typename BL::Params pb{static_cast<decltype(BL::Params::dp)>(dp), am, wg};
+  return launch_kernel(conv_wgrad_x3_kernel<CfgXw, AL, BL>, {"attr(conv_wgrad_x3)", "conv_wgrad_x3 launch"},
+                       p.tiles_m * p.tiles_n * p.splits, CfgXw::THREADS, SL::BYTES, s, pa, pb, slab, p.tiles_m, p.tiles_n,
+                       p.nk, p.ks_per_split);
 }
 
 // bias gradient = sum over the windows that are not dead (arg-max != 4) of the fp32 pooled gradient; deterministic.  A
@@ -578,8 +568,7 @@ static int launch_bias_grad(const float* dp, const uint8_t* am, float* dbias, vo
                        (uint2*)nullptr);
   int rc = check_hip(hipGetLastError(), "conv_bias_grad launch");
   if (rc) return rc;
-  hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((Co + 31) / 32), dim3(256), 0, s, parts, dbias, nparts, Co);
-  return check_hip(hipGetLastError(), "wgrad_bias_reduce launch");
+  return reduce_bias_rows(parts, dbias, nparts, Co, s);
 }
 
 static bool x3_conv_ok(int CiP, int Co, int Wp) { return CiP % BK == 0 && Co % BK == 0 && 2 * Wp >= BK; }
@@ -630,76 +619,42 @@ int vqa_conv3x3_relu_pool_fwd_x3(const void* x, int x_packed, const void* wf, co
                                  int tag, vqa_stream_t stream) {
   VQA_REQUIRE(x && wf && bias && pooled && argmax && B > 0, "vqa_conv3x3_relu_pool_fwd_x3: null pointer");
   VQA_REQUIRE(CiP % BK == 0, "vqa_conv3x3_relu_pool_fwd_x3: CiP=%d must be a multiple of %d", CiP, BK);
-  const int chunk = x3_chunk(B, H, W, CiP, Co, stride);
-  using AF = ConvFwdA<CfgX::NVA, CfgX::LT, true>;
-  using AFn = ConvFwdA<CfgXn::NVA, CfgXn::LT, true>;
-  using AP = ConvFwdAx<CfgX::NVA, CfgX::LT>;
-  using APn = ConvFwdAx<CfgXn::NVA, CfgXn::LT>;
-  const char* xb = static_cast<const char*>(x);
-  const int esz = x_packed ? 6 : 4;
-  VQA_REQUIRE(chunk > 0, "vqa_conv3x3_relu_pool_fwd_x3: one %dx%dx%d image reaches 4 GiB", H, W, CiP);
-  const ConvGeom g1 = make_geom(1, H, W, CiP, Co, stride);
-  set_launch_tag(tag);
-  ProfScope prof(VQA_K_CONV_FWD, (hipStream_t)stream);
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = B - b0 < chunk ? B - b0 : chunk;
-    const int64_t xo = (int64_t)b0 * H * W * CiP, po = (int64_t)b0 * g1.Hp * g1.Wp * Co;
-    const ConvGeom g = make_geom(nb, H, W, CiP, Co, stride);
-    int rc = check_geom("vqa_conv3x3_relu_pool_fwd_x3", g);
-    if (rc) return rc;
-    const void* xc = xb + xo * esz;
-    void* pc = static_cast<char*>(pooled) + po * (pooled_packed ? 6 : 4);
-    hipStream_t st = (hipStream_t)stream;
-#define X3_FWD(CFG, AL, OP) launch_fwd_x3<CFG, AL, OP>(xc, wf, bias, pc, argmax + po, g, st)
-    if (pooled_packed)
-      rc = x_packed ? (Co > 64 ? X3_FWD(CfgX, AP, true) : X3_FWD(CfgXn, APn, true))
-                    : (Co > 64 ? X3_FWD(CfgX, AF, true) : X3_FWD(CfgXn, AFn, true));
-    else
-      rc = x_packed ? (Co > 64 ? X3_FWD(CfgX, AP, false) : X3_FWD(CfgXn, APn, false))
-                    : (Co > 64 ? X3_FWD(CfgX, AF, false) : X3_FWD(CfgXn, AFn, false));
-#undef X3_FWD
-    if (rc) return rc;
-  }
-  return VQA_OK;
+  const ConvWalk w{"vqa_conv3x3_relu_pool_fwd_x3", B, H, W, CiP, Co, stride, x3_chunk(B, H, W, CiP, Co, stride)};
+  hipStream_t s = (hipStream_t)stream;
+  return for_each_chunk(w, VQA_K_CONV_FWD, tag, s, [&](const ConvChunk& c) {
+    return with_flags(x_packed, pooled_packed, [&](auto xp, auto op) {
+      auto go = [&](auto cfg) {
+        return launch_fwd_x3<decltype(cfg), decltype(xp)::value, decltype(op)::value>(
+            static_cast<const char*>(x) + c.xo * (x_packed ? 6 : 4), wf, bias,
+            static_cast<char*>(pooled) + c.po * (pooled_packed ? 6 : 4), argmax + c.po, c.g, s);
+      };
+      return Co > 64 ? go(CfgX{}) : go(CfgXn{});
+    });
+  });
 }
 
 int vqa_conv3x3_dgrad_x3(const void* dpooled, int dp_packed, const uint8_t* argmax, const void* wd, float* dx, int B,
                          int H, int W, int CiP, int Co, int stride, int tag, vqa_stream_t stream) {
   VQA_REQUIRE(dpooled && argmax && wd && dx && B > 0, "vqa_conv3x3_dgrad_x3: null pointer");
   VQA_REQUIRE(Co % BK == 0, "vqa_conv3x3_dgrad_x3: Co=%d must be a multiple of %d", Co, BK);
-  const int chunk = x3_chunk(B, H, W, CiP, Co, stride);
-  VQA_REQUIRE(chunk > 0, "vqa_conv3x3_dgrad_x3: one %dx%dx%d image reaches 4 GiB", H, W, CiP);
-  const ConvGeom g1 = make_geom(1, H, W, CiP, Co, stride);
-  set_launch_tag(tag);
-  ProfScope prof(VQA_K_CONV_DGRAD, (hipStream_t)stream);
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = B - b0 < chunk ? B - b0 : chunk;
-    const int64_t xo = (int64_t)b0 * H * W * CiP, po = (int64_t)b0 * g1.Hp * g1.Wp * Co;
-    const ConvGeom g = make_geom(nb, H, W, CiP, Co, stride);
-    int rc = check_geom("vqa_conv3x3_dgrad_x3", g);
-    if (rc) return rc;
-    const void* dpc = static_cast<const char*>(dpooled) + po * (dp_packed ? 6 : 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (dp_packed)
-      rc = CiP > 64 ? launch_dgrad_x3<CfgXd, ConvDgradAx<CfgXd::NVA, CfgXd::LT>>(dpc, argmax + po, wd, dx + xo, g, st)
-                    : launch_dgrad_x3<CfgXnd, ConvDgradAx<CfgXnd::NVA, CfgXnd::LT>>(dpc, argmax + po, wd, dx + xo, g, st);
-    else
-      rc = CiP > 64 ? launch_dgrad_x3<CfgXd, ConvDgradA<CfgXd::NVA, CfgXd::LT, true>>(dpc, argmax + po, wd, dx + xo, g, st)
-                    : launch_dgrad_x3<CfgXnd, ConvDgradA<CfgXnd::NVA, CfgXnd::LT, true>>(dpc, argmax + po, wd, dx + xo, g, st);
-    if (rc) return rc;
-  }
-  return VQA_OK;
+  const ConvWalk w{"vqa_conv3x3_dgrad_x3", B, H, W, CiP, Co, stride, x3_chunk(B, H, W, CiP, Co, stride)};
+  hipStream_t s = (hipStream_t)stream;
+  return for_each_chunk(w, VQA_K_CONV_DGRAD, tag, s, [&](const ConvChunk& c) {
+    return with_flag(dp_packed, [&](auto dpk) {
+      auto go = [&](auto cfg) {
+        return launch_dgrad_x3<decltype(cfg), decltype(dpk)::value>(
+            static_cast<const char*>(dpooled) + c.po * (dp_packed ? 6 : 4), argmax + c.po, wd, dx + c.xo, c.g, s);
+      };
+      return CiP > 64 ? go(CfgXd{}) : go(CfgXnd{});
+    });
+  });
 }
 
 int64_t vqa_conv3x3_wgrad_x3_workspace_bytes(int B, int H, int W, int CiP, int Co, int stride) {
-  const ConvGeom g1 = make_geom(1, H, W, CiP, Co, stride);
-  if (g1.Hp <= 0 || g1.Wp <= 0 || B <= 0 || CiP % BK) return 0;
-  const int chunk = x3_chunk(B, H, W, CiP, Co, stride);
-  if (chunk <= 0) return 0;
-  int64_t parts = 0;
-  for (int b0 = 0; b0 < B; b0 += chunk)
-    parts += plan_wgrad_x3(make_geom(B - b0 < chunk ? B - b0 : chunk, H, W, CiP, Co, stride)).splits;
-  return parts * (int64_t)9 * CiP * Co * 4 + (int64_t)kBiasParts * Co * 4;
+  if (no_windows(B, H, W, stride) || CiP % BK) return 0;
+  const ConvWalk w{"vqa_conv3x3_wgrad_x3", B, H, W, CiP, Co, stride, x3_chunk(B, H, W, CiP, Co, stride)};
+  if (w.chunk <= 0) return 0;
+  return slab_bytes(w, count_slabs(w, plan_wgrad_x3)) + (int64_t)kBiasParts * Co * 4;
 }
 
 int vqa_conv3x3_wgrad_x3(const void* x, int x_packed, const float* dpooled, const void* dpooled_packed,
@@ -710,68 +665,24 @@ int vqa_conv3x3_wgrad_x3(const void* x, int x_packed, const float* dpooled, cons
   const ConvGeom g1 = make_geom(1, H, W, CiP, Co, stride);
   VQA_REQUIRE(g1.Hp > 0 && g1.Wp > 0 && x3_conv_ok(CiP, Co, g1.Wp),
               "vqa_conv3x3_wgrad_x3: needs CiP, Co multiples of %d and 2*Wp >= %d (CiP=%d Co=%d Wp=%d)", BK, BK, CiP, Co, g1.Wp);
-  const int chunk = x3_chunk(B, H, W, CiP, Co, stride);
-  VQA_REQUIRE(chunk > 0, "vqa_conv3x3_wgrad_x3: one %dx%dx%d image reaches 4 GiB", H, W, CiP);
-  const int64_t need = vqa_conv3x3_wgrad_x3_workspace_bytes(B, H, W, CiP, Co, stride);
-  if (workspace_bytes < need) {
-    set_error("vqa_conv3x3_wgrad_x3: workspace %lld < %lld", (long long)workspace_bytes, (long long)need);
-    return VQA_ERR_WORKSPACE;
-  }
-  const int KI = 9 * CiP;
-  int parts = 0;
-  for (int b0 = 0; b0 < B; b0 += chunk)
-    parts += plan_wgrad_x3(make_geom(B - b0 < chunk ? B - b0 : chunk, H, W, CiP, Co, stride)).splits;
-  float* const bias_parts = workspace + (int64_t)parts * KI * Co;
+  const ConvWalk w{"vqa_conv3x3_wgrad_x3", B, H, W, CiP, Co, stride, x3_chunk(B, H, W, CiP, Co, stride)};
   hipStream_t s = (hipStream_t)stream;
-  set_launch_tag(tag);
-  ProfScope prof(VQA_K_CONV_WGRAD, s);
-  int done = 0, rc;
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int nb = B - b0 < chunk ? B - b0 : chunk;
-    const ConvGeom g = make_geom(nb, H, W, CiP, Co, stride);
-    rc = check_geom("vqa_conv3x3_wgrad_x3", g);
-    if (rc) return rc;
-    const WgradPlanX p = plan_wgrad_x3(g);
-    using SL = SmemLayoutX<CfgXw, false, false>;
-    WgradGeom wg{g.H, g.W, g.CiP, g.Hp, g.Wp, g.Co, g.stride, p.Mtot};
-    const int64_t po = (int64_t)b0 * g1.Hp * g1.Wp * Co;
-    const char* xc = static_cast<const char*>(x) + (int64_t)b0 * H * W * CiP * (x_packed ? 6 : 4);
-    const dim3 grid(p.tiles_m * p.tiles_n * p.splits);
-    float* slab = workspace + (int64_t)done * KI * Co;
-    using AF = WgradA<CfgXw::NVA, CfgXw::LT, true>;
-    using AP = WgradAx<CfgXw::NVA, CfgXw::LT>;
-    using BF = WgradB<CfgXw::NVB, CfgXw::LT, true>;
-    using BP = WgradBx<CfgXw::NVB, CfgXw::LT>;
-#define X3_WGRAD(AL, BL, XPTR, DPTR)                                                                                   \
-    {                                                                                                                  \
-      typename AL::Params pa{XPTR, wg, p.KI};                                                                          \
-      typename BL::Params pb{DPTR, argmax + po, wg};                                                                   \
-      auto kern = conv_wgrad_x3_kernel<CfgXw, AL, BL>;                                                                  \
-      rc = set_smem(kern, SL::BYTES, "attr(conv_wgrad_x3)");                                                           \
-      if (rc) return rc;                                                                                               \
-      hipLaunchKernelGGL(kern, grid, dim3(CfgXw::THREADS), SL::BYTES, s, pa, pb, slab, p.tiles_m, p.tiles_n, p.nk,      \
-                         p.ks_per_split);                                                                              \
-    }
-    const float* xf = reinterpret_cast<const float*>(xc);
-    const float* dpf = dpooled + po;
-    const void* dpp = dpooled_packed ? static_cast<const char*>(dpooled_packed) + po * 6 : nullptr;
-    if (x_packed && dpp) X3_WGRAD(AP, BP, xc, dpp)
-    else if (x_packed) X3_WGRAD(AP, BF, xc, dpf)
-    else if (dpp) X3_WGRAD(AF, BP, xf, dpp)
-    else X3_WGRAD(AF, BF, xf, dpf)
-#undef X3_WGRAD
-    rc = check_hip(hipGetLastError(), "conv_wgrad_x3 launch");
-    if (rc) return rc;
-    done += p.splits;
-  }
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((KI * Co + 63) / 64), dim3(256), 0, s, workspace, dw, parts, KI, CiP, Ci,
-                     Co);
-  rc = check_hip(hipGetLastError(), "wgrad_reduce launch");
-  if (rc) return rc;
-  // bias gradient = sum of the pooled gradient over the windows whose ReLU was alive (arg-max byte != 4); dbias == NULL:
-  // the caller already has it (vqa_x3_pack_pooled_grad)
-  if (!dbias) return VQA_OK;
-  return launch_bias_grad(dpooled, argmax, dbias, nullptr, (int64_t)B * g1.Hp * g1.Wp, Co, bias_parts, s);
+  return wgrad_walk(
+      w, plan_wgrad_x3, (int64_t)kBiasParts * Co * 4, workspace, workspace_bytes, dw, Ci, tag, s,
+      [&](const ConvChunk& c, const WgradPlan& p, float* slab, float*) {
+        const void* xc = static_cast<const char*>(x) + c.xo * (x_packed ? 6 : 4);
+        const void* dpc = dpooled_packed ? static_cast<const void*>(static_cast<const char*>(dpooled_packed) + c.po * 6)
+                                         : static_cast<const void*>(dpooled + c.po);
+        return with_flags(x_packed, dpooled_packed != nullptr, [&](auto xp, auto dpk) {
+          return launch_wgrad_x3<decltype(xp)::value, decltype(dpk)::value>(xc, dpc, argmax + c.po, slab, c.g, p, s);
+        });
+      },
+      // bias gradient = sum of the pooled gradient over the windows whose ReLU was alive (arg-max byte != 4), through the
+      // kBiasParts rows after the slabs; dbias == NULL: the caller already has it (vqa_x3_pack_pooled_grad)
+      [&](float* bias_parts, int) {
+        if (!dbias) return (int)VQA_OK;
+        return launch_bias_grad(dpooled, argmax, dbias, nullptr, (int64_t)B * g1.Hp * g1.Wp, Co, bias_parts, s);
+      });
 }
 
 }  // extern "C"

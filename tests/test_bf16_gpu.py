@@ -171,6 +171,50 @@ def test_conv_bf16_fwd_dgrad_wgrad(B, H, W, Ci, Co, stride):
     check(f"conv_bf16 bias grad {tag}", db, br.grad, 2e-5)
 
 
+@pytest.fixture
+def knob(monkeypatch):
+    """Set a VQA_* knob for one test (the library reads them once: vqa_reload_knobs after every change)."""
+    from dl_vqa_amd import _lib
+
+    def set_knob(name, value):
+        monkeypatch.setenv(name, value)
+        _lib.load().vqa_reload_knobs()
+    yield set_knob
+    monkeypatch.undo()
+    _lib.load().vqa_reload_knobs()
+
+
+def test_conv_bf16_batch_chunking(knob):
+    """Batches whose tensors would pass 4 GiB are walked in chunks inside the C ABI (32-bit offsets per launch);
+    VQA_CONV_CHUNK forces that path on small tensors.  The bf16 entry points count 2 bytes per element of x, pooled and
+    dpooled: forward (pooled, arg-max) and dgrad are bit-identical to one launch; wgrad's chunks are extra split-K slabs
+    and extra partial bias rows of the same fp32 reduces over the same bf16 operands, so dw / dbias agree to 1e-5 of the
+    largest entry (the bound of the fp32 test_conv_batch_chunking for the same comparison)."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(79)
+    B, H, Ci, Co = 5, 26, 64, 64
+    x = torch.randn(B, H, H, Ci, generator=g).to(torch.bfloat16).to(DEV)
+    w = (torch.randn(Co, Ci, 3, 3, generator=g) / math.sqrt(9 * Ci)).to(DEV)
+    b = (torch.randn(Co, generator=g) * 0.1).to(DEV)
+    wfT, wdT = ops.conv_pack_weights_bf16(w, Ci)
+
+    def run():
+        pooled, am = ops.conv_fwd_bf16(x, wfT, b, 1)
+        dp = (torch.sin(pooled.float() * 3.0) + 0.1).to(torch.bfloat16)
+        dw, db = torch.empty_like(w), torch.empty_like(b)
+        ops.conv_wgrad_bf16(x, dp, am, dw, db, 1)
+        dx = ops.conv_dgrad_bf16(dp, am, wdT, x.shape, 1)
+        torch.cuda.synchronize()
+        return pooled, am, dw, db, dx
+
+    ref = run()
+    knob("VQA_CONV_CHUNK", "2")      # 2 + 2 + 1 images
+    got = run()
+    assert torch.equal(ref[0], got[0]) and torch.equal(ref[1], got[1]) and torch.equal(ref[4], got[4])
+    check("chunked bf16 wgrad dw", got[2], ref[2].double(), 1e-5)
+    check("chunked bf16 wgrad db", got[3], ref[3].double(), 1e-5)
+
+
 # ----------------------------------------------------------------------------- the whole module in bf16 mode
 def bf16_cfg(do_option="+", p=0.0):
     return {
