@@ -1073,14 +1073,16 @@ __global__ void softce_kernel(const float* logits, int64_t ld, const int64_t* a_
   float sum = 0.f;
   for (int i = tid; i < A; i += blockDim.x) sum += expf(row[i] - mx);
   sum = block_reduce(sum, red, false);
-  const float lse = mx + logf(sum);
+  // -log_softmax = log(sum) - (logit - max): both terms are >= 0, so nothing cancels.  (max + log(sum)) - logit rounds the
+  // log-sum-exp at the magnitude of the logits: with a common offset of 1e4 that is 5e-4 absolute on a loss term of order 1.
+  const float lsum = logf(sum);
   float wsum = 0.f, loss = 0.f, agree = 0.f;
   for (int k = 0; k < kmax; ++k) {
     const int64_t idx = a_idx[(int64_t)b * kmax + k];
     if (idx <= 0 || idx > A) continue;
     const float w = (float)a_val[(int64_t)b * kmax + k] / 10.0f;
     wsum += w;
-    loss += w * (lse - row[idx - 1]);
+    loss += w * (lsum - (row[idx - 1] - mx));
     if ((int)(idx - 1) == am) agree = (float)a_val[(int64_t)b * kmax + k];
   }
   if (tid == 0) {
