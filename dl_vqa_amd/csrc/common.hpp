@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/vqa_hip.h"
 
 namespace vqa {
@@ -24,6 +26,28 @@ int check_hip(hipError_t e, const char* what);
 // ---------------------------------------------------------------- launch plumbing
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) for a kernel, once per (device, kernel); thread-safe.
 int ensure_dyn_smem(const void* kernel, int bytes, const char* what);
+template <class K>
+static int set_smem(K kern, int bytes, const char* what) {
+  return ensure_dyn_smem(reinterpret_cast<const void*>(kern), bytes, what);
+}
+
+struct KernelNames { const char *attr, *launch; };      // what ensure_dyn_smem / check_hip report
+template <class K, class... A>
+static int launch_kernel(K kern, KernelNames n, dim3 grid, int threads, int lds, hipStream_t s, A... args) {
+  int rc = set_smem(kern, lds, n.attr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, args...);
+  return check_hip(hipGetLastError(), n.launch);
+}
+
+// runtime flag -> template flag: f is a generic lambda that reads decltype(flag)::value, so a tile choice is written once
+template <bool V> struct Flag { static constexpr bool value = V; };
+template <class F>
+static int with_flag(bool v, F&& f) { return v ? f(Flag<true>{}) : f(Flag<false>{}); }
+template <class F>
+static int with_flags(bool a, bool b, F&& f) {
+  return with_flag(a, [&](auto fa) { return with_flag(b, [&](auto fb) { return f(fa, fb); }); });
+}
 
 // VQA_* environment knobs (diagnostics / forced tile variants for the parity tests).  Read ONCE, when the
 // library is first used; vqa_reload_knobs() re-reads them (tests that switch variants inside one process).
@@ -87,6 +111,23 @@ __device__ __forceinline__ float4 drop_scale4(uint64_t seed, uint64_t idx, float
   const uint32_t thr = (uint32_t)(p * 65536.0f);
   return make_float4((h0 & 0xffffu) >= thr ? inv_keep : 0.f, (h0 >> 16) >= thr ? inv_keep : 0.f,
                      (h1 & 0xffffu) >= thr ? inv_keep : 0.f, (h1 >> 16) >= thr ? inv_keep : 0.f);
+}
+
+// The 2x2 max-pool window rule of the conv + ReLU + pool kernels (include/vqa_hip.h): of the window's four pre-activations
+// in the order dy*2+dx the FIRST strict maximum wins (what nn.MaxPool2d returns on ties); the bias is added to the winner
+// (max(z + b) == max(z) + b); where the result is <= 0 the output is 0 and the code byte 4 (dead: no pixel gets the gradient).
+// Three sites spell the same rule out themselves because this helper moves their code: pconv_kernel (conv_patch_bf16.hip;
+// <4, 0, false> goes from 216 to 217 VGPRs), convk_relu_pool_kernel (conv_generic.hip; 42 to 40) and the fp32 wide-store
+// path of conv0_fwd_kernel (conv0.hip; same registers, but the schedule shifts: that kernel is kept instruction-identical).
+struct PoolPick { float v; uint8_t code; };
+__device__ __forceinline__ PoolPick pool_pick(float z0, float z1, float z2, float z3, float bias) {
+  float best = z0;
+  int a = 0;
+  if (z1 > best) { best = z1; a = 1; }
+  if (z2 > best) { best = z2; a = 2; }
+  if (z3 > best) { best = z3; a = 3; }
+  best += bias;
+  return {best > 0.f ? best : 0.f, best > 0.f ? (uint8_t)a : (uint8_t)4};
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -18,8 +18,6 @@
 
 namespace vqa {
 
-constexpr int C0_MAX_NS = 18;   // k2-steps for Cin = 4
-
 __host__ __device__ inline int c0_round_stride(int W, int want_mod) {
   int rs = W + 2;
   while (rs % 32 != want_mod) ++rs;
@@ -47,6 +45,53 @@ __device__ __forceinline__ float4 c0_load4(const void* x, int64_t e, int xh) {
 // the workgroup's first window (lane part one VGPR per tile, group / column block in the scalar offset).
 constexpr int C0_FR = 4;
 constexpr int C0_PR = 2 * C0_FR + 2;
+
+// ---- pieces shared by the forward kernels
+// tap k = (c * 3 + ky) * 3 + kx of the 9 * CI taps (forward and weight-gradient kernels)
+struct C0Tap { int c, ky, kx; };
+__device__ __forceinline__ C0Tap c0_tap(int k) {
+  const int c = k / 9, t = k - 9 * c, ky = t / 3;
+  return {c, ky, t - 3 * ky};
+}
+
+// the A row that lane l31 feeds to M-tile t, in the patch: row i = 4*window + pixel (the engine's window-in-4-registers
+// layout); rows past the last window read window 0
+template <class T>
+__device__ __forceinline__ const T* c0_tile_row(const T* patch, int t, int l31, int nwin, int Wp, int RS) {
+  int wdx = 8 * t + (l31 >> 2);
+  if (wdx >= nwin) wdx = 0;
+  const int wr = (wdx >= Wp ? 1 : 0) + (wdx >= 2 * Wp ? 1 : 0) + (wdx >= 3 * Wp ? 1 : 0);
+  const int px = wdx - __mul24(wr, Wp), j4 = l31 & 3;
+  return patch + __mul24(2 * wr + (j4 >> 1), RS) + 2 * px + (j4 & 1);
+}
+
+// Element-wise store epilogue of tile t: bias / ReLU / pool / arg-max in registers, one 2-byte (OB 1: bf16) or three (OB 2:
+// x3-packed) stores and one byte store per window and channel.  fp32 output (OB 0) always leaves through the wide stores.
+template <int TN, int OB>
+__device__ __forceinline__ void c0_store_elementwise(const f32x16 (&acc)[TN], const float (&bv)[TN], __amdgpu_buffer_rsrc_t rp,
+                                                     __amdgpu_buffer_rsrc_t ra, int t, int nwin, bool inner, int h, int l31) {
+  static_assert(OB == 1 || OB == 2, "bf16 or x3-packed");
+  constexpr int Co = 32 * TN;
+  const uint32_t vl = (uint32_t)__mul24(8 * t + h, Co) + (uint32_t)l31;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const bool ok = inner || 8 * t + 2 * g + h < nwin;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const PoolPick p = pool_pick(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], bv[j]);
+      const uint32_t so = (uint32_t)(2 * g * Co + 32 * j);
+      if (OB == 2) {
+        uint16_t sh, sm, sl;
+        split1(p.v, sh, sm, sl);
+        const uint32_t vx = ok ? 6u * (uint32_t)__mul24(8 * t + h, Co) + x3p_lane(l31) : BUF_OOB;
+        buf_store2(rp, sh, vx, 6u * so);
+        buf_store2(rp, sm, vx, 6u * so + 8u);
+        buf_store2(rp, sl, vx, 6u * so + 16u);
+      } else buf_store2(rp, bf16_bits(p.v), ok ? 2u * vl : BUF_OOB, 2u * so);
+      buf_store1(ra, p.code, ok ? vl : BUF_OOB, so);
+    }
+  }
+}
 
 // OB: 0 = pooled is stored as fp32, 1 = as bf16 (the bf16 path's P_0), 2 = x3-packed (the fp32x3 path: vqa_x3_pack's form)
 template <int CI, int TN, int OB>
@@ -80,8 +125,8 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_kernel(const void* __restric
     const int k = 2 * s + h;
     const bool kok = k < K;
     const int kk = kok ? k : 0;
-    const int c = kk / 9, t = kk - 9 * c, ky = t / 3, kx = t - 3 * ky;
-    koff[s] = c * plane + ky * RS + kx;
+    const C0Tap tp = c0_tap(kk);
+    koff[s] = tp.c * plane + tp.ky * RS + tp.kx;
 #pragma unroll
     for (int j = 0; j < TN; ++j) bf[s][j] = kok ? w[(int64_t)(32 * j + l31) * K + kk] : 0.f;
   }
@@ -96,12 +141,7 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_kernel(const void* __restric
   const __amdgpu_buffer_rsrc_t rp = OB == 2 ? buf_rsrc(pooled16 + 3 * o0) : OB == 1 ? buf_rsrc(pooled16 + o0) : buf_rsrc(pooled + o0),
                                ra = buf_rsrc(amax + o0);
   for (int t = wave; t < ntiles; t += 4) {
-    // A rows: row i = 4*window + pixel (the engine's window-in-4-registers layout)
-    int wdx = 8 * t + (l31 >> 2);
-    if (wdx >= nwin) wdx = 0;
-    const int wr = (wdx >= Wp ? 1 : 0) + (wdx >= 2 * Wp ? 1 : 0) + (wdx >= 3 * Wp ? 1 : 0);
-    const int px = wdx - __mul24(wr, Wp), j4 = l31 & 3;
-    const float* ap = patch + __mul24(2 * wr + (j4 >> 1), RS) + 2 * px + (j4 & 1);
+    const float* ap = c0_tile_row(patch, t, l31, nwin, Wp, RS);
     f32x16 acc[TN];
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -123,6 +163,7 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_kernel(const void* __restric
       for (int g = 0; g < 4; ++g) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
+          // pool_pick's rule (common.hpp), spelled out: the helper shifts this kernel's schedule
           float best = acc[j][4 * g];
           int a = 0;
           if (acc[j][4 * g + 1] > best) { best = acc[j][4 * g + 1]; a = 1; }
@@ -145,7 +186,7 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_kernel(const void* __restric
       }
       {
         const int byte = lane * 16;
-        if (byte < 8 * Co) {                 // arg-max: 8 windows x Co bytes
+        if (byte < 8 * Co) {                 // arg-max: 8 windows x Co bytes (the same store as in conv0_fwd_c16_kernel)
           const int win = byte / Co;
           const float4 v = *reinterpret_cast<const float4*>(sam + byte);
           const bool ok = inner || 8 * t + win < nwin;
@@ -155,31 +196,7 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_kernel(const void* __restric
       asm volatile("" ::: "memory");
       continue;
     }
-    const uint32_t vl = (uint32_t)__mul24(8 * t + h, Co) + (uint32_t)l31;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const bool ok = inner || 8 * t + 2 * g + h < nwin;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        float best = acc[j][4 * g];
-        int a = 0;
-        if (acc[j][4 * g + 1] > best) { best = acc[j][4 * g + 1]; a = 1; }
-        if (acc[j][4 * g + 2] > best) { best = acc[j][4 * g + 2]; a = 2; }
-        if (acc[j][4 * g + 3] > best) { best = acc[j][4 * g + 3]; a = 3; }
-        best += bv[j];
-        const uint32_t so = (uint32_t)(2 * g * Co + 32 * j);
-        if (OB == 2) {
-          uint16_t sh, sm, sl;
-          split1(best > 0.f ? best : 0.f, sh, sm, sl);
-          const uint32_t vx = ok ? 6u * (uint32_t)__mul24(8 * t + h, Co) + x3p_lane(l31) : BUF_OOB;
-          buf_store2(rp, sh, vx, 6u * so);
-          buf_store2(rp, sm, vx, 6u * so + 8u);
-          buf_store2(rp, sl, vx, 6u * so + 16u);
-        } else if (OB == 1) buf_store2(rp, bf16_bits(best > 0.f ? best : 0.f), ok ? 2u * vl : BUF_OOB, 2u * so);
-        else buf_store4(rp, best > 0.f ? best : 0.f, ok ? 4u * vl : BUF_OOB, 4u * so);
-        buf_store1(ra, best > 0.f ? (uint8_t)a : (uint8_t)4, ok ? vl : BUF_OOB, so);
-      }
-    }
+    if constexpr (OB != 0) c0_store_elementwise<TN, OB>(acc, bv, rp, ra, t, nwin, inner, h, l31);
   }
 }
 
@@ -196,6 +213,7 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_bf16_kernel(const void* __re
   extern __shared__ __attribute__((aligned(16))) float patch[];
   constexpr int K = 9 * CI, Co = 32 * TN;
   static_assert(K <= 32, "two 16-deep k-steps cover at most 32 taps");
+  static_assert(!C16, "the C16 layout is written by conv0_fwd_c16_kernel");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int b = blockIdx.y, py0 = C0_FR * blockIdx.x;
   const int nwr = min(C0_FR, Hp - py0);
@@ -221,8 +239,8 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_bf16_kernel(const void* __re
       const int k = 16 * ks + 8 * h + e;
       const bool kok = k < K;
       const int kk = kok ? k : 0;
-      const int c = kk / 9, t = kk - 9 * c, ky = t / 3, kx = t - 3 * ky;
-      koff[ks][e] = c * plane + ky * RS + kx;            // taps >= K read tap 0 (finite) against a zero weight
+      const C0Tap tp = c0_tap(kk);
+      koff[ks][e] = tp.c * plane + tp.ky * RS + tp.kx;            // taps >= K read tap 0 (finite) against a zero weight
 #pragma unroll
       for (int j = 0; j < TN; ++j) wv[j][e] = kok ? w[(int64_t)(32 * j + l31) * K + kk] : 0.f;
     }
@@ -240,15 +258,9 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_bf16_kernel(const void* __re
 
   const int nwin = nwr * Wp, ntiles = (nwin + 7) / 8;
   const int64_t o0 = (int64_t)(b * Hp + py0) * Wp * Co;
-  const int plane16 = Hp * Wp * 16;                     // elements of one 16-channel block of one image
-  const int64_t o16 = ((int64_t)b * (Co / 16) * Hp + py0) * Wp * 16;
-  const __amdgpu_buffer_rsrc_t rp = buf_rsrc(pooled16 + (C16 ? o16 : o0)), ra = buf_rsrc(amax + o0);
+  const __amdgpu_buffer_rsrc_t rp = buf_rsrc(pooled16 + o0), ra = buf_rsrc(amax + o0);
   for (int t = wave; t < ntiles; t += 4) {
-    int wdx = 8 * t + (l31 >> 2);
-    if (wdx >= nwin) wdx = 0;
-    const int wr = (wdx >= Wp ? 1 : 0) + (wdx >= 2 * Wp ? 1 : 0) + (wdx >= 3 * Wp ? 1 : 0);
-    const int px = wdx - __mul24(wr, Wp), j4 = l31 & 3;
-    const float* ap = patch + __mul24(2 * wr + (j4 >> 1), RS) + 2 * px + (j4 & 1);
+    const float* ap = c0_tile_row(patch, t, l31, nwin, Wp, RS);
     f32x16 acc[TN];
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -264,64 +276,7 @@ __global__ __launch_bounds__(256, 4) void conv0_fwd_bf16_kernel(const void* __re
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bw[ks][j], ks == 0 ? zero : acc[j], 0, 0, 0);
     }
     const bool inner = 8 * t + 8 <= nwin;
-    if (C16) {
-      // C16 + wide stores: the tile's 8 windows x Co channels go through a wave-private LDS scratch behind the patch --
-      // pooled as [16-channel block][window][16] bf16, arg-max as [window][Co] bytes -- and leave as ONE 16-byte-per-lane
-      // store each (the element-wise form issued 8 two-byte and 8 one-byte store instructions per tile and was bound by that)
-      char* const scr = reinterpret_cast<char*>(patch) + CI * C0_PR * RS * 4 + wave * (8 * Co * 3);
-      char* const sam = scr + 8 * Co * 2;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          float best = acc[j][4 * g];
-          int a = 0;
-          if (acc[j][4 * g + 1] > best) { best = acc[j][4 * g + 1]; a = 1; }
-          if (acc[j][4 * g + 2] > best) { best = acc[j][4 * g + 2]; a = 2; }
-          if (acc[j][4 * g + 3] > best) { best = acc[j][4 * g + 3]; a = 3; }
-          best += bv[j];
-          const int win = 2 * g + h;
-          *reinterpret_cast<uint16_t*>(scr + (((2 * j + (l31 >> 4)) * 8 + win) * 16 + (l31 & 15)) * 2) = bf16_bits(best > 0.f ? best : 0.f);
-          *reinterpret_cast<uint8_t*>(sam + win * Co + 32 * j + l31) = best > 0.f ? (uint8_t)a : (uint8_t)4;
-        }
-      }
-      asm volatile("" ::: "memory");        // the wave's LDS accesses execute in order; keep the compiler's order as well
-      {
-        const int byte = lane * 16;          // pooled: 2 TN blocks x 8 windows x 32 bytes = 8 * Co * 2 bytes
-        if (byte < 8 * Co * 2) {
-          const int blk = byte >> 8, win = (byte & 255) >> 5, inrun = byte & 31;
-          const float4 v = *reinterpret_cast<const float4*>(scr + byte);
-          const bool ok = inner || 8 * t + win < nwin;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rp,
-                                                 ok ? (int)(blk * plane16 * 2 + (8 * t + win) * 32 + inrun) : (int)BUF_OOB, 0, 0);
-        }
-        if (byte < 8 * Co) {                 // arg-max: 8 windows x Co bytes, contiguous in NHWC
-          const int win = byte / Co;
-          const float4 v = *reinterpret_cast<const float4*>(sam + byte);
-          const bool ok = inner || 8 * t + win < nwin;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ra, ok ? (int)(8 * t * Co + byte) : (int)BUF_OOB, 0, 0);
-        }
-      }
-      asm volatile("" ::: "memory");
-      continue;
-    }
-    const uint32_t vl = (uint32_t)__mul24(8 * t + h, Co) + (uint32_t)l31;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const bool ok = inner || 8 * t + 2 * g + h < nwin;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        float best = acc[j][4 * g];
-        int a = 0;
-        if (acc[j][4 * g + 1] > best) { best = acc[j][4 * g + 1]; a = 1; }
-        if (acc[j][4 * g + 2] > best) { best = acc[j][4 * g + 2]; a = 2; }
-        if (acc[j][4 * g + 3] > best) { best = acc[j][4 * g + 3]; a = 3; }
-        best += bv[j];
-        const uint32_t so = (uint32_t)(2 * g * Co + 32 * j);
-        buf_store2(rp, bf16_bits(best > 0.f ? best : 0.f), ok ? 2u * vl : BUF_OOB, 2u * so);
-        buf_store1(ra, best > 0.f ? (uint8_t)a : (uint8_t)4, ok ? vl : BUF_OOB, so);
-      }
-    }
+    c0_store_elementwise<TN, 1>(acc, bv, rp, ra, t, nwin, inner, h, l31);
   }
 }
 
@@ -368,8 +323,8 @@ __global__ __launch_bounds__(XH ? 512 : 1024, 4) void conv0_fwd_c16_kernel(const
       const int k = 16 * ks + 8 * h + e;
       const bool kok = k < K;
       const int kk = kok ? k : 0;
-      const int c = kk / 9, t = kk - 9 * c, ky = t / 3, kx = t - 3 * ky;
-      ko[e] = c * plane + ky * RS + kx;                  // taps >= K read tap 0 (finite) against a zero weight
+      const C0Tap tp = c0_tap(kk);
+      ko[e] = tp.c * plane + tp.ky * RS + tp.kx;                  // taps >= K read tap 0 (finite) against a zero weight
 #pragma unroll
       for (int j = 0; j < TN; ++j) wv[j][e] = kok ? w[(int64_t)(32 * j + l31) * K + kk] : 0.f;
     }
@@ -444,11 +399,7 @@ __global__ __launch_bounds__(XH ? 512 : 1024, 4) void conv0_fwd_c16_kernel(const
     const int64_t o16 = ((int64_t)b * (Co / 16) * Hp + py0) * Wp * 16;
     const __amdgpu_buffer_rsrc_t rp = buf_rsrc(pooled16 + o16), ra = buf_rsrc(amax + o0);
     for (int t = wave; t < ntiles; t += NWV) {
-      int wdx = 8 * t + (l31 >> 2);
-      if (wdx >= nwin) wdx = 0;
-      const int wr = (wdx >= Wp ? 1 : 0) + (wdx >= 2 * Wp ? 1 : 0) + (wdx >= 3 * Wp ? 1 : 0);
-      const int px = wdx - __mul24(wr, Wp), j4 = l31 & 3;
-      const uint16_t* ap = patch + __mul24(2 * wr + (j4 >> 1), RS) + 2 * px + (j4 & 1);
+      const uint16_t* ap = c0_tile_row(patch, t, l31, nwin, Wp, RS);
       f32x16 acc[TN];
       const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -471,15 +422,10 @@ __global__ __launch_bounds__(XH ? 512 : 1024, 4) void conv0_fwd_c16_kernel(const
       for (int g = 0; g < 4; ++g) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          float best = acc[j][4 * g];
-          int a = 0;
-          if (acc[j][4 * g + 1] > best) { best = acc[j][4 * g + 1]; a = 1; }
-          if (acc[j][4 * g + 2] > best) { best = acc[j][4 * g + 2]; a = 2; }
-          if (acc[j][4 * g + 3] > best) { best = acc[j][4 * g + 3]; a = 3; }
-          best += bv[j];
+          const PoolPick p = pool_pick(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], bv[j]);
           const int win = 2 * g + h;
-          *reinterpret_cast<uint16_t*>(scr + (((2 * j + (l31 >> 4)) * 8 + win) * 16 + (l31 & 15)) * 2) = bf16_bits(best > 0.f ? best : 0.f);
-          *reinterpret_cast<uint8_t*>(sam + win * Co + 32 * j + l31) = best > 0.f ? (uint8_t)a : (uint8_t)4;
+          *reinterpret_cast<uint16_t*>(scr + (((2 * j + (l31 >> 4)) * 8 + win) * 16 + (l31 & 15)) * 2) = bf16_bits(p.v);
+          *reinterpret_cast<uint8_t*>(sam + win * Co + 32 * j + l31) = p.code;
         }
       }
       asm volatile("" ::: "memory");        // the wave's LDS accesses execute in order; keep the compiler's order as well
@@ -492,7 +438,7 @@ __global__ __launch_bounds__(XH ? 512 : 1024, 4) void conv0_fwd_c16_kernel(const
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rp,
                                                  ok ? (int)(blk * plane16 * 2 + (8 * t + win) * 32 + inrun) : (int)BUF_OOB, 0, 0);
         }
-        if (byte < 8 * Co) {                 // arg-max: 8 windows x Co bytes, contiguous in NHWC
+        if (byte < 8 * Co) {                 // arg-max: 8 windows x Co bytes, contiguous in NHWC (twin of conv0_fwd_kernel's)
           const int win = byte / Co;
           const float4 v = *reinterpret_cast<const float4*>(sam + byte);
           const bool ok = inner || 8 * t + win < nwin;
@@ -505,6 +451,69 @@ __global__ __launch_bounds__(XH ? 512 : 1024, 4) void conv0_fwd_c16_kernel(const
 }
 
 // ------------------------------------------------------------------ wgrad
+// ---- pieces shared by the weight-gradient kernels
+template <int TN>
+__device__ __forceinline__ void c0_wgrad_zero(f32x16 (&acc)[TN], float (&bsum)[TN]) {
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    bsum[j] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  }
+}
+
+// one staged pooled row of the fp32 weight gradient: a wave takes every fourth window; A = the taps of a pixel (ap: the
+// lane's tap at window 0), B = dY routed by the arg-max byte
+template <int TN>
+__device__ __forceinline__ void c0_wgrad_row(f32x16 (&acc)[TN], float (&bsum)[TN], const float* ap, const float* dps,
+                                             const uint8_t* ams, int Wp, int RS, int wave, int l31, int h) {
+  constexpr int Co = 32 * TN;
+  for (int px = wave; px < Wp; px += 4) {
+    float d[TN];
+    int id[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) { d[j] = dps[px * Co + 32 * j + l31]; id[j] = ams[px * Co + 32 * j + l31]; }
+#pragma unroll
+    for (int hs = 0; hs < 2; ++hs) {          // pixel pair (dy = hs, dx = h)
+      const float a = ap[hs * RS + 2 * px];
+      const int jj = 2 * hs + h;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const float bvv = id[j] == jj ? d[j] : 0.f;
+        bsum[j] += bvv;
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bvv, acc[j], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// end of a weight-gradient kernel: combine the 4 waves of the workgroup through LDS (the staging area is free, and the
+// launchers make it large enough), then ONE partial per workgroup
+template <int TN>
+__device__ __forceinline__ void c0_wgrad_write_slab(float* lds, const f32x16 (&acc)[TN], const float (&bsum)[TN], float* slab,
+                                                    float* bias_slab, int tid, int wave, int l31, int h) {
+  constexpr int Co = 32 * TN;
+  __syncthreads();
+  float* comb = lds;                               // [4][32][Co] floats
+  float* cb = lds + 4 * 32 * Co;                   // [4][Co]
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
+      comb[(wave * 32 + k) * Co + 32 * j + l31] = acc[j][r];
+    }
+    const float s = bsum[j] + __shfl_xor(bsum[j], 32, 64);
+    if (h == 0) cb[wave * Co + 32 * j + l31] = s;
+  }
+  __syncthreads();
+  float* out = slab + (int64_t)blockIdx.x * 32 * Co;
+  for (int e = tid; e < 32 * Co; e += 256)
+    out[e] = comb[e] + comb[32 * Co + e] + comb[2 * 32 * Co + e] + comb[3 * 32 * Co + e];
+  for (int e = tid; e < Co; e += 256)
+    bias_slab[(int64_t)blockIdx.x * Co + e] = cb[e] + cb[Co + e] + cb[2 * Co + e] + cb[3 * Co + e];
+}
+
 // persistent grid; 256 threads; LDS = CI*PLANE (x patch, 4 rows) + Wp*Co (dP row) floats + Wp*Co bytes (arg-max row)
 template <int CI, int TN>
 __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const void* __restrict__ x, int xh, const float* __restrict__ dp,
@@ -518,16 +527,11 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const void* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   // lane l31 owns tap i = l31 of the 32-row A operand (rows >= K are don't-care: never written out)
   const int i = l31 < K ? l31 : 0;
-  const int c = i / 9, t9 = i - 9 * c, ky = t9 / 3, kx = t9 - 3 * ky;
-  const float* ap = patch + c * PLANE + ky * RS + kx + h;   // + h: the pixel pair (dx = h) of one MFMA
+  const C0Tap tp = c0_tap(i);
+  const float* ap = patch + tp.c * PLANE + tp.ky * RS + tp.kx + h;   // + h: the pixel pair (dx = h) of one MFMA
   f32x16 acc[TN];
   float bsum[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    bsum[j] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  }
+  c0_wgrad_zero<TN>(acc, bsum);
   const int rows_total = B * Hp;
   const int rowv = Wp * Co;   // floats in one pooled-gradient row
   for (int row = blockIdx.x; row < rows_total; row += gridDim.x) {
@@ -548,25 +552,9 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const void* __restrict
       reinterpret_cast<uint32_t*>(ams)[e] = reinterpret_cast<const uint32_t*>(amrow)[e];
     }
     __syncthreads();
-    for (int px = wave; px < Wp; px += 4) {
-      float d[TN];
-      int id[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) { d[j] = dps[px * Co + 32 * j + l31]; id[j] = ams[px * Co + 32 * j + l31]; }
-#pragma unroll
-      for (int hs = 0; hs < 2; ++hs) {          // pixel pair (dy = hs, dx = h)
-        const float a = ap[hs * RS + 2 * px];
-        const int jj = 2 * hs + h;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const float bvv = id[j] == jj ? d[j] : 0.f;
-          bsum[j] += bvv;
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bvv, acc[j], 0, 0, 0);
-        }
-      }
-    }
+    c0_wgrad_row<TN>(acc, bsum, ap, dps, ams, Wp, RS, wave, l31, h);
   }
-  // combine the 4 waves of the workgroup through LDS, then ONE partial per workgroup
+  // c0_wgrad_write_slab, spelled out: through the helper this kernel takes 72 instead of 68 VGPRs at TN = 2
   __syncthreads();
   float* comb = lds;                               // [4][32][Co] floats, fits the staging area
   float* cb = lds + 4 * 32 * Co;                   // [4][Co]
@@ -605,16 +593,11 @@ __global__ __launch_bounds__(256) void conv0_wgrad_pf_kernel(const void* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   // lane l31 owns tap i = l31 of the 32-row A operand (rows >= K are don't-care: never written out)
   const int i = l31 < K ? l31 : 0;
-  const int c = i / 9, t9 = i - 9 * c, ky = t9 / 3, kx = t9 - 3 * ky;
-  const float* ap = patch + c * PLANE + ky * RS + kx + h;   // + h: the pixel pair (dx = h) of one MFMA
+  const C0Tap tp = c0_tap(i);
+  const float* ap = patch + tp.c * PLANE + tp.ky * RS + tp.kx + h;   // + h: the pixel pair (dx = h) of one MFMA
   f32x16 acc[TN];
   float bsum[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    bsum[j] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  }
+  c0_wgrad_zero<TN>(acc, bsum);
   const int rows_total = B * Hp;
   const int rowv = Wp * Co;   // floats in one pooled-gradient row
   // prefetch registers: image = (channel: round, image row: wave, 4-pixel piece: lane), pooled gradient / arg-max = 16-byte /
@@ -672,44 +655,9 @@ __global__ __launch_bounds__(256) void conv0_wgrad_pf_kernel(const void* __restr
     store_row();
     __syncthreads();
     if (row + (int)gridDim.x < rows_total) load_row(row + gridDim.x);     // in flight under this row's MFMAs
-    for (int px = wave; px < Wp; px += 4) {
-      float d[TN];
-      int id[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) { d[j] = dps[px * Co + 32 * j + l31]; id[j] = ams[px * Co + 32 * j + l31]; }
-#pragma unroll
-      for (int hs = 0; hs < 2; ++hs) {          // pixel pair (dy = hs, dx = h)
-        const float a = ap[hs * RS + 2 * px];
-        const int jj = 2 * hs + h;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const float bvv = id[j] == jj ? d[j] : 0.f;
-          bsum[j] += bvv;
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bvv, acc[j], 0, 0, 0);
-        }
-      }
-    }
+    c0_wgrad_row<TN>(acc, bsum, ap, dps, ams, Wp, RS, wave, l31, h);
   }
-  // combine the 4 waves of the workgroup through LDS, then ONE partial per workgroup
-  __syncthreads();
-  float* comb = lds;                               // [4][32][Co] floats, fits the staging area
-  float* cb = lds + 4 * 32 * Co;                   // [4][Co]
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-      comb[(wave * 32 + k) * Co + 32 * j + l31] = acc[j][r];
-    }
-    const float s = bsum[j] + __shfl_xor(bsum[j], 32, 64);
-    if (h == 0) cb[wave * Co + 32 * j + l31] = s;
-  }
-  __syncthreads();
-  float* out = slab + (int64_t)blockIdx.x * 32 * Co;
-  for (int e = tid; e < 32 * Co; e += 256)
-    out[e] = comb[e] + comb[32 * Co + e] + comb[2 * 32 * Co + e] + comb[3 * 32 * Co + e];
-  for (int e = tid; e < Co; e += 256)
-    bias_slab[(int64_t)blockIdx.x * Co + e] = cb[e] + cb[Co + e] + cb[2 * Co + e] + cb[3 * Co + e];
+  c0_wgrad_write_slab<TN>(lds, acc, bsum, slab, bias_slab, tid, wave, l31, h);
 }
 
 // ------------------------------------------------------------------ wgrad on bf16 MFMA (bf16 path, configs[3])
@@ -739,16 +687,11 @@ __global__ __launch_bounds__(256, 2) void conv0_wgrad_bf16_kernel(const void* __
   uint8_t* const ams = reinterpret_cast<uint8_t*>(dps + WpP * Co);                  // [WpP][Co]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int tap = l31 < K ? l31 : 0;                        // rows >= K: any finite data, never written out
-  const int c = tap / 9, t9 = tap - 9 * c, ky = t9 / 3, kx = t9 - 3 * ky;
-  const char* const arow = P16 + ((kx * CI + c) * 4 + ky) * RSTR + 16 * h;   // + hs * RSTR + 32 * g
+  const C0Tap tp = c0_tap(tap);
+  const char* const arow = P16 + ((tp.kx * CI + tp.c) * 4 + tp.ky) * RSTR + 16 * h;   // + hs * RSTR + 32 * g
   f32x16 acc[TN];
   float bsum[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    bsum[j] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  }
+  c0_wgrad_zero<TN>(acc, bsum);
   const int rows_total = B * Hp;
   const int rowv = Wp * Co;
   // prefetch registers: image = (channel cc: round, image row: wave, 8-pixel chunk: lane), 12 pixels each (8 + the 4 the
@@ -849,26 +792,7 @@ __global__ __launch_bounds__(256, 2) void conv0_wgrad_bf16_kernel(const void* __
       }
     }
   }
-  // combine the 4 waves of the workgroup through LDS, then ONE partial per workgroup
-  __syncthreads();
-  float* comb = lds;                               // [4][32][Co] floats
-  float* cb = lds + 4 * 32 * Co;                   // [4][Co]
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int k = (r & 3) + 8 * (r >> 2) + 4 * h;
-      comb[(wave * 32 + k) * Co + 32 * j + l31] = acc[j][r];
-    }
-    const float sv = bsum[j] + __shfl_xor(bsum[j], 32, 64);
-    if (h == 0) cb[wave * Co + 32 * j + l31] = sv;
-  }
-  __syncthreads();
-  float* out = slab + (int64_t)blockIdx.x * 32 * Co;
-  for (int e = tid; e < 32 * Co; e += 256)
-    out[e] = comb[e] + comb[32 * Co + e] + comb[2 * 32 * Co + e] + comb[3 * 32 * Co + e];
-  for (int e = tid; e < Co; e += 256)
-    bias_slab[(int64_t)blockIdx.x * Co + e] = cb[e] + cb[Co + e] + cb[2 * Co + e] + cb[3 * Co + e];
+  c0_wgrad_write_slab<TN>(lds, acc, bsum, slab, bias_slab, tid, wave, l31, h);
 }
 
 // slab[parts][32][Co] -> dw[co][k]; bias_slab[parts][Co] -> dbias[co].  grid = K + 1 blocks of 256 threads.
@@ -889,37 +813,92 @@ __global__ void conv0_wgrad_reduce_kernel(const float* slab, const float* bias_s
   }
 }
 
+// ---- launch geometry: dynamic LDS bytes of each kernel; c0_supported and the launchers both take them from here
+// (the launchers raise the 64 KB default up to one workgroup's 160 KB)
+constexpr size_t kC0LdsMax = 160 * 1024;
+
+// conv0_fwd_kernel / conv0_fwd_bf16_kernel: the fp32 patch; wide_f32 (fp32 output): + the four waves' store scratch
+static size_t c0_fwd_lds(int Ci, int W, int Co, bool wide_f32) {
+  return (size_t)Ci * C0_PR * c0_round_stride(W, 16) * 4 + (wide_f32 ? (size_t)4 * 8 * Co * 5 : 0);
+}
+// conv0_fwd_c16_kernel: the bf16 patch (row stride = 16 mod 64 elements: the two image rows of a gather sit 8 banks apart),
+// the waves' store scratch, the weight fragments
+static int c0_c16_stride(int W) {
+  int rs = W + 2;
+  while (rs % 64 != 16) ++rs;
+  return rs;
+}
+static size_t c0_fwd_c16_lds(int Ci, int W, int Co, int waves) {
+  return (size_t)Ci * C0_PR * c0_c16_stride(W) * 2 + (size_t)waves * 8 * Co * 3 + (size_t)2 * (Co / 32) * 1024;
+}
+// conv0_wgrad_kernel / conv0_wgrad_pf_kernel: patch planes of 4 rows (stride 11 mod 32, plane 3 mod 32), one pooled-gradient
+// row and its arg-max bytes; at least the end-of-kernel combine area
+static int c0_wgrad_plane(int W) {
+  int plane = 4 * c0_round_stride(W, 11);
+  while (plane % 32 != 3) ++plane;
+  return plane;
+}
+static size_t c0_combine_lds(int Co) { return (size_t)(4 * 32 + 4) * Co * 4; }
+static size_t c0_wgrad_lds(int Ci, int W, int Co) {
+  const size_t lds = (((size_t)Ci * c0_wgrad_plane(W) + 3) & ~(size_t)3) * 4 + (size_t)((W - 2) / 2) * Co * 5;
+  return lds < c0_combine_lds(Co) ? c0_combine_lds(Co) : lds;
+}
+// conv0_wgrad_bf16_kernel: three shifted bf16 copies of 4 image rows (RSTR bytes each), NG groups of 8 windows of pooled
+// gradient and arg-max bytes
+static size_t c0_wgrad_bf16_lds(int Ci, int RSTR, int NG, int Co) {
+  const size_t lds = (size_t)3 * Ci * 4 * RSTR + (size_t)8 * NG * Co * 3;
+  return ((lds < c0_combine_lds(Co) ? c0_combine_lds(Co) : lds) + 15) & ~(size_t)15;
+}
+
 static bool c0_supported(int Ci, int H, int W, int Co, int stride) {
   const int Hp = (H - 2) / 2, Wp = (W - 2) / 2;
   // wgrad maps the 9*Ci taps onto the 32 rows of one MFMA A operand: Ci <= 3
   if (!(Ci >= 1 && Ci <= 3 && stride == 1 && (Co == 32 || Co == 64) && W % 4 == 0 && H >= 6 && Hp > 0 && Wp > 0))
     return false;
-  const size_t fwd = (size_t)Ci * C0_PR * c0_round_stride(W, 16) * 4 + (size_t)4 * 8 * Co * 5;
-  const int rs = c0_round_stride(W, 11);
-  int plane = 4 * rs;
-  while (plane % 32 != 3) ++plane;
-  const size_t wg = ((size_t)Ci * plane + 4) * 4 + (size_t)Wp * Co * 5;
-  return fwd <= 160 * 1024 && wg <= 160 * 1024;      // one workgroup's LDS (the launchers raise the 64 KB default)
+  return c0_fwd_lds(Ci, W, Co, true) <= kC0LdsMax && c0_wgrad_lds(Ci, W, Co) <= kC0LdsMax;
 }
 
 constexpr int kC0Blocks = 768;   // persistent wgrad grid: 3 workgroups per CU
+
+// a persistent grid: per_cu workgroups on each of the 256 CUs, at most one per work item
+static int c0_persistent_grid(int per_cu, int work) { return 256 * per_cu < work ? 256 * per_cu : work; }
 
 }  // namespace vqa
 
 using namespace vqa;
 
-#define C0_DISPATCH(CI, TN, ...)                                                          \
-  switch ((CI) * 10 + (TN)) {                                                             \
-    case 11: { constexpr int kCI = 1, kTN = 1; __VA_ARGS__; } break;                      \
-    case 12: { constexpr int kCI = 1, kTN = 2; __VA_ARGS__; } break;                      \
-    case 21: { constexpr int kCI = 2, kTN = 1; __VA_ARGS__; } break;                      \
-    case 22: { constexpr int kCI = 2, kTN = 2; __VA_ARGS__; } break;                      \
-    case 31: { constexpr int kCI = 3, kTN = 1; __VA_ARGS__; } break;                      \
-    case 32: { constexpr int kCI = 3, kTN = 2; __VA_ARGS__; } break;                      \
-    case 41: { constexpr int kCI = 4, kTN = 1; __VA_ARGS__; } break;                      \
-    case 42: { constexpr int kCI = 4, kTN = 2; __VA_ARGS__; } break;                      \
-    default: set_error("conv0: unsupported Ci=%d Co=%d", CI, 32 * (TN)); return VQA_ERR_INVALID; \
+// runtime (Ci, Co / 32) -> template (CI, TN): f is a generic lambda that reads decltype(ci)::value and decltype(tn)::value
+template <int V> using C0Int = std::integral_constant<int, V>;
+template <class F>
+static int c0_dispatch(int Ci, int TN, F&& f) {
+  switch (Ci * 10 + TN) {
+    case 11: return f(C0Int<1>{}, C0Int<1>{});
+    case 12: return f(C0Int<1>{}, C0Int<2>{});
+    case 21: return f(C0Int<2>{}, C0Int<1>{});
+    case 22: return f(C0Int<2>{}, C0Int<2>{});
+    case 31: return f(C0Int<3>{}, C0Int<1>{});
+    case 32: return f(C0Int<3>{}, C0Int<2>{});
   }
+  set_error("conv0: unsupported Ci=%d Co=%d", Ci, 32 * TN);
+  return VQA_ERR_INVALID;
+}
+
+// Both weight-gradient entry points: the workspace check, launch(slab, bias_slab) -- the entry point's kernel on a grid of
+// `parts` workgroups, one slab and one bias row each -- and the reduce into dw / dbias
+template <class F>
+static int c0_wgrad_run(const char* fn, float* workspace, int64_t workspace_bytes, float* dw, float* dbias, int Ci, int Co,
+                        int parts, hipStream_t s, F&& launch) {
+  if (workspace_bytes < vqa_conv0_wgrad_workspace_bytes(Co)) {
+    set_error("%s: workspace too small", fn);
+    return VQA_ERR_WORKSPACE;
+  }
+  float* slab = workspace;
+  float* bias_slab = workspace + (int64_t)kC0Blocks * 32 * Co;
+  const int rc = launch(slab, bias_slab);
+  if (rc) return rc;
+  hipLaunchKernelGGL(conv0_wgrad_reduce_kernel, dim3(9 * Ci + 1), dim3(256), 0, s, slab, bias_slab, dw, dbias, parts, 9 * Ci, Co);
+  return check_hip(hipGetLastError(), "conv0_wgrad_reduce launch");
+}
 
 extern "C" {
 
@@ -932,57 +911,35 @@ int vqa_conv0_relu_pool_fwd(const void* x_nchw, int x_is_fp16, const float* w, c
   VQA_REQUIRE(((uintptr_t)x_nchw % 16) == 0, "vqa_conv0_relu_pool_fwd: input must be 16-byte aligned");
   const int xh = x_is_fp16 ? 1 : 0;
   const int Hp = (H - 2) / 2, Wp = (W - 2) / 2, RS = c0_round_stride(W, 16);
-  const size_t lds = (size_t)Ci * C0_PR * RS * 4;
-  const dim3 grid((Hp + C0_FR - 1) / C0_FR, B);
-#define C0_FWD_LAUNCH(OB)                                                                                              \
-  C0_DISPATCH(Ci, Co / 32, {                                                                                           \
-    auto kern = conv0_fwd_kernel<kCI, kTN, OB>;                                                                        \
-    const size_t ldsk = lds + ((OB) == 0 ? (size_t)4 * 8 * Co * 5 : 0);   /* fp32 output: + the waves' store scratch */    \
-    int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)ldsk, "attr(conv0_fwd)");                      \
-    if (rc0) return rc0;                                                                                               \
-    hipLaunchKernelGGL(kern, grid, dim3(256), ldsk, (hipStream_t)stream, x_nchw, xh, w, bias, pooled, argmax, H, W, Hp, Wp, RS); \
-  })
-  if (pooled_is_bf16 == 2 || pooled_is_bf16 == 4) {      // bf16 MFMA (image and weights rounded to bf16), bf16 output (4: C16)
-    VQA_REQUIRE(Ci <= 3, "vqa_conv0_relu_pool_fwd: the bf16-MFMA first block needs Ci <= 3");
-    VQA_REQUIRE((int64_t)Hp * Wp * Co * 2 < (1LL << 31), "vqa_conv0_relu_pool_fwd: one pooled image reaches 2 GiB");
-    C0_DISPATCH(Ci, Co / 32, {
-      if constexpr (kCI <= 3) {
-        if (pooled_is_bf16 == 4) {
-          // persistent, register-prefetched, bf16 patch (row stride = 16 mod 64 elements: the two image rows of a gather sit
-          // 8 banks apart)
-          int RS16 = W + 2;
-          while (RS16 % 64 != 16) ++RS16;
-          const int nwv = xh ? 8 : 16;
-          const size_t lds16 = (size_t)kCI * C0_PR * RS16 * 2 + (size_t)nwv * 8 * Co * 3 + (size_t)2 * kTN * 1024;
-          VQA_REQUIRE(W <= 512, "vqa_conv0_relu_pool_fwd: image too wide for the C16 kernel (W=%d)", W);
-          const int nblk = (Hp + C0_FR - 1) / C0_FR;
-          int blocks = 256 * (xh ? 2 : 1);
-          if (blocks > B * nblk) blocks = B * nblk;
-          if (xh) {
-            auto kern = conv0_fwd_c16_kernel<kCI, kTN, true>;
-            int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds16, "attr(conv0_fwd_c16)");
-            if (rc0) return rc0;
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds16, (hipStream_t)stream, x_nchw, w, bias, static_cast<uint16_t*>(pooled),
-                               argmax, B, H, W, Hp, Wp, RS16, nblk);
-          } else {
-            auto kern = conv0_fwd_c16_kernel<kCI, kTN, false>;
-            int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds16, "attr(conv0_fwd_c16)");
-            if (rc0) return rc0;
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(1024), lds16, (hipStream_t)stream, x_nchw, w, bias, static_cast<uint16_t*>(pooled),
-                               argmax, B, H, W, Hp, Wp, RS16, nblk);
-          }
-        } else {
-          auto kern = conv0_fwd_bf16_kernel<kCI, kTN, false>;
-          int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds, "attr(conv0_fwd_bf16)");
-          if (rc0) return rc0;
-          hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, x_nchw, xh, w, bias, static_cast<uint16_t*>(pooled),
-                             argmax, H, W, Hp, Wp, RS);
-        }
-      }
-    });
-  } else if (pooled_is_bf16 == 3) { C0_FWD_LAUNCH(2); } else if (pooled_is_bf16) { C0_FWD_LAUNCH(1); } else { C0_FWD_LAUNCH(0); }
-#undef C0_FWD_LAUNCH
-  return check_hip(hipGetLastError(), "conv0_fwd launch");
+  const int nblk = (Hp + C0_FR - 1) / C0_FR;
+  const dim3 grid(nblk, B);
+  const hipStream_t s = (hipStream_t)stream;
+  uint16_t* const pooled16 = static_cast<uint16_t*>(pooled);
+  const bool mfma16 = pooled_is_bf16 == 2 || pooled_is_bf16 == 4;     // bf16 MFMA (image and weights rounded to bf16), bf16 output
+  if (mfma16) VQA_REQUIRE((int64_t)Hp * Wp * Co * 2 < (1LL << 31), "vqa_conv0_relu_pool_fwd: one pooled image reaches 2 GiB");
+  if (pooled_is_bf16 == 4) VQA_REQUIRE(W <= 512, "vqa_conv0_relu_pool_fwd: image too wide for the C16 kernel (W=%d)", W);
+  return c0_dispatch(Ci, Co / 32, [&](auto ci, auto tn) {
+    constexpr int kCI = decltype(ci)::value, kTN = decltype(tn)::value;
+    if (pooled_is_bf16 == 4)        // C16: persistent, register-prefetched, bf16 patch
+      return with_flag(xh != 0, [&](auto fx) {
+        constexpr bool XH = decltype(fx)::value;
+        constexpr int waves = XH ? 8 : 16;
+        return launch_kernel(conv0_fwd_c16_kernel<kCI, kTN, XH>, {"attr(conv0_fwd_c16)", "conv0_fwd launch"},
+                             c0_persistent_grid(XH ? 2 : 1, B * nblk), 64 * waves, (int)c0_fwd_c16_lds(Ci, W, Co, waves), s, x_nchw, w,
+                             bias, pooled16, argmax, B, H, W, Hp, Wp, c0_c16_stride(W), nblk);
+      });
+    if (mfma16)
+      return launch_kernel(conv0_fwd_bf16_kernel<kCI, kTN, false>, {"attr(conv0_fwd_bf16)", "conv0_fwd launch"}, grid, 256,
+                           (int)c0_fwd_lds(Ci, W, Co, false), s, x_nchw, xh, w, bias, pooled16, argmax, H, W, Hp, Wp, RS);
+    auto fwd = [&](auto ob) {       // OB: 0 fp32, 1 bf16, 2 x3-packed
+      constexpr int OB = decltype(ob)::value;
+      return launch_kernel(conv0_fwd_kernel<kCI, kTN, OB>, {"attr(conv0_fwd)", "conv0_fwd launch"}, grid, 256,
+                           (int)c0_fwd_lds(Ci, W, Co, OB == 0), s, x_nchw, xh, w, bias, pooled, argmax, H, W, Hp, Wp, RS);
+    };
+    return pooled_is_bf16 == 3 ? fwd(std::integral_constant<int, 2>{})
+           : pooled_is_bf16    ? fwd(std::integral_constant<int, 1>{})
+                               : fwd(std::integral_constant<int, 0>{});
+  });
 }
 
 int64_t vqa_conv0_wgrad_workspace_bytes(int Co) { return (int64_t)kC0Blocks * (32 + 1) * Co * 4; }
@@ -991,96 +948,51 @@ int vqa_conv0_wgrad(const void* x_nchw, int x_is_fp16, const float* dpooled, con
                     int Ci, int H, int W, int Co, float* workspace, int64_t workspace_bytes, vqa_stream_t stream) {
   VQA_REQUIRE(x_nchw && dpooled && argmax && dw && dbias && workspace, "vqa_conv0_wgrad: null pointer");
   VQA_REQUIRE(c0_supported(Ci, H, W, Co, 1), "vqa_conv0_wgrad: unsupported shape Ci=%d H=%d W=%d Co=%d", Ci, H, W, Co);
-  if (workspace_bytes < vqa_conv0_wgrad_workspace_bytes(Co)) {
-    set_error("vqa_conv0_wgrad: workspace too small");
-    return VQA_ERR_WORKSPACE;
-  }
-  const int Hp = (H - 2) / 2, Wp = (W - 2) / 2, RS = c0_round_stride(W, 11);
-  int PLANE = 4 * RS;
-  while (PLANE % 32 != 3) ++PLANE;
-  size_t lds = (((size_t)Ci * PLANE + 3) & ~(size_t)3) * 4 + (size_t)Wp * Co * 5;
-  if (lds < (size_t)(4 * 32 + 4) * Co * 4) lds = (size_t)(4 * 32 + 4) * Co * 4;   // the end-of-kernel combine area
-  int per_cu = (int)((160 * 1024) / lds);            // resident workgroups per CU by LDS (wide images need > 53 KB)
+  const hipStream_t s = (hipStream_t)stream;
+  const int Hp = (H - 2) / 2, Wp = (W - 2) / 2, RS = c0_round_stride(W, 11), PLANE = c0_wgrad_plane(W);
+  const int lds = (int)c0_wgrad_lds(Ci, W, Co);
+  int per_cu = (int)(kC0LdsMax / lds);                 // resident workgroups per CU by LDS (wide images need > 53 KB)
   if (per_cu > 3) per_cu = 3;
-  if (per_cu < 1) per_cu = 1;
-  int blocks = 256 * per_cu;
-  if (blocks > B * Hp) blocks = B * Hp;
-  float* slab = workspace;
-  float* bias_slab = workspace + (int64_t)kC0Blocks * 32 * Co;
-  hipStream_t s = (hipStream_t)stream;
-  const bool prefetch = W <= 256 && Wp * Co <= 8192;     // the register-prefetching form (conv0_wgrad_pf_kernel)
-  C0_DISPATCH(Ci, Co / 32, {
-    if (prefetch && x_is_fp16) {
-      auto kern = conv0_wgrad_pf_kernel<kCI, kTN, true>;
-      int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds, "attr(conv0_wgrad)");
-      if (rc0) return rc0;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, x_nchw, dpooled, argmax, slab, bias_slab, B, H, W, Hp, Wp, RS, PLANE);
-    } else if (prefetch) {
-      auto kern = conv0_wgrad_pf_kernel<kCI, kTN, false>;
-      int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds, "attr(conv0_wgrad)");
-      if (rc0) return rc0;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, x_nchw, dpooled, argmax, slab, bias_slab, B, H, W, Hp, Wp, RS, PLANE);
-    } else {
-      auto kern = conv0_wgrad_kernel<kCI, kTN>;
-      int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds, "attr(conv0_wgrad)");
-      if (rc0) return rc0;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, x_nchw, x_is_fp16 ? 1 : 0, dpooled, argmax, slab, bias_slab, B, H, W,
-                         Hp, Wp, RS, PLANE);
-    }
+  const int blocks = c0_persistent_grid(per_cu, B * Hp);
+  return c0_wgrad_run("vqa_conv0_wgrad", workspace, workspace_bytes, dw, dbias, Ci, Co, blocks, s, [&](float* slab, float* bias_slab) {
+    const KernelNames names{"attr(conv0_wgrad)", "conv0_wgrad launch"};
+    return c0_dispatch(Ci, Co / 32, [&](auto ci, auto tn) {
+      constexpr int kCI = decltype(ci)::value, kTN = decltype(tn)::value;
+      if (W <= 256 && Wp * Co <= 8192)                 // the register-prefetching form
+        return with_flag(x_is_fp16 != 0, [&](auto fx) {
+          return launch_kernel(conv0_wgrad_pf_kernel<kCI, kTN, decltype(fx)::value>, names, blocks, 256, lds, s, x_nchw, dpooled,
+                               argmax, slab, bias_slab, B, H, W, Hp, Wp, RS, PLANE);
+        });
+      return launch_kernel(conv0_wgrad_kernel<kCI, kTN>, names, blocks, 256, lds, s, x_nchw, x_is_fp16 ? 1 : 0, dpooled, argmax, slab,
+                           bias_slab, B, H, W, Hp, Wp, RS, PLANE);
+    });
   });
-  int rc = check_hip(hipGetLastError(), "conv0_wgrad launch");
-  if (rc) return rc;
-  hipLaunchKernelGGL(conv0_wgrad_reduce_kernel, dim3(9 * Ci + 1), dim3(256), 0, s, slab, bias_slab, dw, dbias,
-                     blocks, 9 * Ci, Co);
-  return check_hip(hipGetLastError(), "conv0_wgrad_reduce launch");
 }
 
 int vqa_conv0_wgrad_bf16(const void* x_nchw, int x_is_fp16, const void* dpooled_bf16, const uint8_t* argmax, float* dw,
                          float* dbias, int B, int Ci, int H, int W, int Co, float* workspace, int64_t workspace_bytes,
                          vqa_stream_t stream) {
   VQA_REQUIRE(x_nchw && dpooled_bf16 && argmax && dw && dbias && workspace, "vqa_conv0_wgrad_bf16: null pointer");
-  VQA_REQUIRE(c0_supported(Ci, H, W, Co, 1) && Ci <= 3, "vqa_conv0_wgrad_bf16: unsupported shape Ci=%d H=%d W=%d Co=%d", Ci, H, W, Co);
+  VQA_REQUIRE(c0_supported(Ci, H, W, Co, 1), "vqa_conv0_wgrad_bf16: unsupported shape Ci=%d H=%d W=%d Co=%d", Ci, H, W, Co);
   VQA_REQUIRE(((uintptr_t)dpooled_bf16 % 16) == 0 && ((uintptr_t)argmax % 8) == 0, "vqa_conv0_wgrad_bf16: dpooled / argmax alignment");
-  if (workspace_bytes < vqa_conv0_wgrad_workspace_bytes(Co)) {
-    set_error("vqa_conv0_wgrad_bf16: workspace too small");
-    return VQA_ERR_WORKSPACE;
-  }
+  const hipStream_t s = (hipStream_t)stream;
   const int Hp = (H - 2) / 2, Wp = (W - 2) / 2;
   const int NG = (2 * Wp + 15) / 16;
   const int RSTR = 32 * NG + 16;                       // bytes per staged image row (+16: rows start on different banks)
-  size_t lds = (size_t)3 * Ci * 4 * RSTR + (size_t)8 * NG * Co * 3;
-  if (lds < (size_t)(4 * 32 + 4) * Co * 4) lds = (size_t)(4 * 32 + 4) * Co * 4;   // the end-of-kernel combine area
-  lds = (lds + 15) & ~(size_t)15;
-  VQA_REQUIRE(lds <= 160 * 1024 && W <= 512 && 8 * NG * Co <= 16384, "vqa_conv0_wgrad_bf16: image too wide (W=%d)", W);
-  int per_cu = (int)((160 * 1024) / lds);
-  if (per_cu > 2) per_cu = 2;                          // 2 waves per SIMD: the prefetch registers
-  int blocks = 256 * per_cu;
-  if (blocks > B * Hp) blocks = B * Hp;
-  float* slab = workspace;
-  float* bias_slab = workspace + (int64_t)kC0Blocks * 32 * Co;
-  hipStream_t s = (hipStream_t)stream;
-  C0_DISPATCH(Ci, Co / 32, {
-    if constexpr (kCI <= 3) {
-      if (x_is_fp16) {
-        auto kern = conv0_wgrad_bf16_kernel<kCI, kTN, true>;
-        int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds, "attr(conv0_wgrad_bf16)");
-        if (rc0) return rc0;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, x_nchw, static_cast<const uint16_t*>(dpooled_bf16), argmax, slab,
-                           bias_slab, B, H, W, Hp, Wp, RSTR, NG);
-      } else {
-        auto kern = conv0_wgrad_bf16_kernel<kCI, kTN, false>;
-        int rc0 = ensure_dyn_smem(reinterpret_cast<const void*>(kern), (int)lds, "attr(conv0_wgrad_bf16)");
-        if (rc0) return rc0;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, x_nchw, static_cast<const uint16_t*>(dpooled_bf16), argmax, slab,
-                           bias_slab, B, H, W, Hp, Wp, RSTR, NG);
-      }
-    }
+  const size_t lds = c0_wgrad_bf16_lds(Ci, RSTR, NG, Co);
+  const int per_cu = kC0LdsMax / lds > 2 ? 2 : (int)(kC0LdsMax / lds);      // 2 waves per SIMD: the prefetch registers
+  const int blocks = c0_persistent_grid(per_cu, B * Hp);
+  return c0_wgrad_run("vqa_conv0_wgrad_bf16", workspace, workspace_bytes, dw, dbias, Ci, Co, blocks, s, [&](float* slab, float* bias_slab) {
+    VQA_REQUIRE(lds <= kC0LdsMax && W <= 512 && 8 * NG * Co <= 16384, "vqa_conv0_wgrad_bf16: image too wide (W=%d)", W);
+    return c0_dispatch(Ci, Co / 32, [&](auto ci, auto tn) {
+      constexpr int kCI = decltype(ci)::value, kTN = decltype(tn)::value;
+      return with_flag(x_is_fp16 != 0, [&](auto fx) {
+        return launch_kernel(conv0_wgrad_bf16_kernel<kCI, kTN, decltype(fx)::value>, {"attr(conv0_wgrad_bf16)", "conv0_wgrad_bf16 launch"},
+                             blocks, 256, (int)lds, s, x_nchw, static_cast<const uint16_t*>(dpooled_bf16), argmax, slab, bias_slab, B, H,
+                             W, Hp, Wp, RSTR, NG);
+      });
+    });
   });
-  int rc = check_hip(hipGetLastError(), "conv0_wgrad_bf16 launch");
-  if (rc) return rc;
-  hipLaunchKernelGGL(conv0_wgrad_reduce_kernel, dim3(9 * Ci + 1), dim3(256), 0, s, slab, bias_slab, dw, dbias,
-                     blocks, 9 * Ci, Co);
-  return check_hip(hipGetLastError(), "conv0_wgrad_reduce launch");
 }
 
 }  // extern "C"

@@ -116,25 +116,20 @@ __device__ __forceinline__ void conv_pool_epilogue(f32x16 (&acc)[Cfg::TM][Cfg::T
         const __amdgpu_buffer_rsrc_t rp = OB ? buf_rsrc(pooled16 + o0) : buf_rsrc(pooled + o0), ra = buf_rsrc(amax + o0);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          float best = acc[i][j][4 * g];
-          int a = 0;
-          if (acc[i][j][4 * g + 1] > best) { best = acc[i][j][4 * g + 1]; a = 1; }
-          if (acc[i][j][4 * g + 2] > best) { best = acc[i][j][4 * g + 2]; a = 2; }
-          if (acc[i][j][4 * g + 3] > best) { best = acc[i][j][4 * g + 3]; a = 3; }
-          best += bv;
+          const PoolPick p = pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], bv);
           const bool ok = INNER || (wt + 2 * g + h < nWin && col < Co);
           const uint32_t so = (uint32_t)(2 * g * Co);
 #ifdef VQA_EXP_NOSTORE_ALL   // timing experiments only: the epilogue's arithmetic without its store instructions
           if (Co < 0)
 #endif
           {
-          if (OB) buf_store2(rp, bf16_bits(best > 0.f ? best : 0.f), ok ? 2u * vl : BUF_OOB, 2u * so);
-          else buf_store4(rp, best > 0.f ? best : 0.f, ok ? 4u * vl : BUF_OOB, 4u * so);
+          if (OB) buf_store2(rp, bf16_bits(p.v), ok ? 2u * vl : BUF_OOB, 2u * so);
+          else buf_store4(rp, p.v, ok ? 4u * vl : BUF_OOB, 4u * so);
           }
 #if defined(VQA_EXP_NOSTORE_ALL) || defined(VQA_EXP_NOSTORE_AM)
           if (Co < 0)
 #endif
-          buf_store1(ra, best > 0.f ? (uint8_t)a : (uint8_t)4, ok ? vl : BUF_OOB, so);
+          buf_store1(ra, p.code, ok ? vl : BUF_OOB, so);
         }
       }
     }
@@ -167,15 +162,10 @@ __device__ __forceinline__ void conv_pool_epilogue_staged(f32x16 (&acc)[Cfg::TM]
     for (int i = 0; i < Cfg::TM; ++i) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        float best = acc[i][j][4 * g];
-        int a = 0;
-        if (acc[i][j][4 * g + 1] > best) { best = acc[i][j][4 * g + 1]; a = 1; }
-        if (acc[i][j][4 * g + 2] > best) { best = acc[i][j][4 * g + 2]; a = 2; }
-        if (acc[i][j][4 * g + 3] > best) { best = acc[i][j][4 * g + 3]; a = 3; }
-        best += bv;
+        const PoolPick p = pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], bv);
         const int w = 8 * i + 2 * g + h;                                 // window of the wave's 16 (rows 32i + 8g + 4h ..+3)
-        sp[w * 64 + 32 * j + c] = best > 0.f ? best : 0.f;
-        sa[w * 64 + 32 * j + c] = best > 0.f ? (uint8_t)a : (uint8_t)4;
+        sp[w * 64 + 32 * j + c] = p.v;
+        sa[w * 64 + 32 * j + c] = p.code;
       }
     }
   }

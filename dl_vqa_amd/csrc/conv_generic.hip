@@ -59,6 +59,7 @@ __global__ __launch_bounds__(256) void convk_relu_pool_kernel(const float4* __re
     uint32_t am = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      // pool_pick's rule (common.hpp) without a bias, spelled out: with the helper the kernel's VGPR count moves (42 -> 40)
       float best = a0[i];
       uint32_t a = 0;
       if (a1[i] > best) { best = a1[i]; a = 1; }

@@ -1,34 +1,12 @@
 // Host-side scaffolding shared by conv.hip, conv_bf16.hip and conv_x3.hip (included inside namespace vqa, after
-// conv_device.inc): geometry checks, the batch-chunk walk, the split-K plan and workspace layout of wgrad, launch helpers.
-template <class K>
-static int set_smem(K kern, int bytes, const char* what) {
-  return ensure_dyn_smem(reinterpret_cast<const void*>(kern), bytes, what);
-}
-
-// ---- launch helpers
-struct KernelNames { const char *attr, *launch; };      // what ensure_dyn_smem / check_hip report
-template <class K, class... A>
-static int launch_kernel(K kern, KernelNames n, int grid, int threads, int lds, hipStream_t s, A... args) {
-  int rc = set_smem(kern, lds, n.attr);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, args...);
-  return check_hip(hipGetLastError(), n.launch);
-}
+// conv_device.inc): geometry checks, the batch-chunk walk, the split-K plan and workspace layout of wgrad.  The generic launch
+// helpers (launch_kernel, with_flag) are in common.hpp.
 // a kernel with one workgroup per tile and its persistent twin take the same arguments; only the grid differs
 template <class KP, class K, class... A>
 static int launch_tiles(bool persistent, KP pkern, KernelNames pn, int pgrid, K kern, KernelNames n, int grid, int threads,
                         int lds, hipStream_t s, A... args) {
   return persistent ? launch_kernel(pkern, pn, pgrid, threads, lds, s, args...)
                     : launch_kernel(kern, n, grid, threads, lds, s, args...);
-}
-
-// runtime flag -> template flag: f is a generic lambda that reads decltype(flag)::value, so a tile choice is written once
-template <bool V> struct Flag { static constexpr bool value = V; };
-template <class F>
-static int with_flag(bool v, F&& f) { return v ? f(Flag<true>{}) : f(Flag<false>{}); }
-template <class F>
-static int with_flags(bool a, bool b, F&& f) {
-  return with_flag(a, [&](auto fa) { return with_flag(b, [&](auto fb) { return f(fa, fb); }); });
 }
 
 static int check_geom(const char* fn, const ConvGeom& g) {

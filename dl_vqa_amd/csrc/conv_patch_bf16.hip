@@ -400,6 +400,7 @@ __global__ __launch_bounds__(512, 2) void pconv_kernel(const PcParams P) {
             const int i = 2 * ip + ii;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
+              // pool_pick's rule (common.hpp), spelled out: the helper costs pconv_kernel<4, 0, false> a VGPR (216 -> 217)
               float best = acc[i][j][4 * g];
               int am = 0;
               if (acc[i][j][4 * g + 1] > best) { best = acc[i][j][4 * g + 1]; am = 1; }

@@ -304,20 +304,15 @@ __device__ __forceinline__ void conv_pool_epilogue_x3p(f32x16 (&acc)[Cfg::TM][Cf
         const __amdgpu_buffer_rsrc_t rp = buf_rsrc(pooled + 6 * o0), ra = buf_rsrc(amax + o0);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          float best = acc[i][j][4 * g];
-          int a = 0;
-          if (acc[i][j][4 * g + 1] > best) { best = acc[i][j][4 * g + 1]; a = 1; }
-          if (acc[i][j][4 * g + 2] > best) { best = acc[i][j][4 * g + 2]; a = 2; }
-          if (acc[i][j][4 * g + 3] > best) { best = acc[i][j][4 * g + 3]; a = 3; }
-          best += bv;
+          const PoolPick p = pool_pick(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], bv);
           const bool ok = INNER || (wt + 2 * g + h < nWin && col < Co);
           const uint32_t so = (uint32_t)(2 * g * Co);
           uint16_t sh, sm, sl;
-          split1(best > 0.f ? best : 0.f, sh, sm, sl);
+          split1(p.v, sh, sm, sl);
           buf_store2(rp, sh, ok ? vx : BUF_OOB, 6u * so);
           buf_store2(rp, sm, ok ? vx : BUF_OOB, 6u * so + 8u);
           buf_store2(rp, sl, ok ? vx : BUF_OOB, 6u * so + 16u);
-          buf_store1(ra, best > 0.f ? (uint8_t)a : (uint8_t)4, ok ? vl : BUF_OOB, so);
+          buf_store1(ra, p.code, ok ? vl : BUF_OOB, so);
         }
       }
     }

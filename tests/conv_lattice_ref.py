@@ -204,7 +204,12 @@ FP32_CASES = [      # B, H, W, Ci, Co, stride: fp32 implicit GEMM
 ]
 KNOB_CASES = [(2, 30, 30, 64, 128, 1), (1, 30, 34, 128, 256, 1)]        # the 64 -> 128 and 128 -> 256 shapes, under forced tiles
 CHUNK_CASE = (5, 26, 26, 32, 64, 1)                                     # VQA_CONV_CHUNK=2: 2 + 2 + 1 images
-CONV0_CASES = [(2, 3, 20, 24, 32), (3, 3, 31, 28, 64), (1, 1, 9, 12, 32), (1, 3, 14, 448, 64)]     # B, Ci, H, W, Co
+# B, Ci, H, W, Co; (2, 2, 13, 20, 64): Ci = 2, Hp = 5 (a one-row tail block), Wp = 9 (a partial 8-window tile)
+CONV0_CASES = [(2, 3, 20, 24, 32), (3, 3, 31, 28, 64), (1, 1, 9, 12, 32), (1, 3, 14, 448, 64), (2, 2, 13, 20, 64)]
+# More work than the persistent first-block kernels have workgroups, so each takes a second item: Hp = 5 is two row blocks
+# per image for the C16 forward (grids of 256 and 512) and five pooled rows for the prefetching weight gradients (512 and
+# 768); B = 257 is the smallest batch with 2 B > 512 (5 B > 768 holds from B = 154 on)
+CONV0_PERSISTENT_CASE = (257, 3, 12, 12, 32)
 # fp32x3 takes layers with 2 * Wp >= 32 only: at stride 2 the 41-wide map of FP32_CASES (Wp = 10) is not one of them, a
 # 67-wide one (Wo = 33, Wp = 16: the narrowest admitted, with a dropped pool column) is
 X3_CASES = [(2, 38, 42, 32, 96, 1), (2, 36, 36, 64, 128, 1), (2, 37, 67, 32, 64, 2)]
@@ -222,7 +227,7 @@ def key(B, H, W, Ci, Co, stride=1, ks=3):
 def all_keys():
     """every case of tests/test_conv_lattice_gpu.py, once"""
     keys = [key(*c) for c in FP32_CASES + [CHUNK_CASE] + X3_CASES + BF16_CASES]
-    keys += [(B, Ci, H, W, Co, 3, 1) for (B, Ci, H, W, Co) in CONV0_CASES]
+    keys += [(B, Ci, H, W, Co, 3, 1) for (B, Ci, H, W, Co) in CONV0_CASES + [CONV0_PERSISTENT_CASE]]
     keys += [key(*c) for c in PCONV_CASES + PCONVF_CASES]
     keys += [(B, Ci, H, W, Co, ks, stride) for (B, H, W, Ci, Co, ks, stride, _) in CONVK_CASES]
     return list(dict.fromkeys(keys))
@@ -231,7 +236,7 @@ def all_keys():
 def bf16_keys():
     """the cases whose operands the bf16 kernels read as bf16 (the x3 split of a bf16 value is the value itself)"""
     return list(dict.fromkeys([key(*c) for c in X3_CASES + BF16_CASES + PCONV_CASES] +
-                              [(B, Ci, H, W, Co, 3, 1) for (B, Ci, H, W, Co) in CONV0_CASES]))
+                              [(B, Ci, H, W, Co, 3, 1) for (B, Ci, H, W, Co) in CONV0_CASES + [CONV0_PERSISTENT_CASE]]))
 
 
 # The default recipe with seed = H; small maps and few channels need more structure to reach the window counts that

@@ -183,8 +183,7 @@ def test_fp32_forward_epilogue_staged_and_direct(ops, knob, forced):
 
 
 # ----------------------------------------------------------------------------- first block (dedicated kernels)
-@pytest.mark.parametrize("shape", L.CONV0_CASES, ids=str)
-def test_first_block(ops, shape):
+def run_first_block(ops, shape):
     """conv0 forward in its five output modes from float and __half images, its two weight-gradient kernels and its
     backward-data kernel.  The bytes of every forward variant equal the reference's -- and so one another's and those of
     the generic kernel on nchw_to_nhwc4(x), which is run here as well: not one byte may differ."""
@@ -238,6 +237,23 @@ def test_first_block(ops, shape):
     dv = ops.conv0_dgrad(dev(dy_r), am, wdv, (B, Ci, H, W), round_w_bf16=True)      # the lattice weights are bf16 values
     t.eq("dgrad with bf16-rounded weights", dv, ref.dx)
     t.done()
+
+
+@pytest.mark.parametrize("shape", L.CONV0_CASES, ids=str)
+def test_first_block(ops, shape):
+    run_first_block(ops, shape)
+
+
+def test_first_block_persistent_kernels_take_a_second_item(ops):
+    """The C16 forward walks (image, block of 4 pooled rows) items on min(256 or 512, items) workgroups, the prefetching
+    weight gradients walk pooled rows on min(512 or 768, rows): here every one of them has more work than workgroups, so the
+    prefetch of the next item, the store of its registers and the compute in between run a second time.  dW and dbias sum
+    257 * 100 pixels per weight; the lattice's budget still holds there (sum |a||b| = 5.6e4 < 2^22, asserted for this case in
+    tests/test_conv_lattice_ref_cpu.py), so they are compared for equality like everything else."""
+    B, Ci, H, W, Co = L.CONV0_PERSISTENT_CASE
+    _, _, Hp, _ = L.out_hw(H, W, 3, 1)
+    assert Hp == 5 and B * 2 > 512 and B * 5 > 768 and B * 5 > 512
+    run_first_block(ops, L.CONV0_PERSISTENT_CASE)
 
 
 # ----------------------------------------------------------------------------- fp32 on the bf16 matrix cores (x3)
