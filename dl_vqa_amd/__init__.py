@@ -4,6 +4,8 @@
 backward run on hand-written HIP kernels (csrc/, bound through the C ABI in include/vqa_hip.h);
 ``train`` mirrors the reference training procedure (train.py) with a fused device-side loss and
 Adam; ``distributed.DataParallel`` shards the minibatch over the GPUs of one node with RCCL.
+``VqaNet.encode_images`` / ``answer`` (inference) and ``VqaNet.forward_shared`` / ``train.run_batch_shared`` (training)
+serve batches in which several questions ask about the same image: the image-only work runs once per image.
 """
 from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image  # noqa: F401
 

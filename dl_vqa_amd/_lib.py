@@ -95,6 +95,10 @@ PROTOTYPES = {
     "vqa_att_score_grouped_fwd": (i32, [f32p, f32p, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_att_apply_gather_fwd": (i32, [f32p, f32p, vp, f32p, f32p, i64, i32, i32, i32, i32, i32, vp]),
     "vqa_att_apply_bwd": (i32,[f32p, i64, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, i32, vp]),
+    "vqa_att_score_grouped_drop_fwd": (i32, [f32p, f32p, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, f32, u64, vp]),
+    "vqa_att_apply_gather_bwd": (i32, [f32p, i64, f32p, f32p, vp, vp, vp, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_score_grouped_tiles": (i32, [i32]),
+    "vqa_att_score_grouped_bwd": (i32, [f32p, f32p, f32p, f32p, i32, vp, vp, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, f32, u64, vp]),
     "vqa_softce_fwd_bwd": (i32, [f32p, i64, i64p, i64p, i32, i32, i32, f32, f32p, f32p, f32p, i64, vp]),
     "vqa_colsum_workspace_bytes": (i64, [i64, i32]),
     "vqa_colsum": (i32, [f32p, i64, u8p, i64, i32, f32p, i32, f32p, i64, vp]),

@@ -994,36 +994,87 @@ __global__ void att_apply_gather_fwd_kernel(const float* score, const float* vn,
 }
 
 // pass 1: one wave per (b,p): dprob -> dscore buffer, dvn row written
+// One (sample b, position pp) row against the image row `v` that b weights there: dprob[b][g][pp] = <v, dout[b][g]> and
+// (d != null) d[c] = sum_g probs[b][g][pp] * dout[b][g*C + c].  v: row b*P + pp in vqa_att_apply_bwd, row img[b]*P + pp in
+// vqa_att_apply_gather_bwd -- the (sample, image) form, as in att_apply_fwd_body.
 template <int G>
+__device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dout_ld, const float* probs, const float4* v,
+                                                  float4* d, float* dprob, int64_t b, int pp, int P, int C, int lane) {
+  const int nch = C >> 2;
+  float pr[G], acc[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) { pr[g] = probs[(b * G + g) * P + pp]; acc[g] = 0.f; }
+  for (int c = lane; c < nch; c += 64) {
+    const float4 x = v[c];
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float4 go = reinterpret_cast<const float4*>(dout + b * dout_ld + (int64_t)g * C)[c];
+      acc[g] += x.x * go.x + x.y * go.y + x.z * go.z + x.w * go.w;
+      o.x += pr[g] * go.x; o.y += pr[g] * go.y; o.z += pr[g] * go.z; o.w += pr[g] * go.w;
+    }
+    if (d) d[c] = o;       // d == null: vqa_l2norm_bwd_joined recomputes this branch where it is consumed
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const float s = wave_sum(acc[g]);
+    if (lane == 0) dprob[(b * G + g) * P + pp] = s;
+  }
+}
+
+// GATHER (vqa_att_apply_gather_bwd, several questions per image): sample b weighted the rows of image img[b] of vn [N][P][C];
+// dvn is null there -- the per-image sum is the kernel below.
+template <int G, bool GATHER>
 __global__ void att_apply_bwd_rows_kernel(const float* dout, int64_t dout_ld, const float* probs, const float* vn,
-                                          float* dprob, float* dvn, int64_t M, int P, int C) {
+                                          const int* img, int N, float* dprob, float* dvn, int64_t M, int P, int C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t m = wave; m < M; m += nwaves) {
+    const int64_t b = m / P;
+    const int pp = (int)(m - b * P);
+    int64_t vm = m;
+    if (GATHER) {
+      int n = img[b];
+      n = n < 0 ? 0 : (n >= N ? N - 1 : n);               // a malformed index reads nothing out of bounds
+      vm = (int64_t)n * P + pp;
+    }
+    att_apply_bwd_row<G>(dout, dout_ld, probs, reinterpret_cast<const float4*>(vn + vm * C),
+                         dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr, dprob, b, pp, P, C, lane);
+  }
+}
+
+// Several questions per image: the weighted-sum branch of d loss / d vn summed per IMAGE, one wave per image row (n, pp):
+// dvn[n][pp][c] = sum over the questions b = order[offsets[n] .. offsets[n+1]) in that order, g ascending inside a question,
+// of probs[b][g][pp] * dout[b][g*C + c] -- the row body's sum for one question.  Every row of dvn is written, zeros for an
+// image nobody asks about.
+template <int G>
+__global__ void att_apply_gather_dvn_kernel(const float* dout, int64_t dout_ld, const float* probs, const int* order,
+                                            const int* offsets, float* dvn, int64_t M, int B, int P, int C) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int nch = C >> 2;
   for (int64_t m = wave; m < M; m += nwaves) {
-    const int64_t b = m / P;
-    const int pp = (int)(m - b * P);
-    float pr[G], acc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) { pr[g] = probs[(b * G + g) * P + pp]; acc[g] = 0.f; }
-    const float4* v = reinterpret_cast<const float4*>(vn + m * C);
+    const int64_t n = m / P;
+    const int pp = (int)(m - n * P);
+    int k0 = offsets[n], k1 = offsets[n + 1];
+    k0 = k0 < 0 ? 0 : k0;
+    k1 = k1 > B ? B : k1;
     float4* d = reinterpret_cast<float4*>(dvn + m * C);
     for (int c = lane; c < nch; c += 64) {
-      const float4 x = v[c];
       float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k = k0; k < k1; ++k) {
+        const int64_t b = order[k];
+        if ((uint64_t)b >= (uint64_t)B) continue;
 #pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float4 go = reinterpret_cast<const float4*>(dout + b * dout_ld + (int64_t)g * C)[c];
-        acc[g] += x.x * go.x + x.y * go.y + x.z * go.z + x.w * go.w;
-        o.x += pr[g] * go.x; o.y += pr[g] * go.y; o.z += pr[g] * go.z; o.w += pr[g] * go.w;
+        for (int g = 0; g < G; ++g) {
+          const float pr = probs[(b * G + g) * P + pp];
+          const float4 go = reinterpret_cast<const float4*>(dout + b * dout_ld + (int64_t)g * C)[c];
+          o.x += pr * go.x; o.y += pr * go.y; o.z += pr * go.z; o.w += pr * go.w;
+        }
       }
-      if (dvn) d[c] = o;       // dvn == null: vqa_l2norm_bwd_joined recomputes this branch where it is consumed
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float s = wave_sum(acc[g]);
-      if (lane == 0) dprob[(b * G + g) * P + pp] = s;
+      d[c] = o;
     }
   }
 }
@@ -1480,9 +1531,36 @@ int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, co
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   VQA_REQUIRE(dout && probs && vn && dscore && C % 4 == 0 && dout_ld % 4 == 0, "vqa_att_apply_bwd: bad args");
   const int64_t M = (int64_t)B * P;
-  DISPATCH_G(G, hipLaunchKernelGGL(att_apply_bwd_rows_kernel<kG>, dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
-                                   dout_ld, probs, vn, dscore, dvn, M, P, C));
+  DISPATCH_G(G, hipLaunchKernelGGL((att_apply_bwd_rows_kernel<kG, false>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
+                                   dout_ld, probs, vn, static_cast<const int*>(nullptr), 0, dscore, dvn, M, P, C));
   int rc = check_hip(hipGetLastError(), "att_apply_bwd_rows launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, STREAM, probs, dscore, P, dscore_rowsum);
+  return check_hip(hipGetLastError(), "softmax_bwd launch");
+}
+
+int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                             const int32_t* order, const int32_t* offsets, float* dscore, float* dvn, float* dscore_rowsum,
+                             int N, int B, int P, int C, int G, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
+  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
+  VQA_REQUIRE(dout && probs && vn && dscore && dvn, "vqa_att_apply_gather_bwd: null pointer");
+  VQA_REQUIRE(img && order && offsets, "vqa_att_apply_gather_bwd: null img / order / offsets");
+  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && C >= 4 && C % 4 == 0 && dout_ld % 4 == 0 && dout_ld >= (int64_t)G * C,
+              "vqa_att_apply_gather_bwd: N=%d, B=%d, P=%d, C=%d (a multiple of 4), dout_ld=%lld out of range", N, B, P, C,
+              (long long)dout_ld);
+  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(vn) | reinterpret_cast<uintptr_t>(dvn)) & 15) == 0,
+              "vqa_att_apply_gather_bwd: dout, vn and dvn must be 16-byte aligned");
+  if (B == 0) return VQA_OK;
+  const int64_t M = (int64_t)B * P, Mn = (int64_t)N * P;
+  DISPATCH_G(G, hipLaunchKernelGGL((att_apply_bwd_rows_kernel<kG, true>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
+                                   dout_ld, probs, vn, img, N, dscore, static_cast<float*>(nullptr), M, P, C));
+  int rc = check_hip(hipGetLastError(), "att_apply_gather_bwd_rows launch");
+  if (rc) return rc;
+  DISPATCH_G(G, hipLaunchKernelGGL(att_apply_gather_dvn_kernel<kG>, dim3(grid_for(Mn, 4)), dim3(256), 0, STREAM, dout, dout_ld,
+                                   probs, order, offsets, dvn, Mn, B, P, C));
+  rc = check_hip(hipGetLastError(), "att_apply_gather_dvn launch");
   if (rc) return rc;
   hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, STREAM, probs, dscore, P, dscore_rowsum);
   return check_hip(hipGetLastError(), "softmax_bwd launch");

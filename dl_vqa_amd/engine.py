@@ -490,6 +490,122 @@ class Engine:
         logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
         return logits, probs, score
 
+    # ------------------------------------------------------------------ training through shared image features
+    # fp32 / fp32x3.  v holds every image ONCE; question b looks at image img[b].  The image encoder, the question encoder,
+    # q_lin and the classifier are the forward's own stages, run on N images and B questions; the attention stage runs on one
+    # v' per image (csrc/att_grouped.hip) and its backward sums the image-side gradients over the questions of an image.
+    # Dropout: the image-side sites (SITE_IMAGE, SITE_ATT_V) draw one mask per IMAGE (logical tensor [N, gh, gw, C]); every
+    # question-side site draws per question as forward() does, SITE_ATT_X over [B, P, xld] indexed by the question.
+    def forward_shared(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor,
+                       img: Tensor, training: bool, seed: int, keep: bool, bad_tokens: Optional[Tensor] = None,
+                       need_dx: bool = False):
+        """v [N,C,S,S]; order / offsets / img: device int32 (model.group_by_image and the image index itself).  Returns
+        (logits [B,A], ctx or None), as forward() does."""
+        assert not self.bf16, "forward_shared: fp32 / fp32x3 only"
+        with torch.cuda.device(v.device):
+            return self._forward_shared(P, v, q, q_len, order, offsets, img, training, seed, keep, bad_tokens, need_dx)
+
+    def _forward_shared(self, P, v, q, q_len, order, offsets, img, training, seed, keep, bad_tokens, need_dx):
+        assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
+            "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
+        v = v.contiguous()
+        need_dx = bool(keep and need_dx)
+        dev = v.device
+        q = q.to(device=dev, dtype=torch.int64).contiguous()
+        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
+        B, T = q.shape
+        N = v.shape[0]
+        C, mid, Dc, GC, G = self.C, self.mid, self.Dc, self.GC, self.G
+        tr = bool(training)
+        p_txt, p_img, p_att, p_cls = (self.p_text, self.p_image, self.p_att, self.p_cls) if tr else (0.0, 0.0, 0.0, 0.0)
+        sd = lambda site: _site_seed(seed, site)
+
+        # ---- question encoder on the side stream, under the convolutions (as forward())
+        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, sd(SITE_TEXT), bad_tokens)       # [T,B,E]
+        combined = torch.empty(B, Dc, dtype=torch.float32, device=dev)
+        (lstm, x16), text_done = self._on_side_stream(dev, lambda: self._question_encoder(P, x_emb, q_len, combined, False))
+
+        # ---- image encoder on the N images, image dropout + L2 normalisation, v' = v_conv(drop(vn)): once per image
+        enc = self._image_encoder(P, v, keep, need_dx)
+        pooled = enc.out
+        Pn = pooled.shape[1] * pooled.shape[2]
+        if p_att > 0:
+            vn, norm, v_in = ops.l2norm_fwd(pooled, p_img, sd(SITE_IMAGE), drop2=(p_att, sd(SITE_ATT_V), torch.float32))
+        else:
+            vn, norm = ops.l2norm_fwd(pooled, p_img, sd(SITE_IMAGE))
+            v_in = vn
+        vprime = torch.empty(N * Pn, mid, dtype=torch.float32, device=dev)
+        ops.gemm(v_in, P["attention.v_conv.weight"], vprime, N * Pn, mid, C, tag=21, x3=self._x3_gemm(N * Pn))
+        torch.cuda.current_stream(dev).wait_event(text_done)
+
+        # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
+        qp, q_in, ld_q, fc = self._q_lin_fwd(P, combined[:, GC:], p_att, seed)
+        score = ops.att_score_grouped_drop_fwd(vprime, qp, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"],
+                                               order, offsets, N, B, Pn, self.att_mode, p_att, sd(SITE_ATT_X))
+        probs = ops.att_apply_gather_fwd(score, vn.view(N, Pn, C), img, combined, Dc)
+
+        # ---- classifier
+        logits, c_in, h1, h1d = self._classifier_fwd(P, combined, p_cls, seed, fc)
+        if not keep:
+            return logits, None
+        ctx = SimpleNamespace(B=B, N=N, T=T, Pn=Pn, q=q, q_len=q_len, order=order, offsets=offsets, img=img, acts=enc.acts,
+                              idxs=enc.idxs, wds=enc.wds, vn=vn, norm=norm, x_emb=x_emb, x16=x16, lstm=lstm, v_in=v_in, q_in=q_in,
+                              ld_q=ld_q, probs=probs, c_in=c_in, h1=h1, h1d=h1d, fast0=enc.fast0, use_pc=enc.use_pc, fc=fc,
+                              vprime=vprime, qp=qp, p_img=p_img, p_txt=p_txt, p_att=p_att, p_cls=p_cls, seed=seed,
+                              stages=dict(pooled=pooled, score=score, combined=combined), need_dx=need_dx, v_dtype=v.dtype,
+                              v_shape=tuple(v.shape))
+        return logits, ctx
+
+    def backward_shared(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
+                        on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:
+        """backward() for a forward_shared context: the image gradient it returns is [N,C,S,S], the questions of an image
+        summed."""
+        with torch.cuda.device(dlogits.device):
+            return self._backward_shared(P, ctx, dlogits, Gr, on_ready)
+
+    def _backward_shared(self, P, ctx, dlogits, Gr, on_ready):
+        dev = dlogits.device
+        ready = on_ready if on_ready is not None else (lambda group: None)
+        B, N, Pn = ctx.B, ctx.N, ctx.Pn
+        G, C, mid, Dc = self.G, self.C, self.mid, self.Dc
+        sd = lambda site: _site_seed(ctx.seed, site)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        dcomb = self._classifier_bwd(P, ctx, dlogits, Gr)
+        ready("classifier")
+        # ---- attention apply + scores: dvn = the weighted-sum branch of d loss / d vn, summed per image
+        ds_rows = new(B, G, 1)
+        dscore, dvn = ops.att_apply_gather_bwd(dcomb, Dc, ctx.probs, ctx.vn.view(N, Pn, C), ctx.img, ctx.order, ctx.offsets,
+                                               rowsum=ds_rows)
+        ops.sum_bgp(ds_rows, Gr["attention.x_conv.bias"])
+        wx = P["attention.x_conv.weight"].view(G, -1)
+        dvprime, dq_part, dwx_part, NT = ops.att_score_grouped_bwd(dscore, ctx.vprime, ctx.qp, wx, ctx.order, ctx.offsets, N, B, Pn,
+                                                                   self.att_mode, ctx.p_att, sd(SITE_ATT_X))
+        ops.colsum(dwx_part, N * NT, wx.numel(), Gr["attention.x_conv.weight"])
+        dqp = new(B, mid)
+        ops.sum_parts(dq_part, dqp, B, NT, mid)
+        # ---- v_conv over the N * Pn image rows: dW = dv'^T . v_in, dv_in = dv' . Wv
+        gx3 = self._x3_gemm(N * Pn)
+        ops.gemm(dvprime, ctx.v_in, Gr["attention.v_conv.weight"], mid, C, N * Pn, transA=True, transB=False, lda=mid, ldb=C,
+                 tag=44, x3=gx3)
+        dv_in = new(N * Pn, C)
+        ops.gemm(dvprime, P["attention.v_conv.weight"], dv_in, N * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
+        self._q_lin_bwd(P, ctx, dqp, dcomb, Gr)
+        ready("attention")
+
+        def question_branch():
+            self._question_bwd(P, ctx, dcomb, Gr)
+            ready("text")
+
+        _, text_done = self._on_side_stream(dev, question_branch, backward=True)
+        # ---- image side: join the two branches of d loss / d vn (attention.drop on v, models/model.py:185), L2-norm backward,
+        # then the conv blocks.  (vqa_l2norm_bwd_joined recomputes a per-SAMPLE weighted sum and cannot be used here.)
+        ops.dropout_add(dv_in, dvn, ctx.p_att, sd(SITE_ATT_V))
+        dP = ops.l2norm_bwd(dvn, ctx.vn, ctx.norm, ctx.p_img, sd(SITE_IMAGE)).view_as(ctx.acts[-1])
+        dv = self._conv_bwd(P, ctx, dP, Gr)
+        ready("image")
+        torch.cuda.current_stream(dev).wait_event(text_done)
+        return dv
+
     # ------------------------------------------------------------------ backward
     def backward(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
                  on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:
@@ -584,7 +700,15 @@ class Engine:
               x3=gx3)
         dv_in = new(B * Pn, C)
         _gemm(dxpre, wv_op, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
-        # ---- q_lin
+        self._q_lin_bwd(P, ctx, dqp, dcomb, Gr)
+        return dv_in
+
+    def _q_lin_bwd(self, P, ctx, dqp, dcomb, Gr):
+        """Gradients of q_lin from dqp = d loss / d q' [B, mid]; adds d loss / d (question features) into dcomb[:, GC:]."""
+        B = ctx.B
+        mid, Dc, GC, Q = self.mid, self.Dc, self.GC, self.Q
+        sd = lambda site: _site_seed(ctx.seed, site)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dcomb.device)
         ops.colsum(dqp, B, mid, Gr["attention.q_lin.bias"])
         fc = ctx.fc
         if fc is not None:
@@ -602,7 +726,6 @@ class Engine:
             if ctx.p_att > 0:
                 ops.dropout(dq_in, ctx.p_att, sd(SITE_ATT_Q), out=dq_in)
             ops.add2d(dcomb[:, GC:], Dc, dq_in, Q, dcomb[:, GC:], Dc, B, Q)
-        return dv_in
 
     def _question_bwd(self, P, ctx, dcomb, Gr):
         """BPTT over the masked steps, the LSTM weight gradients of every direction and the embedding gradient, on the
@@ -670,12 +793,17 @@ class Engine:
         """L2-norm (+ dropout) backward, then the conv blocks from the last to the first.  Returns the image gradient
         (ctx.need_dx) or None."""
         sd = lambda site: _site_seed(ctx.seed, site)
-        dv = None
         c16_hw = tuple(ctx.idxs[-1].shape[2:4]) if self.bf16 and ctx.use_pc else None   # channel-blocked for the routed patches
         dP = ops.l2norm_bwd_joined(dcomb, self.Dc, ctx.probs, dv_in, ctx.p_att, sd(SITE_ATT_V), ctx.vn, ctx.norm, ctx.p_img,
                                    sd(SITE_IMAGE), out_dtype=torch.bfloat16 if self.bf16 else torch.float32, c16_hw=c16_hw)
         if c16_hw is None:
             dP = dP.view_as(ctx.acts[-1])
+        return self._conv_bwd(P, ctx, dP, Gr)
+
+    def _conv_bwd(self, P, ctx, dP, Gr):
+        """The conv blocks from the last to the first, from dP = d loss / d (the last pooled activation).  Returns the image
+        gradient (ctx.need_dx) or None."""
+        dv = None
         for l in range(self.L - 1, -1, -1):
             if self.ks != 3:
                 dP = ops.convk_bwd(ctx.acts[l], dP, ctx.idxs[l], ctx.wds[l], Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"],

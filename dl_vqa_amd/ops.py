@@ -510,6 +510,53 @@ def att_apply_gather_fwd(score, vn, img, out, out_ld):
     return probs
 
 
+def att_score_grouped_drop_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P: int, mode: int, p: float,
+                               seed: int) -> torch.Tensor:
+    """att_score_grouped_fwd with the x_conv dropout mask drop_scale(seed, (b*P + pos)*xld + m) on x (train mode); p = 0
+    runs the same device code as att_score_grouped_fwd."""
+    G, xld = wx.shape[0], wx.shape[1]
+    mid = xld // 2 if mode == 2 else xld
+    _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
+    score = torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+    call("vqa_att_score_grouped_drop_fwd", ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
+         N, B, P, mid, G, mode, p, seed, stream())
+    return score
+
+
+def att_apply_gather_bwd(dout, dout_ld, probs, vn, img, order, offsets, rowsum=None):
+    """att_apply_bwd where sample b weighted the rows of image img[b] (vn [N, P, C]; img / order / offsets device int32):
+    (dscore [B, G, P], dvn [N, P, C] = the weighted-sum branch of d loss / d vn summed over the questions of each image,
+    zeros for an image without questions)."""
+    B, G, P = probs.shape
+    N, C = vn.shape[0], vn.shape[-1]
+    _chk(img, torch.int32), _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert img.numel() == B and order.numel() == B and offsets.numel() == N + 1 and vn.numel() == N * P * C
+    dscore = torch.empty_like(probs)
+    dvn = torch.empty(N, P, C, dtype=torch.float32, device=vn.device)
+    call("vqa_att_apply_gather_bwd", ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(order), ptr(offsets), ptr(dscore), ptr(dvn),
+         ptr(rowsum), N, B, P, C, G, stream())
+    return dscore, dvn
+
+
+def att_score_grouped_bwd(dscore, vprime, qp, wx, order, offsets, N: int, B: int, P: int, mode: int, p: float, seed: int):
+    """Backward of att_score_grouped_drop_fwd: (dvprime [N*P, mid], dq_part [B*NT, mid], dwx_part [N*NT, G*xld], NT);
+    sum_parts(dq_part, out, B, NT, mid) and colsum(dwx_part, N*NT, G*xld, out) finish d loss / d q' and d loss / d wx."""
+    G, xld = wx.shape[0], wx.shape[1]
+    mid = xld // 2 if mode == 2 else xld
+    _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
+    assert dscore.shape == (B, G, P) and dscore.is_contiguous()
+    NT = _lib.load().vqa_att_score_grouped_tiles(P)
+    dev = vprime.device
+    dvprime = torch.empty(N * P, mid, dtype=torch.float32, device=dev)
+    dq_part = torch.empty(B * NT, mid, dtype=torch.float32, device=dev)
+    dwx_part = torch.empty(N * NT, G * xld, dtype=torch.float32, device=dev)
+    call("vqa_att_score_grouped_bwd", ptr(dscore), ptr(vprime), ptr(qp), ptr(wx), xld, ptr(order), ptr(offsets), ptr(dvprime),
+         ptr(dq_part), ptr(dwx_part), N, B, P, mid, G, mode, p, seed, stream())
+    return dvprime, dq_part, dwx_part, NT
+
+
 def att_apply_bwd(dout, dout_ld, probs, vn, dvn_out=None, rowsum=None, want_dvn=True):
     """rowsum: optional [B, G] output, sum over positions of dscore (per-sample x_conv bias gradient).
     want_dvn=False: the weighted-sum branch of d loss / d vn is not written (l2norm_bwd_joined recomputes it)."""

@@ -95,6 +95,29 @@ def run_batch(model, log_softmax, batch_data, max_answers, batch_divisor: Option
     return batch_loss, batch_score
 
 
+def run_batch_shared(model, batch_data, max_answers, image_index, batch_divisor: Optional[int] = None):
+    """run_batch for a batch whose images are deduplicated: batch_data is the loader's 7-tuple with v [N,3,S,S] holding
+    every image once, everything else per question; question b looks at image image_index[b] (a host list or an integer
+    tensor of B entries in [0, N)).  Same fused loss and score; the loss is divided by the number of QUESTIONS
+    (train.py:206 divides by the batch, and a sample of the reference's batch is a question).  The conv blocks and v_conv
+    run once per image, forward and backward (VqaNet.forward_shared, which also states the dropout semantics)."""
+    v, q, a_indices, a_values, a_length, idx, q_len = batch_data
+    n_index = len(image_index) if not torch.is_tensor(image_index) else image_index.numel()
+    if n_index != q.shape[0]:
+        raise ValueError(f"run_batch_shared: {n_index} image_index entries for {q.shape[0]} questions")
+    dev = next(model.parameters()).device
+    v = v.to(dev, non_blocking=True)
+    q = q.to(dev, non_blocking=True)
+    a_indices = a_indices.to(dev, non_blocking=True)
+    a_values = a_values.to(dev, non_blocking=True)
+    validate_question_lengths(q_len, q.shape[1])
+    q_len = q_len.to(dev, non_blocking=True)
+    if v.dtype not in (torch.float32, torch.float16):
+        v = v.float()
+    y_hat = model.forward_shared(v, q, q_len, image_index)
+    return soft_ce_loss_and_score(y_hat, a_indices, a_values, batch_divisor)
+
+
 # ------------------------------------------------------------------ optimiser
 def update_learning_rate(optimizer, iteration, initial_lr):
     """train.py:31-35."""

@@ -27,7 +27,10 @@ extern "C" {
 #endif
 
 /* Bumped whenever an exported entry point changes its argument list or disappears (round 1: 1, round 2: 2, round 3: 3).
- * dl_vqa_amd/_lib.py parses this line and refuses a library that answers differently. */
+ * dl_vqa_amd/_lib.py parses this line and refuses a library that answers differently.
+ * Additions are append-only and do not bump it: the entry points of training through shared image features
+ * (vqa_att_score_grouped_drop_fwd, vqa_att_apply_gather_bwd, vqa_att_score_grouped_tiles, vqa_att_score_grouped_bwd) joined
+ * version 8 that way -- a caller built against the earlier version-8 header finds every prototype it knows unchanged. */
 #define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
@@ -293,6 +296,43 @@ int vqa_att_apply_gather_fwd(const float* score, const float* vn, const int32_t*
 int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn,
                       float* dscore, float* dvn, float* dscore_rowsum, int B, int P, int C, int G,
                       vqa_stream_t stream);
+
+/* ---- training through shared image features (VqaNet.forward_shared): the attention stage with one v' per IMAGE ----------
+ * Grouping as in vqa_att_score_grouped_fwd: order[offsets[n] .. offsets[n+1]) are the questions of image n (device int32).
+ * No entry point below uses atomics: the same inputs give the same bits on every run.
+ *
+ * vqa_att_score_grouped_fwd with the x_conv dropout (attention.drop on x, models/model.py:194) applied to
+ * x = relu(v' (+|*) q') before the product: x[b][p][m] *= keep(seed, (b*P + p)*xld + m) / (1-p) over the logical tensor
+ * [B][P][xld] indexed by the QUESTION b (xld = mid, 2*mid for '|' where the q' half takes channel mid + m) -- the mask
+ * vqa_att_score_fwd applies to a materialised x.  p = 0 runs the device code of vqa_att_score_grouped_fwd (same bits). */
+int vqa_att_score_grouped_drop_fwd(const float* vprime, const float* qp, const float* wx, int wx_ld, const float* bx,
+                                   const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P, int mid,
+                                   int G, int mode, float p, uint64_t seed, vqa_stream_t stream);
+/* vqa_att_apply_bwd where sample b weighted the rows of image img[b] (device int32 [B], entries in [0, N);
+ * models/model.py:208-221 backward); vn is [N][P][C].
+ *   dscore[b][g][p], dscore_rowsum[b][g] (optional)      as vqa_att_apply_bwd, reading vn[img[b]]
+ *   dvn[n][p][c] = sum_{b in n} sum_g probs[b][g][p] * dout[b*dout_ld + g*C + c]      the weighted-sum branch of d loss / d vn,
+ * summed per image in the order of `order`; every row is written, zeros for an image without questions.  C % 4 == 0,
+ * dout_ld % 4 == 0; dout, vn, dvn 16-byte aligned.  With N = B and img = order = 0..B-1 the results equal vqa_att_apply_bwd's
+ * bit for bit (the same row kernel in its (sample, image) form). */
+int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                             const int32_t* order, const int32_t* offsets, float* dscore, float* dvn, float* dscore_rowsum,
+                             int N, int B, int P, int C, int G, vqa_stream_t stream);
+/* Backward of vqa_att_score_grouped_drop_fwd (models/model.py:186-194 backward); x is recomputed from v' and q', never read.
+ * With dxpre[b][p][m] = (x > 0) * mask[b][p][m] * sum_g dscore[b][g][p] * wx[g*wx_ld + m]  (mask as in the forward):
+ *   dvprime[n*P+p][m]          '+': sum_{b in n} dxpre;  '*': sum_{b in n} dxpre * qp[b][m];  '|': as '+' with x = relu(v'),
+ *                              the v' half only; zero rows for an image without questions; every row is written
+ *   dq_part[b*NT+t][mid]       partial sums over the positions of tile t (NT = vqa_att_score_grouped_tiles(P)) of
+ *                              '+': dxpre;  '*': dxpre * v'[n*P+p][m];  '|': (qp > 0) * mask[b][p][mid+m] * sum_g dscore * wx[g][mid+m]
+ *                              -- vqa_sum_parts(batch B, parts NT) finishes d loss / d q'
+ *   dwx_part[n*NT+t][G][xld]   partial sums over the tile's positions and the image's questions of dscore * x * mask (both
+ *                              halves for '|') -- vqa_colsum over the N*NT rows finishes the x_conv weight gradient
+ * mode: 0 '+', 1 '*', 2 '|'.  mid % 4 == 0, mid <= 4096, wx_ld % 4 == 0, G in 1..4, N <= 65535, 0 <= p < 1; every float
+ * pointer except dscore 16-byte aligned.  B == 0 returns without a launch. */
+int vqa_att_score_grouped_tiles(int P);
+int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const float* qp, const float* wx, int wx_ld,
+                              const int32_t* order, const int32_t* offsets, float* dvprime, float* dq_part, float* dwx_part,
+                              int N, int B, int P, int mid, int G, int mode, float p, uint64_t seed, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
