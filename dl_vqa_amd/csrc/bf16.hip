@@ -4,8 +4,7 @@
 // operands and fp32 accumulation; parameters stay fp32 (master copy, Adam), a bf16 copy is made per step.
 // The convolution kernels of the bf16 path live in conv.hip (conv_bf16.inc).
 #include "bf16_core.hpp"
-#include "gemm_epilogue.hpp"
-#include <stdlib.h>
+#include "gemm_host.hpp"
 
 namespace vqa {
 
@@ -63,18 +62,22 @@ static int launch_gemm_bf16(const typename AL::Params& pa, const typename BL::Pa
   return check_hip(hipGetLastError(), "gemm_bf16_kernel launch");
 }
 
-// A: transA = 0 -> [M][K] (type R), 1 -> [K][M] (type C);  B: transB = 1 -> [N][K] (type R), 0 -> [K][N] (type C)
+// a k-contiguous operand (type R) is addressed as packed pairs of bf16, a reduction-major one (type C) element by element
+template <class L>
+static typename L::Params operand_bf16(const void* p, int64_t ld, int rows, int K) {
+  if constexpr (L::kTypeR) return {static_cast<const float*>(p), ld / 2, rows, K / 2};
+  else return {p, ld, rows, K};
+}
+
 template <class Cfg>
 static int dispatch_gemm_bf16(const void* A, int64_t lda, int transA, const void* B, int64_t ldb, int transB,
                               const EpiParams& pe, const GemmPlan& p, int M, int N, int K, hipStream_t s) {
-  using AR = PlainR<Cfg::NVA, Cfg::LT>; using AC = PlainCb<Cfg::BM, Cfg::LT>;
-  using BR = PlainR<Cfg::NVB, Cfg::LT>; using BC = PlainCb<Cfg::BN, Cfg::LT>;
-  const float* Af = static_cast<const float*>(A);
-  const float* Bf = static_cast<const float*>(B);
-  if (!transA && transB) return launch_gemm_bf16<Cfg, AR, BR>({Af, lda / 2, M, K / 2}, {Bf, ldb / 2, N, K / 2}, pe, p, s);
-  if (!transA && !transB) return launch_gemm_bf16<Cfg, AR, BC>({Af, lda / 2, M, K / 2}, {B, ldb, N, K}, pe, p, s);
-  if (transA && transB) return launch_gemm_bf16<Cfg, AC, BR>({A, lda, M, K}, {Bf, ldb / 2, N, K / 2}, pe, p, s);
-  return launch_gemm_bf16<Cfg, AC, BC>({A, lda, M, K}, {B, ldb, N, K}, pe, p, s);
+  return with_layout<PlainR<Cfg::NVA, Cfg::LT>, PlainCb<Cfg::BM, Cfg::LT>, PlainR<Cfg::NVB, Cfg::LT>, PlainCb<Cfg::BN, Cfg::LT>>(
+      transA, transB, [&](auto al, auto bl) {
+        using AL = typename decltype(al)::type;
+        using BL = typename decltype(bl)::type;
+        return launch_gemm_bf16<Cfg, AL, BL>(operand_bf16<AL>(A, lda, M, K), operand_bf16<BL>(B, ldb, N, K), pe, p, s);
+      });
 }
 
 // ------------------------------------------------------------------ converters
@@ -134,75 +137,37 @@ using namespace vqa;
 
 extern "C" {
 
-int64_t vqa_gemm_bf16_workspace_bytes(int M, int N, int K) {
-  const GemmPlan p = plan_gemm(M, N, K, BKB);
-  return p.splits > 1 ? (int64_t)p.splits * M * N * 4 : 0;
-}
+int64_t vqa_gemm_bf16_workspace_bytes(int M, int N, int K) { return slab_bytes(plan_gemm(M, N, K, BKB), M, N); }
 
 int vqa_gemm_bf16(const void* A, int64_t lda, int transA, const void* B, int64_t ldb, int transB, void* C,
                   int64_t ldc, int c_is_bf16, int M, int N, int K, const float* bias1, const float* bias2,
                   const float* rowgroup, int64_t rg_ld, int rg_div, int rg_op, int relu, int accumulate, float* aux,
                   float* workspace, int64_t workspace_bytes, int tag, vqa_stream_t stream) {
-  VQA_REQUIRE(A && B && C, "vqa_gemm_bf16: null operand");
-  VQA_REQUIRE(M > 0 && N > 0 && K > 0, "vqa_gemm_bf16: bad shape M=%d N=%d K=%d", M, N, K);
-  VQA_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && lda % 8 == 0 && ldb % 8 == 0 && K % 8 == 0,
-              "vqa_gemm_bf16: A/B must be 16-byte aligned, leading dimensions and K multiples of 8 (lda=%lld ldb=%lld K=%d)",
-              (long long)lda, (long long)ldb, K);
+  if (int rc = check_gemm_args("vqa_gemm_bf16", 8, A, lda, B, ldb, C, ldc, M, N, K, rowgroup, rg_div)) return rc;
+  VQA_REQUIRE(K % 8 == 0, "vqa_gemm_bf16: K must be a multiple of 8 (K=%d)", K);
   VQA_REQUIRE((!transA || M % 8 == 0) && (transB || N % 8 == 0),
               "vqa_gemm_bf16: a reduction-major operand needs its row length to be a multiple of 8 (M=%d N=%d)", M, N);
-  VQA_REQUIRE(lda < (1 << 21) && ldb < (1 << 21) && ldc < (1 << 21), "vqa_gemm_bf16: leading dimensions must be below 2^21");
-  VQA_REQUIRE(!rowgroup || rg_div > 0, "vqa_gemm_bf16: rg_div must be positive");
   VQA_REQUIRE(!(c_is_bf16 && accumulate), "vqa_gemm_bf16: accumulate needs an fp32 C");
   hipStream_t s = (hipStream_t)stream;
-  const GemmPlan p = plan_gemm(M, N, K, BKB);
-  EpiParams pe{c_is_bf16 ? nullptr : static_cast<float*>(C), ldc, M, N, bias1, bias2, rowgroup, rg_ld, rg_div, rg_op,
-               relu, accumulate, aux, nullptr, c_is_bf16 ? static_cast<uint16_t*>(C) : nullptr};
-  if (p.splits > 1) {
-    const int64_t need = (int64_t)p.splits * M * N * 4;
-    if (!workspace || workspace_bytes < need) {
-      set_error("vqa_gemm_bf16: workspace %lld bytes < %lld needed", (long long)workspace_bytes, (long long)need);
-      return VQA_ERR_WORKSPACE;
-    }
-    pe.slab = workspace;
-  }
-  set_launch_tag(tag);
-  ProfScope prof(VQA_K_GEMM, s);
-  static const int wide_ok = [] { const char* e = getenv("VQA_GEMM_WIDE"); return e && atoi(e) == 0 ? 0 : 1; }();
-  if (wide_ok && transA && !transB && N == 256 && M % 128 == 0 && K >= (1 << 16) && workspace) {
-    // long-K weight gradient with a 256-column output: 128 x 256 tiles, one workgroup per CU, split-K over the 256 slots
-    GemmPlan q = p;
-    q.big = 1;
-    q.tiles_m = M / 128;
-    q.tiles_n = 1;
-    int splits = 256 / q.tiles_m;
-    if (splits < 1) splits = 1;
-    if (splits > 64) splits = 64;
-    q.ks_per_split = (q.nk + splits - 1) / splits;
-    q.splits = (q.nk + q.ks_per_split - 1) / q.ks_per_split;
-    q.order = 0;
-    if (workspace_bytes >= (int64_t)q.splits * M * N * 4) {
-      pe.slab = q.splits > 1 ? workspace : nullptr;
-      using Cfg = CfgB128x256;
-      int rc = launch_gemm_bf16<Cfg, PlainCb<Cfg::BM, Cfg::LT>, PlainCb<Cfg::BN, Cfg::LT>>({A, lda, M, K}, {B, ldb, N, K}, pe, q, s);
-      if (rc) return rc;
-      if (q.splits > 1) rc = launch_splitk_reduce(pe, q.splits, s);
-      return rc;
-    }
-  }
-  int rc = p.big ? dispatch_gemm_bf16<CfgB128>(A, lda, transA, B, ldb, transB, pe, p, M, N, K, s)
-                 : dispatch_gemm_bf16<CfgB64>(A, lda, transA, B, ldb, transB, pe, p, M, N, K, s);
-  if (rc) return rc;
-  if (p.splits > 1) rc = launch_splitk_reduce(pe, p.splits, s);
-  return rc;
+  GemmPlan p = plan_gemm(M, N, K, BKB);
+  EpiParams pe = epi_params(c_is_bf16 ? nullptr : static_cast<float*>(C), c_is_bf16 ? static_cast<uint16_t*>(C) : nullptr, ldc, M, N,
+                            bias1, bias2, rowgroup, rg_ld, rg_div, rg_op, relu, accumulate, aux);
+  // the ordinary plan's workspace is asked for first, whichever plan then runs (plan_gemm_wide: gemm.hip)
+  if (int rc = claim_slab("vqa_gemm_bf16", p, pe, workspace, workspace_bytes)) return rc;
+  const bool wide = plan_gemm_wide(p, M, N, K, transA, transB, workspace != nullptr, workspace_bytes);
+  if (wide) claim_slab("vqa_gemm_bf16", p, pe, workspace, workspace_bytes);      // admitted: the workspace holds its slabs
+  return run_gemm(p, pe, tag, s, [&] {
+    using W = CfgB128x256;
+    return wide    ? launch_gemm_bf16<W, PlainCb<W::BM, W::LT>, PlainCb<W::BN, W::LT>>({A, lda, M, K}, {B, ldb, N, K}, pe, p, s)
+           : p.big ? dispatch_gemm_bf16<CfgB128>(A, lda, transA, B, ldb, transB, pe, p, M, N, K, s)
+                   : dispatch_gemm_bf16<CfgB64>(A, lda, transA, B, ldb, transB, pe, p, M, N, K, s);
+  });
 }
 
 int vqa_f32_to_bf16(const float* x, void* y_bf16, int64_t n, vqa_stream_t stream) {
   VQA_REQUIRE(x && y_bf16 && n > 0, "vqa_f32_to_bf16: bad args");
   VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_bf16 % 16) == 0, "vqa_f32_to_bf16: pointers must be 16-byte aligned");
-  int64_t blocks = (n / 8 + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      static_cast<uint16_t*>(y_bf16), n);
   return check_hip(hipGetLastError(), "f32_to_bf16 launch");
 }
@@ -210,19 +175,14 @@ int vqa_f32_to_bf16(const float* x, void* y_bf16, int64_t n, vqa_stream_t stream
 int vqa_dropout_to_bf16(const float* x, void* y_bf16, int64_t n, float p, uint64_t seed, vqa_stream_t stream) {
   VQA_REQUIRE(x && y_bf16 && n > 0 && p >= 0.f && p < 1.f, "vqa_dropout_to_bf16: bad args");
   VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_bf16 % 16) == 0, "vqa_dropout_to_bf16: pointers must be 16-byte aligned");
-  int64_t blocks = (n / 8 + 255) / 256;
-  if (blocks < 1) blocks = 1;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(dropout_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(dropout_to_bf16_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      static_cast<uint16_t*>(y_bf16), n, p, p > 0.f ? 1.0f / (1.0f - p) : 1.0f, seed);
   return check_hip(hipGetLastError(), "dropout_to_bf16 launch");
 }
 
 int vqa_bf16_to_f32(const void* x_bf16, float* y, int64_t n, vqa_stream_t stream) {
   VQA_REQUIRE(x_bf16 && y && n > 0, "vqa_bf16_to_f32: bad args");
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      static_cast<const uint16_t*>(x_bf16), y, n);
   return check_hip(hipGetLastError(), "bf16_to_f32 launch");
 }

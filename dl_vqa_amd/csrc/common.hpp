@@ -11,7 +11,7 @@
 
 namespace vqa {
 
-// ---------------------------------------------------------------- errors
+// ---------------------------------------------------------------- errors (runtime.hip, as the launch plumbing, knobs and profiling hook)
 void set_error(const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
 
@@ -38,6 +38,18 @@ static int launch_kernel(K kern, KernelNames n, dim3 grid, int threads, int lds,
   if (rc) return rc;
   hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, args...);
   return check_hip(hipGetLastError(), n.launch);
+}
+
+// Workgroups of a persistent kernel that are resident at once on the current device: min(planned, occupancy query) per CU x CUs,
+// cached per (device, kernel).  <= 0: the query failed (vqa_last_error says why).
+int persistent_slots(const void* kernel, int threads, int smem_bytes, int planned_per_cu);
+
+// Blocks of a grid-stride launch over n items, per_block items a block: at least 1, at most cap.
+static inline int grid_for(int64_t n, int per_block, int cap = 8192) {
+  int64_t b = (n + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  if (b > cap) b = cap;
+  return (int)b;
 }
 
 // runtime flag -> template flag: f is a generic lambda that reads decltype(flag)::value, so a tile choice is written once

@@ -15,11 +15,7 @@
 
 namespace vqa {
 
-static inline int grid_for(int64_t n, int per_block, int cap = 1 << 20) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
+static inline int convk_grid(int64_t n) { return grid_for(n, 256, 1 << 20); }
 
 // cols[r][(ky*ks + kx)*CiP + c] = x[b][yo*stride + ky][xo*stride + kx][c],  r = (b*Ho + yo)*Wo + xo
 __global__ __launch_bounds__(256) void convk_im2col_kernel(const float4* __restrict__ x, float4* __restrict__ cols, int64_t total4,
@@ -176,7 +172,7 @@ int vqa_convk_pack_weights(const float* w, float* wk, int Co, int Ci, int CiP, i
   VQA_REQUIRE(w && wk && Co > 0 && Ci > 0 && CiP >= Ci && CiP % 4 == 0 && ks >= 1 && ks <= 15,
               "vqa_convk_pack_weights: bad args (Co=%d Ci=%d CiP=%d ks=%d)", Co, Ci, CiP, ks);
   const int64_t total = (int64_t)Co * ks * ks * CiP;
-  hipLaunchKernelGGL(convk_pack_kernel, dim3(grid_for(total, 256)), dim3(256), 0, STREAM, w, wk, total, Ci, CiP, ks);
+  hipLaunchKernelGGL(convk_pack_kernel, dim3(convk_grid(total)), dim3(256), 0, STREAM, w, wk, total, Ci, CiP, ks);
   return check_hip(hipGetLastError(), "convk_pack launch");
 }
 
@@ -184,7 +180,7 @@ int vqa_convk_unpack_wgrad(const float* dwk, float* dw, int Co, int Ci, int CiP,
   VQA_REQUIRE(dwk && dw && Co > 0 && Ci > 0 && CiP >= Ci && CiP % 4 == 0 && ks >= 1 && ks <= 15,
               "vqa_convk_unpack_wgrad: bad args (Co=%d Ci=%d CiP=%d ks=%d)", Co, Ci, CiP, ks);
   const int64_t total = (int64_t)Co * Ci * ks * ks;
-  hipLaunchKernelGGL(convk_unpack_kernel, dim3(grid_for(total, 256)), dim3(256), 0, STREAM, dwk, dw, total, Ci, CiP, ks);
+  hipLaunchKernelGGL(convk_unpack_kernel, dim3(convk_grid(total)), dim3(256), 0, STREAM, dwk, dw, total, Ci, CiP, ks);
   return check_hip(hipGetLastError(), "convk_unpack launch");
 }
 
@@ -193,7 +189,7 @@ int vqa_convk_im2col(const float* x, float* cols, int B, int H, int W, int CiP, 
   if (int rc = convk_geom("vqa_convk_im2col", B, H, W, CiP, ks, stride, &Ho, &Wo)) return rc;
   VQA_REQUIRE(x && cols && ALIGNED16(x) && ALIGNED16(cols), "vqa_convk_im2col: null or unaligned pointer");
   const int64_t total4 = (int64_t)B * Ho * Wo * ks * ks * (CiP / 4);
-  hipLaunchKernelGGL(convk_im2col_kernel, dim3(grid_for(total4, 256)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(x),
+  hipLaunchKernelGGL(convk_im2col_kernel, dim3(convk_grid(total4)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(x),
                      reinterpret_cast<float4*>(cols), total4, H, W, CiP / 4, ks, stride, Ho, Wo);
   return check_hip(hipGetLastError(), "convk_im2col launch");
 }
@@ -205,7 +201,7 @@ int vqa_convk_relu_pool(const float* y, float* pooled, uint8_t* amax, int B, int
               Wo, Co);
   const int Hp = Ho / 2, Wp = Wo / 2;
   const int64_t total4 = (int64_t)B * Hp * Wp * (Co / 4);
-  hipLaunchKernelGGL(convk_relu_pool_kernel, dim3(grid_for(total4, 256)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(y),
+  hipLaunchKernelGGL(convk_relu_pool_kernel, dim3(convk_grid(total4)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(y),
                      reinterpret_cast<float4*>(pooled), reinterpret_cast<uint32_t*>(amax), total4, Ho, Wo, Hp, Wp, Co / 4);
   return check_hip(hipGetLastError(), "convk_relu_pool launch");
 }
@@ -215,7 +211,7 @@ int vqa_convk_route(const float* dpooled, const uint8_t* amax, float* dy, int B,
               "vqa_convk_route: null or unaligned pointer");
   VQA_REQUIRE(B > 0 && Ho >= 2 && Wo >= 2 && Co > 0 && Co % 4 == 0, "vqa_convk_route: bad shape B=%d Ho=%d Wo=%d Co=%d", B, Ho, Wo, Co);
   const int64_t total4 = (int64_t)B * Ho * Wo * (Co / 4);
-  hipLaunchKernelGGL(convk_route_kernel, dim3(grid_for(total4, 256)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(dpooled),
+  hipLaunchKernelGGL(convk_route_kernel, dim3(convk_grid(total4)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(dpooled),
                      reinterpret_cast<const uint32_t*>(amax), reinterpret_cast<float4*>(dy), total4, Ho, Wo, Ho / 2, Wo / 2, Co / 4);
   return check_hip(hipGetLastError(), "convk_route launch");
 }
@@ -225,7 +221,7 @@ int vqa_convk_col2im(const float* dcols, float* dx, int B, int H, int W, int CiP
   if (int rc = convk_geom("vqa_convk_col2im", B, H, W, CiP, ks, stride, &Ho, &Wo)) return rc;
   VQA_REQUIRE(dcols && dx && ALIGNED16(dcols) && ALIGNED16(dx), "vqa_convk_col2im: null or unaligned pointer");
   const int64_t total4 = (int64_t)B * H * W * (CiP / 4);
-  hipLaunchKernelGGL(convk_col2im_kernel, dim3(grid_for(total4, 256)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(dcols),
+  hipLaunchKernelGGL(convk_col2im_kernel, dim3(convk_grid(total4)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(dcols),
                      reinterpret_cast<float4*>(dx), total4, H, W, CiP / 4, ks, stride, Ho, Wo);
   return check_hip(hipGetLastError(), "convk_col2im launch");
 }

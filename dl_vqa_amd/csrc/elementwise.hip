@@ -28,13 +28,6 @@ __device__ __forceinline__ void st4(void* row, int c, float4 v) {
   else reinterpret_cast<float4*>(row)[c] = v;
 }
 
-static inline int grid_for(int64_t n, int per_block, int cap = 8192) {
-  int64_t b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (int)b;
-}
-
 // ------------------------------------------------------------------ dropout
 __global__ void dropout_kernel(const float* x, float* y, int64_t n, float p, float inv_keep, uint64_t seed) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

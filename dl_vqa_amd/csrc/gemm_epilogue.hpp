@@ -1,4 +1,6 @@
-// Fused GEMM epilogue + split-K reduction, shared by the fp32 engine (gemm.hip) and the bf16 engine (bf16.hip).
+// Fused GEMM epilogue (device side), shared by the fp32 engine (gemm.hip), the 3 x bf16 engine (gemm_x3.hip) and the bf16 engine
+// (bf16.hip).  The split-K reduction kernels that apply it per element (epi_apply) are in runtime.hip; the engines' shared host
+// code is in gemm_host.hpp.
 #pragma once
 #include <type_traits>
 #include "gemm_core.hpp"
@@ -209,76 +211,6 @@ __device__ __forceinline__ void gemm_epilogue_bf16_staged(const EpiParams& pe, f
     const float4 v = *reinterpret_cast<const float4*>(scr + byte);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, (int)((uint32_t)row * (uint32_t)pe.ldc * 2u + inrow), 0, 0);
   }
-}
-
-static __global__ void splitk_reduce_kernel(EpiParams pe, int splits) {
-  const int64_t total = (int64_t)pe.M * pe.N;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    for (int s = 0; s < splits; ++s) v += pe.slab[(int64_t)s * total + e];
-    const int row = (int)(e / pe.N), col = (int)(e - (int64_t)row * pe.N);
-    if (pe.aux) pe.aux[(int64_t)row * pe.ldc + col] = v;
-    const float o = epi_apply(pe, v, row, col);
-    if (pe.Cb) pe.Cb[(int64_t)row * pe.ldc + col] = epi_bf16(o); else pe.C[(int64_t)row * pe.ldc + col] = o;
-  }
-}
-
-// N % 4 == 0: 16-byte slab reads; a block covers 64 float4 outputs with 4 thread groups that each take every 4th
-// split, so all the loads of a thread are in flight at once (the scalar kernel above is a chain of dependent
-// 4-byte loads: 16 us for an 8-split 256 x 1024 output), and the groups combine through LDS in a fixed order.
-static __global__ __launch_bounds__(256) void splitk_reduce4_kernel(EpiParams pe, int splits) {
-  __shared__ float4 part[4][64];
-  const int64_t total4 = (int64_t)pe.M * pe.N / 4;
-  const int n4 = pe.N / 4;
-  const float4* slab = reinterpret_cast<const float4*>(pe.slab);
-  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  for (int64_t e0 = (int64_t)blockIdx.x * 64; e0 < total4; e0 += (int64_t)gridDim.x * 64) {
-    const int64_t e = e0 + lane;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (e < total4) {
-      int s = grp;
-      for (; s + 4 < splits; s += 8) {          // two independent loads per trip
-        const float4 a = slab[(int64_t)s * total4 + e], b = slab[(int64_t)(s + 4) * total4 + e];
-        v.x = (v.x + a.x) + b.x; v.y = (v.y + a.y) + b.y; v.z = (v.z + a.z) + b.z; v.w = (v.w + a.w) + b.w;
-      }
-      if (s < splits) {
-        const float4 a = slab[(int64_t)s * total4 + e];
-        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-      }
-    }
-    part[grp][lane] = v;
-    __syncthreads();
-    if (grp == 0 && e < total4) {
-      const float4 p1 = part[1][lane], p2 = part[2][lane], p3 = part[3][lane];
-      const float r[4] = {(v.x + p1.x) + (p2.x + p3.x), (v.y + p1.y) + (p2.y + p3.y),
-                          (v.z + p1.z) + (p2.z + p3.z), (v.w + p1.w) + (p2.w + p3.w)};
-      const int row = (int)(e / n4), col = 4 * (int)(e - (int64_t)row * n4);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (pe.aux) pe.aux[(int64_t)row * pe.ldc + col + k] = r[k];
-        const float o = epi_apply(pe, r[k], row, col + k);
-        if (pe.Cb) pe.Cb[(int64_t)row * pe.ldc + col + k] = epi_bf16(o); else pe.C[(int64_t)row * pe.ldc + col + k] = o;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-
-// Tile / split-K plan of a plain GEMM (gemm.hip); bk = K-step depth in elements (32 fp32, 64 bf16).
-struct GemmPlan { int big; int tiles_m, tiles_n, nk, splits, ks_per_split, order; };
-GemmPlan plan_gemm(int M, int N, int K, int bk = BK);
-
-// Launch the reduction of split-K slabs (pe.slab [splits][M][N]) with the epilogue applied.
-static inline int launch_splitk_reduce(const EpiParams& pe, int splits, hipStream_t s) {
-  const bool vec = pe.N % 4 == 0;
-  const int64_t total = (int64_t)pe.M * pe.N / (vec ? 4 : 1);
-  int blocks = (int)((total + (vec ? 63 : 255)) / (vec ? 64 : 256));
-  if (blocks > 4096) blocks = 4096;
-  if (vec) hipLaunchKernelGGL(splitk_reduce4_kernel, dim3(blocks), dim3(256), 0, s, pe, splits);
-  else hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, pe, splits);
-  return check_hip(hipGetLastError(), "splitk_reduce launch");
 }
 
 }  // namespace vqa

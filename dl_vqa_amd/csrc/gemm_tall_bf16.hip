@@ -296,20 +296,13 @@ int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, v
   // 256 x 128 tiles, one workgroup of eight waves per CU (1.68 ms at 1.49 M x 1024 x 256); VQA_TALL_BM=128: 128 x 128 tiles on two
   // workgroups of four waves per CU (1.82 ms: the two do not hide each other's phases, and W is fetched twice as often)
   static const int bm256 = [] { const char* e = getenv("VQA_TALL_BM"); return e && atoi(e) == 128 ? 0 : 1; }();
-  if (bm256) {
-    P.tiles_m = (M + 255) / 256;
-    int rc = ensure_dyn_smem(reinterpret_cast<const void*>(gemm_tall_bf16_kernel<4>), TgCfg<4>::LDS, "attr(gemm_tall_bf16)");
-    if (rc) return rc;
-    const int tiles = P.tiles_m * P.tiles_n;
-    hipLaunchKernelGGL(gemm_tall_bf16_kernel<4>, dim3(tiles < 256 ? tiles : 256), dim3(512), TgCfg<4>::LDS, s, P);
-  } else {
-    P.tiles_m = (M + 127) / 128;
-    int rc = ensure_dyn_smem(reinterpret_cast<const void*>(gemm_tall_bf16_kernel<2>), TgCfg<2>::LDS, "attr(gemm_tall_bf16)");
-    if (rc) return rc;
-    const int tiles = P.tiles_m * P.tiles_n;
-    hipLaunchKernelGGL(gemm_tall_bf16_kernel<2>, dim3(tiles < 512 ? tiles : 512), dim3(256), TgCfg<2>::LDS, s, P);
-  }
-  return check_hip(hipGetLastError(), "gemm_tall_bf16 launch");
+  return with_flag(bm256 != 0, [&](auto tall) {
+    constexpr int WM = decltype(tall)::value ? 4 : 2;      // a workgroup: 64 * WM rows, 128 * WM threads, 1024 / WM of them resident
+    P.tiles_m = (M + 64 * WM - 1) / (64 * WM);
+    const int tiles = P.tiles_m * P.tiles_n, slots = 1024 / WM;
+    return launch_kernel(gemm_tall_bf16_kernel<WM>, {"attr(gemm_tall_bf16)", "gemm_tall_bf16 launch"}, dim3(tiles < slots ? tiles : slots),
+                         128 * WM, TgCfg<WM>::LDS, s, P);
+  });
 }
 
 }  // extern "C"

@@ -30,22 +30,30 @@ def _chk(t: torch.Tensor, dtype=torch.float32):
     assert t.is_cuda and t.dtype == dtype, (t.device, t.dtype)
 
 
+def _gemm(name: str, c_kind: tuple, A, B, C, M, N, K, transA, transB, lda, ldb, ldc, bias1, bias2, rowgroup, rg_div, rg_op, relu,
+          accumulate, aux, tag) -> torch.Tensor:
+    """The call of vqa_gemm / vqa_gemm_x3 / vqa_gemm_bf16: leading dimensions default to the stored row length, the workspace
+    is what the entry point's *_workspace_bytes asks for.  c_kind: the arguments between ldc and M (bf16: c_is_bf16)."""
+    lib = _lib.load()
+    lda = lda if lda is not None else (M if transA else K)
+    ldb = ldb if ldb is not None else (K if transB else N)
+    ldc = ldc if ldc is not None else N
+    nbytes = getattr(lib, name + "_workspace_bytes")(M, N, K)
+    ws = workspace(nbytes, A.device) if nbytes else None
+    call(name, ptr(A), lda, int(transA), ptr(B), ldb, int(transB), ptr(C), ldc, *c_kind, M, N, K,
+         ptr(bias1), ptr(bias2), ptr(rowgroup), (rowgroup.stride(0) if rowgroup is not None else 0),
+         rg_div, rg_op, int(relu), int(accumulate), ptr(aux), ptr(ws), (ws.numel() * 4 if ws is not None else 0),
+         tag, stream())
+    return C
+
+
 def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: int, *, transA=False,
          transB=True, lda=None, ldb=None, ldc=None, bias1=None, bias2=None, rowgroup=None, rg_div=1,
          rg_op=0, relu=False, accumulate=False, aux=None, tag=0, x3=False) -> torch.Tensor:
     """C[M,N] = act(op(A) op(B) (op) rowgroup + bias) (+C).  Leading dims default to the stored row length.
     x3: the contraction on the bf16 matrix cores with exact 3 x bf16 operand splits (csrc/x3_core.hpp)."""
-    lib = _lib.load()
-    lda = lda if lda is not None else (M if transA else K)
-    ldb = ldb if ldb is not None else (K if transB else N)
-    ldc = ldc if ldc is not None else N
-    nbytes = (lib.vqa_gemm_x3_workspace_bytes if x3 else lib.vqa_gemm_workspace_bytes)(M, N, K)
-    ws = workspace(nbytes, A.device) if nbytes else None
-    call("vqa_gemm_x3" if x3 else "vqa_gemm", ptr(A), lda, int(transA), ptr(B), ldb, int(transB), ptr(C), ldc, M, N, K,
-         ptr(bias1), ptr(bias2), ptr(rowgroup), (rowgroup.stride(0) if rowgroup is not None else 0),
-         rg_div, rg_op, int(relu), int(accumulate), ptr(aux), ptr(ws), (ws.numel() * 4 if ws is not None else 0),
-         tag, stream())
-    return C
+    return _gemm("vqa_gemm_x3" if x3 else "vqa_gemm", (), A, B, C, M, N, K, transA, transB, lda, ldb, ldc, bias1, bias2, rowgroup,
+                 rg_div, rg_op, relu, accumulate, aux, tag)
 
 
 def nchw_to_nhwc4(x: torch.Tensor) -> torch.Tensor:
@@ -658,18 +666,9 @@ def gemm_bf16(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int,
               lda=None, ldb=None, ldc=None, bias1=None, bias2=None, rowgroup=None, rg_div=1, rg_op=0, relu=False,
               accumulate=False, aux=None, tag=0) -> torch.Tensor:
     """vqa_gemm with bf16 A / B (fp32 accumulation); C fp32 or bf16 by its dtype."""
-    lib = _lib.load()
     assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and C.dtype in (torch.float32, torch.bfloat16)
-    lda = lda if lda is not None else (M if transA else K)
-    ldb = ldb if ldb is not None else (K if transB else N)
-    ldc = ldc if ldc is not None else N
-    nbytes = lib.vqa_gemm_bf16_workspace_bytes(M, N, K)
-    ws = workspace(nbytes, A.device) if nbytes else None
-    call("vqa_gemm_bf16", ptr(A), lda, int(transA), ptr(B), ldb, int(transB), ptr(C), ldc, int(C.dtype == torch.bfloat16),
-         M, N, K, ptr(bias1), ptr(bias2), ptr(rowgroup), (rowgroup.stride(0) if rowgroup is not None else 0),
-         rg_div, rg_op, int(relu), int(accumulate), ptr(aux), ptr(ws), (ws.numel() * 4 if ws is not None else 0),
-         tag, stream())
-    return C
+    return _gemm("vqa_gemm_bf16", (int(C.dtype == torch.bfloat16),), A, B, C, M, N, K, transA, transB, lda, ldb, ldc, bias1, bias2,
+                 rowgroup, rg_div, rg_op, relu, accumulate, aux, tag)
 
 
 def gemm_tall_bf16_supported(M: int, N: int, K: int, rg_div: int = 0, has_rowgroup: bool = False) -> bool:
