@@ -6,7 +6,10 @@ backward run on hand-written HIP kernels (csrc/, bound through the C ABI in incl
 Adam; ``distributed.DataParallel`` shards the minibatch over the GPUs of one node with RCCL.
 ``VqaNet.encode_images`` / ``answer`` (inference) and ``VqaNet.forward_shared`` / ``train.run_batch_shared`` (training)
 serve batches in which several questions ask about the same image: the image-only work runs once per image.
+``topk_answers`` / ``VqaNet.predict`` rank the answers on the device -- the k best per question with their probabilities, in
+the order the VQA score's arg-max uses -- and return them as ``TopAnswers``.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers  # noqa: F401
 
-__all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image"]
+__all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
+           "topk_answers"]

@@ -16,7 +16,7 @@ from __future__ import annotations
 import warnings
 import weakref
 from collections import OrderedDict
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -123,6 +123,53 @@ def group_by_image(image_index, N: int):
         offsets[1:] = torch.cumsum(torch.bincount(idx, minlength=N), 0)
     order = torch.argsort(idx, stable=True)
     return order.to(torch.int32), offsets.to(torch.int32)
+
+
+class TopAnswers(NamedTuple):
+    """What topk_answers / VqaNet.predict return: indices int64 [B, k] (0-based answer columns, best first) and probs
+    fp32 [B, k] (their softmax probabilities)."""
+    indices: torch.Tensor
+    probs: torch.Tensor
+
+
+TOPK_MAX = 64     # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
+
+
+def _check_k(what: str, k, A: int) -> int:
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"{what}: k must be an int, got {k!r}")
+    if k < 1 or k > TOPK_MAX or k > A:
+        raise ValueError(f"{what}: k={k} out of range (1 <= k <= min({TOPK_MAX}, number of answers = {A}))")
+    return k
+
+
+def topk_answers(logits, k: int = 1) -> TopAnswers:
+    """The k best answers of every row of logits [B, A] -- what forward(), forward_shared() or answer() return -- with their
+    softmax probabilities, ranked on the device in one kernel launch (csrc/topk.hip).
+
+    Order: larger logit first; equal logits by smaller column; -0.0 equals +0.0; NaN ranks above +inf (torch.topk's
+    order).  indices[:, 0] is therefore exactly the arg-max the library's VQA score is taken at (train.soft_ce_loss_and_score,
+    torch.max's first maximum), which torch.topk does not promise on ties.  Columns are 0-based positions in the row: the
+    loss head's a_idx is 1-based, so a_idx - 1 names the same answer.  probs = softmax(logits)[indices] in fp32; a row that
+    contains NaN gets NaN probabilities.
+
+    The result is detached (no autograd; a pending backward of `logits` stays usable).  ValueError for k < 1, k > A, k > 64
+    or a tensor that is not 2-D, RuntimeError for a CPU tensor (there is no CPU fallback); a float dtype other than fp32 is
+    widened with .float()."""
+    logits = torch.as_tensor(logits)
+    if logits.dim() != 2:
+        raise ValueError(f"topk_answers: logits [B, A] expected, got {tuple(logits.shape)}")
+    k = _check_k("topk_answers", k, logits.shape[1])
+    if not logits.is_cuda:
+        raise RuntimeError("dl_vqa_amd.topk_answers needs a CUDA (HIP) tensor; there is no CPU fallback")
+    x = logits.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()                  # the kernel reads rows of unit stride, ld = stride(0) >= A apart
+    with torch.cuda.device(x.device):
+        idx, prob = ops.softmax_topk(x, k)
+    return TopAnswers(idx.long(), prob)
 
 
 class ImageFeatures:
@@ -535,3 +582,21 @@ class VqaNet(nn.Module):
         if return_attention:
             return logits, probs.view(B, eng.G, *feats.grid)
         return logits
+
+    @torch.no_grad()
+    def predict(self, feats: ImageFeatures, q, q_len, image_index, k: int = 1, return_attention: bool = False):
+        """answer() and the ranking of its logits in one call: TopAnswers(indices int64 [B, k], probs fp32 [B, k]), the k best
+        answers of every question and their softmax probabilities, best first, in topk_answers' order (larger logit first,
+        equal logits by smaller column: indices[:, 0] is the arg-max the VQA score is taken at; 0-based, a_idx - 1).
+        return_attention: (TopAnswers, att [B, G, gh, gw]) with answer()'s attention tensor.
+
+        k is validated first (ValueError for k < 1, k > 64 or k > the number of answers); everything else is answer()'s:
+        eval mode only, fp32 / fp32x3, the feature-ownership checks, its errors, and nothing kept for a backward.  The
+        ranking kernel runs on answer()'s device and stream, behind the classifier; B == 0 gives empty [0, k] tensors."""
+        k = _check_k("VqaNet.predict", k, self._engine.A)
+        out = self.answer(feats, q, q_len, image_index, return_attention=return_attention)
+        logits = out[0] if return_attention else out
+        with torch.cuda.device(logits.device):
+            idx, prob = ops.softmax_topk(logits, k)
+        top = TopAnswers(idx.long(), prob)
+        return (top, out[1]) if return_attention else top

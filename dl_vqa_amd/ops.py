@@ -587,6 +587,22 @@ def softce(logits, ld, a_idx, a_val, A, inv_batch, dlogits=None, dld=0):
     return loss_rows, score_rows
 
 
+def softmax_topk(logits: torch.Tensor, k: int, want_lse: bool = False):
+    """(idx int32 [B,k], prob fp32 [B,k][, lse fp32 [B]]): the first k columns of every row -- larger value first, equal
+    values by smaller column (the score kernel's arg-max rule), NaN above +inf -- with their softmax probabilities, in one
+    launch (include/vqa_hip.h vqa_softmax_topk).  logits: any 2-D fp32 CUDA tensor with stride(1) == 1; a row view into a
+    padded buffer is read in place (ld = stride(0))."""
+    _chk(logits)
+    assert logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1), (tuple(logits.shape), logits.stride())
+    B, A = logits.shape
+    ld = logits.stride(0) if B > 1 else A
+    idx = torch.empty(B, k, dtype=torch.int32, device=logits.device)
+    prob = torch.empty(B, k, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(B, dtype=torch.float32, device=logits.device) if want_lse else None
+    call("vqa_softmax_topk", ptr(logits), ld, B, A, k, ptr(idx), ptr(prob), ptr(lse), stream())
+    return (idx, prob, lse) if want_lse else (idx, prob)
+
+
 def colsum(x: torch.Tensor, rows: int, cols: int, out: torch.Tensor, *, ld=None, mask=None, accumulate=False):
     lib = _lib.load()
     nbytes = lib.vqa_colsum_workspace_bytes(rows, cols)

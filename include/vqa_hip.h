@@ -30,7 +30,8 @@ extern "C" {
  * dl_vqa_amd/_lib.py parses this line and refuses a library that answers differently.
  * Additions are append-only and do not bump it: the entry points of training through shared image features
  * (vqa_att_score_grouped_drop_fwd, vqa_att_apply_gather_bwd, vqa_att_score_grouped_tiles, vqa_att_score_grouped_bwd) joined
- * version 8 that way -- a caller built against the earlier version-8 header finds every prototype it knows unchanged. */
+ * version 8 that way, and vqa_softmax_topk after them -- a caller built against the earlier version-8 header finds every
+ * prototype it knows unchanged. */
 #define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
@@ -341,6 +342,24 @@ int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const fl
 int vqa_softce_fwd_bwd(const float* logits, int64_t ld, const int64_t* a_idx, const int64_t* a_val,
                        int kmax, int B, int A, float inv_batch, float* loss_rows, float* score_rows,
                        float* dlogits, int64_t dld, vqa_stream_t stream);
+
+/* ---- the answers themselves (csrc/topk.hip; VqaNet.predict, dl_vqa_amd.topk_answers; the reference leaves this to
+ * torch.max in utils/train_utils.py:12-25 and to the caller) -- the k best columns of every logits row with their softmax
+ * probabilities, one launch.  idx[b][0..k) are the first k columns of row b under ONE total order:
+ *   larger value first; equal values: smaller column first;
+ *   -0.0 and +0.0 are equal; NaN ranks above +inf (torch.topk's order), several NaNs by column.
+ * idx[b][0] is therefore exactly the arg-max vqa_softce_fwd_bwd takes the score at (torch.max: the first maximum).
+ * Columns are 0-based positions in the row; the loss head's a_idx is 1-based, so a_idx - 1 names the same column.
+ *   prob[b][j] = exp(x[idx[b][j]] - max) / sum_i exp(x[i] - max)   fp32, expf (not the fast intrinsic); the sum runs in a
+ *                fixed order (per lane, then the wave butterfly; no atomics): the same input gives the same bits
+ *   lse[b]     = max + log(sum)   (optional, NULL: not written)
+ * A row that contains NaN gets NaN probabilities and a NaN lse (its idx are still the order above).  Infinities follow the
+ * arithmetic: -inf entries beside finite ones get probability 0; a row whose maximum is +inf, or that is all -inf, gets
+ * NaN probabilities (inf - inf) and a NaN lse.
+ * 1 <= k <= 64, k <= A, A >= 1, ld >= A (elements); no alignment demand on logits or ld.  B == 0 returns without a launch.
+ * Nothing outside idx[B][k], prob[B][k] and lse[B] is written. */
+int vqa_softmax_topk(const float* logits, int64_t ld, int B, int A, int k, int32_t* idx /* [B][k] */, float* prob /* [B][k] */,
+                     float* lse /* [B], optional */, vqa_stream_t stream);
 
 /* ---- reductions / pointwise helpers -------------------------------------------------------- */
 /* out[n] (+)= sum_m x[m*ld + n]; if mask != NULL rows of x where mask[m*cols+n] == 4 are skipped
