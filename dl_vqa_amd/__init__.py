@@ -8,8 +8,10 @@ Adam; ``distributed.DataParallel`` shards the minibatch over the GPUs of one nod
 serve batches in which several questions ask about the same image: the image-only work runs once per image.
 ``topk_answers`` / ``VqaNet.predict`` rank the answers on the device -- the k best per question with their probabilities, in
 the order the VQA score's arg-max uses -- and return them as ``TopAnswers``.
+``VqaNet.encode_questions`` / ``answer_pairs`` / ``predict_pairs`` are the mirror image of the image cache: every distinct
+question is encoded once (``unique_questions`` deduplicates a batch) and (image, question) pairs are answered from the two caches.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
-           "topk_answers"]
+           "topk_answers", "QuestionFeatures", "unique_questions"]

@@ -11,6 +11,9 @@
 // DROP (vqa_att_score_grouped_drop_fwd, train mode): x is multiplied by the x_conv dropout mask (models/model.py:194) before
 // the product, drop_scale(seed, (b*P + p)*xld + m) over the logical [B][P][xld] tensor x -- indexed by the QUESTION b, as
 // vqa_att_score_fwd does; for '|' the q' half takes channel mid + m.  DROP = false is the code the inference entry point runs.
+// PAIRS (vqa_att_score_grouped_pairs_fwd, answers from cached question features): pair b reads the q' row qp[qrow[b]] of a
+// table [M][mid] of distinct questions; everything else is still indexed by b.  Only the row address changes: the operation
+// order above is the same, so the scores equal the PAIRS = false kernels' on the expanded qp[qrow], bit for bit.
 #include "common.hpp"
 
 namespace vqa {
@@ -53,17 +56,26 @@ __device__ __forceinline__ void att_group_range(const int* offsets, int n, int B
   k1 = k1 > B ? B : k1;
 }
 
+// the q' row that question / pair b reads, -1: skip b (b outside [0, B); PAIRS: qrow[b] outside [0, M))
+template <bool PAIRS>
+__device__ __forceinline__ int att_q_row(const int* qrow, int b, int B, int M) {
+  if ((unsigned)b >= (unsigned)B) return -1;
+  if (!PAIRS) return b;
+  const int r = qrow[b];
+  return (unsigned)r < (unsigned)M ? r : -1;
+}
+
 // '+' / '*', mid = 256 * IT <= 1024: x_conv weights and the question's q' row in registers, 4 positions per wave.
 // grid (ceil(P/16), N), 256 threads, 16 * mid floats of dynamic LDS.
 __device__ __forceinline__ float4 mul4(const float4 a, const float4 b) {
   return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
 
-template <int G, int IT, bool MUL, bool DROP>
-__global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vprime, const float* qp, const float* wx, int wx_ld,
-                                                                const float* bx, const int* order, const int* offsets,
-                                                                float* score, int B, int P, float p, float inv_keep,
-                                                                uint64_t seed) {
+template <int G, int IT, bool MUL, bool DROP, bool PAIRS>
+__global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vprime, const float* qp, const int* qrow, int M,
+                                                                const float* wx, int wx_ld, const float* bx, const int* order,
+                                                                const int* offsets, float* score, int B, int P, float p,
+                                                                float inv_keep, uint64_t seed) {
   extern __shared__ __attribute__((aligned(16))) float tile[];
   constexpr int mid = 256 * IT, PW = 4, TP = 16;
   const int n = blockIdx.y, p0 = blockIdx.x * TP;
@@ -88,10 +100,11 @@ __global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vpr
 #pragma unroll
   for (int i = 0; i < IT; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   int b = order[k0];
-  bool ok = (unsigned)b < (unsigned)B;
+  const int r0 = att_q_row<PAIRS>(qrow, b, B, M);
+  bool ok = r0 >= 0;
   if (ok) {
 #pragma unroll
-    for (int i = 0; i < IT; ++i) q[i] = reinterpret_cast<const float4*>(qp + (int64_t)b * mid)[lane + 64 * i];
+    for (int i = 0; i < IT; ++i) q[i] = reinterpret_cast<const float4*>(qp + (int64_t)r0 * mid)[lane + 64 * i];
   }
   for (int k = k0; k < k1; ++k) {
     // the next question's q' row is in flight while this one is reduced
@@ -102,10 +115,11 @@ __global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vpr
     bool okn = false;
     if (k + 1 < k1) {
       bn = order[k + 1];
-      okn = (unsigned)bn < (unsigned)B;
+      const int rn = att_q_row<PAIRS>(qrow, bn, B, M);
+      okn = rn >= 0;
       if (okn) {
 #pragma unroll
-        for (int i = 0; i < IT; ++i) qn[i] = reinterpret_cast<const float4*>(qp + (int64_t)bn * mid)[lane + 64 * i];
+        for (int i = 0; i < IT; ++i) qn[i] = reinterpret_cast<const float4*>(qp + (int64_t)rn * mid)[lane + 64 * i];
       }
     }
     if (ok) {
@@ -148,11 +162,11 @@ __global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vpr
 
 // Any mid % 4 == 0 and every mode: the channel walk is a run-time loop (weights and q' re-read through L1 per position),
 // `pw` positions per wave (the tile is 4 * pw rows).  Same per-lane operation order as the kernel above.
-template <int G, bool DROP>
-__global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const float* vprime, const float* qp, const float* wx,
-                                                                        int wx_ld, const float* bx, const int* order,
-                                                                        const int* offsets, float* score, int B, int P, int mid,
-                                                                        int pw, int mode, float p, float inv_keep,
+template <int G, bool DROP, bool PAIRS>
+__global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const float* vprime, const float* qp, const int* qrow,
+                                                                        int M, const float* wx, int wx_ld, const float* bx,
+                                                                        const int* order, const int* offsets, float* score, int B,
+                                                                        int P, int mid, int pw, int mode, float p, float inv_keep,
                                                                         uint64_t seed) {
   extern __shared__ __attribute__((aligned(16))) float tile[];
   const int TP = 4 * pw;
@@ -186,8 +200,9 @@ __global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const fl
     }
     for (int k = k0; k < k1; ++k) {
       const int b = order[k];
-      if ((unsigned)b >= (unsigned)B) continue;
-      const float4* qrow = reinterpret_cast<const float4*>(qp + (int64_t)b * mid);
+      const int r = att_q_row<PAIRS>(qrow, b, B, M);
+      if (r < 0) continue;
+      const float4* qv = reinterpret_cast<const float4*>(qp + (int64_t)r * mid);
       float acc[G];
 #pragma unroll
       for (int g = 0; g < G; ++g) acc[g] = 0.f;
@@ -204,14 +219,14 @@ __global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const fl
           for (int g = 0; g < G; ++g) { vpart[g] = wave_sum(acc[g]) + bx[g]; acc[g] = 0.f; }
         }
         for (int c = lane; c < nq; c += 64) {
-          float4 x = relu4(qrow[c]);
+          float4 x = relu4(qv[c]);
           if (DROP) x = mul4(x, drop_scale4(seed, e0 + mid + 4 * c, p, inv_keep));
 #pragma unroll
           for (int g = 0; g < G; ++g) acc[g] += dot4(x, reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld + mid)[c]);
         }
       } else {
         for (int c = lane; c < nq; c += 64) {
-          float4 x = mode == 1 ? att_combine<true>(vrow[c], qrow[c]) : att_combine<false>(vrow[c], qrow[c]);
+          float4 x = mode == 1 ? att_combine<true>(vrow[c], qv[c]) : att_combine<false>(vrow[c], qv[c]);
           if (DROP) x = mul4(x, drop_scale4(seed, e0 + 4 * c, p, inv_keep));
 #pragma unroll
           for (int g = 0; g < G; ++g) acc[g] += dot4(x, reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[c]);
@@ -402,20 +417,29 @@ static int with_it(int it, F&& f) {
   VQA_REQUIRE(((reinterpret_cast<uintptr_t>(vprime) | reinterpret_cast<uintptr_t>(qp) | reinterpret_cast<uintptr_t>(wx)) & 15) == 0, \
               who ": vprime, qp and wx must be 16-byte aligned")
 
-// the launch of both forward entry points: p == 0 runs the DROP = false kernels, the inference entry point's code
-static int grouped_fwd_launch(const float* vprime, const float* qp, const float* wx, int wx_ld, const float* bx,
-                              const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P, int mid, int G,
-                              int mode, float p, uint64_t seed, hipStream_t s) {
+// the launch of the forward entry points: p == 0 runs the DROP = false kernels, the inference entry point's code; qrow != NULL
+// (inference only, p == 0) runs their PAIRS instantiations over the q' table qp [M][mid]
+static int grouped_fwd_launch(const float* vprime, const float* qp, const int32_t* qrow, int M, const float* wx, int wx_ld,
+                              const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P,
+                              int mid, int G, int mode, float p, uint64_t seed, hipStream_t s) {
   const float ik = keep_scale(p);
+  const bool pairs = qrow != nullptr;              // the pairs entry point passes p = 0: DROP x PAIRS is never instantiated
   if (mode != 2 && mid % 256 == 0 && mid <= 1024) {
     const dim3 grid((P + 15) / 16, N);
     const size_t lds = (size_t)16 * mid * 4;
     with_glimpses(G, [&](auto g) {
       return with_it(mid / 256, [&](auto it) {
-        return with_flags(mode == 1, p > 0.f, [&](auto mul, auto drop) {
-          hipLaunchKernelGGL((att_score_grouped_kernel<decltype(g)::value, decltype(it)::value, decltype(mul)::value,
-                                                       decltype(drop)::value>),
-                             grid, dim3(256), lds, s, vprime, qp, wx, wx_ld, bx, order, offsets, score, B, P, p, ik, seed);
+        return with_flags(mode == 1, pairs ? false : p > 0.f, [&](auto mul, auto drop) {
+          if (pairs)
+            hipLaunchKernelGGL((att_score_grouped_kernel<decltype(g)::value, decltype(it)::value, decltype(mul)::value, false,
+                                                         true>),
+                               grid, dim3(256), lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, 0.f, 1.f,
+                               (uint64_t)0);
+          else
+            hipLaunchKernelGGL((att_score_grouped_kernel<decltype(g)::value, decltype(it)::value, decltype(mul)::value,
+                                                         decltype(drop)::value, false>),
+                               grid, dim3(256), lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, p, ik,
+                               seed);
           return 0;
         });
       });
@@ -427,9 +451,13 @@ static int grouped_fwd_launch(const float* vprime, const float* qp, const float*
   const dim3 grid((P + TP - 1) / TP, N);
   const size_t lds = (size_t)TP * mid * 4;
   with_glimpses(G, [&](auto g) {
-    return with_flag(p > 0.f, [&](auto drop) {
-      hipLaunchKernelGGL((att_score_grouped_general_kernel<decltype(g)::value, decltype(drop)::value>), grid, dim3(256), lds, s,
-                         vprime, qp, wx, wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, p, ik, seed);
+    return with_flag(pairs ? false : p > 0.f, [&](auto drop) {
+      if (pairs)
+        hipLaunchKernelGGL((att_score_grouped_general_kernel<decltype(g)::value, false, true>), grid, dim3(256), lds, s, vprime,
+                           qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, 0.f, 1.f, (uint64_t)0);
+      else
+        hipLaunchKernelGGL((att_score_grouped_general_kernel<decltype(g)::value, decltype(drop)::value, false>), grid, dim3(256),
+                           lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, p, ik, seed);
       return 0;
     });
   });
@@ -445,7 +473,21 @@ int vqa_att_score_grouped_fwd(const float* vprime, const float* qp, const float*
   ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
   GROUPED_FWD_REQUIRE("vqa_att_score_grouped_fwd");
   if (B == 0) return VQA_OK;
-  return grouped_fwd_launch(vprime, qp, wx, wx_ld, bx, order, offsets, score, N, B, P, mid, G, mode, 0.f, 0, (hipStream_t)stream);
+  return grouped_fwd_launch(vprime, qp, nullptr, 0, wx, wx_ld, bx, order, offsets, score, N, B, P, mid, G, mode, 0.f, 0,
+                            (hipStream_t)stream);
+}
+
+int vqa_att_score_grouped_pairs_fwd(const float* vprime, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                    const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                                    int M, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  GROUPED_FWD_REQUIRE("vqa_att_score_grouped_pairs_fwd");
+  VQA_REQUIRE(qrow, "vqa_att_score_grouped_pairs_fwd: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_score_grouped_pairs_fwd: M=%d question rows (>= 1)", M);
+  if (B == 0) return VQA_OK;
+  return grouped_fwd_launch(vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, N, B, P, mid, G, mode, 0.f, 0,
+                            (hipStream_t)stream);
 }
 
 int vqa_att_score_grouped_drop_fwd(const float* vprime, const float* qp, const float* wx, int wx_ld, const float* bx,
@@ -456,7 +498,7 @@ int vqa_att_score_grouped_drop_fwd(const float* vprime, const float* qp, const f
   GROUPED_FWD_REQUIRE("vqa_att_score_grouped_drop_fwd");
   VQA_REQUIRE(p >= 0.f && p < 1.f, "vqa_att_score_grouped_drop_fwd: dropout p=%g outside [0, 1)", (double)p);
   if (B == 0) return VQA_OK;
-  return grouped_fwd_launch(vprime, qp, wx, wx_ld, bx, order, offsets, score, N, B, P, mid, G, mode, p, seed,
+  return grouped_fwd_launch(vprime, qp, nullptr, 0, wx, wx_ld, bx, order, offsets, score, N, B, P, mid, G, mode, p, seed,
                             (hipStream_t)stream);
 }
 

@@ -1246,6 +1246,27 @@ __global__ void add2d_kernel(const float* a, int64_t lda, const float* b, int64_
   }
 }
 
+// dst[b][0:cols] = src[rows[b]][0:cols], zeros for a row index outside [0, M); VEC: one float4 per thread and iteration
+template <bool VEC>
+__global__ void gather_rows_kernel(const float* src, int64_t src_ld, const int* rows, float* dst, int64_t dst_ld, int B, int M,
+                                   int cols) {
+  const int cw = VEC ? cols >> 2 : cols;
+  const int64_t n = (int64_t)B * cw;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / cw;
+    const int c = (int)(i - b * cw);
+    const int r = rows[b];
+    const bool in = (unsigned)r < (unsigned)M;
+    if (VEC) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in) v = reinterpret_cast<const float4*>(src + (int64_t)r * src_ld)[c];
+      reinterpret_cast<float4*>(dst + b * dst_ld)[c] = v;
+    } else {
+      dst[b * dst_ld + c] = in ? src[(int64_t)r * src_ld + c] : 0.f;
+    }
+  }
+}
+
 // fp16 -> fp32, 8 values (16 bytes in, 32 bytes out) per thread and iteration
 __global__ void half_to_float_kernel(const __half* x, float* y, int64_t n) {
   const int64_t n8 = n / 8;
@@ -1605,6 +1626,24 @@ int vqa_add2d(const float* a, int64_t lda, const float* b, int64_t ldb, float* y
   hipLaunchKernelGGL(add2d_kernel, dim3(grid_for(rows * cols, 256)), dim3(256), 0, STREAM, a, lda, b, ldb, y, ldy,
                      rows, cols);
   return check_hip(hipGetLastError(), "add2d launch");
+}
+
+int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float* dst, int64_t dst_ld, int B, int M, int cols,
+                    vqa_stream_t stream) {
+  VQA_REQUIRE(src && rows && dst, "vqa_gather_rows: null pointer");
+  VQA_REQUIRE(B >= 0 && M >= 1 && cols >= 1, "vqa_gather_rows: B=%d, M=%d, cols=%d out of range", B, M, cols);
+  VQA_REQUIRE(src_ld >= cols && dst_ld >= cols, "vqa_gather_rows: src_ld=%lld and dst_ld=%lld must be >= cols=%d",
+              (long long)src_ld, (long long)dst_ld, cols);
+  if (B == 0) return VQA_OK;
+  const bool vec = cols % 4 == 0 && src_ld % 4 == 0 && dst_ld % 4 == 0 &&
+                   ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(grid_for((int64_t)B * (cols / 4), 256)), dim3(256), 0, STREAM, src, src_ld,
+                       rows, dst, dst_ld, B, M, cols);
+  else
+    hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(grid_for((int64_t)B * cols, 256)), dim3(256), 0, STREAM, src, src_ld, rows,
+                       dst, dst_ld, B, M, cols);
+  return check_hip(hipGetLastError(), "gather_rows launch");
 }
 
 int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t stream) {

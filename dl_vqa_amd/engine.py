@@ -490,6 +490,50 @@ class Engine:
         logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
         return logits, probs, score
 
+    # ------------------------------------------------------------------ cached question features (inference)
+    # The mirror image of encode_images / answer: the question encoder and q_lin run once per DISTINCT question, and
+    # (image, question) pairs are answered from the two caches -- no recurrence, no convolution in answer_pairs.
+    def encode_questions(self, P: Dict[str, Tensor], q: Tensor, q_len: Tensor, dev, bad_tokens: Optional[Tensor] = None):
+        """q [M,T], q_len [M] -> (qf [M,Q]: the final cell states, a view with row stride Dc; q' = q_lin(qf) [M,mid])."""
+        assert not self.bf16, "encode_questions: fp32 / fp32x3 only"
+        with torch.cuda.device(dev):
+            return self._encode_questions(P, q, q_len, dev, bad_tokens)
+
+    def _encode_questions(self, P, q, q_len, dev, bad_tokens):
+        q = q.to(device=dev, dtype=torch.int64).contiguous()
+        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
+        M = q.shape[0]
+        # the forward's own stages on M rows, eval mode; the encoder writes the question half of a classifier-input buffer
+        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], 0.0, 0, bad_tokens)                     # [T,M,E]
+        combined = torch.empty(M, self.Dc, dtype=torch.float32, device=dev)
+        self._question_encoder(P, x_emb, q_len, combined, l16=False)
+        qf = combined[:, self.GC:]
+        qp = self._q_lin_fwd(P, qf, 0.0, 0)[0]
+        return qf, qp
+
+    def answer_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor, qrow: Tensor):
+        """B pairs from the encoded images `feats` (vn, vprime) and the encoded questions `qfeats` (qf, qprime): pair b
+        looks at image img[b] with question qrow[b]; order / offsets (device int32) group the pairs by image.  Returns
+        (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
+        assert not self.bf16, "answer_pairs: fp32 / fp32x3 only"
+        with torch.cuda.device(feats.vn.device):
+            return self._answer_pairs(P, feats, qfeats, order, offsets, img, qrow)
+
+    def _answer_pairs(self, P, feats, qfeats, order, offsets, img, qrow):
+        dev = feats.vn.device
+        B = img.numel()
+        N, Pn, _ = feats.vn.shape
+        # ---- attention: scores from v' (one per image) and q' (one per distinct question)
+        score = ops.att_score_grouped_pairs_fwd(feats.vprime, qfeats.qprime, qrow, P["attention.x_conv.weight"].view(self.G, -1),
+                                                P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode)
+        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=dev)
+        probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, self.Dc)
+        # ---- the question half of the classifier input (models/model.py:64), one cached row per pair
+        ops.gather_rows(qfeats.qf, qrow, combined[:, self.GC:], self.Q)
+        # ---- classifier
+        logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
+        return logits, probs, score
+
     # ------------------------------------------------------------------ training through shared image features
     # fp32 / fp32x3.  v holds every image ONCE; question b looks at image img[b].  The image encoder, the question encoder,
     # q_lin and the classifier are the forward's own stages, run on N images and B questions; the attention stage runs on one

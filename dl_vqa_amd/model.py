@@ -184,6 +184,54 @@ class ImageFeatures:
         self._flat_ptr = model._flat_param.data_ptr()     # a re-flattened model (moved, new storage) no longer matches
 
 
+class QuestionFeatures:
+    """What VqaNet.encode_questions returns and VqaNet.answer_pairs reads: the question features `qf` [M, Q] (the LSTM's final
+    cell states, what the classifier input holds behind the weighted image features; possibly a strided view), their attention
+    projection `qprime` = q_lin(qf) [M, mid], and M.  A plain holder of CUDA tensors, owned like ImageFeatures: it belongs to
+    the model that encoded it and to that model's current weights."""
+    __slots__ = ("qf", "qprime", "M", "_model", "_flat_ptr")
+
+    def __init__(self, qf, qprime, model):
+        self.qf, self.qprime, self.M = qf, qprime, qf.shape[0]
+        self._model = weakref.ref(model)
+        self._flat_ptr = model._flat_param.data_ptr()
+
+
+def unique_questions(q, q_len):
+    """Deduplicate a batch of questions on the host: q [B, T] token ids, q_len [B] -> (q_unique [M, T], q_len_unique [M],
+    question_index int64 [B]) with q_unique[question_index[b]] the question of row b.  Two questions are equal when their
+    lengths and their first q_len tokens are equal (the recurrence never reads what lies behind q_len; the returned rows
+    hold 0 there).  Distinct questions come in order of first occurrence.  CPU tensors come back, whatever device q was on;
+    lengths below 1 or above T raise as validate_question_lengths does."""
+    q = torch.as_tensor(q).detach().cpu()
+    q_len = torch.as_tensor(q_len).detach().cpu()
+    if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
+        raise ValueError(f"unique_questions: q [B,T] and q_len [B] expected, got {tuple(q.shape)} and {tuple(q_len.shape)}")
+    B, T = q.shape
+    validate_question_lengths(q_len, T)
+    if B == 0:
+        return q.clone(), q_len.clone(), torch.empty(0, dtype=torch.int64)
+    masked = q * (torch.arange(T)[None, :] < q_len.to(torch.int64)[:, None]).to(q.dtype)
+    keys = torch.cat([q_len.to(torch.int64)[:, None], masked.to(torch.int64)], dim=1)
+    _, inverse = torch.unique(keys, dim=0, return_inverse=True)          # sorted groups; renumbered below
+    M = int(inverse.max()) + 1
+    first = torch.full((M,), B, dtype=torch.int64).scatter_reduce(0, inverse, torch.arange(B), reduce="amin")
+    by_first = torch.argsort(first)                                      # group ids in order of first occurrence
+    rank = torch.empty(M, dtype=torch.int64)
+    rank[by_first] = torch.arange(M)
+    rows = first[by_first]
+    return masked[rows], q_len[rows], rank[inverse]
+
+
+def _pair_index(what: str, index, rows: int, of: str) -> torch.Tensor:
+    """One index of answer_pairs on the host: int64 [B], IndexError for an entry outside [0, rows)."""
+    idx = torch.as_tensor(index).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        bad = int(idx.min()) if int(idx.min()) < 0 else int(idx.max())
+        raise IndexError(f"{what} entry {bad} out of range [0, {rows}) ({rows} encoded {of})")
+    return idx
+
+
 def _node_backward(ctx, dlogits, lead: int, engine_backward):
     """backward of an autograd node of this module (_VqaFunction, _VqaSharedFunction): the gradient-buffer rules of
     _VqaFunction's docstring, once.  `lead`: how many inputs precede the parameters (input 1 is the image v);
@@ -595,6 +643,97 @@ class VqaNet(nn.Module):
         ranking kernel runs on answer()'s device and stream, behind the classifier; B == 0 gives empty [0, k] tensors."""
         k = _check_k("VqaNet.predict", k, self._engine.A)
         out = self.answer(feats, q, q_len, image_index, return_attention=return_attention)
+        logits = out[0] if return_attention else out
+        with torch.cuda.device(logits.device):
+            idx, prob = ops.softmax_topk(logits, k)
+        top = TopAnswers(idx.long(), prob)
+        return (top, out[1]) if return_attention else top
+
+    # ------------------------------------------------------------------ cached question features (inference)
+    @torch.no_grad()
+    def encode_questions(self, q, q_len) -> QuestionFeatures:
+        """The question-only part of the forward, once per question: embedding, the LSTM and q' = q_lin(qf).  q [M,T] token
+        ids, q_len [M] (host or CUDA).  Eval mode, compute_dtype fp32 or fp32x3; no autograd graph.  Token ids and lengths
+        are validated as answer() validates them; M == 0 gives empty features.
+
+        The result belongs to this model and to its current weights, exactly as encode_images' does: answer_pairs()
+        refuses features of another model instance or of moved parameters, but cannot see weights that changed IN PLACE --
+        re-encode after an optimiser step or load_state_dict.  dl_vqa_amd.unique_questions deduplicates a batch first."""
+        self._check_inference("encode_questions")
+        self._ensure_flat()
+        q = torch.as_tensor(q)
+        q_len = torch.as_tensor(q_len)
+        if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
+            raise ValueError(f"VqaNet.encode_questions: q [M,T] and q_len [M] expected, got {tuple(q.shape)} and "
+                             f"{tuple(q_len.shape)}")
+        self._validate_tokens(q)
+        validate_question_lengths(q_len, q.shape[1])
+        dev = self._flat_param.device
+        eng = self._engine
+        if q.shape[0] == 0:
+            return QuestionFeatures(torch.empty(0, eng.Q, dtype=torch.float32, device=dev),
+                                    torch.empty(0, eng.mid, dtype=torch.float32, device=dev), self)
+        qf, qprime = eng.encode_questions(self._param_dict(), q.detach(), q_len.detach(), dev,
+                                          bad_tokens=self._bad_tokens if q.is_cuda else None)
+        self._after_forward_tokens(q)
+        return QuestionFeatures(qf, qprime, self)
+
+    @torch.no_grad()
+    def answer_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
+                     return_attention: bool = False):
+        """Logits [B, A] of B (image, question) pairs from the two caches: pair b looks at image image_index[b] of `feats`
+        (encode_images) with question question_index[b] of `qfeats` (encode_questions).  No recurrence and no convolution
+        runs here.  Both indices follow answer()'s rules for image_index: host lists or integer tensors (a CUDA tensor is
+        copied to the host, which synchronises once), any order, repeats, and unused images or questions allowed.
+        return_attention: also att [B, G, gh, gw], as from answer().
+
+        ValueError when the indices differ in length, IndexError outside [0, N) / [0, M), TypeError for anything that did
+        not come from encode_images / encode_questions, RuntimeError when a cache belongs to another model instance, to
+        moved parameters, or to another device than the other cache.  Nothing is kept for a backward: _last_ctx, the
+        gradient buffer and the dropout seed stream are left alone."""
+        self._check_inference("answer_pairs")
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError("VqaNet.answer_pairs: feats must come from VqaNet.encode_images")
+        if not isinstance(qfeats, QuestionFeatures):
+            raise TypeError("VqaNet.answer_pairs: qfeats must come from VqaNet.encode_questions")
+        N, M = feats.N, qfeats.M
+        n_img, n_q = torch.as_tensor(image_index).numel(), torch.as_tensor(question_index).numel()
+        if n_img != n_q:
+            raise ValueError(f"VqaNet.answer_pairs: {n_img} image_index entries for {n_q} question_index entries")
+        order, offsets = group_by_image(image_index, N)
+        qidx = _pair_index("question_index", question_index, M, "questions")
+        self._ensure_flat()
+        for held, what, call in ((feats, "image", "encode_images"), (qfeats, "question", "encode_questions")):
+            if held._model() is not self or held._flat_ptr != self._flat_param.data_ptr():
+                raise RuntimeError(f"VqaNet.answer_pairs: these {what} features belong elsewhere -- they were encoded by "
+                                   "another model instance, or this model's parameters have moved to new storage since "
+                                   f"(.to(), a re-flatten); call {call} again on this model")
+        dev = feats.vn.device
+        if qfeats.qprime.device != dev:
+            raise RuntimeError(f"VqaNet.answer_pairs: the image features are on {dev} and the question features on "
+                               f"{qfeats.qprime.device}; encode both on the model's device")
+        eng = self._engine
+        B = qidx.numel()
+        if B == 0:
+            logits = torch.empty(0, eng.A, dtype=torch.float32, device=dev)
+            return (logits, torch.empty(0, eng.G, *feats.grid, dtype=torch.float32, device=dev)) if return_attention else logits
+        img = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int32).reshape(-1)
+        # one upload: order [B] | offsets [N+1] | img [B] | qrow [B]
+        idx = torch.cat([order, offsets, img, qidx.to(torch.int32)]).to(dev)
+        logits, probs, _score = eng.answer_pairs(self._param_dict(), feats, qfeats, idx[:B], idx[B:B + N + 1],
+                                                 idx[B + N + 1:2 * B + N + 1], idx[2 * B + N + 1:])
+        if return_attention:
+            return logits, probs.view(B, eng.G, *feats.grid)
+        return logits
+
+    @torch.no_grad()
+    def predict_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, k: int = 1,
+                      return_attention: bool = False):
+        """answer_pairs() and the ranking of its logits in one call, as predict() wraps answer(): TopAnswers(indices int64
+        [B, k], probs fp32 [B, k]) in topk_answers' order; return_attention: (TopAnswers, att [B, G, gh, gw]).  k is
+        validated first; everything else is answer_pairs()'s."""
+        k = _check_k("VqaNet.predict_pairs", k, self._engine.A)
+        out = self.answer_pairs(feats, qfeats, image_index, question_index, return_attention=return_attention)
         logits = out[0] if return_attention else out
         with torch.cuda.device(logits.device):
             idx, prob = ops.softmax_topk(logits, k)

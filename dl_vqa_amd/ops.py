@@ -507,6 +507,37 @@ def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P:
     return score
 
 
+def att_score_grouped_pairs_fwd(vprime, qp, qrow, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
+    """att_score_grouped_fwd for B (image, question) pairs over a table qp [M, mid] of distinct questions: pair b reads the
+    row qp[qrow[b]] (qrow device int32 [B]).  Bit-identical to att_score_grouped_fwd(vprime, qp[qrow], ...)."""
+    G, xld = wx.shape[0], wx.shape[1]
+    mid = xld // 2 if mode == 2 else xld
+    M = qp.shape[0]
+    _chk(order, torch.int32), _chk(offsets, torch.int32), _chk(qrow, torch.int32), _chk(qp)
+    assert order.numel() == B and offsets.numel() == N + 1 and qrow.numel() == B
+    assert vprime.shape == (N * P, mid) and qp.shape == (M, mid)
+    score = torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+    call("vqa_att_score_grouped_pairs_fwd", ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets),
+         ptr(score), N, B, M, P, mid, G, mode, stream())
+    return score
+
+
+def gather_rows(src, rows, dst, cols: Optional[int] = None):
+    """dst[b, :cols] = src[rows[b], :cols] (rows device int32 [B]; zeros for an index outside [0, M)).  src [M, >= cols] and
+    dst [B, >= cols] are fp32 row-major views with unit column stride: a column range of a wider buffer is written in
+    place (the leading dimensions are the views' row strides)."""
+    M, B = src.shape[0], dst.shape[0]
+    cols = src.shape[1] if cols is None else cols
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.is_cuda and dst.is_cuda
+    _chk(rows, torch.int32)
+    assert rows.numel() == B and src.shape[1] >= cols and dst.shape[1] >= cols
+    assert (cols == 1 or (src.stride(1) == 1 and dst.stride(1) == 1))
+    src_ld = src.stride(0) if M > 1 else max(src.shape[1], cols)
+    dst_ld = dst.stride(0) if B > 1 else max(dst.shape[1], cols)
+    call("vqa_gather_rows", ptr(src), src_ld, ptr(rows), ptr(dst), dst_ld, B, M, cols, stream())
+    return dst
+
+
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C]."""
     B, G, P = score.shape

@@ -30,8 +30,9 @@ extern "C" {
  * dl_vqa_amd/_lib.py parses this line and refuses a library that answers differently.
  * Additions are append-only and do not bump it: the entry points of training through shared image features
  * (vqa_att_score_grouped_drop_fwd, vqa_att_apply_gather_bwd, vqa_att_score_grouped_tiles, vqa_att_score_grouped_bwd) joined
- * version 8 that way, and vqa_softmax_topk after them -- a caller built against the earlier version-8 header finds every
- * prototype it knows unchanged. */
+ * version 8 that way, vqa_softmax_topk after them, and the two entry points of cached question features
+ * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that -- a caller built against the earlier version-8 header finds
+ * every prototype it knows unchanged. */
 #define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
@@ -334,6 +335,23 @@ int vqa_att_score_grouped_tiles(int P);
 int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const float* qp, const float* wx, int wx_ld,
                               const int32_t* order, const int32_t* offsets, float* dvprime, float* dq_part, float* dwx_part,
                               int N, int B, int P, int mid, int G, int mode, float p, uint64_t seed, vqa_stream_t stream);
+
+/* ---- cached question features (VqaNet.encode_questions / answer_pairs): (image, question) pairs from two caches ----------
+ * vqa_att_score_grouped_fwd (models/model.py:186-195: x = relu(v' (+|*) q'), x_conv) where pair b reads the q' row
+ * qp[qrow[b]] instead of qp[b]: qp is [M][mid], one row per DISTINCT question, qrow device int32 [B].  Everything else is
+ * still indexed by the pair b (order, offsets, the score row).  Same device code as vqa_att_score_grouped_fwd under a
+ * compile-time flag, same per-lane operation order: score equals vqa_att_score_grouped_fwd on the expanded qp[qrow] bit
+ * for bit.  A qrow[b] outside [0, M) skips pair b as a bad `order` entry is skipped: nothing is read, its score row is
+ * left unwritten.  No atomics.  M >= 1; the other limits are vqa_att_score_grouped_fwd's.  B == 0 returns without a launch. */
+int vqa_att_score_grouped_pairs_fwd(const float* vprime, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                    const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                                    int M, int P, int mid, int G, int mode, vqa_stream_t stream);
+/* dst[b*dst_ld + c] = src[rows[b]*src_ld + c] for b < B, c < cols: the question half of the classifier input
+ * combined = cat[weighted v, q] (models/model.py:64) taken from cached question features, rows device int32 [B] with
+ * entries in [0, M); an entry outside writes a row of zeros.  16-byte accesses when cols, both leading dimensions
+ * (elements) and both pointers allow it, scalar otherwise.  src_ld, dst_ld >= cols.  B == 0 returns without a launch. */
+int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float* dst, int64_t dst_ld, int B, int M, int cols,
+                    vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
