@@ -111,6 +111,8 @@ PROTOTYPES = {
     "vqa_add2d": (i32, [f32p, i64, f32p, i64, f32p, i64, i64, i32, vp]),
     "vqa_scale_by": (i32, [f32p, i64, f32p, vp]),
     "vqa_half_to_float": (i32, [vp, f32p, i64, vp]),
+    "vqa_preprocess_supported": (i32, [vp, vp, i64, i32, i32]),
+    "vqa_preprocess_images": (i32, [u8p, i64, vp, vp, i64, vp, vp, i32, i32, vp, i32, vp, vp]),
     "vqa_f32_to_bf16": (i32, [f32p, vp, i64, vp]),
     "vqa_bf16_to_f32": (i32, [vp, f32p, i64, vp]),
     "vqa_dropout_to_bf16": (i32, [f32p, vp, i64, f32, u64, vp]),

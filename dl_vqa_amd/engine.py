@@ -689,6 +689,10 @@ class Engine:
         B, Dc, hid, A = ctx.B, self.Dc, self.hid, self.A
         dev = dlogits.device
         sd = lambda site: _site_seed(ctx.seed, site)
+        # autograd hands the gradient of a reduction (y.sum()) over as an expanded view with strides 0: add2d and the GEMMs
+        # read rows of unit column stride that do not overlap, so such a view is materialised first
+        if (A > 1 and dlogits.stride(1) != 1) or (B > 1 and dlogits.stride(0) < A):
+            dlogits = dlogits.contiguous()
         # dlogits as a GEMM operand needs a leading dimension that is a multiple of 4
         ldA = (A + 3) // 4 * 4
         if ldA != A or not dlogits.is_contiguous() or dlogits.data_ptr() % 16:

@@ -678,6 +678,36 @@ def half_to_float(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# ---------------------------------------------------------------------------- image preprocessing (csrc/preprocess.hip)
+def last_error() -> str:
+    return _lib.load().vqa_last_error().decode()
+
+
+def preprocess_supported(desc, coef, S: int) -> int:
+    """Band height the preprocessing kernel would use for the batch that desc / coef (dl_vqa_amd.preprocess.build_plan: HOST
+    numpy arrays) describe, 0 when it does not cover it (last_error() says why).  Host code only: needs no GPU."""
+    assert desc.dtype.itemsize == 56 and coef.dtype.kind == "i" and coef.dtype.itemsize == 4
+    assert desc.flags.c_contiguous and coef.flags.c_contiguous
+    return _lib.load().vqa_preprocess_supported(desc.ctypes.data, coef.ctypes.data, coef.size, len(desc), S)
+
+
+def preprocess_images(src: torch.Tensor, src_bytes: int, desc, coef, desc_dev: torch.Tensor, coef_dev: torch.Tensor, S: int,
+                      lut: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out [N,3,S,S] (fp16 or fp32) from the packed uint8 source buffer src, one launch (include/vqa_hip.h
+    vqa_preprocess_images).  desc / coef are the host plan (numpy), desc_dev / coef_dev its device copy (uint8 views of the
+    same bytes); lut is the [3,256] table of out's dtype on the device."""
+    N = len(desc)
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.numel() >= src_bytes
+    assert desc.dtype.itemsize == 56 and desc.flags.c_contiguous and coef.dtype.itemsize == 4 and coef.flags.c_contiguous
+    assert desc_dev.is_cuda and desc_dev.numel() * desc_dev.element_size() == desc.nbytes
+    assert coef_dev.is_cuda and coef_dev.numel() * coef_dev.element_size() == coef.nbytes
+    assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (N, 3, S, S) and out.dtype in (torch.float16, torch.float32)
+    assert lut.is_cuda and lut.is_contiguous() and lut.dtype == out.dtype and tuple(lut.shape) == (3, 256)
+    call("vqa_preprocess_images", ptr(src), src_bytes, desc.ctypes.data, coef.ctypes.data, coef.size, ptr(desc_dev),
+         ptr(coef_dev), N, S, ptr(lut), int(out.dtype == torch.float32), ptr(out), stream())
+    return out
+
+
 # ---------------------------------------------------------------------------- bf16 path (BASELINE configs[3])
 def to_bf16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 -> bf16 copy (round to nearest even) by the library's converter."""

@@ -31,8 +31,8 @@ extern "C" {
  * Additions are append-only and do not bump it: the entry points of training through shared image features
  * (vqa_att_score_grouped_drop_fwd, vqa_att_apply_gather_bwd, vqa_att_score_grouped_tiles, vqa_att_score_grouped_bwd) joined
  * version 8 that way, vqa_softmax_topk after them, and the two entry points of cached question features
- * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that -- a caller built against the earlier version-8 header finds
- * every prototype it knows unchanged. */
+ * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that, then image preprocessing (vqa_preprocess_supported,
+ * vqa_preprocess_images) -- a caller built against the earlier version-8 header finds every prototype it knows unchanged. */
 #define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
@@ -406,6 +406,56 @@ int vqa_scale_by(float* x, int64_t n, const float* scalar, vqa_stream_t stream);
  * (preprocessing/data_preprocessing.py:167-176); here the fp16 batch is uploaded as is (half the PCIe bytes)
  * and widened on the device.  x and y 16-byte aligned or n small; layout unchanged (NCHW). */
 int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t stream);
+
+/* ---- image preprocessing (csrc/preprocess.hip; dl_vqa_amd.preprocess_images) -------------------------------------------
+ * Raw RGB bytes -> the image tensor v [N,3,S,S] the entry points above start from, in ONE launch for a batch of images
+ * of different sizes, bit for bit what the reference computes per image on the host through PIL and torchvision
+ * (preprocessing/preprocess_images.py:8-15 _get_transformations, 50-52; evaluate_vqa.py:45-51 runs it when the processed
+ * file is missing).  For one RGB uint8 image [H][W][3], target size S and central_fraction cf in (0, 1]:
+ *   1. resize size: R = int(S / cf); the short side becomes R: W <= H ? (ow, oh) = (R, int(R * H / W))
+ *                                                                       : (oh, ow) = (R, int(R * W / H))   (double division)
+ *   2. resample: PIL's bilinear filter with antialiasing, separable, the horizontal pass first, the intermediate rounded
+ *      and clipped to uint8; a pass whose output size equals its input size is skipped.  For an axis of n input and m
+ *      output samples: scale = n / m, fs = max(scale, 1), support = fs, ss = 1 / fs; per output index i
+ *        center = (i + 0.5) * scale, lo = max((int)(center - support + 0.5), 0), hi = min((int)(center + support + 0.5), n)
+ *        w_x = max(0, 1 - |(x + lo - center + 0.5) * ss|) for x in [0, hi - lo), summed in that order in double and each
+ *        divided by the sum; k_x = (int)(0.5 + w_x * 2^22);
+ *        out[i] = clip((2^21 + sum_x in[lo + x] * k_x) >> 22, 0, 255)
+ *      The tables are computed on the HOST in double exactly so (dl_vqa_amd/preprocess.py, cached per (n, m)); the
+ *      kernel does integer arithmetic only.  A skipped pass is the table lo = i, len = 1, k = 2^22, which returns the byte.
+ *   3. centre crop to S x S: top = round((oh - S) / 2.0), left = round((ow - S) / 2.0), halves to the EVEN integer
+ *      (Python's round).  Only the window's rows and columns are computed: the tables hold its S entries per axis.
+ *   4. float tail: x = (byte / 255 - mean[c]) / std[c] in fp32, mean = {0.485, 0.456, 0.406}, std = {0.229, 0.224, 0.225},
+ *      then rounded to fp16: a function of (c, byte) alone, read from a 3 x 256 table `lut` the caller builds with the
+ *      reference's own operations (fp16 entries, or fp32 entries without the last rounding when out_is_f32).
+ *   5. out[n][c][y][x], NCHW, fp16 (the dataset's storage format) or fp32.
+ * Coefficient table of one axis of one image, at int32 offset *_off of `coef`: lo[S], len[S], k[S][*_taps] (k is 0 past
+ * len).  Images may share tables.  A workgroup owns a band of output rows of one image: it runs the horizontal pass for
+ * the source rows that band needs into an LDS tile of uint8 [rows][S][3], then the vertical pass out of LDS, the table
+ * look-up and the stores of the three channel planes.  No atomics, no floating point, no branch on a pixel value. */
+typedef struct {
+  int64_t src_offset;     /* byte offset of pixel (0, 0) in the packed source buffer */
+  int64_t pitch;          /* bytes from one source row to the next, >= 3 * W */
+  int32_t H, W;           /* source size */
+  int32_t oh, ow;         /* resized size (step 1); both >= S */
+  int32_t top, left;      /* origin of the crop window in the resized image (step 3) */
+  int32_t h_off, h_taps;  /* horizontal table (ow from W, columns left .. left + S) */
+  int32_t v_off, v_taps;  /* vertical table (oh from H, rows top .. top + S) */
+} vqa_pre_image_t;        /* 56 bytes */
+
+/* Band height (output rows per workgroup, > 0) the kernel would use for this batch, or 0 when it does not cover it
+ * (vqa_last_error says why): a descriptor or table that is out of range (any lo + len > n, len < 1, len > taps, a window
+ * outside the resized image, a resized side < S), or a scale so large that the source rows of ONE output row do not fit
+ * the LDS tile.  Pure host code: images and coef are HOST pointers, no HIP call is made.  src_offset / pitch are not read. */
+int vqa_preprocess_supported(const vqa_pre_image_t* images, const int32_t* coef, int64_t coef_len, int N, int S);
+
+/* images_host / coef_host: the HOST copies of the DEVICE arrays images_dev / coef_dev (the same bytes): every check --
+ * null pointers, N < 0, S < 1, what vqa_preprocess_supported checks, and every image's bytes inside [0, src_bytes) --
+ * runs on them before any launch, so the kernel never reads outside src, coef or its LDS tile.  N == 0 returns VQA_OK
+ * without a launch.  src, lut and out are device pointers; lut is [3][256] fp16 (out_is_f32: fp32), out [N][3][S][S]. */
+int vqa_preprocess_images(const uint8_t* src, int64_t src_bytes, const vqa_pre_image_t* images_host, const int32_t* coef_host,
+                          int64_t coef_len, const vqa_pre_image_t* images_dev, const int32_t* coef_dev, int N, int S,
+                          const void* lut, int out_is_f32, void* out, vqa_stream_t stream);
 
 /* ---- bf16 path (BASELINE configs[3]: bf16 MFMA conv / FC, fp32 accumulate, fp32 LSTM) -------------------
  * Opt-in second instantiation of the engine on v_mfma_f32_32x32x16_bf16.  Parameters, Adam state, the LSTM and
