@@ -10,11 +10,14 @@ serve batches in which several questions ask about the same image: the image-onl
 the order the VQA score's arg-max uses -- and return them as ``TopAnswers``.
 ``VqaNet.encode_questions`` / ``answer_pairs`` / ``predict_pairs`` are the mirror image of the image cache: every distinct
 question is encoded once (``unique_questions`` deduplicates a batch) and (image, question) pairs are answered from the two caches.
+``VqaNet.forward_features`` / ``train.run_batch_features`` train the question encoder, the attention stage and the classifier on
+cached image features (``encode_images(v, with_vprime=False)``, ``ImageFeatures.cat``) with the image encoder frozen: no
+convolution runs in the step, and only the bank rows a batch asks about are touched (``compact_image_index``).
 ``preprocess_images`` turns decoded RGB images of any sizes into the ``v [N,3,S,S]`` all of these start from -- the reference's
 resize, centre crop, normalisation and fp16 cast (preprocessing/preprocess_images.py), bit for bit, in one kernel launch.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
-           "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images"]
+           "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index"]

@@ -101,6 +101,8 @@ PROTOTYPES = {
     "vqa_att_score_grouped_bwd": (i32, [f32p, f32p, f32p, f32p, i32, vp, vp, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, f32, u64, vp]),
     "vqa_att_score_grouped_pairs_fwd": (i32, [f32p, f32p, vp, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_gather_rows": (i32, [f32p, i64, vp, f32p, i64, i32, i32, i32, vp]),
+    "vqa_gather_rows_drop": (i32, [f32p, vp, f32p, i32, i32, i64, f32, u64, vp]),
+    "vqa_att_apply_gather_dscore": (i32, [f32p, i64, f32p, f32p, vp, f32p, f32p, i32, i32, i32, i32, i32, vp]),
     "vqa_softce_fwd_bwd": (i32, [f32p, i64, i64p, i64p, i32, i32, i32, f32, f32p, f32p, f32p, i64, vp]),
     "vqa_softmax_topk": (i32, [f32p, i64, i32, i32, i32, vp, f32p, f32p, vp]),
     "vqa_colsum_workspace_bytes": (i64, [i64, i32]),

@@ -1267,6 +1267,45 @@ __global__ void gather_rows_kernel(const float* src, int64_t src_ld, const int* 
   }
 }
 
+// dst[j][0:row_len] = src[rows[j]][0:row_len] * drop_scale(seed, rows[j]*row_len + i): rows of a large bank compacted and
+// dropped in one pass, the mask indexed by the BANK row (64-bit flat index), zeros for a row index outside [0, M).  Rows are
+// long (one image's features), so the flat range n * row_len is spread over a capped grid; a thread divides once and then
+// walks (row, column) by the grid stride split on the host into (step_j, step_c) = divmod(stride, width).  VEC: one float4
+// per thread and iteration (row_len % 4 == 0, so a row start is a multiple of 4 for drop_scale4).
+template <bool VEC>
+__global__ void gather_rows_drop_kernel(const float* src, const int* rows, float* dst, int n, int M, int64_t row_len,
+                                        int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
+  const int64_t rw = VEC ? row_len >> 2 : row_len;
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t j = first / rw, c = first - j * rw;
+  while (j < n) {
+    const int r = rows[j];
+    const bool in = (unsigned)r < (unsigned)M;
+    const int64_t s = (int64_t)r * row_len, d = j * row_len;
+    if (VEC) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (in) {
+        v = reinterpret_cast<const float4*>(src + s)[c];
+        if (p > 0.f) {
+          const float4 ds_ = drop_scale4(seed, (uint64_t)(s + 4 * c), p, inv_keep);
+          v.x *= ds_.x; v.y *= ds_.y; v.z *= ds_.z; v.w *= ds_.w;
+        }
+      }
+      reinterpret_cast<float4*>(dst + d)[c] = v;
+    } else {
+      float v = 0.f;
+      if (in) {
+        v = src[s + c];
+        if (p > 0.f) v *= drop_scale(seed, (uint64_t)(s + c), p, inv_keep);
+      }
+      dst[d + c] = v;
+    }
+    j += step_j;
+    c += step_c;
+    if (c >= rw) { c -= rw; ++j; }
+  }
+}
+
 // fp16 -> fp32, 8 values (16 bytes in, 32 bytes out) per thread and iteration
 __global__ void half_to_float_kernel(const __half* x, float* y, int64_t n) {
   const int64_t n8 = n / 8;
@@ -1580,6 +1619,28 @@ int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* pr
   return check_hip(hipGetLastError(), "softmax_bwd launch");
 }
 
+int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                                float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
+  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
+  VQA_REQUIRE(dout && probs && vn && dscore, "vqa_att_apply_gather_dscore: null pointer");
+  VQA_REQUIRE(img, "vqa_att_apply_gather_dscore: null img");
+  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && C >= 4 && C % 4 == 0 && dout_ld % 4 == 0 && dout_ld >= (int64_t)G * C,
+              "vqa_att_apply_gather_dscore: N=%d, B=%d, P=%d, C=%d (a multiple of 4), dout_ld=%lld out of range", N, B, P, C,
+              (long long)dout_ld);
+  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(vn)) & 15) == 0,
+              "vqa_att_apply_gather_dscore: dout and vn must be 16-byte aligned");
+  if (B == 0) return VQA_OK;
+  const int64_t M = (int64_t)B * P;
+  DISPATCH_G(G, hipLaunchKernelGGL((att_apply_bwd_rows_kernel<kG, true>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
+                                   dout_ld, probs, vn, img, N, dscore, static_cast<float*>(nullptr), M, P, C));
+  int rc = check_hip(hipGetLastError(), "att_apply_gather_dscore rows launch");
+  if (rc) return rc;
+  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, STREAM, probs, dscore, P, dscore_rowsum);
+  return check_hip(hipGetLastError(), "softmax_bwd launch");
+}
+
 int vqa_softce_fwd_bwd(const float* logits, int64_t ld, const int64_t* a_idx, const int64_t* a_val, int kmax, int B,
                        int A, float inv_batch, float* loss_rows, float* score_rows, float* dlogits, int64_t dld,
                        vqa_stream_t stream) {
@@ -1644,6 +1705,26 @@ int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float
     hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(grid_for((int64_t)B * cols, 256)), dim3(256), 0, STREAM, src, src_ld, rows,
                        dst, dst_ld, B, M, cols);
   return check_hip(hipGetLastError(), "gather_rows launch");
+}
+
+int vqa_gather_rows_drop(const float* src, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
+                         uint64_t seed, vqa_stream_t stream) {
+  VQA_REQUIRE(src && rows && dst, "vqa_gather_rows_drop: null pointer");
+  VQA_REQUIRE(n >= 0 && M >= 1 && row_len >= 1, "vqa_gather_rows_drop: n=%d, M=%d, row_len=%lld out of range", n, M,
+              (long long)row_len);
+  VQA_REQUIRE(p >= 0.f && p < 1.f, "vqa_gather_rows_drop: p=%g outside [0, 1)", (double)p);
+  if (n == 0) return VQA_OK;
+  const bool vec = row_len % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  const int64_t rw = vec ? row_len / 4 : row_len;
+  const int grid = grid_for((int64_t)n * rw, 256);
+  const int64_t stride = (int64_t)grid * 256;
+  if (vec)
+    hipLaunchKernelGGL(gather_rows_drop_kernel<true>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
+                       stride / rw, stride % rw, p, KEEP(p), seed);
+  else
+    hipLaunchKernelGGL(gather_rows_drop_kernel<false>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
+                       stride / rw, stride % rw, p, KEEP(p), seed);
+  return check_hip(hipGetLastError(), "gather_rows_drop launch");
 }
 
 int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t stream) {

@@ -446,21 +446,23 @@ class Engine:
     # ------------------------------------------------------------------ many questions per image (inference)
     # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder, the question encoder, q_lin and the
     # classifier are the forward's own stages; the attention stage runs on ONE v' per image (csrc/att_grouped.hip).
-    def encode_images(self, P: Dict[str, Tensor], v: Tensor):
-        """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid], (gh, gw))."""
+    def encode_images(self, P: Dict[str, Tensor], v: Tensor, with_vprime: bool = True):
+        """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid] or None (with_vprime=False), (gh, gw))."""
         assert not self.bf16, "encode_images: fp32 / fp32x3 only"
         with torch.cuda.device(v.device):
-            return self._encode_images(P, v)
+            return self._encode_images(P, v, with_vprime)
 
-    def _encode_images(self, P, v):
+    def _encode_images(self, P, v, with_vprime=True):
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
         x = self._image_encoder(P, v.contiguous(), keep=False).out
         N, gh, gw, C = x.shape
         Pn = gh * gw
         vn, _ = ops.l2norm_fwd(x, 0.0, 0)
-        vprime = torch.empty(N * Pn, self.mid, dtype=torch.float32, device=v.device)
-        ops.gemm(vn, P["attention.v_conv.weight"], vprime, N * Pn, self.mid, C, tag=21, x3=self._x3_gemm(N * Pn))
+        vprime = None
+        if with_vprime:
+            vprime = torch.empty(N * Pn, self.mid, dtype=torch.float32, device=v.device)
+            ops.gemm(vn, P["attention.v_conv.weight"], vprime, N * Pn, self.mid, C, tag=21, x3=self._x3_gemm(N * Pn))
         return vn.view(N, Pn, C), vprime, (gh, gw)
 
     def answer(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
@@ -649,6 +651,97 @@ class Engine:
         ready("image")
         torch.cuda.current_stream(dev).wait_event(text_done)
         return dv
+
+    # ------------------------------------------------------------------ training on cached image features
+    # fp32 / fp32x3.  The image encoder is frozen: `vn` [M,Pn,C] is a bank of its eval-mode outputs (encode_images), question b
+    # looks at bank row img[b].  Only the n_u DISTINCT asked rows are touched: rows (ascending) names them, order / offsets group
+    # the questions by their slot in rows.  No kernel's grid or byte count depends on M.  v' is recomputed from the current
+    # v_conv weight every step.  Dropout: SITE_IMAGE is not applied; SITE_ATT_V draws per BANK row (logical tensor [M, gh, gw, C]);
+    # the question-side sites draw per question as forward_shared does.
+    def forward_features(self, P: Dict[str, Tensor], vn: Tensor, q: Tensor, q_len: Tensor, rows: Tensor, order: Tensor,
+                         offsets: Tensor, img: Tensor, training: bool, seed: int, keep: bool,
+                         bad_tokens: Optional[Tensor] = None):
+        """vn [M,Pn,C]; rows [n_u], order [B], offsets [n_u+1], img [B]: device int32 (model.compact_image_index and the image
+        index itself).  Returns (logits [B,A], ctx or None)."""
+        assert not self.bf16, "forward_features: fp32 / fp32x3 only"
+        with torch.cuda.device(vn.device):
+            return self._forward_features(P, vn, q, q_len, rows, order, offsets, img, training, seed, keep, bad_tokens)
+
+    def _forward_features(self, P, vn, q, q_len, rows, order, offsets, img, training, seed, keep, bad_tokens):
+        assert vn.is_cuda and vn.dtype == torch.float32 and vn.dim() == 3 and vn.is_contiguous()
+        dev = vn.device
+        q = q.to(device=dev, dtype=torch.int64).contiguous()
+        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
+        B, T = q.shape
+        _, Pn, C = vn.shape
+        n_u = rows.numel()
+        mid, Dc, GC, G = self.mid, self.Dc, self.GC, self.G
+        assert C == self.C
+        tr = bool(training)
+        p_txt, p_att, p_cls = (self.p_text, self.p_att, self.p_cls) if tr else (0.0, 0.0, 0.0)
+        sd = lambda site: _site_seed(seed, site)
+
+        # ---- question encoder on the side stream, under the gather and the v_conv product
+        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, sd(SITE_TEXT), bad_tokens)       # [T,B,E]
+        combined = torch.empty(B, Dc, dtype=torch.float32, device=dev)
+        (lstm, x16), text_done = self._on_side_stream(dev, lambda: self._question_encoder(P, x_emb, q_len, combined, False))
+
+        # ---- the asked rows of the bank, compacted, with attention.drop(v) indexed by the bank row; v' = v_conv of them
+        v_in = ops.gather_rows_drop(vn, rows, p_att, sd(SITE_ATT_V))                                      # [n_u,Pn,C]
+        vprime = torch.empty(n_u * Pn, mid, dtype=torch.float32, device=dev)
+        ops.gemm(v_in, P["attention.v_conv.weight"], vprime, n_u * Pn, mid, C, tag=21, x3=self._x3_gemm(n_u * Pn))
+        torch.cuda.current_stream(dev).wait_event(text_done)
+
+        # ---- attention: scores from v' (one per asked row) and q'; the weighted sum reads the bank itself, undropped
+        qp, q_in, ld_q, fc = self._q_lin_fwd(P, combined[:, GC:], p_att, seed)
+        score = ops.att_score_grouped_drop_fwd(vprime, qp, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"],
+                                               order, offsets, n_u, B, Pn, self.att_mode, p_att, sd(SITE_ATT_X))
+        probs = ops.att_apply_gather_fwd(score, vn, img, combined, Dc)
+
+        # ---- classifier
+        logits, c_in, h1, h1d = self._classifier_fwd(P, combined, p_cls, seed, fc)
+        if not keep:
+            return logits, None
+        ctx = SimpleNamespace(B=B, N=n_u, T=T, Pn=Pn, q=q, q_len=q_len, order=order, offsets=offsets, img=img, rows=rows, vn=vn,
+                              x_emb=x_emb, x16=x16, lstm=lstm, v_in=v_in, q_in=q_in, ld_q=ld_q, probs=probs, c_in=c_in, h1=h1,
+                              h1d=h1d, fc=fc, vprime=vprime, qp=qp, p_txt=p_txt, p_att=p_att, p_cls=p_cls, seed=seed,
+                              stages=dict(score=score, combined=combined))
+        return logits, ctx
+
+    def backward_features(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
+                          on_ready: Optional[Callable[[str], None]] = None) -> None:
+        """backward() for a forward_features context: writes the gradients of classifier, attention and text into Gr; the
+        image.* entries of Gr are not touched and there is no image gradient."""
+        with torch.cuda.device(dlogits.device):
+            return self._backward_features(P, ctx, dlogits, Gr, on_ready)
+
+    def _backward_features(self, P, ctx, dlogits, Gr, on_ready):
+        dev = dlogits.device
+        ready = on_ready if on_ready is not None else (lambda group: None)
+        B, n_u, Pn = ctx.B, ctx.N, ctx.Pn
+        G, C, mid, Dc = self.G, self.C, self.mid, self.Dc
+        sd = lambda site: _site_seed(ctx.seed, site)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        dcomb = self._classifier_bwd(P, ctx, dlogits, Gr)
+        ready("classifier")
+        # ---- attention apply + scores; d loss / d vn has no reader
+        ds_rows = new(B, G, 1)
+        dscore = ops.att_apply_gather_dscore(dcomb, Dc, ctx.probs, ctx.vn, ctx.img, rowsum=ds_rows)
+        ops.sum_bgp(ds_rows, Gr["attention.x_conv.bias"])
+        wx = P["attention.x_conv.weight"].view(G, -1)
+        dvprime, dq_part, dwx_part, NT = ops.att_score_grouped_bwd(dscore, ctx.vprime, ctx.qp, wx, ctx.order, ctx.offsets, n_u, B,
+                                                                   Pn, self.att_mode, ctx.p_att, sd(SITE_ATT_X))
+        ops.colsum(dwx_part, n_u * NT, wx.numel(), Gr["attention.x_conv.weight"])
+        dqp = new(B, mid)
+        ops.sum_parts(dq_part, dqp, B, NT, mid)
+        # ---- v_conv over the n_u * Pn asked rows: dW = dv'^T . v_in only
+        ops.gemm(dvprime, ctx.v_in, Gr["attention.v_conv.weight"], mid, C, n_u * Pn, transA=True, transB=False, lda=mid, ldb=C,
+                 tag=44, x3=self._x3_gemm(n_u * Pn))
+        self._q_lin_bwd(P, ctx, dqp, dcomb, Gr)
+        ready("attention")
+        self._question_bwd(P, ctx, dcomb, Gr)
+        ready("text")
+        return None
 
     # ------------------------------------------------------------------ backward
     def backward(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],

@@ -110,19 +110,36 @@ def validate_question_lengths(q_len, T: int) -> None:
                            "(pack_padded_sequence would raise: models/model.py:159-162)")
 
 
-def group_by_image(image_index, N: int):
-    """Group questions by the image they ask about: image_index[b] in [0, N) -> (order int32 [B], offsets int32 [N+1]) on
-    the host; the questions of image n are order[offsets[n]:offsets[n+1]], in their original order (a stable counting
-    sort).  IndexError for an entry outside [0, N)."""
+def _host_image_index(image_index, N: int) -> torch.Tensor:
+    """image_index on the host as int64 [B]; IndexError for an entry outside [0, N)."""
     idx = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
     if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
         bad = int(idx.min()) if int(idx.min()) < 0 else int(idx.max())
         raise IndexError(f"image_index entry {bad} out of range [0, {N})")
+    return idx
+
+
+def group_by_image(image_index, N: int):
+    """Group questions by the image they ask about: image_index[b] in [0, N) -> (order int32 [B], offsets int32 [N+1]) on
+    the host; the questions of image n are order[offsets[n]:offsets[n+1]], in their original order (a stable counting
+    sort).  IndexError for an entry outside [0, N)."""
+    idx = _host_image_index(image_index, N)
     offsets = torch.zeros(N + 1, dtype=torch.int64)
     if idx.numel():
         offsets[1:] = torch.cumsum(torch.bincount(idx, minlength=N), 0)
     order = torch.argsort(idx, stable=True)
     return order.to(torch.int32), offsets.to(torch.int32)
+
+
+def compact_image_index(image_index, N: int):
+    """The distinct rows of an N-row feature bank that a batch asks about, and the batch grouped by them: image_index[b] in
+    [0, N) -> (rows int32 [n_u], slot int32 [B], order int32 [B], offsets int32 [n_u+1]) on the host.  rows holds the distinct
+    entries of image_index, ascending; slot[b] is the position of image_index[b] in rows (rows[slot[b]] == image_index[b]);
+    (order, offsets) = group_by_image(slot, n_u).  IndexError for an entry outside [0, N), as group_by_image raises it."""
+    idx = _host_image_index(image_index, N)
+    rows, slot = torch.unique(idx, sorted=True, return_inverse=True)
+    order, offsets = group_by_image(slot, rows.numel())
+    return rows.to(torch.int32), slot.to(torch.int32), order, offsets
 
 
 class TopAnswers(NamedTuple):
@@ -175,13 +192,44 @@ def topk_answers(logits, k: int = 1) -> TopAnswers:
 class ImageFeatures:
     """What VqaNet.encode_images returns and VqaNet.answer reads: the L2-normalised image features `vn` [N, P, C], their
     attention projection `vprime` = v_conv(vn) [N*P, mid], the grid (gh, gw) with P = gh * gw, and N.  A plain holder of
-    CUDA tensors; it can be kept across many answer() calls, as long as the weights it was computed from stay the same."""
+    CUDA tensors; it can be kept across many answer() calls, as long as the weights it was computed from stay the same.
+    `vprime` is None for features encoded with with_vprime=False: a bank for VqaNet.forward_features, which reads `vn`
+    alone (v' is 4x the size of vn in the reference's configuration and is recomputed there from the trained v_conv)."""
     __slots__ = ("vn", "vprime", "grid", "N", "_model", "_flat_ptr")
 
     def __init__(self, vn, vprime, grid, model):
         self.vn, self.vprime, self.grid, self.N = vn, vprime, tuple(grid), vn.shape[0]
         self._model = weakref.ref(model)
         self._flat_ptr = model._flat_param.data_ptr()     # a re-flattened model (moved, new storage) no longer matches
+
+    @classmethod
+    def cat(cls, parts):
+        """Concatenate features of the same model and grid along N (a data set encoded in chunks): rows keep the order of
+        `parts`.  vprime is concatenated when every part has one, otherwise the result has none.  TypeError for anything
+        that is not an ImageFeatures, ValueError for an empty list or differing grids / feature widths, RuntimeError for
+        parts of different models (or of a model whose parameters moved between two encode_images calls)."""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("ImageFeatures.cat: nothing to concatenate")
+        for f in parts:
+            if not isinstance(f, cls):
+                raise TypeError("ImageFeatures.cat: every part must come from VqaNet.encode_images")
+        first = parts[0]
+        model = first._model()
+        if model is None:
+            raise RuntimeError("ImageFeatures.cat: the model that encoded these features no longer exists")
+        for f in parts[1:]:
+            if f._model() is not model or f._flat_ptr != first._flat_ptr:
+                raise RuntimeError("ImageFeatures.cat: the parts were encoded by different models (or the model's parameters "
+                                   "moved to new storage between the encode_images calls)")
+            if f.grid != first.grid or f.vn.shape[1:] != first.vn.shape[1:] or f.vn.device != first.vn.device:
+                raise ValueError(f"ImageFeatures.cat: grids / feature shapes differ ({first.grid} {tuple(first.vn.shape[1:])} "
+                                 f"and {f.grid} {tuple(f.vn.shape[1:])})")
+        vn = torch.cat([f.vn for f in parts], dim=0)
+        vprime = torch.cat([f.vprime for f in parts], dim=0) if all(f.vprime is not None for f in parts) else None
+        out = cls(vn, vprime, first.grid, model)
+        out._flat_ptr = first._flat_ptr
+        return out
 
 
 class QuestionFeatures:
@@ -232,10 +280,12 @@ def _pair_index(what: str, index, rows: int, of: str) -> torch.Tensor:
     return idx
 
 
-def _node_backward(ctx, dlogits, lead: int, engine_backward):
-    """backward of an autograd node of this module (_VqaFunction, _VqaSharedFunction): the gradient-buffer rules of
-    _VqaFunction's docstring, once.  `lead`: how many inputs precede the parameters (input 1 is the image v);
-    engine_backward(P, saved, dlogits, Gr, on_ready) is the engine schedule that matches the node's forward."""
+def _node_backward(ctx, dlogits, lead: int, engine_backward, frozen=()):
+    """backward of an autograd node of this module (_VqaFunction, _VqaSharedFunction, _VqaFeaturesFunction): the
+    gradient-buffer rules of _VqaFunction's docstring, once.  `lead`: how many inputs precede the parameters (input 1 is
+    the image v); engine_backward(P, saved, dlogits, Gr, on_ready) is the engine schedule that matches the node's forward.
+    `frozen`: names of parameters the schedule computes no gradient for -- they get None (autograd leaves their p.grad
+    alone) and their slots of the gradient buffer are not written."""
     model = ctx.model
     if ctx.saved is None:
         raise RuntimeError("dl_vqa_amd.VqaNet: backward through the same forward twice (the saved "
@@ -270,7 +320,7 @@ def _node_backward(ctx, dlogits, lead: int, engine_backward):
         sync.finish(model)
     ctx.saved = None
     model._pending.discard(ctx)
-    return (None, dv) + none_lead + tuple(Gr[n] for n in names)
+    return (None, dv) + none_lead + tuple(None if n in frozen else Gr[n] for n in names)
 
 
 class _VqaFunction(torch.autograd.Function):
@@ -329,6 +379,37 @@ class _VqaSharedFunction(torch.autograd.Function):
         return _node_backward(ctx, dlogits, 6, ctx.model._engine.backward_shared)
 
 
+class _VqaFeaturesFunction(torch.autograd.Function):
+    """Autograd node of one VqaNet.forward_features call: the image encoder is not part of the graph.  vn is the bank's
+    feature tensor (no gradient), idx the device int32 tensor rows [n_u] | slot [B] | order [B] | offsets [n_u+1] | image
+    index [B] (one upload).  Every parameter is an input, so that gradient storage follows _VqaFunction's rules through the
+    same helper; the image.* parameters get None."""
+
+    @staticmethod
+    def forward(ctx, model, vn, q, q_len, seed, idx, n_u, *params):
+        P = model._param_dict()
+        B = q.shape[0]
+        rows, order, offsets, img = _split_feature_index(idx, n_u, B)
+        logits, saved = model._engine.forward_features(P, vn, q, q_len, rows, order, offsets, img, model.training, seed,
+                                                       keep=True, bad_tokens=model._bad_tokens)
+        ctx.model = model
+        ctx.saved = saved
+        model._last_ctx = saved
+        model._pending.add(ctx)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        model = ctx.model
+        return _node_backward(ctx, dlogits, 7, model._engine.backward_features, model._image_names)
+
+
+def _split_feature_index(idx, n_u: int, B: int):
+    """(rows, order, offsets, img) views of forward_features' one uploaded index tensor."""
+    o = n_u + B                                 # behind rows [n_u] and slot [B]
+    return idx[:n_u], idx[o:o + B], idx[o + B:o + B + n_u + 1], idx[o + B + n_u + 1:]
+
+
 class VqaNet(nn.Module):
     """MI355X-native VqaNet (reference: models/model.py:7-67)."""
 
@@ -361,6 +442,7 @@ class VqaNet(nn.Module):
         self._names: List[str] = list(named.keys())                    # state_dict order (autograd inputs)
         self._params: List[nn.Parameter] = list(named.values())
         self._flat_names = _flat_order(self._names)
+        self._image_names = frozenset(n for n in self._names if n.startswith("image."))   # frozen in forward_features
         self._flat_param: Optional[torch.Tensor] = None
         self._flat_grad: Optional[torch.Tensor] = None
         self._offsets: Dict[str, tuple] = {}
@@ -560,6 +642,79 @@ class VqaNet(nn.Module):
         self._after_forward_tokens(q)
         return logits
 
+    # ------------------------------------------------------------------ training on cached image features
+    def forward_features(self, feats, q, q_len, image_index):
+        """forward_shared() with the image encoder frozen and run beforehand: feats is an ImageFeatures of this model
+        (encode_images, possibly with_vprime=False, possibly an ImageFeatures.cat of chunks) with N rows, and question b
+        (q[b], q_len[b]) looks at row image_index[b].  Returns logits [B, A].  No convolution runs here, forward or
+        backward, and only the rows that are asked about are touched: the cost does not depend on N.
+
+        image_index follows answer()'s rules: a host list or an integer tensor (a CUDA tensor is copied to the host, which
+        synchronises once); repeats, any order and rows nobody asks about are allowed; IndexError outside [0, N).
+
+        Works in train and eval mode and is differentiable with respect to every parameter of text, attention (v_conv,
+        q_lin, x_conv) and classifier; their gradients follow forward()'s buffer rules (FusedAdam works unchanged).  The
+        parameters under image. are not part of the graph: their p.grad stays None, their slots of the flat gradient
+        buffer are not written, and FusedAdam skips them.  Outside a grad context it returns the same logits and keeps
+        nothing.  Only feats.vn is read: v' = v_conv(vn) is recomputed every step from the current v_conv.weight, so
+        in-place optimiser steps never make feats stale for THIS call (they do for answer(), see encode_images).  feats
+        must belong to this model instance and its current parameter storage, as for answer().
+
+        Dropout in train mode: image.drop (models/model.py:84) is NOT applied -- the features are the encoder's eval-mode
+        output; that is what frozen means here.  attention.drop on v (model.py:185) draws one mask per feature ROW of the
+        bank: the logical tensor is [feats.N, gh, gw, C], element (n, p, c) at flat index (n*P + p)*C + c with n the row in
+        feats, not the slot in the batch -- forward_shared's convention for the same images in the same order, so with
+        image.dropout = 0 the two calls are the same function of the seed.  Every question-side site (text, attention.drop
+        on q and on x, both classifier sites) draws per question exactly as forward_shared does.  One seed is drawn per
+        training forward, none in eval mode.
+
+        NotImplementedError for compute_dtype "bf16" and for a model wrapped by dl_vqa_amd.distributed.DataParallel,
+        TypeError for a feats that is not an ImageFeatures, RuntimeError for CPU tensors or foreign features, ValueError
+        for wrong ranks, a wrong image_index count or an empty batch."""
+        if self.compute_dtype == "bf16":
+            raise NotImplementedError("VqaNet.forward_features: compute_dtype='bf16' is not supported (fp32 and fp32x3 are); the "
+                                      "bf16 path rounds x = relu(v' (+|*) q') to bf16, a tensor this path never forms")
+        if self._grad_sync is not None:
+            raise NotImplementedError("VqaNet.forward_features: data-parallel training on cached image features is not "
+                                      "supported (the model is wrapped by dl_vqa_amd.distributed.DataParallel)")
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError("VqaNet.forward_features: feats must come from VqaNet.encode_images (or ImageFeatures.cat)")
+        q, q_len = torch.as_tensor(q), torch.as_tensor(q_len)
+        if not feats.vn.is_cuda or not self._params[0].is_cuda:
+            raise RuntimeError("dl_vqa_amd.VqaNet.forward_features needs CUDA (HIP) tensors; there is no CPU fallback")
+        if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
+            raise ValueError(f"VqaNet.forward_features: q [B,T] and q_len [B] expected, got {tuple(q.shape)} and "
+                             f"{tuple(q_len.shape)}")
+        self._ensure_flat()
+        if feats._model() is not self or feats._flat_ptr != self._flat_param.data_ptr():
+            raise RuntimeError("VqaNet.forward_features: these image features belong elsewhere -- they were encoded by another "
+                               "model instance, or this model's parameters have moved to new storage since (.to(), a "
+                               "re-flatten); call encode_images again on this model")
+        B, N = q.shape[0], feats.N
+        img = _host_image_index(image_index, N)                      # one copy to the host, reused below
+        rows, slot, order, offsets = compact_image_index(img, N)
+        if order.numel() != B:
+            raise ValueError(f"VqaNet.forward_features: {order.numel()} image_index entries for {B} questions")
+        if N == 0 or B == 0:
+            raise ValueError(f"VqaNet.forward_features: an empty batch ({N} feature rows, {B} questions)")
+        self._validate_tokens(q)
+        validate_question_lengths(q_len, q.shape[1])
+        dev = feats.vn.device
+        n_u = rows.numel()
+        # one upload: rows [n_u] | slot [B] | order [B] | offsets [n_u+1] | img [B]
+        idx = torch.cat([rows, slot, order, offsets, img.to(torch.int32)]).to(dev)
+        seed = self._next_seed() if self.training else 0
+        need_grad = torch.is_grad_enabled() and any(p.requires_grad for n, p in zip(self._names, self._params)
+                                                    if n not in self._image_names)
+        if need_grad:
+            logits = _VqaFeaturesFunction.apply(self, feats.vn, q, q_len, seed, idx, n_u, *self._params)
+        else:
+            r, o, f, i = _split_feature_index(idx, n_u, B)
+            logits, _ = self._engine.forward_features(self._param_dict(), feats.vn, q, q_len, r, o, f, i, self.training, seed,
+                                                      keep=False, bad_tokens=self._bad_tokens if q.is_cuda else None)
+        self._after_forward_tokens(q)
+        return logits
+
     # ------------------------------------------------------------------ many questions per image (inference)
     def _check_inference(self, what: str):
         if self.compute_dtype == "bf16":
@@ -570,10 +725,19 @@ class VqaNet(nn.Module):
                                "and classifier dropout sites (models/model.py:84,185,186,194) draw a new mask per forward, so "
                                "image features cached across questions would be meaningless; call model.eval() first")
 
+    @staticmethod
+    def _need_vprime(what: str, feats):
+        if feats.vprime is None:
+            raise RuntimeError(f"VqaNet.{what}: these image features were encoded with with_vprime=False (a bank for "
+                               "forward_features: vn only); encode them with with_vprime=True to answer from them")
+
     @torch.no_grad()
-    def encode_images(self, v) -> ImageFeatures:
+    def encode_images(self, v, with_vprime: bool = True) -> ImageFeatures:
         """The image-only part of the forward, once per image: conv blocks, L2 normalisation and v' = v_conv(vn).
         v [N,3,S,S] fp32 or fp16, CUDA.  Eval mode, compute_dtype fp32 or fp32x3; no autograd graph.
+
+        with_vprime=False skips the v_conv product and leaves feats.vprime None: a bank for forward_features, which reads
+        vn alone (chunks are joined by ImageFeatures.cat).  answer / predict / answer_pairs raise RuntimeError on it.
 
         The result belongs to this model and to its current weights.  answer() refuses features of another model instance
         or of a model whose parameters have moved to new storage, but it cannot see weights that changed IN PLACE (FusedAdam
@@ -585,7 +749,7 @@ class VqaNet(nn.Module):
             raise RuntimeError("dl_vqa_amd.VqaNet.encode_images needs CUDA (HIP) tensors; there is no CPU fallback")
         if v.dtype not in (torch.float32, torch.float16):
             v = v.float()
-        vn, vprime, grid = self._engine.encode_images(self._param_dict(), v.detach())
+        vn, vprime, grid = self._engine.encode_images(self._param_dict(), v.detach(), with_vprime=bool(with_vprime))
         return ImageFeatures(vn, vprime, grid, self)
 
     @torch.no_grad()
@@ -607,6 +771,7 @@ class VqaNet(nn.Module):
             raise RuntimeError("VqaNet.answer: these image features belong elsewhere -- they were encoded by another model "
                                "instance, or this model's parameters have moved to new storage since (.to(), a re-flatten); "
                                "call encode_images again on this model")
+        self._need_vprime("answer", feats)
         q = torch.as_tensor(q)
         q_len = torch.as_tensor(q_len)
         if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
@@ -708,6 +873,7 @@ class VqaNet(nn.Module):
                 raise RuntimeError(f"VqaNet.answer_pairs: these {what} features belong elsewhere -- they were encoded by "
                                    "another model instance, or this model's parameters have moved to new storage since "
                                    f"(.to(), a re-flatten); call {call} again on this model")
+        self._need_vprime("answer_pairs", feats)
         dev = feats.vn.device
         if qfeats.qprime.device != dev:
             raise RuntimeError(f"VqaNet.answer_pairs: the image features are on {dev} and the question features on "

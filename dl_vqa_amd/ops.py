@@ -538,6 +538,34 @@ def gather_rows(src, rows, dst, cols: Optional[int] = None):
     return dst
 
 
+def gather_rows_drop(src, rows, p: float, seed: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[j] = dropout_{p, seed}(src)[rows[j]] without forming the dropped src: src [M, ...] is a contiguous fp32 bank of
+    rows, rows device int32 [n]; the mask of element i of bank row r is drop_scale(seed, r * row_len + i) (64-bit), the one
+    dropout(src, p, seed) applies.  p = 0 copies; an index outside [0, M) gives a row of zeros.  Returns [n, ...]."""
+    _chk(src), _chk(rows, torch.int32)
+    assert src.is_contiguous()
+    M, n = src.shape[0], rows.numel()
+    row_len = src.numel() // M
+    if out is None:
+        out = torch.empty((n,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() == n * row_len
+    call("vqa_gather_rows_drop", ptr(src), ptr(rows), ptr(out), n, M, row_len, p, seed, stream())
+    return out
+
+
+def att_apply_gather_dscore(dout, dout_ld, probs, vn, img, rowsum=None):
+    """The dscore half of att_apply_gather_bwd (same device code, same bits), for a vn nobody wants a gradient of: vn
+    [N, P, C] may be a large bank, only the rows img[b] (device int32 [B]) are read."""
+    B, G, P = probs.shape
+    N, C = vn.shape[0], vn.shape[-1]
+    _chk(img, torch.int32)
+    assert img.numel() == B and vn.numel() == N * P * C
+    dscore = torch.empty_like(probs)
+    call("vqa_att_apply_gather_dscore", ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(dscore), ptr(rowsum), N, B, P, C, G,
+         stream())
+    return dscore
+
+
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C]."""
     B, G, P = score.shape

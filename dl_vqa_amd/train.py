@@ -118,6 +118,26 @@ def run_batch_shared(model, batch_data, max_answers, image_index, batch_divisor:
     return soft_ce_loss_and_score(y_hat, a_indices, a_values, batch_divisor)
 
 
+def run_batch_features(model, batch_data, max_answers, feats, image_index, batch_divisor: Optional[int] = None):
+    """run_batch_shared with the image encoder frozen and run beforehand: `feats` (VqaNet.encode_images, a bank of N feature
+    rows) stands in for the images and question b looks at row image_index[b] (a host list or an integer tensor of B
+    entries in [0, N)).  batch_data is the loader's 7-tuple; its v entry is ignored and may be None.  Same fused loss and
+    score; the loss is divided by the number of QUESTIONS.  No convolution runs, and the image.* parameters get no gradient
+    (VqaNet.forward_features, which also states the dropout semantics)."""
+    _v, q, a_indices, a_values, a_length, idx, q_len = batch_data
+    n_index = len(image_index) if not torch.is_tensor(image_index) else image_index.numel()
+    if n_index != q.shape[0]:
+        raise ValueError(f"run_batch_features: {n_index} image_index entries for {q.shape[0]} questions")
+    dev = next(model.parameters()).device
+    q = q.to(dev, non_blocking=True)
+    a_indices = a_indices.to(dev, non_blocking=True)
+    a_values = a_values.to(dev, non_blocking=True)
+    validate_question_lengths(q_len, q.shape[1])
+    q_len = q_len.to(dev, non_blocking=True)
+    y_hat = model.forward_features(feats, q, q_len, image_index)
+    return soft_ce_loss_and_score(y_hat, a_indices, a_values, batch_divisor)
+
+
 # ------------------------------------------------------------------ optimiser
 def update_learning_rate(optimizer, iteration, initial_lr):
     """train.py:31-35."""

@@ -32,7 +32,9 @@ extern "C" {
  * (vqa_att_score_grouped_drop_fwd, vqa_att_apply_gather_bwd, vqa_att_score_grouped_tiles, vqa_att_score_grouped_bwd) joined
  * version 8 that way, vqa_softmax_topk after them, and the two entry points of cached question features
  * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that, then image preprocessing (vqa_preprocess_supported,
- * vqa_preprocess_images) -- a caller built against the earlier version-8 header finds every prototype it knows unchanged. */
+ * vqa_preprocess_images), then the two entry points of training on cached image features (vqa_gather_rows_drop,
+ * vqa_att_apply_gather_dscore) -- a caller built against the earlier version-8 header finds every prototype it knows
+ * unchanged. */
 #define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
@@ -352,6 +354,26 @@ int vqa_att_score_grouped_pairs_fwd(const float* vprime, const float* qp, const 
  * (elements) and both pointers allow it, scalar otherwise.  src_ld, dst_ld >= cols.  B == 0 returns without a launch. */
 int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float* dst, int64_t dst_ld, int B, int M, int cols,
                     vqa_stream_t stream);
+
+/* ---- training on cached image features (VqaNet.forward_features): a frozen image encoder, a bank of feature rows --------
+ * Neither entry point uses atomics, and neither launches work that grows with the size of the bank.
+ *
+ * The asked rows of a bank, compacted and dropped in one pass (attention.drop on v, models/model.py:185, with the mask
+ * indexed by the BANK row, as if it had been drawn over the whole bank):
+ *   dst[j*row_len + i] = src[rows[j]*row_len + i] * keep(seed, rows[j]*row_len + i) / (1-p)      j < n, i < row_len
+ * src is [M][row_len], dst [n][row_len], rows device int32 [n]; the flat index is 64-bit (the mask vqa_dropout applies to
+ * the whole bank).  p = 0 is a pure copy; a rows[j] outside [0, M) writes a row of zeros.  16-byte accesses when
+ * row_len % 4 == 0 and both pointers are 16-byte aligned, scalar otherwise (same bits).  The flat range n * row_len is
+ * spread over a capped grid, so one long row fills the device.  n >= 0, M >= 1, row_len >= 1, 0 <= p < 1; n == 0 returns
+ * without a launch. */
+int vqa_gather_rows_drop(const float* src, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
+                         uint64_t seed, vqa_stream_t stream);
+/* vqa_att_apply_gather_bwd without the per-image sum dvn (the image encoder is frozen: nobody reads d loss / d vn):
+ * dscore [B][G][P] and dscore_rowsum [B][G] (optional) from the same device code, bit for bit; vn is [N][P][C] and only the
+ * rows img[b] are read.  Limits as vqa_att_apply_gather_bwd: C % 4 == 0, dout_ld % 4 == 0, dout_ld >= G*C, G in 1..4,
+ * N >= 1; dout and vn 16-byte aligned.  B == 0 returns without a launch. */
+int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                                float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
