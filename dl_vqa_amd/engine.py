@@ -7,6 +7,8 @@ activations time-major [T][B][*], the classifier input `combined` = [weighted v 
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import os
 from types import SimpleNamespace
 from typing import Callable, Dict, Optional
@@ -37,6 +39,22 @@ def _gemm(A, B, C, M, N, K, x3=False, **kw):
         return ops.gemm_bf16(A, B, C, M, N, K, **kw)
     return ops.gemm(A, B, C, M, N, K, x3=x3, **kw)
 
+
+def _device_current(name: str, device=lambda x: x.device):
+    """Decorator of an Engine schedule: the argument called `name` says where the schedule's tensors live (device(argument):
+    a tensor's device unless told otherwise), and that device is current while the schedule runs."""
+    def deco(schedule):
+        pos = list(inspect.signature(schedule).parameters).index(name) - 1      # behind self
+
+        @functools.wraps(schedule)
+        def guarded(self, *args, **kw):
+            with torch.cuda.device(device(args[pos] if pos < len(args) else kw[name])):
+                return schedule(self, *args, **kw)
+        return guarded
+    return deco
+
+
+_cache_device = lambda feats: feats.vn.device       # of an ImageFeatures
 
 
 class Engine:
@@ -201,40 +219,28 @@ class Engine:
         return x if fc is None else self._rows16(x, ld, fc.B, cols, fc.B8)
 
     # ------------------------------------------------------------------ forward
+    # kernels launch on HIP's CURRENT device and torch's current stream of that device: _device_current makes the
+    # tensors' device current for the whole schedule (a model on cuda:1 while cuda:0 is current would otherwise
+    # launch on GPU 0 with GPU-1 pointers)
+    @_device_current("v")
     def forward(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, training: bool, seed: int,
                 keep: bool, bad_tokens: Optional[Tensor] = None, need_dx: bool = False):
         """Returns (logits [B,A], ctx or None). `keep` = save what backward needs.
         bad_tokens: optional device int32 [1] that counts token ids outside the vocabulary.
         need_dx (with keep): backward also returns the gradient w.r.t. the image v."""
-        # kernels launch on HIP's CURRENT device and torch's current stream of that device: make the tensors'
-        # device current for the whole schedule (a model on cuda:1 while cuda:0 is current would otherwise
-        # launch on GPU 0 with GPU-1 pointers)
-        with torch.cuda.device(v.device):
-            return self._forward(P, v, q, q_len, training, seed, keep, bad_tokens, need_dx)
-
-    def _forward(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, training: bool, seed: int,
-                 keep: bool, bad_tokens: Optional[Tensor] = None, need_dx: bool = False):
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [B,C,S,S]"
         v = v.contiguous()
         need_dx = bool(keep and need_dx)
         dev = v.device
-        q = q.to(device=dev, dtype=torch.int64).contiguous()
-        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
         B, T = q.shape
-        C, mid, Dc, GC = self.C, self.mid, self.Dc, self.GC
-        tr = bool(training)
-        p_txt, p_img, p_att, p_cls = (self.p_text, self.p_image, self.p_att, self.p_cls) if tr else (0.0, 0.0, 0.0, 0.0)
+        C, mid, GC = self.C, self.mid, self.GC
+        p_txt, p_img, p_att, p_cls = self._rates(training)
         sd = lambda site: _site_seed(seed, site)
 
         # ---- question encoder (model.py:155-166)
-        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, sd(SITE_TEXT), bad_tokens)       # [T,B,E]
-        combined = torch.empty(B, Dc, dtype=torch.float32, device=dev)
-        # The question branch is a chain of small (M = B) launches, independent of the image branch until the
-        # attention stage; it runs on a side stream, under the convolutions (VQA_STREAMS=2, the default; 1: the main
-        # stream waits for it before the convolutions start; 0: everything on one stream).
-        l16 = self.lstm16 and (T * B) % 8 == 0
-        (lstm, x16), text_done = self._on_side_stream(dev, lambda: self._question_encoder(P, x_emb, q_len, combined, l16))
+        txt, text_done = self._question_front(P, q, q_len, dev, p_txt, seed, bad_tokens, side=True,
+                                              l16=self.lstm16 and (T * B) % 8 == 0)
 
         # ---- image encoder, image dropout + L2 normalisation over channels (model.py:84,56)
         img = self._image_encoder(P, v, keep, need_dx)
@@ -254,21 +260,56 @@ class Engine:
 
         # ---- attention (model.py:183-195): v' = v_conv(drop(v)), q' = q_lin(drop(q)), x = relu(v' + q')
         wv16 = ops.to_bf16(P["attention.v_conv.weight"].view(mid, C)) if self.bf16 else None
-        qp, q_in, ld_q, fc = self._q_lin_fwd(P, combined[:, GC:], p_att, seed)
+        qlin = self._q_lin_fwd(P, txt.combined[:, GC:], p_att, seed)
         v_op, wv_op = (v16.view(B * Pn, C), wv16) if self.bf16 else (v_in, P["attention.v_conv.weight"])
-        xs, vprime, score, probs = self._attention_fwd(P, v_op, wv_op, vn, qp, combined, B, Pn, p_att, seed, keep)
+        xs, vprime, score, probs = self._attention_fwd(P, v_op, wv_op, vn, qlin[0], txt.combined, B, Pn, p_att, seed, keep)
 
         # ---- classifier (model.py:198-205)
-        logits, c_in, h1, h1d = self._classifier_fwd(P, combined, p_cls, seed, fc)
-
+        logits, *cls = self._classifier_fwd(P, txt.combined, p_cls, seed, qlin[3])
         if not keep:
             return logits, None
-        ctx = SimpleNamespace(B=B, T=T, Pn=Pn, q=q, q_len=q_len, acts=img.acts, idxs=img.idxs, wds=img.wds, vn=vn, norm=norm,
-                              x_emb=x_emb, x16=x16, lstm=lstm, v_in=v_in, v16=v16, wv16=wv16, q_in=q_in, ld_q=ld_q, xs=xs, probs=probs,
-                              c_in=c_in, h1=h1, h1d=h1d, fast0=img.fast0, use_pc=img.use_pc, fc=fc, vprime=vprime, qp=qp, p_img=p_img, p_txt=p_txt, p_att=p_att, p_cls=p_cls,
-                              seed=seed, stages=dict(pooled=pooled, score=score, combined=combined),
-                              need_dx=need_dx, v_dtype=v.dtype, v_shape=tuple(v.shape))
-        return logits, ctx
+        return logits, self._saved(txt, qlin, cls, seed, (p_txt, p_att, p_cls), Pn, vn, v_in, vprime, score, probs, v16=v16,
+                                   wv16=wv16, xs=xs, pooled=pooled, **self._encoder_saved(img, norm, p_img, need_dx, v))
+
+    def _rates(self, training):
+        """(p_text, p_image, p_att, p_cls) of one forward: the configured dropout rates in train mode, zeros in eval mode."""
+        return (self.p_text, self.p_image, self.p_att, self.p_cls) if training else (0.0, 0.0, 0.0, 0.0)
+
+    def _question_front(self, P, q, q_len, dev, p_txt, seed, bad_tokens, side, l16=False):
+        """The question prelude of every schedule: q / q_len on the device as int64, embedding + dropout + tanh, the
+        classifier-input buffer `combined` [B, Dc], and the question encoder, which fills combined[:, GC:].  Returns (a
+        namespace of q, q_len, x_emb [T,B,E], combined, lstm, x16; the event to join on, or None).
+        side: the question branch is a chain of small (M = B) launches, independent of the image branch until the
+        attention stage; it runs on a side stream, under the convolutions (VQA_STREAMS=2, the default; 1: the main
+        stream waits for it before the convolutions start; 0: everything on one stream).  Not side: on the current
+        stream (the inference calls have no convolutions to hide it under)."""
+        q = q.to(device=dev, dtype=torch.int64).contiguous()
+        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
+        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, _site_seed(seed, SITE_TEXT), bad_tokens)
+        combined = torch.empty(q.shape[0], self.Dc, dtype=torch.float32, device=dev)
+        encode = lambda: self._question_encoder(P, x_emb, q_len, combined, l16)
+        (lstm, x16), done = self._on_side_stream(dev, encode) if side else (encode(), None)
+        return SimpleNamespace(q=q, q_len=q_len, x_emb=x_emb, combined=combined, lstm=lstm, x16=x16), done
+
+    @staticmethod
+    def _saved(txt, qlin, cls, seed, rates, Pn, vn, v_in, vprime, score, probs, pooled=None, **own):
+        """What a backward reads again and what tests and tools look at (stages): the fields every training schedule saves,
+        from _question_front's namespace and the results of _q_lin_fwd and _classifier_fwd; `own`: the schedule's own."""
+        (qp, q_in, ld_q, fc), (c_in, h1, h1d), (p_txt, p_att, p_cls) = qlin, cls, rates
+        B, T = txt.q.shape
+        stages = dict(score=score, combined=txt.combined)
+        if pooled is not None:
+            stages["pooled"] = pooled
+        return SimpleNamespace(B=B, T=T, Pn=Pn, q=txt.q, q_len=txt.q_len, x_emb=txt.x_emb, x16=txt.x16, lstm=txt.lstm, vn=vn,
+                               v_in=v_in, vprime=vprime, qp=qp, q_in=q_in, ld_q=ld_q, fc=fc, probs=probs, c_in=c_in, h1=h1,
+                               h1d=h1d, p_txt=p_txt, p_att=p_att, p_cls=p_cls, seed=seed, stages=stages, **own)
+
+    @staticmethod
+    def _encoder_saved(enc, norm, p_img, need_dx, v):
+        """The saved fields of a schedule that ran _image_encoder on the image batch v: what the L2-norm backward and
+        _conv_bwd read."""
+        return dict(acts=enc.acts, idxs=enc.idxs, wds=enc.wds, norm=norm, fast0=enc.fast0, use_pc=enc.use_pc, p_img=p_img,
+                    need_dx=need_dx, v_dtype=v.dtype, v_shape=tuple(v.shape))
 
     def _question_encoder(self, P, x_emb, q_len, combined, l16):
         """LSTM over the embedded question x_emb [T,B,E] on the current stream; the final cell states land in combined[:, GC:].
@@ -446,13 +487,10 @@ class Engine:
     # ------------------------------------------------------------------ many questions per image (inference)
     # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder, the question encoder, q_lin and the
     # classifier are the forward's own stages; the attention stage runs on ONE v' per image (csrc/att_grouped.hip).
+    @_device_current("v")
     def encode_images(self, P: Dict[str, Tensor], v: Tensor, with_vprime: bool = True):
         """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid] or None (with_vprime=False), (gh, gw))."""
         assert not self.bf16, "encode_images: fp32 / fp32x3 only"
-        with torch.cuda.device(v.device):
-            return self._encode_images(P, v, with_vprime)
-
-    def _encode_images(self, P, v, with_vprime=True):
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
         x = self._image_encoder(P, v.contiguous(), keep=False).out
@@ -465,176 +503,184 @@ class Engine:
             ops.gemm(vn, P["attention.v_conv.weight"], vprime, N * Pn, self.mid, C, tag=21, x3=self._x3_gemm(N * Pn))
         return vn.view(N, Pn, C), vprime, (gh, gw)
 
+    @_device_current("feats", _cache_device)
     def answer(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
                bad_tokens: Optional[Tensor] = None):
         """B questions against the N encoded images of `feats` (vn, vprime): question b looks at image img[b]; order /
         offsets (device int32) group the questions by image.  Returns (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer: fp32 / fp32x3 only"
-        with torch.cuda.device(feats.vn.device):
-            return self._answer(P, feats, q, q_len, order, offsets, img, bad_tokens)
-
-    def _answer(self, P, feats, q, q_len, order, offsets, img, bad_tokens):
-        dev = feats.vn.device
-        q = q.to(device=dev, dtype=torch.int64).contiguous()
-        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
-        B = q.shape[0]
         N, Pn, _ = feats.vn.shape
         # ---- question encoder and q_lin, eval mode, on the current stream (there are no convolutions to hide them under)
-        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], 0.0, 0, bad_tokens)                     # [T,B,E]
-        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=dev)
-        self._question_encoder(P, x_emb, q_len, combined, l16=False)
-        qp = self._q_lin_fwd(P, combined[:, self.GC:], 0.0, 0)[0]
+        txt, _ = self._question_front(P, q, q_len, feats.vn.device, 0.0, 0, bad_tokens, side=False)
+        qp = self._q_lin_fwd(P, txt.combined[:, self.GC:], 0.0, 0)[0]
         # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
         score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
-                                          P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode)
+                                          P["attention.x_conv.bias"], order, offsets, N, q.shape[0], Pn, self.att_mode)
+        return self._answer_tail(P, feats, score, img, txt.combined)
+
+    def _answer_tail(self, P, feats, score, img, combined, cached=None):
+        """What answer and answer_pairs end with: softmax over positions + weighted sum of the image img[b]'s features into
+        combined[:, :GC], and the eval-mode classifier.  cached = (qf, qrow): answer_pairs' question half of the classifier
+        input (models/model.py:64), one cached row per pair; answer's encoder has written it.  Returns (logits, probs, score)."""
         probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, self.Dc)
-        # ---- classifier
+        if cached is not None:
+            ops.gather_rows(*cached, combined[:, self.GC:], self.Q)
         logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
         return logits, probs, score
 
     # ------------------------------------------------------------------ cached question features (inference)
     # The mirror image of encode_images / answer: the question encoder and q_lin run once per DISTINCT question, and
     # (image, question) pairs are answered from the two caches -- no recurrence, no convolution in answer_pairs.
+    @_device_current("dev", lambda dev: dev)
     def encode_questions(self, P: Dict[str, Tensor], q: Tensor, q_len: Tensor, dev, bad_tokens: Optional[Tensor] = None):
         """q [M,T], q_len [M] -> (qf [M,Q]: the final cell states, a view with row stride Dc; q' = q_lin(qf) [M,mid])."""
         assert not self.bf16, "encode_questions: fp32 / fp32x3 only"
-        with torch.cuda.device(dev):
-            return self._encode_questions(P, q, q_len, dev, bad_tokens)
-
-    def _encode_questions(self, P, q, q_len, dev, bad_tokens):
-        q = q.to(device=dev, dtype=torch.int64).contiguous()
-        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
-        M = q.shape[0]
         # the forward's own stages on M rows, eval mode; the encoder writes the question half of a classifier-input buffer
-        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], 0.0, 0, bad_tokens)                     # [T,M,E]
-        combined = torch.empty(M, self.Dc, dtype=torch.float32, device=dev)
-        self._question_encoder(P, x_emb, q_len, combined, l16=False)
-        qf = combined[:, self.GC:]
-        qp = self._q_lin_fwd(P, qf, 0.0, 0)[0]
-        return qf, qp
+        txt, _ = self._question_front(P, q, q_len, dev, 0.0, 0, bad_tokens, side=False)
+        qf = txt.combined[:, self.GC:]
+        return qf, self._q_lin_fwd(P, qf, 0.0, 0)[0]
 
+    @_device_current("feats", _cache_device)
     def answer_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor, qrow: Tensor):
         """B pairs from the encoded images `feats` (vn, vprime) and the encoded questions `qfeats` (qf, qprime): pair b
         looks at image img[b] with question qrow[b]; order / offsets (device int32) group the pairs by image.  Returns
         (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer_pairs: fp32 / fp32x3 only"
-        with torch.cuda.device(feats.vn.device):
-            return self._answer_pairs(P, feats, qfeats, order, offsets, img, qrow)
-
-    def _answer_pairs(self, P, feats, qfeats, order, offsets, img, qrow):
-        dev = feats.vn.device
         B = img.numel()
         N, Pn, _ = feats.vn.shape
         # ---- attention: scores from v' (one per image) and q' (one per distinct question)
         score = ops.att_score_grouped_pairs_fwd(feats.vprime, qfeats.qprime, qrow, P["attention.x_conv.weight"].view(self.G, -1),
                                                 P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode)
-        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=dev)
-        probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, self.Dc)
-        # ---- the question half of the classifier input (models/model.py:64), one cached row per pair
-        ops.gather_rows(qfeats.qf, qrow, combined[:, self.GC:], self.Q)
-        # ---- classifier
-        logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
-        return logits, probs, score
+        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=feats.vn.device)
+        return self._answer_tail(P, feats, score, img, combined, cached=(qfeats.qf, qrow))
 
-    # ------------------------------------------------------------------ training through shared image features
-    # fp32 / fp32x3.  v holds every image ONCE; question b looks at image img[b].  The image encoder, the question encoder,
-    # q_lin and the classifier are the forward's own stages, run on N images and B questions; the attention stage runs on one
-    # v' per image (csrc/att_grouped.hip) and its backward sums the image-side gradients over the questions of an image.
+    # ------------------------------------------------------------------ training through grouped image features
+    # fp32 / fp32x3.  Question b looks at image img[b]; order / offsets group the questions by image.  The question encoder,
+    # q_lin and the classifier are the forward's own stages on B questions; the attention stage runs on one v' per image
+    # (csrc/att_grouped.hip) and its backward sums the image-side gradients over the questions of an image.  One schedule
+    # (_forward_grouped / backward_grouped) with two image sides:
+    #
+    # forward_shared: v holds every image ONCE and the image encoder runs on those N images, as a part of the graph.
     # Dropout: the image-side sites (SITE_IMAGE, SITE_ATT_V) draw one mask per IMAGE (logical tensor [N, gh, gw, C]); every
     # question-side site draws per question as forward() does, SITE_ATT_X over [B, P, xld] indexed by the question.
+    #
+    # forward_features: the image encoder is frozen: `vn` [M,Pn,C] is a bank of its eval-mode outputs (encode_images).  Only the
+    # n_u DISTINCT asked rows are touched: rows (ascending) names them, order / offsets group the questions by their slot in
+    # rows.  No kernel's grid or byte count depends on M.  v' is recomputed from the current v_conv weight every step.
+    # Dropout: SITE_IMAGE is not applied; SITE_ATT_V draws per BANK row (logical tensor [M, gh, gw, C]); the question-side
+    # sites draw per question as forward_shared does.
+    @_device_current("v")
     def forward_shared(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor,
                        img: Tensor, training: bool, seed: int, keep: bool, bad_tokens: Optional[Tensor] = None,
                        need_dx: bool = False):
         """v [N,C,S,S]; order / offsets / img: device int32 (model.group_by_image and the image index itself).  Returns
         (logits [B,A], ctx or None), as forward() does."""
         assert not self.bf16, "forward_shared: fp32 / fp32x3 only"
-        with torch.cuda.device(v.device):
-            return self._forward_shared(P, v, q, q_len, order, offsets, img, training, seed, keep, bad_tokens, need_dx)
-
-    def _forward_shared(self, P, v, q, q_len, order, offsets, img, training, seed, keep, bad_tokens, need_dx):
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
         v = v.contiguous()
         need_dx = bool(keep and need_dx)
-        dev = v.device
-        q = q.to(device=dev, dtype=torch.int64).contiguous()
-        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
-        B, T = q.shape
-        N = v.shape[0]
-        C, mid, Dc, GC, G = self.C, self.mid, self.Dc, self.GC, self.G
-        tr = bool(training)
-        p_txt, p_img, p_att, p_cls = (self.p_text, self.p_image, self.p_att, self.p_cls) if tr else (0.0, 0.0, 0.0, 0.0)
-        sd = lambda site: _site_seed(seed, site)
+        side = lambda p_img, p_att: self._encoded_images(P, v, keep, need_dx, p_img, p_att, seed)
+        return self._forward_grouped(P, side, v.device, q, q_len, order, offsets, img, training, seed, keep, bad_tokens)
 
-        # ---- question encoder on the side stream, under the convolutions (as forward())
-        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, sd(SITE_TEXT), bad_tokens)       # [T,B,E]
-        combined = torch.empty(B, Dc, dtype=torch.float32, device=dev)
-        (lstm, x16), text_done = self._on_side_stream(dev, lambda: self._question_encoder(P, x_emb, q_len, combined, False))
+    @_device_current("vn")
+    def forward_features(self, P: Dict[str, Tensor], vn: Tensor, q: Tensor, q_len: Tensor, rows: Tensor, order: Tensor,
+                         offsets: Tensor, img: Tensor, training: bool, seed: int, keep: bool,
+                         bad_tokens: Optional[Tensor] = None):
+        """vn [M,Pn,C]; rows [n_u], order [B], offsets [n_u+1], img [B]: device int32 (model.compact_image_index and the image
+        index itself).  Returns (logits [B,A], ctx or None)."""
+        assert not self.bf16, "forward_features: fp32 / fp32x3 only"
+        assert vn.is_cuda and vn.dtype == torch.float32 and vn.dim() == 3 and vn.is_contiguous() and vn.shape[2] == self.C
+        side = lambda p_img, p_att: self._bank_rows(vn, rows, p_att, seed)
+        return self._forward_grouped(P, side, vn.device, q, q_len, order, offsets, img, training, seed, keep, bad_tokens)
 
-        # ---- image encoder on the N images, image dropout + L2 normalisation, v' = v_conv(drop(vn)): once per image
+    def _encoded_images(self, P, v, keep, need_dx, p_img, p_att, seed):
+        """forward_shared's image side: the image encoder on the N images, image dropout + L2 normalisation, attention.drop(v)
+        as the same pass's second output.  Returns (vn [N,Pn,C], v_in, N, the schedule's own saved fields)."""
         enc = self._image_encoder(P, v, keep, need_dx)
-        pooled = enc.out
-        Pn = pooled.shape[1] * pooled.shape[2]
+        N, gh, gw, C = enc.out.shape
         if p_att > 0:
-            vn, norm, v_in = ops.l2norm_fwd(pooled, p_img, sd(SITE_IMAGE), drop2=(p_att, sd(SITE_ATT_V), torch.float32))
+            vn, norm, v_in = ops.l2norm_fwd(enc.out, p_img, _site_seed(seed, SITE_IMAGE),
+                                            drop2=(p_att, _site_seed(seed, SITE_ATT_V), torch.float32))
         else:
-            vn, norm = ops.l2norm_fwd(pooled, p_img, sd(SITE_IMAGE))
+            vn, norm = ops.l2norm_fwd(enc.out, p_img, _site_seed(seed, SITE_IMAGE))
             v_in = vn
-        vprime = torch.empty(N * Pn, mid, dtype=torch.float32, device=dev)
-        ops.gemm(v_in, P["attention.v_conv.weight"], vprime, N * Pn, mid, C, tag=21, x3=self._x3_gemm(N * Pn))
+        own = dict(encoded=True, pooled=enc.out, **self._encoder_saved(enc, norm, p_img, need_dx, v))
+        return vn.view(N, gh * gw, C), v_in, N, own
+
+    def _bank_rows(self, vn, rows, p_att, seed):
+        """forward_features' image side: the asked rows of the bank vn [M,Pn,C], compacted, with attention.drop(v) indexed by
+        the bank row.  Returns (vn: the weighted sum reads the bank itself, undropped; v_in [n_u,Pn,C]; n_u; the schedule's own
+        saved fields)."""
+        v_in = ops.gather_rows_drop(vn, rows, p_att, _site_seed(seed, SITE_ATT_V))
+        return vn, v_in, rows.numel(), dict(encoded=False, rows=rows)
+
+    def _forward_grouped(self, P, image_side, dev, q, q_len, order, offsets, img, training, seed, keep, bad_tokens):
+        """The schedule of forward_shared and forward_features.  image_side(p_img, p_att) -> (vn [*,Pn,C]: what the weighted
+        sum reads at row img[b]; v_in [n,Pn,C]: v_conv's input, one entry per group of order / offsets; n; saved fields)."""
+        B = q.shape[0]
+        C, mid, GC, G = self.C, self.mid, self.GC, self.G
+        p_txt, p_img, p_att, p_cls = self._rates(training)
+
+        # ---- question encoder on the side stream, under the image side (as forward())
+        txt, text_done = self._question_front(P, q, q_len, dev, p_txt, seed, bad_tokens, side=True)
+
+        # ---- image side, then v' = v_conv(v_in): once per image
+        vn, v_in, n, own = image_side(p_img, p_att)
+        Pn = vn.shape[1]
+        vprime = torch.empty(n * Pn, mid, dtype=torch.float32, device=dev)
+        ops.gemm(v_in, P["attention.v_conv.weight"], vprime, n * Pn, mid, C, tag=21, x3=self._x3_gemm(n * Pn))
         torch.cuda.current_stream(dev).wait_event(text_done)
 
         # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
-        qp, q_in, ld_q, fc = self._q_lin_fwd(P, combined[:, GC:], p_att, seed)
-        score = ops.att_score_grouped_drop_fwd(vprime, qp, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"],
-                                               order, offsets, N, B, Pn, self.att_mode, p_att, sd(SITE_ATT_X))
-        probs = ops.att_apply_gather_fwd(score, vn.view(N, Pn, C), img, combined, Dc)
+        qlin = self._q_lin_fwd(P, txt.combined[:, GC:], p_att, seed)
+        score = ops.att_score_grouped_drop_fwd(vprime, qlin[0], P["attention.x_conv.weight"].view(G, -1),
+                                               P["attention.x_conv.bias"], order, offsets, n, B, Pn, self.att_mode, p_att,
+                                               _site_seed(seed, SITE_ATT_X))
+        probs = ops.att_apply_gather_fwd(score, vn, img, txt.combined, self.Dc)
 
         # ---- classifier
-        logits, c_in, h1, h1d = self._classifier_fwd(P, combined, p_cls, seed, fc)
+        logits, *cls = self._classifier_fwd(P, txt.combined, p_cls, seed, qlin[3])
         if not keep:
             return logits, None
-        ctx = SimpleNamespace(B=B, N=N, T=T, Pn=Pn, q=q, q_len=q_len, order=order, offsets=offsets, img=img, acts=enc.acts,
-                              idxs=enc.idxs, wds=enc.wds, vn=vn, norm=norm, x_emb=x_emb, x16=x16, lstm=lstm, v_in=v_in, q_in=q_in,
-                              ld_q=ld_q, probs=probs, c_in=c_in, h1=h1, h1d=h1d, fast0=enc.fast0, use_pc=enc.use_pc, fc=fc,
-                              vprime=vprime, qp=qp, p_img=p_img, p_txt=p_txt, p_att=p_att, p_cls=p_cls, seed=seed,
-                              stages=dict(pooled=pooled, score=score, combined=combined), need_dx=need_dx, v_dtype=v.dtype,
-                              v_shape=tuple(v.shape))
-        return logits, ctx
+        return logits, self._saved(txt, qlin, cls, seed, (p_txt, p_att, p_cls), Pn, vn, v_in, vprime, score, probs, N=n,
+                                   order=order, offsets=offsets, img=img, **own)
 
-    def backward_shared(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
-                        on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:
-        """backward() for a forward_shared context: the image gradient it returns is [N,C,S,S], the questions of an image
-        summed."""
-        with torch.cuda.device(dlogits.device):
-            return self._backward_shared(P, ctx, dlogits, Gr, on_ready)
-
-    def _backward_shared(self, P, ctx, dlogits, Gr, on_ready):
+    @_device_current("dlogits")
+    def backward_grouped(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
+                         on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:
+        """backward() for a forward_shared or forward_features context.  forward_shared: the image gradient it returns is
+        [N,C,S,S], the questions of an image summed.  forward_features: writes the gradients of classifier, attention and
+        text into Gr; the image.* entries of Gr are not touched and there is no image gradient."""
         dev = dlogits.device
         ready = on_ready if on_ready is not None else (lambda group: None)
-        B, N, Pn = ctx.B, ctx.N, ctx.Pn
+        B, n, Pn = ctx.B, ctx.N, ctx.Pn
         G, C, mid, Dc = self.G, self.C, self.mid, self.Dc
+        encoded = ctx.encoded                   # forward_shared: the gradient goes on into the image encoder
         sd = lambda site: _site_seed(ctx.seed, site)
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         dcomb = self._classifier_bwd(P, ctx, dlogits, Gr)
         ready("classifier")
-        # ---- attention apply + scores: dvn = the weighted-sum branch of d loss / d vn, summed per image
+        # ---- attention apply + scores; dvn = the weighted-sum branch of d loss / d vn, summed per image (a bank's has no reader)
         ds_rows = new(B, G, 1)
-        dscore, dvn = ops.att_apply_gather_bwd(dcomb, Dc, ctx.probs, ctx.vn.view(N, Pn, C), ctx.img, ctx.order, ctx.offsets,
-                                               rowsum=ds_rows)
+        if encoded:
+            dscore, dvn = ops.att_apply_gather_bwd(dcomb, Dc, ctx.probs, ctx.vn, ctx.img, ctx.order, ctx.offsets, rowsum=ds_rows)
+        else:
+            dscore = ops.att_apply_gather_dscore(dcomb, Dc, ctx.probs, ctx.vn, ctx.img, rowsum=ds_rows)
         ops.sum_bgp(ds_rows, Gr["attention.x_conv.bias"])
         wx = P["attention.x_conv.weight"].view(G, -1)
-        dvprime, dq_part, dwx_part, NT = ops.att_score_grouped_bwd(dscore, ctx.vprime, ctx.qp, wx, ctx.order, ctx.offsets, N, B, Pn,
+        dvprime, dq_part, dwx_part, NT = ops.att_score_grouped_bwd(dscore, ctx.vprime, ctx.qp, wx, ctx.order, ctx.offsets, n, B, Pn,
                                                                    self.att_mode, ctx.p_att, sd(SITE_ATT_X))
-        ops.colsum(dwx_part, N * NT, wx.numel(), Gr["attention.x_conv.weight"])
+        ops.colsum(dwx_part, n * NT, wx.numel(), Gr["attention.x_conv.weight"])
         dqp = new(B, mid)
         ops.sum_parts(dq_part, dqp, B, NT, mid)
-        # ---- v_conv over the N * Pn image rows: dW = dv'^T . v_in, dv_in = dv' . Wv
-        gx3 = self._x3_gemm(N * Pn)
-        ops.gemm(dvprime, ctx.v_in, Gr["attention.v_conv.weight"], mid, C, N * Pn, transA=True, transB=False, lda=mid, ldb=C,
+        # ---- v_conv over the n * Pn image rows: dW = dv'^T . v_in and, towards the encoder, dv_in = dv' . Wv
+        gx3 = self._x3_gemm(n * Pn)
+        ops.gemm(dvprime, ctx.v_in, Gr["attention.v_conv.weight"], mid, C, n * Pn, transA=True, transB=False, lda=mid, ldb=C,
                  tag=44, x3=gx3)
-        dv_in = new(N * Pn, C)
-        ops.gemm(dvprime, P["attention.v_conv.weight"], dv_in, N * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
+        if encoded:
+            dv_in = new(n * Pn, C)
+            ops.gemm(dvprime, P["attention.v_conv.weight"], dv_in, n * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
         self._q_lin_bwd(P, ctx, dqp, dcomb, Gr)
         ready("attention")
 
@@ -642,6 +688,9 @@ class Engine:
             self._question_bwd(P, ctx, dcomb, Gr)
             ready("text")
 
+        if not encoded:
+            question_branch()
+            return None
         _, text_done = self._on_side_stream(dev, question_branch, backward=True)
         # ---- image side: join the two branches of d loss / d vn (attention.drop on v, models/model.py:185), L2-norm backward,
         # then the conv blocks.  (vqa_l2norm_bwd_joined recomputes a per-SAMPLE weighted sum and cannot be used here.)
@@ -652,98 +701,8 @@ class Engine:
         torch.cuda.current_stream(dev).wait_event(text_done)
         return dv
 
-    # ------------------------------------------------------------------ training on cached image features
-    # fp32 / fp32x3.  The image encoder is frozen: `vn` [M,Pn,C] is a bank of its eval-mode outputs (encode_images), question b
-    # looks at bank row img[b].  Only the n_u DISTINCT asked rows are touched: rows (ascending) names them, order / offsets group
-    # the questions by their slot in rows.  No kernel's grid or byte count depends on M.  v' is recomputed from the current
-    # v_conv weight every step.  Dropout: SITE_IMAGE is not applied; SITE_ATT_V draws per BANK row (logical tensor [M, gh, gw, C]);
-    # the question-side sites draw per question as forward_shared does.
-    def forward_features(self, P: Dict[str, Tensor], vn: Tensor, q: Tensor, q_len: Tensor, rows: Tensor, order: Tensor,
-                         offsets: Tensor, img: Tensor, training: bool, seed: int, keep: bool,
-                         bad_tokens: Optional[Tensor] = None):
-        """vn [M,Pn,C]; rows [n_u], order [B], offsets [n_u+1], img [B]: device int32 (model.compact_image_index and the image
-        index itself).  Returns (logits [B,A], ctx or None)."""
-        assert not self.bf16, "forward_features: fp32 / fp32x3 only"
-        with torch.cuda.device(vn.device):
-            return self._forward_features(P, vn, q, q_len, rows, order, offsets, img, training, seed, keep, bad_tokens)
-
-    def _forward_features(self, P, vn, q, q_len, rows, order, offsets, img, training, seed, keep, bad_tokens):
-        assert vn.is_cuda and vn.dtype == torch.float32 and vn.dim() == 3 and vn.is_contiguous()
-        dev = vn.device
-        q = q.to(device=dev, dtype=torch.int64).contiguous()
-        q_len = q_len.to(device=dev, dtype=torch.int64).contiguous()
-        B, T = q.shape
-        _, Pn, C = vn.shape
-        n_u = rows.numel()
-        mid, Dc, GC, G = self.mid, self.Dc, self.GC, self.G
-        assert C == self.C
-        tr = bool(training)
-        p_txt, p_att, p_cls = (self.p_text, self.p_att, self.p_cls) if tr else (0.0, 0.0, 0.0)
-        sd = lambda site: _site_seed(seed, site)
-
-        # ---- question encoder on the side stream, under the gather and the v_conv product
-        x_emb = ops.embed_tanh_fwd(q, P["text.embedding.weight"], p_txt, sd(SITE_TEXT), bad_tokens)       # [T,B,E]
-        combined = torch.empty(B, Dc, dtype=torch.float32, device=dev)
-        (lstm, x16), text_done = self._on_side_stream(dev, lambda: self._question_encoder(P, x_emb, q_len, combined, False))
-
-        # ---- the asked rows of the bank, compacted, with attention.drop(v) indexed by the bank row; v' = v_conv of them
-        v_in = ops.gather_rows_drop(vn, rows, p_att, sd(SITE_ATT_V))                                      # [n_u,Pn,C]
-        vprime = torch.empty(n_u * Pn, mid, dtype=torch.float32, device=dev)
-        ops.gemm(v_in, P["attention.v_conv.weight"], vprime, n_u * Pn, mid, C, tag=21, x3=self._x3_gemm(n_u * Pn))
-        torch.cuda.current_stream(dev).wait_event(text_done)
-
-        # ---- attention: scores from v' (one per asked row) and q'; the weighted sum reads the bank itself, undropped
-        qp, q_in, ld_q, fc = self._q_lin_fwd(P, combined[:, GC:], p_att, seed)
-        score = ops.att_score_grouped_drop_fwd(vprime, qp, P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"],
-                                               order, offsets, n_u, B, Pn, self.att_mode, p_att, sd(SITE_ATT_X))
-        probs = ops.att_apply_gather_fwd(score, vn, img, combined, Dc)
-
-        # ---- classifier
-        logits, c_in, h1, h1d = self._classifier_fwd(P, combined, p_cls, seed, fc)
-        if not keep:
-            return logits, None
-        ctx = SimpleNamespace(B=B, N=n_u, T=T, Pn=Pn, q=q, q_len=q_len, order=order, offsets=offsets, img=img, rows=rows, vn=vn,
-                              x_emb=x_emb, x16=x16, lstm=lstm, v_in=v_in, q_in=q_in, ld_q=ld_q, probs=probs, c_in=c_in, h1=h1,
-                              h1d=h1d, fc=fc, vprime=vprime, qp=qp, p_txt=p_txt, p_att=p_att, p_cls=p_cls, seed=seed,
-                              stages=dict(score=score, combined=combined))
-        return logits, ctx
-
-    def backward_features(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
-                          on_ready: Optional[Callable[[str], None]] = None) -> None:
-        """backward() for a forward_features context: writes the gradients of classifier, attention and text into Gr; the
-        image.* entries of Gr are not touched and there is no image gradient."""
-        with torch.cuda.device(dlogits.device):
-            return self._backward_features(P, ctx, dlogits, Gr, on_ready)
-
-    def _backward_features(self, P, ctx, dlogits, Gr, on_ready):
-        dev = dlogits.device
-        ready = on_ready if on_ready is not None else (lambda group: None)
-        B, n_u, Pn = ctx.B, ctx.N, ctx.Pn
-        G, C, mid, Dc = self.G, self.C, self.mid, self.Dc
-        sd = lambda site: _site_seed(ctx.seed, site)
-        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        dcomb = self._classifier_bwd(P, ctx, dlogits, Gr)
-        ready("classifier")
-        # ---- attention apply + scores; d loss / d vn has no reader
-        ds_rows = new(B, G, 1)
-        dscore = ops.att_apply_gather_dscore(dcomb, Dc, ctx.probs, ctx.vn, ctx.img, rowsum=ds_rows)
-        ops.sum_bgp(ds_rows, Gr["attention.x_conv.bias"])
-        wx = P["attention.x_conv.weight"].view(G, -1)
-        dvprime, dq_part, dwx_part, NT = ops.att_score_grouped_bwd(dscore, ctx.vprime, ctx.qp, wx, ctx.order, ctx.offsets, n_u, B,
-                                                                   Pn, self.att_mode, ctx.p_att, sd(SITE_ATT_X))
-        ops.colsum(dwx_part, n_u * NT, wx.numel(), Gr["attention.x_conv.weight"])
-        dqp = new(B, mid)
-        ops.sum_parts(dq_part, dqp, B, NT, mid)
-        # ---- v_conv over the n_u * Pn asked rows: dW = dv'^T . v_in only
-        ops.gemm(dvprime, ctx.v_in, Gr["attention.v_conv.weight"], mid, C, n_u * Pn, transA=True, transB=False, lda=mid, ldb=C,
-                 tag=44, x3=self._x3_gemm(n_u * Pn))
-        self._q_lin_bwd(P, ctx, dqp, dcomb, Gr)
-        ready("attention")
-        self._question_bwd(P, ctx, dcomb, Gr)
-        ready("text")
-        return None
-
     # ------------------------------------------------------------------ backward
+    @_device_current("dlogits")
     def backward(self, P: Dict[str, Tensor], ctx, dlogits: Tensor, Gr: Dict[str, Tensor],
                  on_ready: Optional[Callable[[str], None]] = None) -> Optional[Tensor]:
         """Writes the gradient of every parameter into Gr[name] (caller-owned, same shapes as P).  Returns the gradient
@@ -752,10 +711,6 @@ class Engine:
         `on_ready(group)` is called after the kernels producing a parameter group have been enqueued
         ('classifier', 'attention', 'text', 'image'): the data-parallel wrapper starts that bucket's
         all-reduce there, overlapping the rest of backward."""
-        with torch.cuda.device(dlogits.device):
-            return self._backward(P, ctx, dlogits, Gr, on_ready)
-
-    def _backward(self, P, ctx, dlogits, Gr, on_ready):
         dev = dlogits.device
         ready = on_ready if on_ready is not None else (lambda group: None)
         dcomb = self._classifier_bwd(P, ctx, dlogits, Gr)

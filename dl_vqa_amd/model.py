@@ -110,20 +110,32 @@ def validate_question_lengths(q_len, T: int) -> None:
                            "(pack_padded_sequence would raise: models/model.py:159-162)")
 
 
-def _host_image_index(image_index, N: int) -> torch.Tensor:
-    """image_index on the host as int64 [B]; IndexError for an entry outside [0, N)."""
-    idx = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+def _host_image_index(index, rows: int, what: str = "image_index", of: str = "") -> torch.Tensor:
+    """An index into `rows` rows (image_index, or answer_pairs' question_index into `of`) on the host as int64 [B];
+    IndexError for an entry outside [0, rows).  The one place where a CUDA index is copied to the host, which synchronises:
+    an entry point converts once and hands the result on -- a host int64 tensor passes through as it is."""
+    idx = torch.as_tensor(index).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
         bad = int(idx.min()) if int(idx.min()) < 0 else int(idx.max())
-        raise IndexError(f"image_index entry {bad} out of range [0, {N})")
+        raise IndexError(f"{what} entry {bad} out of range [0, {rows})" + (f" ({rows} encoded {of})" if of else ""))
     return idx
+
+
+def _upload_index(dev, *parts):
+    """The host index tensors `parts` on the device `dev` as int32: views of ONE tensor, uploaded in a single copy."""
+    return torch.split(torch.cat([p.to(torch.int32) for p in parts]).to(dev), [p.numel() for p in parts])
 
 
 def group_by_image(image_index, N: int):
     """Group questions by the image they ask about: image_index[b] in [0, N) -> (order int32 [B], offsets int32 [N+1]) on
     the host; the questions of image n are order[offsets[n]:offsets[n+1]], in their original order (a stable counting
-    sort).  IndexError for an entry outside [0, N)."""
-    idx = _host_image_index(image_index, N)
+    sort).  IndexError for an entry outside [0, N).  An index that is on the host as int64 already is used as it is."""
+    return _group(_host_image_index(image_index, N), N)
+
+
+def _group(idx, N: int):
+    """group_by_image of an index that _host_image_index has converted and checked: the VqaNet entry points convert theirs
+    once and group that tensor."""
     offsets = torch.zeros(N + 1, dtype=torch.int64)
     if idx.numel():
         offsets[1:] = torch.cumsum(torch.bincount(idx, minlength=N), 0)
@@ -138,7 +150,7 @@ def compact_image_index(image_index, N: int):
     (order, offsets) = group_by_image(slot, n_u).  IndexError for an entry outside [0, N), as group_by_image raises it."""
     idx = _host_image_index(image_index, N)
     rows, slot = torch.unique(idx, sorted=True, return_inverse=True)
-    order, offsets = group_by_image(slot, rows.numel())
+    order, offsets = _group(slot, rows.numel())
     return rows.to(torch.int32), slot.to(torch.int32), order, offsets
 
 
@@ -184,8 +196,15 @@ def topk_answers(logits, k: int = 1) -> TopAnswers:
         x = x.float()
     if (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
         x = x.contiguous()                  # the kernel reads rows of unit stride, ld = stride(0) >= A apart
-    with torch.cuda.device(x.device):
-        idx, prob = ops.softmax_topk(x, k)
+    return _ranked(x, k)
+
+
+def _ranked(out, k: int):
+    """TopAnswers of the fp32 CUDA logits `out`, ranked on their device; an (logits, attention) pair keeps its attention."""
+    if isinstance(out, tuple):
+        return _ranked(out[0], k), out[1]
+    with torch.cuda.device(out.device):
+        idx, prob = ops.softmax_topk(out, k)
     return TopAnswers(idx.long(), prob)
 
 
@@ -253,8 +272,7 @@ def unique_questions(q, q_len):
     lengths below 1 or above T raise as validate_question_lengths does."""
     q = torch.as_tensor(q).detach().cpu()
     q_len = torch.as_tensor(q_len).detach().cpu()
-    if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
-        raise ValueError(f"unique_questions: q [B,T] and q_len [B] expected, got {tuple(q.shape)} and {tuple(q_len.shape)}")
+    _check_question_ranks("unique_questions", q, q_len)
     B, T = q.shape
     validate_question_lengths(q_len, T)
     if B == 0:
@@ -271,13 +289,28 @@ def unique_questions(q, q_len):
     return masked[rows], q_len[rows], rank[inverse]
 
 
-def _pair_index(what: str, index, rows: int, of: str) -> torch.Tensor:
-    """One index of answer_pairs on the host: int64 [B], IndexError for an entry outside [0, rows)."""
-    idx = torch.as_tensor(index).detach().to(device="cpu", dtype=torch.int64).reshape(-1)
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
-        bad = int(idx.min()) if int(idx.min()) < 0 else int(idx.max())
-        raise IndexError(f"{what} entry {bad} out of range [0, {rows}) ({rows} encoded {of})")
-    return idx
+def _check_question_ranks(what: str, q, q_len, rows: str = "B", v=None):
+    """ValueError unless q is [rows, T] and q_len [rows] (and the image batch v, where there is one, 4-D)."""
+    if (v is not None and v.dim() != 4) or q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
+        got = f"{tuple(q.shape)} and {tuple(q_len.shape)}"
+        lead, got = ("v [N,3,S,S], ", f"{tuple(v.shape)}, " + got) if v is not None else ("", got)
+        raise ValueError(f"{what}: {lead}q [{rows},T] and q_len [{rows}] expected, got {got}")
+
+
+def _need_cuda(what: str, on_device: bool):
+    if not on_device:
+        raise RuntimeError(f"dl_vqa_amd.VqaNet.{what} needs CUDA (HIP) tensors; there is no CPU fallback")
+
+
+def _node_forward(ctx, model, run):
+    """forward of an autograd node of this module: run(P) is the engine schedule, (logits, saved activations); the rest
+    is what _node_backward and the model read afterwards."""
+    logits, saved = run(model._param_dict())
+    ctx.model = model
+    ctx.saved = saved
+    model._last_ctx = saved
+    model._pending.add(ctx)          # weak: a graph that is dropped without backward leaves the set
+    return logits
 
 
 def _node_backward(ctx, dlogits, lead: int, engine_backward, frozen=()):
@@ -340,16 +373,10 @@ class _VqaFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, v, q, q_len, seed, *params):
-        P = model._param_dict()
         # v.requires_grad: the forward keeps what the first block's backward-data needs
         extra = {"need_dx": True} if ctx.needs_input_grad[1] else {}
-        logits, saved = model._engine.forward(P, v, q, q_len, model.training, seed, keep=True,
-                                              bad_tokens=model._bad_tokens, **extra)
-        ctx.model = model
-        ctx.saved = saved
-        model._last_ctx = saved
-        model._pending.add(ctx)          # weak: a graph that is dropped without backward leaves the set
-        return logits
+        return _node_forward(ctx, model, lambda P: model._engine.forward(
+            P, v, q, q_len, model.training, seed, keep=True, bad_tokens=model._token_counter(q), **extra))
 
     @staticmethod
     def backward(ctx, dlogits):
@@ -357,57 +384,36 @@ class _VqaFunction(torch.autograd.Function):
 
 
 class _VqaSharedFunction(torch.autograd.Function):
-    """Autograd node of one VqaNet.forward_shared call: _VqaFunction with the image batch holding every image once.  idx is
-    the device int32 tensor order [B] | offsets [N+1] | image index [B] (one upload); gradient storage follows
+    """Autograd node of one VqaNet.forward_shared call: _VqaFunction with the image batch holding every image once.  index
+    is the device int32 triple (order [B], offsets [N+1], image index [B]) of _upload_index; gradient storage follows
     _VqaFunction's rules through the same helper."""
 
     @staticmethod
-    def forward(ctx, model, v, q, q_len, seed, idx, *params):
-        P = model._param_dict()
-        B, N = q.shape[0], v.shape[0]
-        logits, saved = model._engine.forward_shared(P, v, q, q_len, idx[:B], idx[B:B + N + 1], idx[B + N + 1:], model.training,
-                                                     seed, keep=True, bad_tokens=model._bad_tokens,
-                                                     need_dx=bool(ctx.needs_input_grad[1]))
-        ctx.model = model
-        ctx.saved = saved
-        model._last_ctx = saved
-        model._pending.add(ctx)
-        return logits
+    def forward(ctx, model, v, q, q_len, seed, index, *params):
+        return _node_forward(ctx, model, lambda P: model._engine.forward_shared(
+            P, v, q, q_len, *index, model.training, seed, keep=True, bad_tokens=model._token_counter(q),
+            need_dx=bool(ctx.needs_input_grad[1])))
 
     @staticmethod
     def backward(ctx, dlogits):
-        return _node_backward(ctx, dlogits, 6, ctx.model._engine.backward_shared)
+        return _node_backward(ctx, dlogits, 6, ctx.model._engine.backward_grouped)
 
 
 class _VqaFeaturesFunction(torch.autograd.Function):
     """Autograd node of one VqaNet.forward_features call: the image encoder is not part of the graph.  vn is the bank's
-    feature tensor (no gradient), idx the device int32 tensor rows [n_u] | slot [B] | order [B] | offsets [n_u+1] | image
-    index [B] (one upload).  Every parameter is an input, so that gradient storage follows _VqaFunction's rules through the
-    same helper; the image.* parameters get None."""
+    feature tensor (no gradient), index the device int32 views (rows [n_u], order [B], offsets [n_u+1], image index [B]) of
+    _upload_index.  Every parameter is an input, so that gradient storage follows _VqaFunction's rules through the same
+    helper; the image.* parameters get None."""
 
     @staticmethod
-    def forward(ctx, model, vn, q, q_len, seed, idx, n_u, *params):
-        P = model._param_dict()
-        B = q.shape[0]
-        rows, order, offsets, img = _split_feature_index(idx, n_u, B)
-        logits, saved = model._engine.forward_features(P, vn, q, q_len, rows, order, offsets, img, model.training, seed,
-                                                       keep=True, bad_tokens=model._bad_tokens)
-        ctx.model = model
-        ctx.saved = saved
-        model._last_ctx = saved
-        model._pending.add(ctx)
-        return logits
+    def forward(ctx, model, vn, q, q_len, seed, index, *params):
+        return _node_forward(ctx, model, lambda P: model._engine.forward_features(
+            P, vn, q, q_len, *index, model.training, seed, keep=True, bad_tokens=model._token_counter(q)))
 
     @staticmethod
     def backward(ctx, dlogits):
         model = ctx.model
-        return _node_backward(ctx, dlogits, 7, model._engine.backward_features, model._image_names)
-
-
-def _split_feature_index(idx, n_u: int, B: int):
-    """(rows, order, offsets, img) views of forward_features' one uploaded index tensor."""
-    o = n_u + B                                 # behind rows [n_u] and slot [B]
-    return idx[:n_u], idx[o:o + B], idx[o + B:o + B + n_u + 1], idx[o + B + n_u + 1:]
+        return _node_backward(ctx, dlogits, 6, model._engine.backward_grouped, model._image_names)
 
 
 class VqaNet(nn.Module):
@@ -541,6 +547,11 @@ class VqaNet(nn.Module):
             self._bad_host = torch.zeros(1, dtype=torch.int32).pin_memory()
             self._bad_event = None
 
+    def _token_counter(self, q):
+        """What the engine gets as bad_tokens: the device counter for ids that are on the device, nothing for ids that
+        _validate_tokens has checked on the host."""
+        return self._bad_tokens if q.is_cuda else None
+
     def _after_forward_tokens(self, q):
         if q.is_cuda and self._bad_tokens is not None:
             self._bad_host.copy_(self._bad_tokens, non_blocking=True)
@@ -568,8 +579,7 @@ class VqaNet(nn.Module):
 
     def forward(self, v, q, q_len):
         self._ensure_flat()
-        if not v.is_cuda:
-            raise RuntimeError("dl_vqa_amd.VqaNet.forward needs CUDA (HIP) tensors; there is no CPU fallback")
+        _need_cuda("forward", v.is_cuda)
         self._validate_tokens(q)
         validate_question_lengths(q_len, q.shape[1])
         # v may be the dataset's fp16 storage format (preprocessing/preprocess_images.py:39-53): the first-block kernels read
@@ -583,9 +593,35 @@ class VqaNet(nn.Module):
             logits = _VqaFunction.apply(self, v, q, q_len, seed, *self._params)
         else:
             logits, _ = self._engine.forward(self._param_dict(), v, q, q_len, self.training, seed, keep=False,
-                                             bad_tokens=self._bad_tokens)
+                                             bad_tokens=self._token_counter(q))
         self._after_forward_tokens(q)
         return logits
+
+    # ------------------------------------------------------------------ argument checks of the grouped paths
+    def _refuse_bf16(self, what: str):
+        if self.compute_dtype == "bf16":
+            raise NotImplementedError(f"VqaNet.{what}: compute_dtype='bf16' is not supported (fp32 and fp32x3 are); the bf16 "
+                                      "path rounds x = relu(v' (+|*) q') to bf16, a tensor this path never forms")
+
+    def _check_grouped_training(self, what: str, how: str):
+        self._refuse_bf16(what)
+        if self._grad_sync is not None:
+            raise NotImplementedError(f"VqaNet.{what}: data-parallel training {how} is not supported (the model is wrapped "
+                                      "by dl_vqa_amd.distributed.DataParallel)")
+
+    def _check_owned(self, what: str, held, kind: str, call: str):
+        """RuntimeError unless the feature cache `held` (kind "image" / "question", made by `call`) belongs to this model and
+        to its current parameter storage (after _ensure_flat)."""
+        if held._model() is not self or held._flat_ptr != self._flat_param.data_ptr():
+            raise RuntimeError(f"VqaNet.{what}: these {kind} features belong elsewhere -- they were encoded by another model "
+                               "instance, or this model's parameters have moved to new storage since (.to(), a re-flatten); "
+                               f"call {call} again on this model")
+
+    def _no_answers(self, feats, return_attention: bool):
+        """What answer / answer_pairs return for an empty batch."""
+        eng, dev = self._engine, feats.vn.device
+        logits = torch.empty(0, eng.A, dtype=torch.float32, device=dev)
+        return (logits, torch.empty(0, eng.G, *feats.grid, dtype=torch.float32, device=dev)) if return_attention else logits
 
     # ------------------------------------------------------------------ training through shared image features
     def forward_shared(self, v, q, q_len, image_index):
@@ -606,20 +642,13 @@ class VqaNet(nn.Module):
         both classifier sites) draws per question exactly as forward() does.  One seed is drawn per training forward.
 
         compute_dtype "bf16" and a model wrapped by dl_vqa_amd.distributed.DataParallel raise NotImplementedError."""
-        if self.compute_dtype == "bf16":
-            raise NotImplementedError("VqaNet.forward_shared: compute_dtype='bf16' is not supported (fp32 and fp32x3 are); the "
-                                      "bf16 path rounds x = relu(v' (+|*) q') to bf16, a tensor this path never forms")
-        if self._grad_sync is not None:
-            raise NotImplementedError("VqaNet.forward_shared: data-parallel training through shared image features is not "
-                                      "supported (the model is wrapped by dl_vqa_amd.distributed.DataParallel)")
+        self._check_grouped_training("forward_shared", "through shared image features")
         v, q, q_len = torch.as_tensor(v), torch.as_tensor(q), torch.as_tensor(q_len)
-        if not v.is_cuda:
-            raise RuntimeError("dl_vqa_amd.VqaNet.forward_shared needs CUDA (HIP) tensors; there is no CPU fallback")
-        if v.dim() != 4 or q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
-            raise ValueError(f"VqaNet.forward_shared: v [N,3,S,S], q [B,T] and q_len [B] expected, got {tuple(v.shape)}, "
-                             f"{tuple(q.shape)} and {tuple(q_len.shape)}")
+        _need_cuda("forward_shared", v.is_cuda)
+        _check_question_ranks("VqaNet.forward_shared", q, q_len, v=v)
         B, N = q.shape[0], v.shape[0]
-        order, offsets = group_by_image(image_index, N)
+        img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
+        order, offsets = _group(img, N)
         if order.numel() != B:
             raise ValueError(f"VqaNet.forward_shared: {order.numel()} image_index entries for {B} questions")
         if N == 0 or B == 0:
@@ -629,16 +658,14 @@ class VqaNet(nn.Module):
         validate_question_lengths(q_len, q.shape[1])
         if v.dtype not in (torch.float32, torch.float16):
             v = v.float()
-        img = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int32).reshape(-1)
-        idx = torch.cat([order, offsets, img]).to(v.device)          # one upload: order [B] | offsets [N+1] | img [B]
+        index = _upload_index(v.device, order, offsets, img)
         seed = self._next_seed() if self.training else 0
         need_grad = torch.is_grad_enabled() and (v.requires_grad or any(p.requires_grad for p in self._params))
         if need_grad:
-            logits = _VqaSharedFunction.apply(self, v, q, q_len, seed, idx, *self._params)
+            logits = _VqaSharedFunction.apply(self, v, q, q_len, seed, index, *self._params)
         else:
-            logits, _ = self._engine.forward_shared(self._param_dict(), v, q, q_len, idx[:B], idx[B:B + N + 1], idx[B + N + 1:],
-                                                    self.training, seed, keep=False,
-                                                    bad_tokens=self._bad_tokens if q.is_cuda else None)
+            logits, _ = self._engine.forward_shared(self._param_dict(), v, q, q_len, *index, self.training, seed, keep=False,
+                                                    bad_tokens=self._token_counter(q))
         self._after_forward_tokens(q)
         return logits
 
@@ -671,55 +698,38 @@ class VqaNet(nn.Module):
         NotImplementedError for compute_dtype "bf16" and for a model wrapped by dl_vqa_amd.distributed.DataParallel,
         TypeError for a feats that is not an ImageFeatures, RuntimeError for CPU tensors or foreign features, ValueError
         for wrong ranks, a wrong image_index count or an empty batch."""
-        if self.compute_dtype == "bf16":
-            raise NotImplementedError("VqaNet.forward_features: compute_dtype='bf16' is not supported (fp32 and fp32x3 are); the "
-                                      "bf16 path rounds x = relu(v' (+|*) q') to bf16, a tensor this path never forms")
-        if self._grad_sync is not None:
-            raise NotImplementedError("VqaNet.forward_features: data-parallel training on cached image features is not "
-                                      "supported (the model is wrapped by dl_vqa_amd.distributed.DataParallel)")
+        self._check_grouped_training("forward_features", "on cached image features")
         if not isinstance(feats, ImageFeatures):
             raise TypeError("VqaNet.forward_features: feats must come from VqaNet.encode_images (or ImageFeatures.cat)")
         q, q_len = torch.as_tensor(q), torch.as_tensor(q_len)
-        if not feats.vn.is_cuda or not self._params[0].is_cuda:
-            raise RuntimeError("dl_vqa_amd.VqaNet.forward_features needs CUDA (HIP) tensors; there is no CPU fallback")
-        if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
-            raise ValueError(f"VqaNet.forward_features: q [B,T] and q_len [B] expected, got {tuple(q.shape)} and "
-                             f"{tuple(q_len.shape)}")
+        _need_cuda("forward_features", feats.vn.is_cuda and self._params[0].is_cuda)
+        _check_question_ranks("VqaNet.forward_features", q, q_len)
         self._ensure_flat()
-        if feats._model() is not self or feats._flat_ptr != self._flat_param.data_ptr():
-            raise RuntimeError("VqaNet.forward_features: these image features belong elsewhere -- they were encoded by another "
-                               "model instance, or this model's parameters have moved to new storage since (.to(), a "
-                               "re-flatten); call encode_images again on this model")
+        self._check_owned("forward_features", feats, "image", "encode_images")
         B, N = q.shape[0], feats.N
-        img = _host_image_index(image_index, N)                      # one copy to the host, reused below
-        rows, slot, order, offsets = compact_image_index(img, N)
+        img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
+        rows, _slot, order, offsets = compact_image_index(img, N)
         if order.numel() != B:
             raise ValueError(f"VqaNet.forward_features: {order.numel()} image_index entries for {B} questions")
         if N == 0 or B == 0:
             raise ValueError(f"VqaNet.forward_features: an empty batch ({N} feature rows, {B} questions)")
         self._validate_tokens(q)
         validate_question_lengths(q_len, q.shape[1])
-        dev = feats.vn.device
-        n_u = rows.numel()
-        # one upload: rows [n_u] | slot [B] | order [B] | offsets [n_u+1] | img [B]
-        idx = torch.cat([rows, slot, order, offsets, img.to(torch.int32)]).to(dev)
+        index = _upload_index(feats.vn.device, rows, order, offsets, img)
         seed = self._next_seed() if self.training else 0
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for n, p in zip(self._names, self._params)
                                                     if n not in self._image_names)
         if need_grad:
-            logits = _VqaFeaturesFunction.apply(self, feats.vn, q, q_len, seed, idx, n_u, *self._params)
+            logits = _VqaFeaturesFunction.apply(self, feats.vn, q, q_len, seed, index, *self._params)
         else:
-            r, o, f, i = _split_feature_index(idx, n_u, B)
-            logits, _ = self._engine.forward_features(self._param_dict(), feats.vn, q, q_len, r, o, f, i, self.training, seed,
-                                                      keep=False, bad_tokens=self._bad_tokens if q.is_cuda else None)
+            logits, _ = self._engine.forward_features(self._param_dict(), feats.vn, q, q_len, *index, self.training, seed,
+                                                      keep=False, bad_tokens=self._token_counter(q))
         self._after_forward_tokens(q)
         return logits
 
     # ------------------------------------------------------------------ many questions per image (inference)
     def _check_inference(self, what: str):
-        if self.compute_dtype == "bf16":
-            raise NotImplementedError(f"VqaNet.{what}: compute_dtype='bf16' is not supported (fp32 and fp32x3 are); the bf16 "
-                                      "path rounds x = relu(v' (+|*) q') to bf16, a tensor this path never forms")
+        self._refuse_bf16(what)
         if self.training:
             raise RuntimeError(f"VqaNet.{what} is an inference call and the model is in training mode: the image, attention "
                                "and classifier dropout sites (models/model.py:84,185,186,194) draw a new mask per forward, so "
@@ -745,8 +755,7 @@ class VqaNet(nn.Module):
         optimiser step or load_state_dict."""
         self._check_inference("encode_images")
         self._ensure_flat()
-        if not v.is_cuda:
-            raise RuntimeError("dl_vqa_amd.VqaNet.encode_images needs CUDA (HIP) tensors; there is no CPU fallback")
+        _need_cuda("encode_images", v.is_cuda)
         if v.dtype not in (torch.float32, torch.float16):
             v = v.float()
         vn, vprime, grid = self._engine.encode_images(self._param_dict(), v.detach(), with_vprime=bool(with_vprime))
@@ -767,30 +776,23 @@ class VqaNet(nn.Module):
         self._ensure_flat()
         if not isinstance(feats, ImageFeatures):
             raise TypeError("VqaNet.answer: feats must come from VqaNet.encode_images")
-        if feats._model() is not self or feats._flat_ptr != self._flat_param.data_ptr():
-            raise RuntimeError("VqaNet.answer: these image features belong elsewhere -- they were encoded by another model "
-                               "instance, or this model's parameters have moved to new storage since (.to(), a re-flatten); "
-                               "call encode_images again on this model")
+        self._check_owned("answer", feats, "image", "encode_images")
         self._need_vprime("answer", feats)
         q = torch.as_tensor(q)
         q_len = torch.as_tensor(q_len)
-        if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
-            raise ValueError(f"VqaNet.answer: q [B,T] and q_len [B] expected, got {tuple(q.shape)} and {tuple(q_len.shape)}")
+        _check_question_ranks("VqaNet.answer", q, q_len)
         self._validate_tokens(q)
         validate_question_lengths(q_len, q.shape[1])
         B, N = q.shape[0], feats.N
-        order, offsets = group_by_image(image_index, N)
+        img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
+        order, offsets = _group(img, N)
         if order.numel() != B:
             raise ValueError(f"VqaNet.answer: {order.numel()} image_index entries for {B} questions")
-        dev = feats.vn.device
-        eng = self._engine
         if B == 0:
-            logits = torch.empty(0, eng.A, dtype=torch.float32, device=dev)
-            return (logits, torch.empty(0, eng.G, *feats.grid, dtype=torch.float32, device=dev)) if return_attention else logits
-        img = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int32).reshape(-1)
-        idx = torch.cat([order, offsets, img]).to(dev)               # one upload: order [B] | offsets [N+1] | img [B]
-        logits, probs, _score = eng.answer(self._param_dict(), feats, q, q_len, idx[:B], idx[B:B + N + 1], idx[B + N + 1:],
-                                           bad_tokens=self._bad_tokens if q.is_cuda else None)
+            return self._no_answers(feats, return_attention)
+        eng = self._engine
+        logits, probs, _score = eng.answer(self._param_dict(), feats, q, q_len, *_upload_index(feats.vn.device, order, offsets, img),
+                                           bad_tokens=self._token_counter(q))
         self._after_forward_tokens(q)
         if return_attention:
             return logits, probs.view(B, eng.G, *feats.grid)
@@ -807,12 +809,7 @@ class VqaNet(nn.Module):
         eval mode only, fp32 / fp32x3, the feature-ownership checks, its errors, and nothing kept for a backward.  The
         ranking kernel runs on answer()'s device and stream, behind the classifier; B == 0 gives empty [0, k] tensors."""
         k = _check_k("VqaNet.predict", k, self._engine.A)
-        out = self.answer(feats, q, q_len, image_index, return_attention=return_attention)
-        logits = out[0] if return_attention else out
-        with torch.cuda.device(logits.device):
-            idx, prob = ops.softmax_topk(logits, k)
-        top = TopAnswers(idx.long(), prob)
-        return (top, out[1]) if return_attention else top
+        return _ranked(self.answer(feats, q, q_len, image_index, return_attention=return_attention), k)
 
     # ------------------------------------------------------------------ cached question features (inference)
     @torch.no_grad()
@@ -828,9 +825,7 @@ class VqaNet(nn.Module):
         self._ensure_flat()
         q = torch.as_tensor(q)
         q_len = torch.as_tensor(q_len)
-        if q.dim() != 2 or q_len.dim() != 1 or q_len.shape[0] != q.shape[0]:
-            raise ValueError(f"VqaNet.encode_questions: q [M,T] and q_len [M] expected, got {tuple(q.shape)} and "
-                             f"{tuple(q_len.shape)}")
+        _check_question_ranks("VqaNet.encode_questions", q, q_len, rows="M")
         self._validate_tokens(q)
         validate_question_lengths(q_len, q.shape[1])
         dev = self._flat_param.device
@@ -839,7 +834,7 @@ class VqaNet(nn.Module):
             return QuestionFeatures(torch.empty(0, eng.Q, dtype=torch.float32, device=dev),
                                     torch.empty(0, eng.mid, dtype=torch.float32, device=dev), self)
         qf, qprime = eng.encode_questions(self._param_dict(), q.detach(), q_len.detach(), dev,
-                                          bad_tokens=self._bad_tokens if q.is_cuda else None)
+                                          bad_tokens=self._token_counter(q))
         self._after_forward_tokens(q)
         return QuestionFeatures(qf, qprime, self)
 
@@ -865,14 +860,12 @@ class VqaNet(nn.Module):
         n_img, n_q = torch.as_tensor(image_index).numel(), torch.as_tensor(question_index).numel()
         if n_img != n_q:
             raise ValueError(f"VqaNet.answer_pairs: {n_img} image_index entries for {n_q} question_index entries")
-        order, offsets = group_by_image(image_index, N)
-        qidx = _pair_index("question_index", question_index, M, "questions")
+        img = _host_image_index(image_index, N)                      # each index: one copy to the host, reused below
+        order, offsets = _group(img, N)
+        qidx = _host_image_index(question_index, M, "question_index", "questions")
         self._ensure_flat()
-        for held, what, call in ((feats, "image", "encode_images"), (qfeats, "question", "encode_questions")):
-            if held._model() is not self or held._flat_ptr != self._flat_param.data_ptr():
-                raise RuntimeError(f"VqaNet.answer_pairs: these {what} features belong elsewhere -- they were encoded by "
-                                   "another model instance, or this model's parameters have moved to new storage since "
-                                   f"(.to(), a re-flatten); call {call} again on this model")
+        self._check_owned("answer_pairs", feats, "image", "encode_images")
+        self._check_owned("answer_pairs", qfeats, "question", "encode_questions")
         self._need_vprime("answer_pairs", feats)
         dev = feats.vn.device
         if qfeats.qprime.device != dev:
@@ -881,13 +874,8 @@ class VqaNet(nn.Module):
         eng = self._engine
         B = qidx.numel()
         if B == 0:
-            logits = torch.empty(0, eng.A, dtype=torch.float32, device=dev)
-            return (logits, torch.empty(0, eng.G, *feats.grid, dtype=torch.float32, device=dev)) if return_attention else logits
-        img = torch.as_tensor(image_index).detach().to(device="cpu", dtype=torch.int32).reshape(-1)
-        # one upload: order [B] | offsets [N+1] | img [B] | qrow [B]
-        idx = torch.cat([order, offsets, img, qidx.to(torch.int32)]).to(dev)
-        logits, probs, _score = eng.answer_pairs(self._param_dict(), feats, qfeats, idx[:B], idx[B:B + N + 1],
-                                                 idx[B + N + 1:2 * B + N + 1], idx[2 * B + N + 1:])
+            return self._no_answers(feats, return_attention)
+        logits, probs, _score = eng.answer_pairs(self._param_dict(), feats, qfeats, *_upload_index(dev, order, offsets, img, qidx))
         if return_attention:
             return logits, probs.view(B, eng.G, *feats.grid)
         return logits
@@ -899,9 +887,4 @@ class VqaNet(nn.Module):
         [B, k], probs fp32 [B, k]) in topk_answers' order; return_attention: (TopAnswers, att [B, G, gh, gw]).  k is
         validated first; everything else is answer_pairs()'s."""
         k = _check_k("VqaNet.predict_pairs", k, self._engine.A)
-        out = self.answer_pairs(feats, qfeats, image_index, question_index, return_attention=return_attention)
-        logits = out[0] if return_attention else out
-        with torch.cuda.device(logits.device):
-            idx, prob = ops.softmax_topk(logits, k)
-        top = TopAnswers(idx.long(), prob)
-        return (top, out[1]) if return_attention else top
+        return _ranked(self.answer_pairs(feats, qfeats, image_index, question_index, return_attention=return_attention), k)
