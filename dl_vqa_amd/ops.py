@@ -442,8 +442,9 @@ def lstm_seq_fwd(dirs, q_len, B: int, T: int, H: int, cf_ld: int = 0, use_graph:
 
 
 def lstm_seq_bwd(dirs, q_len, B: int, T: int, H: int, use_graph: bool = True):
-    """BPTT of the recurrence: fills dgates [T,B,4H] per direction; dh (zeros) / dc (d loss / d c_n) are updated in
-    place.  Needs gates, Hs, Cs of the forward pass and w_hh."""
+    """BPTT of the recurrence: fills dgates [T,B,4H] per direction; dh (d loss / d h_n: zeros for the model) / dc
+    (d loss / d c_n) are updated in place and hold, on return, d loss / d h written by the first processed time and
+    d loss / d c_0 (include/vqa_hip.h).  Needs gates, Hs, Cs of the forward pass and w_hh."""
     import ctypes
     arr = _lstm_dirs(dirs)
     call("vqa_lstm_seq_bwd", ctypes.addressof(arr), len(dirs), ptr(q_len), B, T, H, int(use_graph), stream())

@@ -248,8 +248,11 @@ typedef struct {
   float* Cs;         /* [T+1][B][H] */
   float* c_final;    /* fwd: optional [B][cf_ld], final cell state c_n (the question feature, model.py:164-166) */
   float* dgates;     /* bwd: [T][B][4H] out: gradient w.r.t. the gate pre-activations */
-  float* dh;         /* bwd: [B][H] work; on entry d loss / d h_n (zeros for this model) */
-  float* dc;         /* bwd: [B][H] work; on entry d loss / d c_n, on exit d loss / d c at the first processed time */
+  float* dh;         /* bwd: [B][H] work; on entry d loss / d h_n (zeros for this model), on exit d loss / d h at the first
+                      * processed time: the total gradient w.r.t. the h that time WROTE (T == 1: the entry value).  It is
+                      * not d loss / d h_0: that is dgates[first time] . W_hh + this value for the samples inactive there */
+  float* dc;         /* bwd: [B][H] work; on entry d loss / d c_n, on exit d loss / d c at the first processed time: the
+                      * gradient w.r.t. the c that time READ, i.e. d loss / d c_0 */
   int reverse;       /* 0: t = 0 .. T-1, 1: t = T-1 .. 0 */
 } vqa_lstm_dir_t;
 int vqa_lstm_step_supported(int H);
