@@ -11,18 +11,25 @@
 // edges.  A tile is instead a SEGMENT of SEG consecutive positions of the image's output in row-major order with the padded
 // row length W' = W + 2 (the pre-pool gradient, offset by the 2-pixel border, is exactly W' wide): output m = y * W' + x
 // reads flat[m + ky * W' + kx], so a tap is still ONE constant shift of the LDS patch, an MFMA A fragment is 32 consecutive
-// floats (conflict-free), and the only waste is the 2 garbage columns per row (x >= W) and the last segment of an image:
-// 92.6 % (111 x 111) and 94.9 % (54 x 54) useful.
-//   * workgroup = 8 waves, one per CU; a wave owns 128 positions x 64 channels = 4 x 2 accumulators of
-//     v_mfma_f32_32x32x2_f32 (exact fp32); WM = 8 waves along the segment: SEG = 1024 positions x 64 channels, or 4 x 2:
-//     512 x 128;
-//   * a stage = the patch [8 channels][SEG + 2 W' + 2] fp32, channel-planar, + the slice's weights for all nine taps
-//     [tap][k][n] fp32, pre-packed flipped and transposed (LDS-DMA, 1 KiB per piece, spread behind the taps): 288 MFMAs of 64
-//     cycles per wave and stage -- one s_barrier per 18 k cycles;
+// floats (conflict-free), and the only waste is the 2 garbage columns per row (x >= W) and the rounding of an image's last
+// segment to whole row blocks (below).
+//   * workgroup = 8 waves, one per CU; in a FULL tile (every tile but an image's last, see the last bullet) a wave owns 128
+//     positions x 64 channels = 4 x 2 accumulators of v_mfma_f32_32x32x2_f32 (exact fp32); WM = 8 waves along the segment:
+//     SEG = 1024 positions x 64 channels, or 4 x 2: 512 x 128;
+//   * a stage = the patch [8 channels][SEG + 2 W' + 2] fp32 (full tile), channel-planar, + the slice's weights for all nine
+//     taps [tap][k][n] fp32, pre-packed flipped and transposed (LDS-DMA, 1 KiB per piece, spread behind the taps): in a full
+//     tile 288 MFMAs of 64 cycles per wave and stage -- one s_barrier per 18 k cycles;
 //   * the patch is ROUTED: thread t takes one 2 x 2 window of the EXTENDED window grid (border and uncovered pixels are
 //     windows without data, so every patch position is written by exactly one thread -- no zero fill), loads 8 channels of dP +
 //     arg-max for stage q + 2 during stage q and writes the window's four pixels per channel during stage q + 1;
-//   * epilogue: lane (channel, h) holds 16 positions of one channel per accumulator: 32 lanes write one pixel's 128 bytes.
+//   * epilogue: lane (channel, h) holds 16 positions of one channel per accumulator: 32 lanes write one pixel's 128 bytes;
+//     (y, x) of a lane's first position by ONE division per tile, carried over the fixed element offsets (+1 +1 +1 +5) after that;
+//   * the LAST segment of an image is right-sized: a tile has NI row blocks of 32 positions per wave (4 everywhere but there,
+//     ceil(positions left / (WM * 32)) in the last one), wave wm owns [wm * 32 NI, (wm + 1) * 32 NI), the patch is
+//     WM * 32 NI + 2 W' + 2 long, and all eight waves' MFMA counts shrink together: at 111 x 111 the 13th tile holds 255
+//     positions and costs a quarter of a tile instead of a whole one -- 12 544 computed positions for 12 321 outputs, 98.2 %
+//     useful (54 x 54: 464 of the last 512 positions are real, NI stays 4, 94.9 %).  Every element is still summed K-slice by
+//     K-slice, tap by tap, k by k: the bits do not depend on NI.
 #include "bf16_core.hpp"
 #include <stdlib.h>
 
@@ -52,6 +59,7 @@ struct PfParams {
   int B, Cin, N, H, W, Wp2, Hq, Wq;        // Wp2 = W + 2
   int EW;               // extended windows per row: (Wp2 + 1) / 2
   int segs, nunits;     // segments per image, B * segs
+  int ni_last;          // row blocks per wave of an image's last segment: ceil(positions left / (WM * 32)), 1..4
   int nslabs, nslices;
   int dbg;              // timing experiments (VQA_PCONVF_DBG): 1 = no routing after the prologue, 2 = no weight DMA after the prologue, 4 = no epilogue stores
 };
@@ -90,10 +98,12 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
   const int my_tiles = stream < P.nunits ? (P.nunits - stream + nstreams - 1) / nstreams : 0;
   if (my_tiles == 0) return;                         // uniform over the workgroup
   const int n_slab0 = slab * C::NSLAB;
-  const int PLEN = C::SEG + 2 * P.Wp2 + 2;           // patch positions of a tile
+  // row blocks per wave of a unit's tile, and the patch positions of a tile of ni row blocks
+  auto seg_ni = [&](int seg) { return seg == P.segs - 1 ? P.ni_last : 4; };
+  auto ni_plen = [&](int ni) { return C::WM * 32 * ni + 2 * P.Wp2 + 2; };
 
-  // fragment bases (bytes): A = patch[2 ks + h][wm*128 + 32 i + r + ky W' + kx], B = w[tap][2 ks + h][wn*64 + 32 j + r]
-  const uint32_t a_lane = (uint32_t)((h * C::PLANE + wm * 128 + r) * 4);
+  // fragment bases (bytes): A = patch[2 ks + h][wm*32 NI + 32 i + r + ky W' + kx], B = w[tap][2 ks + h][wn*64 + 32 j + r]
+  const uint32_t a_lane = (uint32_t)((h * C::PLANE + r) * 4);
   const uint32_t b_lane = (uint32_t)(2 * C::PATCH_BYTES + (h * C::NSLAB + wn * 64 + r) * 4);
 
   // ---- weights by DMA: piece i = wave + 8 n of the stage's W_INSTR linear KiB
@@ -111,12 +121,13 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
 
   // ---- routed patch.  Extended window grid: window (er, e) covers the padded pixels (2 er + dy, 2 e + dx); it has data iff
   // qy = er - 1 in [0, Hq) and qx = e - 1 in [0, Wq).  Task t of a tile = window (er0 + t / EW, t % EW), er0 = first patch row / 2.
-  int t_er[C::RT_K], t_e[C::RT_K];
+  int t_er[C::RT_K], t_e[C::RT_K], t_first[C::RT_K];      // t_first: the window's first pixel, in positions from row 2 er0
 #pragma unroll
   for (int k = 0; k < C::RT_K; ++k) {
     const int t = k * 512 + (int)threadIdx.x;
     t_er[k] = t / P.EW;
     t_e[k] = t - t_er[k] * P.EW;
+    t_first[k] = 2 * t_er[k] * P.Wp2 + 2 * t_e[k];
   }
   float4 rt_d0[C::RT_K], rt_d1[C::RT_K];
   uint2 rt_a[C::RT_K];
@@ -126,13 +137,15 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
     const bool on = rt_count < rt_total;
     const int img = rt_unit / P.segs, seg = rt_unit - img * P.segs;
     const int er0 = (seg * C::SEG / P.Wp2) >> 1;
+    // a window whose FIRST pixel lies at or past the end of the tile's patch has no pixel in it: not loaded, not written
+    const int first_end = seg * C::SEG + ni_plen(seg_ni(seg)) - 2 * er0 * P.Wp2;
     const int64_t ibase = (int64_t)img * P.Hq * P.Wq * P.Cin;
     const uint32_t ibytes = (uint32_t)(P.Hq * P.Wq * P.Cin);
     const __amdgpu_buffer_rsrc_t rd = buf_rsrc(P.dp + ibase * 4, ibytes * 4u), ra = buf_rsrc(P.am + ibase, ibytes);
 #pragma unroll
     for (int k = 0; k < C::RT_K; ++k) {
       const int qy = er0 + t_er[k] - 1, qx = t_e[k] - 1;
-      const bool ok = on && (unsigned)qy < (unsigned)P.Hq && (unsigned)qx < (unsigned)P.Wq;
+      const bool ok = on && t_first[k] < first_end && (unsigned)qy < (unsigned)P.Hq && (unsigned)qx < (unsigned)P.Wq;
       const uint32_t o = (uint32_t)((qy * P.Wq + qx) * P.Cin + 8 * rt_slice);
       rt_d0[k] = buf_load16(rd, ok ? o * 4u : BUF_OOB);
       rt_d1[k] = buf_load16(rd, ok ? o * 4u + 16u : BUF_OOB);
@@ -142,7 +155,8 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
     if (++rt_slice == P.nslices) { rt_slice = 0; rt_unit += nstreams; }
   };
   // the registers -> the four pixels of each task's window, in patch buffer `buf`, for the tile whose first position is p0
-  auto rt_route = [&](int buf, int p0) {
+  // and whose patch is plen positions long
+  auto rt_route = [&](int buf, int p0, int plen) {
     char* const dst = smem + buf * C::PATCH_BYTES;
     const int er0 = (p0 / P.Wp2) >> 1;
 #pragma unroll
@@ -152,7 +166,7 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int pl = (yy + (j >> 1)) * P.Wp2 + xx + (j & 1) - p0;       // position in the patch
-        if (xx + (j & 1) < P.Wp2 && pl >= 0 && pl < PLEN) {
+        if (xx + (j & 1) < P.Wp2 && pl >= 0 && pl < plen) {
 #pragma unroll
           for (int ch = 0; ch < 8; ++ch) {
             const uint32_t code = ((ch < 4 ? rt_a[k].x : rt_a[k].y) >> (8 * (ch & 3))) & 0xffu;
@@ -186,13 +200,20 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
 #pragma unroll
   for (int n = 0; n < C::WK; ++n) issue_piece(n);
   rt_load();
-  rt_route(0, (stream % P.segs) * C::SEG);
+  rt_route(0, (stream % P.segs) * C::SEG, ni_plen(seg_ni(stream % P.segs)));
   rt_load();
   int buf = 0, gstage = 0;
   int unit = stream;
-  for (int k = 0; k < my_tiles; ++k, unit += nstreams) {
+  const int w_store = (P.dbg & 4) ? 0 : P.W;          // columns that are stored
+  const uint32_t pix = (uint32_t)(P.N * 4);           // bytes from a pixel of dX to the next
+
+  // one tile of NI row blocks per wave: its stages, then its epilogue
+  auto run_tile = [&](auto ni_c) __attribute__((always_inline)) {
+    constexpr int NI = decltype(ni_c)::value;
     const int img = unit / P.segs, seg = unit - img * P.segs;
     const int p0 = seg * C::SEG;
+    const int plen = ni_plen(NI);
+    const uint32_t a_tile = a_lane + (uint32_t)(wm * 32 * NI * 4);
     for (int slice = 0; slice < P.nslices; ++slice, ++gstage) {
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // this wave's DMA pieces and patch writes are done
       __builtin_amdgcn_s_barrier();
@@ -203,14 +224,15 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
         ns_on = gstage + 1 < rt_total;
       }
       // first position of the NEXT stage's tile (its patch is routed during this stage)
-      const int np0 = last_slice ? ((unit + nstreams) % P.segs) * C::SEG : p0;
-      const char* const pa = smem + buf * C::PATCH_BYTES + a_lane;
+      const int nseg = last_slice ? (unit + nstreams) % P.segs : seg;
+      const int np0 = nseg * C::SEG, nplen = last_slice ? ni_plen(seg_ni(nseg)) : plen;
+      const char* const pa = smem + buf * C::PATCH_BYTES + a_tile;
       const char* const pb = smem + buf * C::W_BYTES + b_lane;
-      float a[2][4], b[2][2];
+      float a[2][NI], b[2][2];
       auto fetch = [&](int t, int ks, int set) {
         const char* const pat = pa + toff[t];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[set][i] = *reinterpret_cast<const float*>(pat + ((2 * ks) * C::PLANE + 32 * i) * 4);
+        for (int i = 0; i < NI; ++i) a[set][i] = *reinterpret_cast<const float*>(pat + ((2 * ks) * C::PLANE + 32 * i) * 4);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           b[set][j] = *reinterpret_cast<const float*>(pb + ((t * 8 + 2 * ks) * C::NSLAB + 32 * j) * 4);
@@ -227,35 +249,58 @@ __global__ __launch_bounds__(512, 2) void pconvf_dgrad_kernel(const PfParams P) 
           if (q + 1 < 36) fetch((q + 1) >> 2, (q + 1) & 3, (q + 1) & 1);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
+          for (int i = 0; i < NI; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q & 1][i], b[q & 1][j], acc[i][j], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (t == 0) { if (ns_on && !(P.dbg & 1)) rt_route(buf ^ 1, np0); }  // the next stage's patch (registers loaded a stage ago)
+        if (t == 0) { if (ns_on && !(P.dbg & 1)) rt_route(buf ^ 1, np0, nplen); }  // the next stage's patch (registers loaded a stage ago)
         else if (t == 1) rt_load();                          // the stage after that
         else if (t < 2 + C::WK) { if (!(P.dbg & 2)) issue_piece(t - 2); }   // the next stage's weights
         __builtin_amdgcn_sched_barrier(0);
       }
       buf ^= 1;
     }
-    // ---- epilogue: position m = p0 + wm*128 + 32 i + (e & 3) + 8 (e >> 2) + 4 h -> (y, x) = (m / W', m % W'), valid for x < W, y < H
+    // ---- epilogue: position m = p0 + wm*32 NI + 32 i + (e & 3) + 8 (e >> 2) + 4 h -> (y, x) = (m / W', m % W'), stored for
+    // x < W (and y < H: only an image's last tile reaches past it).  One division for the lane's first position; from one
+    // element to the next m grows by 1, 1, 1, 5 (also from a row block to the next: 27 -> 32) and 5 < 6 <= W', so x wraps at
+    // most once, where the address (y W + x) N steps back over the two garbage columns.
     const int64_t obase = (int64_t)img * P.H * P.W * P.N + n_slab0 + wn * 64;
     const __amdgpu_buffer_rsrc_t ro = buf_rsrc(P.out + obase);
+    auto store_tile = [&](auto last_c) __attribute__((always_inline)) {
+      constexpr bool LAST = decltype(last_c)::value;
+      const int m0 = p0 + wm * 32 * NI + 4 * h;
+      int y = m0 / P.Wp2, x = m0 - y * P.Wp2;
+      uint32_t vo = (uint32_t)(((y * P.W + x) * P.N + r) * 4);
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < NI; ++i)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = p0 + wm * 128 + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const int y = m / P.Wp2, x = m - y * P.Wp2;
-        const bool ok = x < P.W && y < P.H && !(P.dbg & 4);
-        const uint32_t vo = ok ? (uint32_t)(((y * P.W + x) * P.N + r) * 4) : BUF_OOB;
+        for (int e = 0; e < 16; ++e) {
+          if (i || e) {
+            const int d = (e & 3) ? 1 : 5;
+            x += d;
+            const bool wrap = x >= P.Wp2;
+            vo += wrap ? (uint32_t)(d - 2) * pix : (uint32_t)d * pix;
+            if (wrap) { x -= P.Wp2; ++y; }
+          }
+          const bool ok = LAST ? (x < w_store && y < P.H) : x < w_store;
+          const uint32_t so = ok ? vo : BUF_OOB;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) buf_store4(ro, acc[i][j][e], vo, (uint32_t)(32 * j * 4));
-      }
+          for (int j = 0; j < 2; ++j) buf_store4(ro, acc[i][j][e], so, (uint32_t)(32 * j * 4));
+        }
+    };
+    if (NI < 4 || seg == P.segs - 1) store_tile(std::true_type{}); else store_tile(std::false_type{});
     zero_acc();
+  };
+  for (int k = 0; k < my_tiles; ++k, unit += nstreams) {
+    switch (seg_ni(unit % P.segs)) {                  // uniform over the workgroup
+      case 1: run_tile(std::integral_constant<int, 1>{}); break;
+      case 2: run_tile(std::integral_constant<int, 2>{}); break;
+      case 3: run_tile(std::integral_constant<int, 3>{}); break;
+      default: run_tile(std::integral_constant<int, 4>{}); break;
+    }
   }
 }
 
@@ -283,6 +328,8 @@ static int pf_launch(PfParams P, hipStream_t s) {
   using C = PfCfg<WMv>;
   P.segs = (P.H * P.Wp2 + C::SEG - 1) / C::SEG;
   P.nunits = P.B * P.segs;
+  const int valid_last = P.H * P.Wp2 - (P.segs - 1) * C::SEG;        // positions of an image's last segment, 1..SEG
+  P.ni_last = (valid_last + C::WM * 32 - 1) / (C::WM * 32);
   auto kern = pconvf_dgrad_kernel<WMv>;
   int rc = ensure_dyn_smem(reinterpret_cast<const void*>(kern), C::LDS, "attr(pconvf_dgrad)");
   if (rc) return rc;
