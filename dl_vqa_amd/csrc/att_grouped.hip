@@ -382,40 +382,20 @@ __global__ __launch_bounds__(256) void att_score_grouped_bwd_general_kernel(cons
 
 using namespace vqa;
 
-// 1 / (1 - p), 1 at p = 0
-static float keep_scale(float p) { return p > 0.f ? 1.0f / (1.0f - p) : 1.0f; }
-
-template <class F>
-static int with_glimpses(int G, F&& f) {
-  switch (G) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    default: return f(std::integral_constant<int, 4>{});
-  }
-}
-template <class F>
-static int with_it(int it, F&& f) {
-  switch (it) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    default: return f(std::integral_constant<int, 4>{});
-  }
-}
-
-// what both forward entry points check (`who` names the caller in the messages)
-#define GROUPED_FWD_REQUIRE(who)                                                                                                  \
+// what the four entry points check (`who` names the caller in the messages); `rest` is the entry point's own data pointers
+// beside vprime, qp and wx: all non-null, and 16-byte aligned where `quads` holds their bits
+#define GROUPED_REQUIRE(who, rest, quads)                                                                                         \
   VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);                                                             \
   VQA_REQUIRE(mode >= 0 && mode <= 2, who ": mode %d (0 '+', 1 '*', 2 '|')", mode);                                               \
-  VQA_REQUIRE(vprime && qp && wx && bx && score, who ": null pointer");                                                           \
+  VQA_REQUIRE(vprime && qp && wx && (rest), who ": null pointer");                                                                \
   VQA_REQUIRE(order && offsets, who ": null order / offsets");                                                                    \
   VQA_REQUIRE(N >= 1 && N <= 65535 && B >= 0 && P >= 1, who ": N=%d (1..65535), B=%d, P=%d out of range", N, B, P);               \
   VQA_REQUIRE(mid >= 4 && mid % 4 == 0 && wx_ld % 4 == 0 && wx_ld >= (mode == 2 ? 2 * mid : mid),                                 \
               who ": bad args (mid=%d and wx_ld=%d must be multiples of 4, wx_ld >= channels of x)", mid, wx_ld);                 \
-  VQA_REQUIRE(mid <= 4096, who ": mid=%d too large for the LDS tile (4 rows x mid fp32 <= 64 KiB)", mid);                         \
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(vprime) | reinterpret_cast<uintptr_t>(qp) | reinterpret_cast<uintptr_t>(wx)) & 15) == 0, \
-              who ": vprime, qp and wx must be 16-byte aligned")
+  VQA_REQUIRE(mid <= 4096, who ": mid=%d too large (the forward's LDS tile: 4 rows x mid fp32 <= 64 KiB)", mid);                  \
+  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(vprime) | reinterpret_cast<uintptr_t>(qp) | reinterpret_cast<uintptr_t>(wx) |         \
+                (uintptr_t)(quads)) & 15) == 0, who ": vprime, qp, wx and the outputs read as quads must be 16-byte aligned")
+#define GROUPED_FWD_REQUIRE(who) GROUPED_REQUIRE(who, bx && score, 0)
 
 // the launch of the forward entry points: p == 0 runs the DROP = false kernels, the inference entry point's code; qrow != NULL
 // (inference only, p == 0) runs their PAIRS instantiations over the q' table qp [M][mid]
@@ -427,8 +407,8 @@ static int grouped_fwd_launch(const float* vprime, const float* qp, const int32_
   if (mode != 2 && mid % 256 == 0 && mid <= 1024) {
     const dim3 grid((P + 15) / 16, N);
     const size_t lds = (size_t)16 * mid * 4;
-    with_glimpses(G, [&](auto g) {
-      return with_it(mid / 256, [&](auto it) {
+    with_int14(G, [&](auto g) {
+      return with_int14(mid / 256, [&](auto it) {
         return with_flags(mode == 1, pairs ? false : p > 0.f, [&](auto mul, auto drop) {
           if (pairs)
             hipLaunchKernelGGL((att_score_grouped_kernel<decltype(g)::value, decltype(it)::value, decltype(mul)::value, false,
@@ -450,7 +430,7 @@ static int grouped_fwd_launch(const float* vprime, const float* qp, const int32_
   const int TP = 4 * pw;
   const dim3 grid((P + TP - 1) / TP, N);
   const size_t lds = (size_t)TP * mid * 4;
-  with_glimpses(G, [&](auto g) {
+  with_int14(G, [&](auto g) {
     return with_flag(pairs ? false : p > 0.f, [&](auto drop) {
       if (pairs)
         hipLaunchKernelGGL((att_score_grouped_general_kernel<decltype(g)::value, false, true>), grid, dim3(256), lds, s, vprime,
@@ -509,26 +489,16 @@ int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const fl
                               int N, int B, int P, int mid, int G, int mode, float p, uint64_t seed, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
-  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
-  VQA_REQUIRE(mode >= 0 && mode <= 2, "vqa_att_score_grouped_bwd: mode %d (0 '+', 1 '*', 2 '|')", mode);
-  VQA_REQUIRE(dscore && vprime && qp && wx && dvprime && dq_part && dwx_part, "vqa_att_score_grouped_bwd: null pointer");
-  VQA_REQUIRE(order && offsets, "vqa_att_score_grouped_bwd: null order / offsets");
-  VQA_REQUIRE(N >= 1 && N <= 65535 && B >= 0 && P >= 1, "vqa_att_score_grouped_bwd: N=%d (1..65535), B=%d, P=%d out of range", N,
-              B, P);
-  VQA_REQUIRE(mid >= 4 && mid % 4 == 0 && mid <= 4096 && wx_ld % 4 == 0 && wx_ld >= (mode == 2 ? 2 * mid : mid),
-              "vqa_att_score_grouped_bwd: bad args (mid=%d: a multiple of 4 up to 4096; wx_ld=%d: a multiple of 4, >= channels of x)",
-              mid, wx_ld);
+  GROUPED_REQUIRE("vqa_att_score_grouped_bwd", dscore && dvprime && dq_part && dwx_part,
+                  reinterpret_cast<uintptr_t>(dvprime) | reinterpret_cast<uintptr_t>(dq_part) | reinterpret_cast<uintptr_t>(dwx_part));
   VQA_REQUIRE(p >= 0.f && p < 1.f, "vqa_att_score_grouped_bwd: dropout p=%g outside [0, 1)", (double)p);
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(vprime) | reinterpret_cast<uintptr_t>(qp) | reinterpret_cast<uintptr_t>(wx) |
-                reinterpret_cast<uintptr_t>(dvprime) | reinterpret_cast<uintptr_t>(dq_part) | reinterpret_cast<uintptr_t>(dwx_part)) & 15) == 0,
-              "vqa_att_score_grouped_bwd: vprime, qp, wx, dvprime, dq_part and dwx_part must be 16-byte aligned");
   if (B == 0) return VQA_OK;
   hipStream_t s = (hipStream_t)stream;
   const float ik = keep_scale(p);
   const dim3 grid(vqa_att_score_grouped_tiles(P), N);
   if (mode != 2 && mid % 256 == 0 && mid <= 1024) {
-    with_glimpses(G, [&](auto g) {
-      return with_it(mid / 256, [&](auto it) {
+    with_int14(G, [&](auto g) {
+      return with_int14(mid / 256, [&](auto it) {
         return with_flags(mode == 1, p > 0.f, [&](auto mul, auto drop) {
           hipLaunchKernelGGL((att_score_grouped_bwd_kernel<decltype(g)::value, decltype(it)::value, decltype(mul)::value,
                                                            decltype(drop)::value>),
@@ -541,7 +511,7 @@ int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const fl
     return check_hip(hipGetLastError(), "att_score_grouped_bwd launch");
   }
 #define GROUPED_BWD_GENERAL(kMODE)                                                                                                \
-  with_glimpses(G, [&](auto g) {                                                                                                  \
+  with_int14(G, [&](auto g) {                                                                                                     \
     return with_flag(p > 0.f, [&](auto drop) {                                                                                    \
       hipLaunchKernelGGL((att_score_grouped_bwd_general_kernel<decltype(g)::value, kMODE, decltype(drop)::value>), grid,          \
                          dim3(256), 0, s, dscore, vprime, qp, wx, wx_ld, order, offsets, dvprime, dq_part, dwx_part, B, P, mid,   \

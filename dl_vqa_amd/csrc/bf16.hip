@@ -176,7 +176,7 @@ int vqa_dropout_to_bf16(const float* x, void* y_bf16, int64_t n, float p, uint64
   VQA_REQUIRE(x && y_bf16 && n > 0 && p >= 0.f && p < 1.f, "vqa_dropout_to_bf16: bad args");
   VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_bf16 % 16) == 0, "vqa_dropout_to_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(dropout_to_bf16_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     static_cast<uint16_t*>(y_bf16), n, p, p > 0.f ? 1.0f / (1.0f - p) : 1.0f, seed);
+                     static_cast<uint16_t*>(y_bf16), n, p, keep_scale(p), seed);
   return check_hip(hipGetLastError(), "dropout_to_bf16 launch");
 }
 

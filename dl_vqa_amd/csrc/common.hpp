@@ -60,6 +60,20 @@ template <class F>
 static int with_flags(bool a, bool b, F&& f) {
   return with_flag(a, [&](auto fa) { return with_flag(b, [&](auto fb) { return f(fa, fb); }); });
 }
+// the same for a run-time count in 1..4 (glimpses, 256-channel steps): f reads decltype(n)::value.  The caller has checked
+// the range -- there is no error path in here, and a value outside it would run as 4.
+template <class F>
+static int with_int14(int v, F&& f) {
+  switch (v) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
+// what a kept element is multiplied by under dropout p: 1 / (1 - p), 1 at p = 0
+static inline float keep_scale(float p) { return p > 0.f ? 1.0f / (1.0f - p) : 1.0f; }
 
 // VQA_* environment knobs (diagnostics / forced tile variants for the parity tests).  Read ONCE, when the
 // library is first used; vqa_reload_knobs() re-reads them (tests that switch variants inside one process).

@@ -904,20 +904,17 @@ __device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* sc
   }
 }
 
-template <int G>
-__global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, float* probs, float* out, int64_t out_ld,
-                                        int P, int C) {
+// GATHER (vqa_att_apply_gather_fwd): n = img[b], and a sample whose index is outside [0, N) is left unwritten (block-uniform
+// exit).  Otherwise n = b, and img / N are not read.
+template <int G, bool GATHER>
+__global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
+                                        int64_t out_ld, int P, int C, int N) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, blockIdx.x);
-}
-
-// the same with an image index; a sample whose index is outside [0, N) is left unwritten (block-uniform exit)
-template <int G>
-__global__ void att_apply_gather_fwd_v4_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
-                                               int64_t out_ld, int P, int C, int N) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int n = img[blockIdx.x];
-  if ((unsigned)n >= (unsigned)N) return;
+  int n = blockIdx.x;
+  if (GATHER) {
+    n = img[blockIdx.x];
+    if ((unsigned)n >= (unsigned)N) return;
+  }
   att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
 }
 
@@ -929,21 +926,7 @@ __device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score
   float* red = sm + G * P;   // [16]
   float* part = red + 16;    // [4][G][64]
   const int tid = threadIdx.x;
-  for (int g = 0; g < G; ++g) {
-    const float* s = score + ((int64_t)b * G + g) * P;
-    float mx = -INFINITY;
-    for (int i = tid; i < P; i += blockDim.x) mx = fmaxf(mx, s[i]);
-    mx = block_reduce(mx, red, true);
-    float sum = 0.f;
-    for (int i = tid; i < P; i += blockDim.x) { const float e = expf(s[i] - mx); pr[g * P + i] = e; sum += e; }
-    sum = block_reduce(sum, red, false);
-    const float inv = 1.f / sum;
-    for (int i = tid; i < P; i += blockDim.x) {
-      const float v = pr[g * P + i] * inv;
-      pr[g * P + i] = v;
-      if (blockIdx.y == 0) probs[((int64_t)b * G + g) * P + i] = v;
-    }
-  }
+  att_softmax_to_lds<G>(score, probs, pr, red, b, P, blockIdx.y == 0);
   __syncthreads();
   const int cl = tid & 63, pg = tid >> 6;
   const int c = blockIdx.y * 64 + cl;
@@ -970,19 +953,15 @@ __device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score
   }
 }
 
-template <int G>
-__global__ void att_apply_fwd_kernel(const float* score, const float* vn, float* probs, float* out,
-                                     int64_t out_ld, int P, int C) {
+template <int G, bool GATHER>
+__global__ void att_apply_fwd_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
+                                     int64_t out_ld, int P, int C, int N) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, blockIdx.x);
-}
-
-template <int G>
-__global__ void att_apply_gather_fwd_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
-                                            int64_t out_ld, int P, int C, int N) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int n = img[blockIdx.x];
-  if ((unsigned)n >= (unsigned)N) return;
+  int n = blockIdx.x;
+  if (GATHER) {
+    n = img[blockIdx.x];
+    if ((unsigned)n >= (unsigned)N) return;
+  }
   att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
 }
 
@@ -1341,7 +1320,6 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, int64_
 using namespace vqa;
 
 #define STREAM ((hipStream_t)stream)
-#define KEEP(p) ((p) > 0.f ? 1.0f / (1.0f - (p)) : 1.0f)
 
 template <int G>
 static void l2norm_bwd_launch(const float* dvn, const float* vn, const float* norm, void* dpooled, int mode, int64_t rows,
@@ -1349,9 +1327,79 @@ static void l2norm_bwd_launch(const float* dvn, const float* vn, const float* no
                               const float* probs, const float* dv_in, float p_v, uint64_t seed_v, hipStream_t s) {
 #define L2B(OB)                                                                                                            \
   hipLaunchKernelGGL((l2norm_bwd_kernel<OB, G>), dim3(grid_for(rows, 4)), dim3(256), 0, s, dvn, vn, norm, dpooled, rows, C, p, \
-                     KEEP(p), seed, positions, dout, dout_ld, probs, dv_in, p_v, KEEP(p_v), seed_v)
+                     keep_scale(p), seed, positions, dout, dout_ld, probs, dv_in, p_v, keep_scale(p_v), seed_v)
   if (mode == 2) L2B(2); else if (mode == 1) L2B(1); else L2B(0);
 #undef L2B
+}
+
+// ---------------------------------------------------------------- softmax + weighted sum: the host side of vqa_att_apply_*
+// dynamic LDS of both forward kernels (the scalar one uses less of it): probs [G][P], 16 reduction slots, part [16][G][64]
+static size_t att_apply_fwd_lds(int G, int P) { return ((size_t)G * P + 16 + 16 * G * 64) * 4; }
+
+static uintptr_t quad_bits(const void* a, const void* b, const void* c) {
+  return reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
+}
+
+// What the five entry points check, before any HIP call (`who` names the caller in the messages).  backward: the kernels
+// read dout / vn and write dvn as float4, so C and the leading dimension are multiples of 4 and `quads` (quad_bits of those
+// pointers, a null one counts as aligned) is 16-byte aligned.  pointers / indices: the form's data pointers and its
+// img / order / offsets are all there (true for a form without indices).  N: 1 for a form without an image count.
+static int att_apply_check(const char* who, bool backward, bool pointers, bool indices, int N, int B, int P, int C, int G,
+                           int64_t ld, uintptr_t quads) {
+  VQA_REQUIRE(G >= 1 && G <= 4, "%s: glimpses=%d unsupported (1..4)", who, G);
+  VQA_REQUIRE(pointers, "%s: null pointer", who);
+  VQA_REQUIRE(indices, "%s: null pointer among img / order / offsets", who);
+  const bool widths = backward ? C >= 4 && C % 4 == 0 && ld % 4 == 0 : C >= 1;
+  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && widths && ld >= (int64_t)G * C, "%s: N=%d, B=%d, P=%d, C=%d%s, %s=%lld out of range",
+              who, N, B, P, C, backward ? " (a multiple of 4)" : "", backward ? "dout_ld" : "out_ld", (long long)ld);
+  VQA_REQUIRE(backward || att_apply_fwd_lds(G, P) <= 64 * 1024, "%s: G*P=%d too large for LDS", who, G * P);
+  VQA_REQUIRE((quads & 15) == 0, "%s: dout, vn and dvn must be 16-byte aligned", who);
+  return VQA_OK;
+}
+
+// img == null: sample b weights its own image (vqa_att_apply_fwd), N is not read.  The 16-byte kernels need whole quads
+// of channels and an aligned vn; anything else runs the scalar ones.
+static int att_apply_fwd_launch(const float* score, const float* vn, const int32_t* img, float* probs, float* out,
+                                int64_t out_ld, int N, int B, int P, int C, int G, hipStream_t s) {
+  if (B == 0) return VQA_OK;
+  const dim3 grid(B, (C + 63) / 64);
+  const size_t lds = att_apply_fwd_lds(G, P);
+  return with_int14(G, [&](auto g) {
+    return with_flags(C % 4 == 0 && (reinterpret_cast<uintptr_t>(vn) & 15) == 0, img != nullptr, [&](auto v4, auto gather) {
+      if (decltype(v4)::value)
+        hipLaunchKernelGGL((att_apply_fwd_v4_kernel<decltype(g)::value, decltype(gather)::value>), grid, dim3(256), lds, s, score,
+                           vn, img, probs, out, out_ld, P, C, N);
+      else
+        hipLaunchKernelGGL((att_apply_fwd_kernel<decltype(g)::value, decltype(gather)::value>), grid, dim3(256), lds, s, score,
+                           vn, img, probs, out, out_ld, P, C, N);
+      return check_hip(hipGetLastError(), "att_apply_fwd launch");
+    });
+  });
+}
+
+// img == null: the plain form, whose rows kernel writes dvn [B][P][C] itself (dvn == null: nobody wants it).  With img the
+// rows kernel leaves dvn alone, and order / offsets (with dvn [N][P][C]) add the per-image sum; then the softmax backward.
+static int att_apply_bwd_launch(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                                const int32_t* order, const int32_t* offsets, float* dscore, float* dvn, float* dscore_rowsum,
+                                int N, int B, int P, int C, int G, hipStream_t s) {
+  if (B == 0) return VQA_OK;
+  const int64_t M = (int64_t)B * P, Mn = (int64_t)N * P;
+  int rc = with_int14(G, [&](auto g) {
+    return with_flag(img != nullptr, [&](auto gather) {
+      hipLaunchKernelGGL((att_apply_bwd_rows_kernel<decltype(g)::value, decltype(gather)::value>), dim3(grid_for(M, 4)), dim3(256),
+                         0, s, dout, dout_ld, probs, vn, img, N, dscore, decltype(gather)::value ? nullptr : dvn, M, P, C);
+      return check_hip(hipGetLastError(), "att_apply_bwd_rows launch");
+    });
+  });
+  if (rc == VQA_OK && order)
+    rc = with_int14(G, [&](auto g) {
+      hipLaunchKernelGGL(att_apply_gather_dvn_kernel<decltype(g)::value>, dim3(grid_for(Mn, 4)), dim3(256), 0, s, dout, dout_ld,
+                         probs, order, offsets, dvn, Mn, B, P, C);
+      return check_hip(hipGetLastError(), "att_apply_gather_dvn launch");
+    });
+  if (rc) return rc;
+  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, s, probs, dscore, P, dscore_rowsum);
+  return check_hip(hipGetLastError(), "softmax_bwd launch");
 }
 
 extern "C" {
@@ -1361,7 +1409,7 @@ int vqa_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, vqa
   ProfScope prof(VQA_K_DROPOUT, (hipStream_t)stream);
   VQA_REQUIRE(x && y && n >= 0 && p >= 0.f && p < 1.f, "vqa_dropout: bad args");
   if (n == 0) return VQA_OK;
-  hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM, x, y, n, p, KEEP(p), seed);
+  hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM, x, y, n, p, keep_scale(p), seed);
   return check_hip(hipGetLastError(), "dropout launch");
 }
 
@@ -1370,7 +1418,7 @@ int vqa_dropout_add(const float* x, float* y, int64_t n, float p, uint64_t seed,
   ProfScope prof(VQA_K_DROPOUT, (hipStream_t)stream);
   VQA_REQUIRE(x && y && n > 0 && p >= 0.f && p < 1.f, "vqa_dropout_add: bad args");
   VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0, "vqa_dropout_add: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, STREAM, x, y, n, p, KEEP(p), seed);
+  hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, STREAM, x, y, n, p, keep_scale(p), seed);
   return check_hip(hipGetLastError(), "dropout_add launch");
 }
 
@@ -1382,21 +1430,12 @@ int vqa_l2norm_fwd(const float* pooled, float* vn, float* norm, int64_t rows, in
   VQA_REQUIRE(p2 >= 0.f && p2 < 1.f, "vqa_l2norm_fwd: p2 must be in [0, 1)");
   if (vdrop && vdrop_is_bf16)
     hipLaunchKernelGGL(l2norm_fwd_kernel<true>, dim3(grid_for(rows, 4)), dim3(256), 0, STREAM, pooled, vn, norm, rows, C, p,
-                       KEEP(p), seed, vdrop, p2, KEEP(p2), seed2);
+                       keep_scale(p), seed, vdrop, p2, keep_scale(p2), seed2);
   else
     hipLaunchKernelGGL(l2norm_fwd_kernel<false>, dim3(grid_for(rows, 4)), dim3(256), 0, STREAM, pooled, vn, norm, rows, C, p,
-                       KEEP(p), seed, vdrop, p2, KEEP(p2), seed2);
+                       keep_scale(p), seed, vdrop, p2, keep_scale(p2), seed2);
   return check_hip(hipGetLastError(), "l2norm_fwd launch");
 }
-
-#define DISPATCH_G(G, ...)                                         \
-  switch (G) {                                                     \
-    case 1: { constexpr int kG = 1; __VA_ARGS__; } break;          \
-    case 2: { constexpr int kG = 2; __VA_ARGS__; } break;          \
-    case 3: { constexpr int kG = 3; __VA_ARGS__; } break;          \
-    case 4: { constexpr int kG = 4; __VA_ARGS__; } break;          \
-    default: set_error("glimpses=%d unsupported (1..4)", G); return VQA_ERR_INVALID; \
-  }
 
 int vqa_l2norm_bwd(const float* dvn, const float* vn, const float* norm, void* dpooled, int dpooled_mode, int64_t rows,
                    int positions, int C, float p, uint64_t seed, vqa_stream_t stream) {
@@ -1418,16 +1457,19 @@ int vqa_l2norm_bwd_joined(const float* dout, int64_t dout_ld, const float* probs
   VQA_REQUIRE(dout && probs && dv_in && vn && norm && dpooled && rows > 0 && C % 4 == 0 && dout_ld % 4 == 0 && dpooled_mode >= 0 &&
                   dpooled_mode <= 2 && positions > 0 && rows % positions == 0, "vqa_l2norm_bwd_joined: bad args");
   VQA_REQUIRE(dpooled_mode != 2 || C % 16 == 0, "vqa_l2norm_bwd_joined: the channel-blocked output needs C %% 16 == 0 (C=%d)", C);
-  DISPATCH_G(G, l2norm_bwd_launch<kG>(nullptr, vn, norm, dpooled, dpooled_mode, rows, positions, C, p, seed, dout, dout_ld, probs,
-                                      dv_in, p_v, seed_v, STREAM));
-  return check_hip(hipGetLastError(), "l2norm_bwd_joined launch");
+  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
+  return with_int14(G, [&](auto g) {
+    l2norm_bwd_launch<decltype(g)::value>(nullptr, vn, norm, dpooled, dpooled_mode, rows, positions, C, p, seed, dout, dout_ld,
+                                          probs, dv_in, p_v, seed_v, STREAM);
+    return check_hip(hipGetLastError(), "l2norm_bwd_joined launch");
+  });
 }
 
 int vqa_embed_tanh_fwd(const int64_t* q, const float* emb, float* x, int B, int T, int E, int V, float p,
                        uint64_t seed, int32_t* bad_tokens, vqa_stream_t stream) {
   VQA_REQUIRE(q && emb && x && B > 0 && T > 0 && E > 0 && V > 0, "vqa_embed_tanh_fwd: bad args");
   hipLaunchKernelGGL(embed_tanh_fwd_kernel, dim3(grid_for((int64_t)B * T * E, 256)), dim3(256), 0, STREAM, q, emb, x,
-                     B, T, E, V, p, KEEP(p), seed, bad_tokens);
+                     B, T, E, V, p, keep_scale(p), seed, bad_tokens);
   return check_hip(hipGetLastError(), "embed_tanh_fwd launch");
 }
 
@@ -1440,7 +1482,7 @@ int vqa_embed_tanh_bwd(const int64_t* q, const float* x, const float* dx, float*
                        float p, uint64_t seed, void* workspace, int64_t workspace_bytes, vqa_stream_t stream) {
   VQA_REQUIRE(q && x && dx && demb && B > 0 && T > 0 && E > 0 && V > 0, "vqa_embed_tanh_bwd: bad args");
   if (!workspace) {                                              // no workspace: the scanning kernel, O(V * B*T)
-    hipLaunchKernelGGL(embed_tanh_bwd_kernel, dim3(V), dim3(256), 0, STREAM, q, x, dx, demb, B, T, E, V, p, KEEP(p), seed);
+    hipLaunchKernelGGL(embed_tanh_bwd_kernel, dim3(V), dim3(256), 0, STREAM, q, x, dx, demb, B, T, E, V, p, keep_scale(p), seed);
     return check_hip(hipGetLastError(), "embed_tanh_bwd launch");
   }
   if (workspace_bytes < vqa_embed_tanh_bwd_workspace_bytes(B, T, V)) {
@@ -1458,7 +1500,7 @@ int vqa_embed_tanh_bwd(const int64_t* q, const float* x, const float* dx, float*
   hipLaunchKernelGGL(embed_hist_kernel, dim3((N + 255) / 256), dim3(256), 0, STREAM, q, N, V, counts);
   hipLaunchKernelGGL(embed_scan_kernel, dim3(1), dim3(1024), 0, STREAM, counts, offsets, cursor, V);
   hipLaunchKernelGGL(embed_fill_kernel, dim3((N + 255) / 256), dim3(256), 0, STREAM, q, N, V, cursor, slots);
-  hipLaunchKernelGGL(embed_tanh_bwd_binned_kernel, dim3(V), dim3(256), 0, STREAM, q, x, dx, demb, B, T, E, V, p, KEEP(p), seed,
+  hipLaunchKernelGGL(embed_tanh_bwd_binned_kernel, dim3(V), dim3(256), 0, STREAM, q, x, dx, demb, B, T, E, V, p, keep_scale(p), seed,
                      offsets, slots);
   return check_hip(hipGetLastError(), "embed_tanh_bwd(binned) launch");
 }
@@ -1486,31 +1528,32 @@ int vqa_att_score_fwd(const void* xs, int xs_is_bf16, const float* wx, int wx_ld
   ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
   VQA_REQUIRE(xs && wx && bx && score && mid % 4 == 0 && wx_ld % 4 == 0 && wx_ld >= (qcat ? 2 * mid : mid),
               "vqa_att_score_fwd: bad args");
+  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
   const int64_t M = (int64_t)B * P;
-  if (xs_is_bf16 && !qcat && mid % 8 == 0 && mid <= 1024 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0) {
-    DISPATCH_G(G, hipLaunchKernelGGL((att_score_fwd_bf16_kernel<kG>), dim3(grid_for(M, 8)), dim3(256), 0, STREAM,
-                                     static_cast<const uint16_t*>(xs), wx, wx_ld, bx, score, M, P, mid, p, KEEP(p), seed));
-  } else if (xs_is_bf16) {
-    DISPATCH_G(G, hipLaunchKernelGGL((att_score_fwd_kernel<kG, true>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, xs, wx,
-                                     wx_ld, bx, score, M, P, mid, p, KEEP(p), seed, qcat));
-  } else if (!qcat && G <= 2 && mid % 256 == 0 && mid <= 1024 && (reinterpret_cast<uintptr_t>(xs) & 15) == 0) {
-#define ROWS_LAUNCH(kG, kIT)                                                                                                  \
-  hipLaunchKernelGGL((att_score_fwd_rows_kernel<kG, kIT>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM,                        \
-                     static_cast<const float*>(xs), wx, wx_ld, bx, score, M, P, p, KEEP(p), seed)
-    switch ((G - 1) * 4 + mid / 256 - 1) {
-      case 0: ROWS_LAUNCH(1, 1); break;
-      case 1: ROWS_LAUNCH(1, 2); break;
-      case 2: ROWS_LAUNCH(1, 3); break;
-      case 3: ROWS_LAUNCH(1, 4); break;
-      case 4: ROWS_LAUNCH(2, 1); break;
-      case 5: ROWS_LAUNCH(2, 2); break;
-      case 6: ROWS_LAUNCH(2, 3); break;
-      default: ROWS_LAUNCH(2, 4); break;
-    }
-#undef ROWS_LAUNCH
+  const bool quads = (reinterpret_cast<uintptr_t>(xs) & 15) == 0;
+  const float ik = keep_scale(p);
+  if (xs_is_bf16 && !qcat && mid % 8 == 0 && mid <= 1024 && quads) {
+    with_int14(G, [&](auto g) {
+      hipLaunchKernelGGL((att_score_fwd_bf16_kernel<decltype(g)::value>), dim3(grid_for(M, 8)), dim3(256), 0, STREAM,
+                         static_cast<const uint16_t*>(xs), wx, wx_ld, bx, score, M, P, mid, p, ik, seed);
+      return 0;
+    });
+  } else if (!xs_is_bf16 && !qcat && G <= 2 && mid % 256 == 0 && mid <= 1024 && quads) {
+    with_flag(G == 2, [&](auto two) {               // the rows kernel exists for one and two glimpses only
+      return with_int14(mid / 256, [&](auto it) {
+        hipLaunchKernelGGL((att_score_fwd_rows_kernel<decltype(two)::value ? 2 : 1, decltype(it)::value>), dim3(grid_for(M, 4)),
+                           dim3(256), 0, STREAM, static_cast<const float*>(xs), wx, wx_ld, bx, score, M, P, p, ik, seed);
+        return 0;
+      });
+    });
   } else {
-    DISPATCH_G(G, hipLaunchKernelGGL((att_score_fwd_kernel<kG, false>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, xs, wx,
-                                     wx_ld, bx, score, M, P, mid, p, KEEP(p), seed, qcat));
+    with_int14(G, [&](auto g) {
+      return with_flag(xs_is_bf16 != 0, [&](auto bf16) {
+        hipLaunchKernelGGL((att_score_fwd_kernel<decltype(g)::value, decltype(bf16)::value>), dim3(grid_for(M, 4)), dim3(256), 0,
+                           STREAM, xs, wx, wx_ld, bx, score, M, P, mid, p, ik, seed, qcat);
+        return 0;
+      });
+    });
   }
   return check_hip(hipGetLastError(), "att_score_fwd launch");
 }
@@ -1531,65 +1574,44 @@ int vqa_att_score_bwd(const float* dscore, const float* wx, int wx_ld, void* xs_
                   wx_ld >= (mode == 2 ? 2 * mid : mid),
               "vqa_att_score_bwd: mode %d needs its operands (vprime/qp) and a matching wx_ld", mode);
   const int RS = vqa_att_row_splits(P);
-  if (xs_is_bf16) {
-    DISPATCH_G(G, hipLaunchKernelGGL((att_score_bwd_kernel<kG, true>), dim3(B, RS), dim3(256), 0, STREAM, dscore, wx, wx_ld,
-                                     xs_inout, dwx_part, dq_part, P, mid, RS, p, KEEP(p), seed, mode, vprime, qp));
-  } else {
-    DISPATCH_G(G, hipLaunchKernelGGL((att_score_bwd_kernel<kG, false>), dim3(B, RS), dim3(256), 0, STREAM, dscore, wx, wx_ld,
-                                     xs_inout, dwx_part, dq_part, P, mid, RS, p, KEEP(p), seed, mode, vprime, qp));
-  }
-  return check_hip(hipGetLastError(), "att_score_bwd launch");
+  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
+  return with_int14(G, [&](auto g) {
+    return with_flag(xs_is_bf16 != 0, [&](auto bf16) {
+      hipLaunchKernelGGL((att_score_bwd_kernel<decltype(g)::value, decltype(bf16)::value>), dim3(B, RS), dim3(256), 0, STREAM,
+                         dscore, wx, wx_ld, xs_inout, dwx_part, dq_part, P, mid, RS, p, keep_scale(p), seed, mode, vprime, qp);
+      return check_hip(hipGetLastError(), "att_score_bwd launch");
+    });
+  });
 }
 
+// vqa_att_apply_fwd and vqa_att_apply_bwd take the checks of their gather forms: what used to reach a launch with undefined
+// results (out_ld / dout_ld < G*C, P < 1, a dout, vn or dvn that the backward cannot read as float4, G outside 1..4) is
+// VQA_ERR_INVALID, and B == 0 is VQA_OK without a launch.  Every argument set that was valid runs the kernels it ran, on the
+// same grid, block and LDS size; a vn that is not 16-byte aligned now takes the forward's scalar kernels.
 int vqa_att_apply_fwd(const float* score, const float* vn, float* probs, float* out, int64_t out_ld, int B, int P,
                       int C, int G, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
-  VQA_REQUIRE(score && vn && probs && out, "vqa_att_apply_fwd: null pointer");
-  const size_t lds = ((size_t)G * P + 16 + 16 * G * 64) * 4;
-  VQA_REQUIRE(lds <= 64 * 1024, "vqa_att_apply_fwd: G*P=%d too large for LDS", G * P);
-  if (C % 4 == 0) {
-    DISPATCH_G(G, hipLaunchKernelGGL(att_apply_fwd_v4_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score,
-                                     vn, probs, out, out_ld, P, C));
-    return check_hip(hipGetLastError(), "att_apply_fwd launch");
-  }
-  DISPATCH_G(G, hipLaunchKernelGGL(att_apply_fwd_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score, vn,
-                                   probs, out, out_ld, P, C));
-  return check_hip(hipGetLastError(), "att_apply_fwd launch");
+  const int rc = att_apply_check("vqa_att_apply_fwd", false, score && vn && probs && out, true, 1, B, P, C, G, out_ld, 0);
+  return rc ? rc : att_apply_fwd_launch(score, vn, nullptr, probs, out, out_ld, 0, B, P, C, G, STREAM);
 }
 
 int vqa_att_apply_gather_fwd(const float* score, const float* vn, const int32_t* img, float* probs, float* out,
                              int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
-  VQA_REQUIRE(score && vn && img && probs && out, "vqa_att_apply_gather_fwd: null pointer");
-  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && C >= 1 && out_ld >= (int64_t)G * C,
-              "vqa_att_apply_gather_fwd: N=%d, B=%d, P=%d, C=%d, out_ld=%lld out of range", N, B, P, C, (long long)out_ld);
-  const size_t lds = ((size_t)G * P + 16 + 16 * G * 64) * 4;
-  VQA_REQUIRE(lds <= 64 * 1024, "vqa_att_apply_gather_fwd: G*P=%d too large for LDS", G * P);
-  if (B == 0) return VQA_OK;
-  if (C % 4 == 0) {
-    DISPATCH_G(G, hipLaunchKernelGGL(att_apply_gather_fwd_v4_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score,
-                                     vn, img, probs, out, out_ld, P, C, N));
-    return check_hip(hipGetLastError(), "att_apply_gather_fwd launch");
-  }
-  DISPATCH_G(G, hipLaunchKernelGGL(att_apply_gather_fwd_kernel<kG>, dim3(B, (C + 63) / 64), dim3(256), lds, STREAM, score, vn,
-                                   img, probs, out, out_ld, P, C, N));
-  return check_hip(hipGetLastError(), "att_apply_gather_fwd launch");
+  const int rc = att_apply_check("vqa_att_apply_gather_fwd", false, score && vn && probs && out, img, N, B, P, C, G, out_ld, 0);
+  return rc ? rc : att_apply_fwd_launch(score, vn, img, probs, out, out_ld, N, B, P, C, G, STREAM);
 }
 
 int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, float* dscore,
                       float* dvn, float* dscore_rowsum, int B, int P, int C, int G, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  VQA_REQUIRE(dout && probs && vn && dscore && C % 4 == 0 && dout_ld % 4 == 0, "vqa_att_apply_bwd: bad args");
-  const int64_t M = (int64_t)B * P;
-  DISPATCH_G(G, hipLaunchKernelGGL((att_apply_bwd_rows_kernel<kG, false>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
-                                   dout_ld, probs, vn, static_cast<const int*>(nullptr), 0, dscore, dvn, M, P, C));
-  int rc = check_hip(hipGetLastError(), "att_apply_bwd_rows launch");
-  if (rc) return rc;
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, STREAM, probs, dscore, P, dscore_rowsum);
-  return check_hip(hipGetLastError(), "softmax_bwd launch");
+  const int rc = att_apply_check("vqa_att_apply_bwd", true, dout && probs && vn && dscore, true, 1, B, P, C, G, dout_ld,
+                                 quad_bits(dout, vn, dvn));
+  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, nullptr, nullptr, nullptr, dscore, dvn, dscore_rowsum, 0, B, P,
+                                        C, G, STREAM);
 }
 
 int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
@@ -1597,48 +1619,20 @@ int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* pr
                              int N, int B, int P, int C, int G, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
-  VQA_REQUIRE(dout && probs && vn && dscore && dvn, "vqa_att_apply_gather_bwd: null pointer");
-  VQA_REQUIRE(img && order && offsets, "vqa_att_apply_gather_bwd: null img / order / offsets");
-  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && C >= 4 && C % 4 == 0 && dout_ld % 4 == 0 && dout_ld >= (int64_t)G * C,
-              "vqa_att_apply_gather_bwd: N=%d, B=%d, P=%d, C=%d (a multiple of 4), dout_ld=%lld out of range", N, B, P, C,
-              (long long)dout_ld);
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(vn) | reinterpret_cast<uintptr_t>(dvn)) & 15) == 0,
-              "vqa_att_apply_gather_bwd: dout, vn and dvn must be 16-byte aligned");
-  if (B == 0) return VQA_OK;
-  const int64_t M = (int64_t)B * P, Mn = (int64_t)N * P;
-  DISPATCH_G(G, hipLaunchKernelGGL((att_apply_bwd_rows_kernel<kG, true>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
-                                   dout_ld, probs, vn, img, N, dscore, static_cast<float*>(nullptr), M, P, C));
-  int rc = check_hip(hipGetLastError(), "att_apply_gather_bwd_rows launch");
-  if (rc) return rc;
-  DISPATCH_G(G, hipLaunchKernelGGL(att_apply_gather_dvn_kernel<kG>, dim3(grid_for(Mn, 4)), dim3(256), 0, STREAM, dout, dout_ld,
-                                   probs, order, offsets, dvn, Mn, B, P, C));
-  rc = check_hip(hipGetLastError(), "att_apply_gather_dvn launch");
-  if (rc) return rc;
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, STREAM, probs, dscore, P, dscore_rowsum);
-  return check_hip(hipGetLastError(), "softmax_bwd launch");
+  const int rc = att_apply_check("vqa_att_apply_gather_bwd", true, dout && probs && vn && dscore && dvn, img && order && offsets,
+                                 N, B, P, C, G, dout_ld, quad_bits(dout, vn, dvn));
+  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, order, offsets, dscore, dvn, dscore_rowsum, N, B, P, C, G,
+                                        STREAM);
 }
 
 int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
                                 float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
-  VQA_REQUIRE(dout && probs && vn && dscore, "vqa_att_apply_gather_dscore: null pointer");
-  VQA_REQUIRE(img, "vqa_att_apply_gather_dscore: null img");
-  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && C >= 4 && C % 4 == 0 && dout_ld % 4 == 0 && dout_ld >= (int64_t)G * C,
-              "vqa_att_apply_gather_dscore: N=%d, B=%d, P=%d, C=%d (a multiple of 4), dout_ld=%lld out of range", N, B, P, C,
-              (long long)dout_ld);
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(vn)) & 15) == 0,
-              "vqa_att_apply_gather_dscore: dout and vn must be 16-byte aligned");
-  if (B == 0) return VQA_OK;
-  const int64_t M = (int64_t)B * P;
-  DISPATCH_G(G, hipLaunchKernelGGL((att_apply_bwd_rows_kernel<kG, true>), dim3(grid_for(M, 4)), dim3(256), 0, STREAM, dout,
-                                   dout_ld, probs, vn, img, N, dscore, static_cast<float*>(nullptr), M, P, C));
-  int rc = check_hip(hipGetLastError(), "att_apply_gather_dscore rows launch");
-  if (rc) return rc;
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, STREAM, probs, dscore, P, dscore_rowsum);
-  return check_hip(hipGetLastError(), "softmax_bwd launch");
+  const int rc = att_apply_check("vqa_att_apply_gather_dscore", true, dout && probs && vn && dscore, img, N, B, P, C, G, dout_ld,
+                                 quad_bits(dout, vn, nullptr));
+  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, nullptr, nullptr, dscore, nullptr, dscore_rowsum, N, B, P,
+                                        C, G, STREAM);
 }
 
 int vqa_softce_fwd_bwd(const float* logits, int64_t ld, const int64_t* a_idx, const int64_t* a_val, int kmax, int B,
@@ -1677,7 +1671,7 @@ int vqa_sum_parts(const float* part, float* out, int batch, int parts, int cols,
 int vqa_relu_drop_bwd(const float* y, const float* dy, float* dx, int64_t n, float p, uint64_t seed,
                       vqa_stream_t stream) {
   VQA_REQUIRE(y && dy && dx, "vqa_relu_drop_bwd: null pointer");
-  hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM, y, dy, dx, n, p, KEEP(p), seed);
+  hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM, y, dy, dx, n, p, keep_scale(p), seed);
   return check_hip(hipGetLastError(), "relu_drop_bwd launch");
 }
 
@@ -1720,10 +1714,10 @@ int vqa_gather_rows_drop(const float* src, const int32_t* rows, float* dst, int 
   const int64_t stride = (int64_t)grid * 256;
   if (vec)
     hipLaunchKernelGGL(gather_rows_drop_kernel<true>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
-                       stride / rw, stride % rw, p, KEEP(p), seed);
+                       stride / rw, stride % rw, p, keep_scale(p), seed);
   else
     hipLaunchKernelGGL(gather_rows_drop_kernel<false>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
-                       stride / rw, stride % rw, p, KEEP(p), seed);
+                       stride / rw, stride % rw, p, keep_scale(p), seed);
   return check_hip(hipGetLastError(), "gather_rows_drop launch");
 }
 

@@ -464,10 +464,14 @@ def lstm_cell_bwd(gates, c_in, c_out, q_len, t, dh, dc, dgates):
          B, H, stream())
 
 
+def _score_dims(wx, concat: bool):
+    """(G, xld, mid) of the x_conv weights wx [G, xld]: xld = mid ('+', '*') or 2*mid ('|', concat)."""
+    return wx.shape[0], wx.shape[1], wx.shape[1] // 2 if concat else wx.shape[1]
+
+
 def att_score_fwd(xs, wx, bx, B, P, p: float, seed: int, qcat=None) -> torch.Tensor:
     """wx [G, xld] with xld = mid ('+', '*') or 2*mid ('|', qcat = q' [B, mid])."""
-    G, xld = wx.shape[0], wx.shape[1]
-    mid = xld // 2 if qcat is not None else xld
+    G, xld, mid = _score_dims(wx, qcat is not None)
     score = torch.empty(B, G, P, dtype=torch.float32, device=xs.device)
     call("vqa_att_score_fwd", ptr(xs), int(xs.dtype == torch.bfloat16), ptr(wx), xld, ptr(bx), ptr(score), B, P, mid, G, p,
          seed, ptr(qcat), stream())
@@ -475,10 +479,8 @@ def att_score_fwd(xs, wx, bx, B, P, p: float, seed: int, qcat=None) -> torch.Ten
 
 
 def att_score_bwd(dscore, wx, xs_inout, B, P, p: float, seed: int, mode: int = 0, vprime=None, qp=None):
-    lib = _lib.load()
-    G, xld = wx.shape[0], wx.shape[1]
-    mid = xld // 2 if mode == 2 else xld
-    RS = lib.vqa_att_row_splits(P)
+    G, xld, mid = _score_dims(wx, mode == 2)
+    RS = _lib.load().vqa_att_row_splits(P)
     dwx_part = torch.empty(B * RS, G * xld, dtype=torch.float32, device=wx.device)
     dq_part = torch.empty(B * RS, mid, dtype=torch.float32, device=wx.device)
     call("vqa_att_score_bwd", ptr(dscore), ptr(wx), xld, ptr(xs_inout), int(xs_inout.dtype == torch.bfloat16), ptr(dwx_part),
@@ -494,15 +496,19 @@ def att_apply_fwd(score, vn, out, out_ld):
     return probs
 
 
+def _grouped_score_head(vprime, qp, wx, order, offsets, N: int, B: int, P: int, mode: int, q_rows: int):
+    """What the att_score_grouped_*_fwd wrappers check and allocate: (G, xld, mid, score [B, G, P]); qp is [q_rows, mid]."""
+    G, xld, mid = _score_dims(wx, mode == 2)
+    _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (q_rows, mid)
+    return G, xld, mid, torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+
+
 def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
     """Scores [B, G, P] of B questions against N images from ONE v' [N*P, mid] per image: order / offsets (device int32,
     model.group_by_image) list the questions of image n as order[offsets[n]:offsets[n+1]].  mode 0 '+', 1 '*', 2 '|'
     (wx [G, 2*mid])."""
-    G, xld = wx.shape[0], wx.shape[1]
-    mid = xld // 2 if mode == 2 else xld
-    _chk(order, torch.int32), _chk(offsets, torch.int32)
-    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
-    score = torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+    G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, B)
     call("vqa_att_score_grouped_fwd", ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
          N, B, P, mid, G, mode, stream())
     return score
@@ -511,13 +517,10 @@ def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P:
 def att_score_grouped_pairs_fwd(vprime, qp, qrow, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
     """att_score_grouped_fwd for B (image, question) pairs over a table qp [M, mid] of distinct questions: pair b reads the
     row qp[qrow[b]] (qrow device int32 [B]).  Bit-identical to att_score_grouped_fwd(vprime, qp[qrow], ...)."""
-    G, xld = wx.shape[0], wx.shape[1]
-    mid = xld // 2 if mode == 2 else xld
     M = qp.shape[0]
-    _chk(order, torch.int32), _chk(offsets, torch.int32), _chk(qrow, torch.int32), _chk(qp)
-    assert order.numel() == B and offsets.numel() == N + 1 and qrow.numel() == B
-    assert vprime.shape == (N * P, mid) and qp.shape == (M, mid)
-    score = torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+    _chk(qrow, torch.int32), _chk(qp)
+    assert qrow.numel() == B
+    G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, M)
     call("vqa_att_score_grouped_pairs_fwd", ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets),
          ptr(score), N, B, M, P, mid, G, mode, stream())
     return score
@@ -554,13 +557,18 @@ def gather_rows_drop(src, rows, p: float, seed: int, out: Optional[torch.Tensor]
     return out
 
 
+def _apply_gather_head(probs, vn, img):
+    """What the att_apply_gather_* wrappers check: (B, G, P, N, C) of probs-shaped [B, G, P], vn [N, P, C], img int32 [B]."""
+    (B, G, P), N, C = probs.shape, vn.shape[0], vn.shape[-1]
+    _chk(img, torch.int32)
+    assert img.numel() == B and vn.numel() == N * P * C
+    return B, G, P, N, C
+
+
 def att_apply_gather_dscore(dout, dout_ld, probs, vn, img, rowsum=None):
     """The dscore half of att_apply_gather_bwd (same device code, same bits), for a vn nobody wants a gradient of: vn
     [N, P, C] may be a large bank, only the rows img[b] (device int32 [B]) are read."""
-    B, G, P = probs.shape
-    N, C = vn.shape[0], vn.shape[-1]
-    _chk(img, torch.int32)
-    assert img.numel() == B and vn.numel() == N * P * C
+    B, G, P, N, C = _apply_gather_head(probs, vn, img)
     dscore = torch.empty_like(probs)
     call("vqa_att_apply_gather_dscore", ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(dscore), ptr(rowsum), N, B, P, C, G,
          stream())
@@ -569,10 +577,7 @@ def att_apply_gather_dscore(dout, dout_ld, probs, vn, img, rowsum=None):
 
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C]."""
-    B, G, P = score.shape
-    N, C = vn.shape[0], vn.shape[-1]
-    _chk(img, torch.int32)
-    assert img.numel() == B and vn.numel() == N * P * C
+    B, G, P, N, C = _apply_gather_head(score, vn, img)
     probs = torch.empty_like(score)
     call("vqa_att_apply_gather_fwd", ptr(score), ptr(vn), ptr(img), ptr(probs), ptr(out), out_ld, N, B, P, C, G, stream())
     return probs
@@ -582,11 +587,7 @@ def att_score_grouped_drop_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: in
                                seed: int) -> torch.Tensor:
     """att_score_grouped_fwd with the x_conv dropout mask drop_scale(seed, (b*P + pos)*xld + m) on x (train mode); p = 0
     runs the same device code as att_score_grouped_fwd."""
-    G, xld = wx.shape[0], wx.shape[1]
-    mid = xld // 2 if mode == 2 else xld
-    _chk(order, torch.int32), _chk(offsets, torch.int32)
-    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
-    score = torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
+    G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, B)
     call("vqa_att_score_grouped_drop_fwd", ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
          N, B, P, mid, G, mode, p, seed, stream())
     return score
@@ -596,10 +597,9 @@ def att_apply_gather_bwd(dout, dout_ld, probs, vn, img, order, offsets, rowsum=N
     """att_apply_bwd where sample b weighted the rows of image img[b] (vn [N, P, C]; img / order / offsets device int32):
     (dscore [B, G, P], dvn [N, P, C] = the weighted-sum branch of d loss / d vn summed over the questions of each image,
     zeros for an image without questions)."""
-    B, G, P = probs.shape
-    N, C = vn.shape[0], vn.shape[-1]
-    _chk(img, torch.int32), _chk(order, torch.int32), _chk(offsets, torch.int32)
-    assert img.numel() == B and order.numel() == B and offsets.numel() == N + 1 and vn.numel() == N * P * C
+    B, G, P, N, C = _apply_gather_head(probs, vn, img)
+    _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert order.numel() == B and offsets.numel() == N + 1
     dscore = torch.empty_like(probs)
     dvn = torch.empty(N, P, C, dtype=torch.float32, device=vn.device)
     call("vqa_att_apply_gather_bwd", ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(order), ptr(offsets), ptr(dscore), ptr(dvn),
@@ -610,8 +610,7 @@ def att_apply_gather_bwd(dout, dout_ld, probs, vn, img, order, offsets, rowsum=N
 def att_score_grouped_bwd(dscore, vprime, qp, wx, order, offsets, N: int, B: int, P: int, mode: int, p: float, seed: int):
     """Backward of att_score_grouped_drop_fwd: (dvprime [N*P, mid], dq_part [B*NT, mid], dwx_part [N*NT, G*xld], NT);
     sum_parts(dq_part, out, B, NT, mid) and colsum(dwx_part, N*NT, G*xld, out) finish d loss / d q' and d loss / d wx."""
-    G, xld = wx.shape[0], wx.shape[1]
-    mid = xld // 2 if mode == 2 else xld
+    G, xld, mid = _score_dims(wx, mode == 2)
     _chk(order, torch.int32), _chk(offsets, torch.int32)
     assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
     assert dscore.shape == (B, G, P) and dscore.is_contiguous()
