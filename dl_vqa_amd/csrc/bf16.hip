@@ -164,6 +164,21 @@ int vqa_gemm_bf16(const void* A, int64_t lda, int transA, const void* B, int64_t
   });
 }
 
+int vqa_gemm_plan(int engine, int M, int N, int K, int transA, int transB, int64_t workspace_bytes, int32_t* out, int n_out) {
+  VQA_REQUIRE(engine >= 0 && engine <= 2 && M > 0 && N > 0 && K > 0 && out && n_out >= 10,
+              "vqa_gemm_plan: bad args (engine=%d M=%d N=%d K=%d n_out=%d)", engine, M, N, K, n_out);
+  GemmPlan p = engine == 1 ? plan_gemm_x3(M, N, K) : plan_gemm(M, N, K, engine == 2 ? BKB : BK);
+  // vqa_gemm_bf16 claims the ordinary plan's workspace before it asks for the wide plan
+  const bool wide = engine == 2 && workspace_bytes >= slab_bytes(p, M, N) &&
+                    plan_gemm_wide(p, M, N, K, transA, transB, workspace_bytes > 0, workspace_bytes);
+  const int bm = engine == 1 ? X3_BM : p.big == 2 ? 256 : p.big ? 128 : 64;
+  const int bn = engine == 1 ? X3_BN : wide ? 256 : p.big ? 128 : 64;
+  const bool persistent = engine == 0 ? gemm_runs_persistent(p) : engine == 1 && gemm_x3_runs_persistent(p);
+  const int32_t v[10] = {bm, bn, p.tiles_m, p.tiles_n, p.nk, p.splits, p.ks_per_split, p.order, persistent, wide};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return VQA_OK;
+}
+
 int vqa_f32_to_bf16(const float* x, void* y_bf16, int64_t n, vqa_stream_t stream) {
   VQA_REQUIRE(x && y_bf16 && n > 0, "vqa_f32_to_bf16: bad args");
   VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_bf16 % 16) == 0, "vqa_f32_to_bf16: pointers must be 16-byte aligned");

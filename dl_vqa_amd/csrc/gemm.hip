@@ -97,9 +97,7 @@ int launch_gemm(const typename AL::Params& pa, const typename BL::Params& pb, co
     // share of a tile's life: v_conv forward 1.13 -> 1.04 ms, LSTM input GEMM 0.116 -> 0.105 ms); with long K
     // the static tile striding loses more to imbalance than it saves (v_conv dgrad 0.82 -> 0.88 ms), so those
     // keep one workgroup per tile and the hardware's dynamic dispatch.  VQA_PERSISTENT=0/1 forces the choice.
-    const int pt = knobs().persistent;
-    const bool persistent = pt >= 0 ? pt == 1 : p.nk <= 16;
-    if (p.splits == 1 && persistent) {
+    if (gemm_runs_persistent(p)) {
       auto pk = gemm_persistent_kernel<Cfg, AL, BL>;
       int rc = ensure_dyn_smem(reinterpret_cast<const void*>(pk), SL::BYTES, "hipFuncSetAttribute(gemm_persistent)");
       if (rc) return rc;

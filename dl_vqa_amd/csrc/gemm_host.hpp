@@ -14,6 +14,20 @@ inline void split_k(GemmPlan& p, int splits) { p.ks_per_split = (p.nk + splits -
 GemmPlan plan_gemm(int M, int N, int K, int bk = BK);
 // vqa_gemm_bf16 only: replaces p by the 128 x 256 plan of a long-K weight gradient and returns true where that plan is admitted
 bool plan_gemm_wide(GemmPlan& p, int M, int N, int K, int transA, int transB, bool has_workspace, int64_t workspace_bytes);
+// vqa_gemm_x3's plan (gemm_x3.hip): one tile shape, X3_BM x X3_BN
+constexpr int X3_BM = 192, X3_BN = 128;
+GemmPlan plan_gemm_x3(int M, int N, int K);
+
+// Whether a plan runs on the persistent kernel: asked by the launcher and by vqa_gemm_plan.
+// vqa_gemm: tiles above 64 x 64 only, unsplit, K short (<= 16 K-steps) unless VQA_PERSISTENT=0/1 forces the choice
+inline bool gemm_runs_persistent(const GemmPlan& p) {
+  const int pt = knobs().persistent;
+  return p.big != 0 && p.splits == 1 && (pt >= 0 ? pt == 1 : p.nk <= 16);
+}
+// vqa_gemm_x3: unsplit with more tiles than the 256 workgroups of its grid, unless VQA_PERSISTENT=0
+inline bool gemm_x3_runs_persistent(const GemmPlan& p) {
+  return p.splits == 1 && p.tiles_m * p.tiles_n > 256 && knobs().persistent != 0;
+}
 
 // Split-K partials [splits][M][N] in fp32: what *_workspace_bytes report and what the entry points claim.
 inline int64_t slab_bytes(const GemmPlan& p, int M, int N) { return p.splits > 1 ? (int64_t)p.splits * M * N * 4 : 0; }

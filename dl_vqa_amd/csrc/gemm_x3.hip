@@ -15,7 +15,7 @@ namespace vqa {
 #ifndef VQA_X3_PF
 #define VQA_X3_PF 2
 #endif
-using CfgG = TileCfg<192, 128, 2, 2, 4, VQA_X3_PF>;   // one workgroup per CU: 4 MFMA waves of 96 x 64 + 4 loader waves
+using CfgG = TileCfg<X3_BM, X3_BN, 2, 2, 4, VQA_X3_PF>;   // one workgroup per CU: 4 MFMA waves of 96 x 64 + 4 loader waves
 
 // Part 0 sees this declaration only; the definition and its kernels are compiled by the part that owns the layout (AL, BL).
 template <class AL, class BL>
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_x3_persistent_kernel(typ
 template <class AL, class BL>
 int launch_gemm_x3(const typename AL::Params& pa, const typename BL::Params& pb, const EpiParams& pe, const GemmPlan& p, hipStream_t s) {
   using SL = SmemLayoutX<CfgG, AL::kTypeR, BL::kTypeR>;
-  if (p.splits == 1 && p.tiles_m * p.tiles_n > 256 && knobs().persistent != 0) {
+  if (gemm_x3_runs_persistent(p)) {
     auto pk = gemm_x3_persistent_kernel<CfgG, AL, BL>;
     int rc = ensure_dyn_smem(reinterpret_cast<const void*>(pk), SL::BYTES, "hipFuncSetAttribute(gemm_x3_p)");
     if (rc) return rc;
@@ -105,7 +105,7 @@ VQA_GX3_OWN(PlainC, PlainC)
 }  // namespace vqa
 
 #else  // VQA_GEMM_PART == 0: the planner and the C entry point
-static GemmPlan plan_gemm_x3(int M, int N, int K) {
+GemmPlan plan_gemm_x3(int M, int N, int K) {
   GemmPlan p;
   p.big = p.order = 0;                     // one tile shape, one tile order
   p.tiles_m = (M + CfgG::BM - 1) / CfgG::BM;

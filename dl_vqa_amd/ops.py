@@ -21,9 +21,14 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     key = (str(device), torch.cuda.current_stream(device).cuda_stream)
     t = _ws.get(key)
     if t is None or t.numel() * 4 < nbytes:
-        t = torch.empty(max(nbytes // 4 + 1024, 1 << 20), dtype=torch.float32, device=device)
+        t = torch.empty(_workspace_floats(nbytes), dtype=torch.float32, device=device)
         _ws[key] = t
     return t
+
+
+def _workspace_floats(nbytes: int) -> int:
+    """Elements of a workspace made for a claim of nbytes."""
+    return max(nbytes // 4 + 1024, 1 << 20)
 
 
 def _chk(t: torch.Tensor, dtype=torch.float32):
@@ -54,6 +59,24 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, M: int, N: int, K: i
     x3: the contraction on the bf16 matrix cores with exact 3 x bf16 operand splits (csrc/x3_core.hpp)."""
     return _gemm("vqa_gemm_x3" if x3 else "vqa_gemm", (), A, B, C, M, N, K, transA, transB, lda, ldb, ldc, bias1, bias2, rowgroup,
                  rg_div, rg_op, relu, accumulate, aux, tag)
+
+
+GEMM_ENGINES = {"vqa_gemm": 0, "vqa_gemm_x3": 1, "vqa_gemm_bf16": 2}
+GEMM_PLAN_FIELDS = ("BM", "BN", "tiles_m", "tiles_n", "nk", "splits", "ks_per_split", "order", "persistent", "wide")
+
+
+def gemm_plan(engine: str, M: int, N: int, K: int, *, transA=False, transB=True, workspace_bytes=None) -> dict:
+    """The plan vqa_gemm / vqa_gemm_x3 / vqa_gemm_bf16 (engine: the entry point's name) runs for this shape under the VQA_* knobs
+    in force, from the planners the launchers use (vqa_gemm_plan); makes no HIP call.  workspace_bytes: what the call would pass;
+    the default is what _gemm passes with a workspace made for this claim (an older, larger workspace passes more)."""
+    import ctypes
+    lib = _lib.load()
+    if workspace_bytes is None:
+        nbytes = getattr(lib, engine + "_workspace_bytes")(M, N, K) if min(M, N, K) > 0 else 0     # vqa_gemm_plan rejects the rest
+        workspace_bytes = _workspace_floats(nbytes) * 4 if nbytes else 0
+    out = (ctypes.c_int32 * len(GEMM_PLAN_FIELDS))()
+    call("vqa_gemm_plan", GEMM_ENGINES[engine], M, N, K, int(transA), int(transB), workspace_bytes, out, len(out))
+    return dict(zip(GEMM_PLAN_FIELDS, out))
 
 
 def nchw_to_nhwc4(x: torch.Tensor) -> torch.Tensor:

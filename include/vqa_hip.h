@@ -33,7 +33,7 @@ extern "C" {
  * version 8 that way, vqa_softmax_topk after them, and the two entry points of cached question features
  * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that, then image preprocessing (vqa_preprocess_supported,
  * vqa_preprocess_images), then the two entry points of training on cached image features (vqa_gather_rows_drop,
- * vqa_att_apply_gather_dscore) -- a caller built against the earlier version-8 header finds every prototype it knows
+ * vqa_att_apply_gather_dscore), then the plan query vqa_gemm_plan -- a caller built against the earlier version-8 header finds every prototype it knows
  * unchanged. */
 #define VQA_ABI_VERSION 8
 
@@ -500,6 +500,12 @@ int vqa_gemm_bf16(const void* A, int64_t lda, int transA, const void* B, int64_t
                   int64_t ldc, int c_is_bf16, int M, int N, int K, const float* bias1, const float* bias2,
                   const float* rowgroup, int64_t rg_ld, int rg_div, int rg_op, int relu, int accumulate,
                   float* aux, float* workspace, int64_t workspace_bytes, int tag, vqa_stream_t stream);
+
+/* The plan the three entry points above run for a shape, as their launchers compute it under the VQA_* knobs in force; no HIP
+ * call is made.  engine: 0 vqa_gemm, 1 vqa_gemm_x3, 2 vqa_gemm_bf16.  workspace_bytes: what the caller would pass (it only
+ * decides whether vqa_gemm_bf16 admits its 128 x 256 plan).  out[0..9] = BM, BN, tiles_m, tiles_n, nk (K-steps), splits,
+ * ks_per_split, order (0: tiles row-major, 1: column-major), persistent, wide; n_out >= 10. */
+int vqa_gemm_plan(int engine, int M, int N, int K, int transA, int transB, int64_t workspace_bytes, int32_t* out, int n_out);
 
 /* Tall bf16 GEMM with a short reduction (csrc/gemm_tall_bf16.hip): C[M][N] = act(A[M][K] . W[N][K]^T (+|*) rowgroup), bf16
  * result -- the v_conv forward of the bf16 path (models/model.py:173,187-193: M = B * positions, N = mid, K = image

@@ -113,12 +113,19 @@ def test_gemm_tall_bf16(Bn, P, K, N, op):
     assert float((C.cpu() != near).float().mean()) < 2e-3          # a bf16 rounding flips only where fp32 sums differ in the last bit
 
 
-@pytest.mark.parametrize("Bn,P,K,N", [(3, 200, 256, 256), (2, 676, 64, 1024), (5, 129, 96, 136)])
-def test_gemm_bf16_staged_bf16_output(Bn, P, K, N):
+@pytest.mark.parametrize("Bn,P,K,N", [(3, 200, 256, 256), (2, 676, 64, 1024), (5, 129, 96, 136), (3, 200, 1024, 256), (5, 129, 1088, 136),
+                                      (2, 676, 1024, 384)])
+def test_gemm_bf16_staged_bf16_output(Bn, P, K, N, knob):
     """bf16 result of 128 x 128 tiles: interior tiles store through the wave-private LDS scratch (16 bytes per lane), edge
     tiles keep the element-wise stores; row-group term (one / two groups per tile), bias, ReLU.  The bf16 result must be
-    the rounded fp32 result of the same GEMM, element for element."""
+    the rounded fp32 result of the same GEMM, element for element.  The planner gives shapes this small 64 x 64 tiles, which
+    have no staged epilogue: the shapes with 16 or more K-steps run under VQA_SPLIT_TARGET=1, which plans them 128 x 128 tiles
+    without split-K (asserted)."""
     ops = _ops()
+    if K >= 1024:
+        knob("VQA_SPLIT_TARGET", "1")
+        plan = ops.gemm_plan("vqa_gemm_bf16", Bn * P, N, K)
+        assert (plan["BM"], plan["BN"], plan["splits"], plan["wide"]) == (128, 128, 1, 0), plan
     g = torch.Generator().manual_seed(Bn * 100 + N)
     M = Bn * P
     A, W = rb(torch.randn(M, K, generator=g)), rb(torch.randn(N, K, generator=g))

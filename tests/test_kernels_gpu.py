@@ -52,6 +52,8 @@ def check(name, got, ref, tol):
                                    (70, 50, 45), (40, 33, 7), (200, 130, 1001)])   # K tails: K % 4 != 0, K < BK
 @pytest.mark.parametrize("transA,transB", [(False, True), (False, False), (True, True), (True, False)])
 def test_gemm_layouts(M, N, K, transA, transB):
+    """The padding between a row's length and its leading dimension holds NaN: a loader that lost its K-tail mask (or its
+    row / column bound) poisons the result."""
     ops = _ops()
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
     A = torch.randn(M, K, generator=g)
@@ -59,13 +61,13 @@ def test_gemm_layouts(M, N, K, transA, transB):
     ref = A.double() @ Bm.double()
     pad = lambda n: (n + 3) // 4 * 4
     if transA:   # stored [K][M]
-        As = torch.zeros(K, pad(M)); As[:, :M] = A.t(); lda = pad(M)
+        As = torch.full((K, pad(M)), float("nan")); As[:, :M] = A.t(); lda = pad(M)
     else:
-        As = torch.zeros(M, pad(K)); As[:, :K] = A; lda = pad(K)
+        As = torch.full((M, pad(K)), float("nan")); As[:, :K] = A; lda = pad(K)
     if transB:   # stored [N][K]
-        Bs = torch.zeros(N, pad(K)); Bs[:, :K] = Bm.t(); ldb = pad(K)
+        Bs = torch.full((N, pad(K)), float("nan")); Bs[:, :K] = Bm.t(); ldb = pad(K)
     else:
-        Bs = torch.zeros(K, pad(N)); Bs[:, :N] = Bm; ldb = pad(N)
+        Bs = torch.full((K, pad(N)), float("nan")); Bs[:, :N] = Bm; ldb = pad(N)
     Cd = torch.full((M, N + 3), 7.0, device=DEV)
     ops.gemm(As.to(DEV), Bs.to(DEV), Cd, M, N, K, transA=transA, transB=transB, lda=lda, ldb=ldb, ldc=N + 3)
     torch.cuda.synchronize()
@@ -863,6 +865,13 @@ def test_persistent_tiles_forced(persistent, knob):
     test_gemm_layouts(1030, 260, 3584, False, True)
     test_gemm_layouts(300, 200, 100, False, False)
     test_gemm_epilogue_bias_rowgroup_relu_accumulate()
+    # gemm_persistent_kernel exists for tiles above 64 x 64 only, and the planner gives the shapes above 64 x 64 tiles:
+    # VQA_SPLIT_TARGET=1 plans 128 x 128 tiles, unsplit, for any M, N >= 128 with 16 or more K-steps
+    knob("VQA_SPLIT_TARGET", "1")
+    for M, N, K, tA, tB in ((1030, 260, 3584, False, True), (200, 130, 1001, True, False)):
+        plan = _ops().gemm_plan("vqa_gemm", M, N, K, transA=tA, transB=tB)
+        assert (plan["BM"], plan["BN"], plan["splits"], plan["persistent"]) == (128, 128, 1, int(persistent)), plan
+        test_gemm_layouts(M, N, K, tA, tB)
 
 
 @pytest.mark.parametrize("big", ["0", "1", "2", "3"])
@@ -877,3 +886,11 @@ def test_tile_configurations_forced(big, knob):
     test_gemm_layouts(1030, 260, 3584, False, True)
     test_gemm_layouts(1030, 260, 3584, False, False)
     test_gemm_layouts(300, 200, 100, True, True)
+    # VQA_BIG_TILES=2 acts only on a plan that already has 128-row tiles and no split-K, which none of the shapes above has:
+    # VQA_SPLIT_TARGET=1 gives them that plan (M, N >= 128, 16 or more K-steps), and the 256 x 128 kernels run in every layout
+    knob("VQA_SPLIT_TARGET", "1")
+    for M, N, K in ((1030, 260, 3584), (200, 130, 1001)):
+        plan = _ops().gemm_plan("vqa_gemm", M, N, K)
+        assert (plan["BM"], plan["BN"], plan["splits"]) == (256 if big == "2" else 128, 128, 1), plan
+        for tA, tB in ((False, True), (False, False), (True, True), (True, False)):
+            test_gemm_layouts(M, N, K, tA, tB)
