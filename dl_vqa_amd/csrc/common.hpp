@@ -156,6 +156,12 @@ __device__ __forceinline__ PoolPick pool_pick(float z0, float z1, float z2, floa
   return {best > 0.f ? best : 0.f, best > 0.f ? (uint8_t)a : (uint8_t)4};
 }
 
+__device__ __forceinline__ uint32_t f2bf16_pair(float lo, float hi) {      // round to nearest even (v_cvt_pk_bf16_f32)
+  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+  const bf2 v = {(__bf16)lo, (__bf16)hi};
+  return __builtin_bit_cast(uint32_t, v);
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __device__ __forceinline__ float wave_sum(float v) {

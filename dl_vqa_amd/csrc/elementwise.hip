@@ -1,32 +1,10 @@
 // Memory-bound stages of the VQA hot path: dropout, L2-norm, embedding+tanh, LSTM cell, attention
-// score / softmax / weighted sum, soft-target cross entropy, reductions, Adam.
+// softmax / weighted sum, soft-target cross entropy, reductions, Adam.
 // All are HBM-bound streaming kernels: 16-byte per-lane accesses, wave64 shuffles for reductions.
 #include <hip/hip_fp16.h>
 #include "common.hpp"
 
 namespace vqa {
-
-__device__ __forceinline__ uint32_t f2bf16_pair(float lo, float hi) {      // round to nearest even (v_cvt_pk_bf16_f32)
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  const bf2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-// 4 consecutive elements of an fp32 or bf16 row, as floats
-template <bool XB>
-__device__ __forceinline__ float4 ld4(const void* row, int c) {
-  if (XB) {
-    const uint2 w = reinterpret_cast<const uint2*>(row)[c];
-    return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
-                       __uint_as_float(w.y & 0xffff0000u));
-  }
-  return reinterpret_cast<const float4*>(row)[c];
-}
-template <bool XB>
-__device__ __forceinline__ void st4(void* row, int c, float4 v) {
-  if (XB) reinterpret_cast<uint2*>(row)[c] = make_uint2(f2bf16_pair(v.x, v.y), f2bf16_pair(v.z, v.w));
-  else reinterpret_cast<float4*>(row)[c] = v;
-}
 
 // ------------------------------------------------------------------ dropout
 __global__ void dropout_kernel(const float* x, float* y, int64_t n, float p, float inv_keep, uint64_t seed) {
@@ -530,286 +508,6 @@ __global__ void lstm_cell_bwd_kernel(const float* gates, const float* c_in, cons
       dh[i] = 0.f;
     }
     dgates[g0] = di; dgates[g0 + H] = df; dgates[g0 + 2 * H] = dg; dgates[g0 + 3 * H] = dgo;
-  }
-}
-
-// ------------------------------------------------------------------ attention score (x_conv)
-// x = relu(v' (+|*) q') is xs [M][mid]; for do_option '|' x = relu(cat[v', tile(q')]) has 2*mid channels:
-// the v' half is xs, the q' half is relu(qcat[b][:]) replicated over positions (but with its own
-// per-position dropout mask, as nn.Dropout acts on the concatenated tensor).  xld = channels of x.
-// XB: xs holds bf16 (the bf16 path stores x = relu(v' (+|*) q') as bf16)
-template <int G, bool XB>
-__global__ void att_score_fwd_kernel(const void* xs, const float* wx, int wx_ld, const float* bx, float* score,
-                                     int64_t M, int P, int mid, float p, float inv_keep, uint64_t seed,
-                                     const float* qcat) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int nch = mid >> 2;
-  const int xld = qcat ? 2 * mid : mid;
-  for (int64_t m = wave; m < M; m += nwaves) {
-    const int64_t b = m / P;
-    const int pp = (int)(m - b * P);
-    const char* row = static_cast<const char*>(xs) + m * mid * (XB ? 2 : 4);
-    float acc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) acc[g] = 0.f;
-    for (int c = lane; c < nch; c += 64) {
-      float4 x = ld4<XB>(row, c);
-      if (p > 0.f) {
-        const uint64_t e = (uint64_t)m * xld + 4 * c;
-        { const float4 ds_ = drop_scale4(seed, e, p, inv_keep); x.x *= ds_.x; x.y *= ds_.y; x.z *= ds_.z; x.w *= ds_.w; }
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float4 w = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[c];
-        acc[g] += x.x * w.x + x.y * w.y + x.z * w.z + x.w * w.w;
-      }
-      if (qcat) {
-        float4 q = reinterpret_cast<const float4*>(qcat + b * mid)[c];
-        q.x = fmaxf(q.x, 0.f); q.y = fmaxf(q.y, 0.f); q.z = fmaxf(q.z, 0.f); q.w = fmaxf(q.w, 0.f);
-        if (p > 0.f) {
-          const uint64_t e = (uint64_t)m * xld + mid + 4 * c;
-          { const float4 ds_ = drop_scale4(seed, e, p, inv_keep); q.x *= ds_.x; q.y *= ds_.y; q.z *= ds_.z; q.w *= ds_.w; }
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const float4 w = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld + mid)[c];
-          acc[g] += q.x * w.x + q.y * w.y + q.z * w.z + q.w * w.w;
-        }
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float v = wave_sum(acc[g]);
-      if (lane == 0) score[(b * G + g) * P + pp] = v + bx[g];
-    }
-  }
-}
-
-// fp32 x without the concatenated half, mid a multiple of 256 up to 1024 (the reference's 1024): the general kernel above walks
-// a row in mid/256 DEPENDENT rounds of 16-byte loads with one row per wave in flight and re-reads the x_conv weights for every
-// row (3.9 TB/s).  Here a lane issues all IT loads of a row before it touches the first value, the next row's loads are issued
-// before the current row is reduced, and the weights live in registers.  Same per-lane operation order as the general kernel.
-template <int G, int IT>
-__global__ __launch_bounds__(256) void att_score_fwd_rows_kernel(const float* xs, const float* wx, int wx_ld, const float* bx,
-                                                                 float* score, int64_t M, int P, float p, float inv_keep,
-                                                                 uint64_t seed) {
-  constexpr int mid = 256 * IT;
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  float4 w[IT][G];
-#pragma unroll
-  for (int i = 0; i < IT; ++i)
-#pragma unroll
-    for (int g = 0; g < G; ++g) w[i][g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[lane + 64 * i];
-  float bias[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) bias[g] = bx[g];
-  float4 cur[IT], nxt[IT];
-  int64_t m = wave;
-  if (m < M) {
-#pragma unroll
-    for (int i = 0; i < IT; ++i) cur[i] = reinterpret_cast<const float4*>(xs + m * mid)[lane + 64 * i];
-  }
-  for (; m < M; m += nwaves) {
-    const int64_t mn = m + nwaves;
-    if (mn < M) {
-#pragma unroll
-      for (int i = 0; i < IT; ++i) nxt[i] = reinterpret_cast<const float4*>(xs + mn * mid)[lane + 64 * i];
-    }
-    float acc[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) acc[g] = 0.f;
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      float4 x = cur[i];
-      if (p > 0.f) {
-        const uint64_t e = (uint64_t)m * mid + 4 * (lane + 64 * i);
-        const float4 ds_ = drop_scale4(seed, e, p, inv_keep);
-        x.x *= ds_.x; x.y *= ds_.y; x.z *= ds_.z; x.w *= ds_.w;
-      }
-#pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] += x.x * w[i][g].x + x.y * w[i][g].y + x.z * w[i][g].z + x.w * w[i][g].w;
-    }
-    const int64_t b = m / P;
-    const int pp = (int)(m - b * P);
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float v = wave_sum(acc[g]);
-      if (lane == 0) score[(b * G + g) * P + pp] = v + bias[g];
-    }
-#pragma unroll
-    for (int i = 0; i < IT; ++i) cur[i] = nxt[i];
-  }
-}
-
-// The bf16 path's form of the above (x = relu(v' (+|*) q') stored as bf16, no concatenated half, mid <= 1024): the generic
-// kernel walked a row in four dependent rounds of 8-byte loads and re-read the x_conv weights for every row -- 2.3 TB/s.  Here
-// a lane owns 8 channels per round (16-byte loads), keeps its weights in registers for the whole kernel, and a wave has the
-// loads of TWO rows in flight before it touches the first value.
-template <int G>
-__global__ __launch_bounds__(256) void att_score_fwd_bf16_kernel(const uint16_t* xs, const float* wx, int wx_ld, const float* bx,
-                                                                 float* score, int64_t M, int P, int mid, float p, float inv_keep,
-                                                                 uint64_t seed) {
-  constexpr int IT = 2;                                   // rounds of 64 lanes x 8 channels: mid <= 1024
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int n8 = mid >> 3;
-  float w[IT][G][8];
-#pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int c8 = lane + 64 * i;
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) w[i][g][k] = c8 < n8 ? wx[(int64_t)g * wx_ld + 8 * c8 + k] : 0.f;
-  }
-  float bias[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) bias[g] = bx[g];
-  for (int64_t m0 = 2 * wave; m0 < M; m0 += 2 * nwaves) {
-    uint4 xr[2][IT];
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-      for (int i = 0; i < IT; ++i) {
-        const int c8 = lane + 64 * i;
-        xr[rr][i] = (m0 + rr < M && c8 < n8) ? *reinterpret_cast<const uint4*>(xs + (m0 + rr) * mid + 8 * c8) : make_uint4(0u, 0u, 0u, 0u);
-      }
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      const int64_t m = m0 + rr;
-      float acc[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] = 0.f;
-#pragma unroll
-      for (int i = 0; i < IT; ++i) {
-        const int c8 = lane + 64 * i;
-        const uint32_t u[4] = {xr[rr][i].x, xr[rr][i].y, xr[rr][i].z, xr[rr][i].w};
-        float x[8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x[2 * k] = __uint_as_float(u[k] << 16); x[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u); }
-        if (p > 0.f) {
-          const uint64_t e = (uint64_t)m * mid + 8 * c8;
-          const float4 s0 = drop_scale4(seed, e, p, inv_keep), s1 = drop_scale4(seed, e + 4, p, inv_keep);
-          x[0] *= s0.x; x[1] *= s0.y; x[2] *= s0.z; x[3] *= s0.w; x[4] *= s1.x; x[5] *= s1.y; x[6] *= s1.z; x[7] *= s1.w;
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) acc[g] += x[k] * w[i][g][k];
-      }
-      if (m < M) {
-        const int64_t b = m / P;
-        const int pp = (int)(m - b * P);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const float v = wave_sum(acc[g]);
-          if (lane == 0) score[(b * G + g) * P + pp] = v + bias[g];
-        }
-      }
-    }
-  }
-}
-
-// grid (B, RS); thread -> float4 column chunks; loops the rows of its split.
-// mode 0 '+': xs <- dz = (x>0) * mask * sum_g ds*wx            dq' part = sum_p dz
-// mode 1 '*': xs <- dv' = dz * q'[b]                             dq' part = sum_p dz * v'
-// mode 2 '|': xs <- dv' = dz (v' half);  q' half: dq' part = (q'>0) * sum_p mask_q * sum_g ds*wx[g][mid+n]
-// dwx_part[part][G][xld]: sum_p ds[g] * dropout(x) over the rows of the part (both halves for '|').
-template <int G, bool XB>
-__global__ void att_score_bwd_kernel(const float* dscore, const float* wx, int wx_ld, void* xs, float* dwx_part,
-                                     float* dq_part, int P, int mid, int RS, float p, float inv_keep, uint64_t seed,
-                                     int mode, const float* vprime, const float* qp) {
-  const int b = blockIdx.x, rs = blockIdx.y;
-  const int rows_per = (P + RS - 1) / RS;
-  const int p0 = rs * rows_per, p1 = min(P, p0 + rows_per);
-  const int nch = mid >> 2;
-  const int xld = mode == 2 ? 2 * mid : mid;
-  const int64_t part = (int64_t)b * RS + rs;
-  for (int c = threadIdx.x; c < nch; c += blockDim.x) {
-    float4 w[G], dw[G], w2[G], dw2[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      w[g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[c];
-      dw[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-      dw2[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-      w2[g] = mode == 2 ? reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld + mid)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mode != 0) qv = reinterpret_cast<const float4*>(qp + (int64_t)b * mid)[c];
-    const float4 rq = make_float4(fmaxf(qv.x, 0.f), fmaxf(qv.y, 0.f), fmaxf(qv.z, 0.f), fmaxf(qv.w, 0.f));
-    float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
-    // rows in batches of four: the four loads of x (and the batch's dscore values) are issued before the first of them is
-    // used -- xs is rewritten in place, so hipcc may not move a row's load above the previous row's store by itself, and one
-    // dependent load -> compute -> store chain per row left the kernel at 4 TB/s
-    for (int pb = p0; pb < p1; pb += 4) {
-      float4 xb[4];
-      float dsb[4][G];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int pp = pb + u < p1 ? pb + u : p1 - 1;
-        const int64_t m = (int64_t)b * P + pp;
-        xb[u] = ld4<XB>(static_cast<const char*>(xs) + m * mid * (XB ? 2 : 4), c);
-#pragma unroll
-        for (int g = 0; g < G; ++g) dsb[u][g] = dscore[((int64_t)b * G + g) * P + pp];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-      const int pp = pb + u;
-      if (pp >= p1) break;
-      const int64_t m = (int64_t)b * P + pp;
-      char* xrow = static_cast<char*>(xs) + m * mid * (XB ? 2 : 4);
-      const float4 x = xb[u];
-      float4 sc = make_float4(1.f, 1.f, 1.f, 1.f);
-      if (p > 0.f) {
-        const uint64_t e = (uint64_t)m * xld + 4 * c;
-        sc = drop_scale4(seed, e, p, inv_keep);
-      }
-      float ds[G];
-      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        ds[g] = dsb[u][g];
-        t.x += ds[g] * w[g].x; t.y += ds[g] * w[g].y; t.z += ds[g] * w[g].z; t.w += ds[g] * w[g].w;
-        dw[g].x += ds[g] * x.x * sc.x; dw[g].y += ds[g] * x.y * sc.y; dw[g].z += ds[g] * x.z * sc.z; dw[g].w += ds[g] * x.w * sc.w;
-      }
-      float4 d;
-      d.x = x.x > 0.f ? t.x * sc.x : 0.f; d.y = x.y > 0.f ? t.y * sc.y : 0.f;
-      d.z = x.z > 0.f ? t.z * sc.z : 0.f; d.w = x.w > 0.f ? t.w * sc.w : 0.f;
-      if (mode == 0) {
-        dq.x += d.x; dq.y += d.y; dq.z += d.z; dq.w += d.w;
-      } else if (mode == 1) {
-        const float4 vp = reinterpret_cast<const float4*>(vprime + m * mid)[c];
-        dq.x += d.x * vp.x; dq.y += d.y * vp.y; dq.z += d.z * vp.z; dq.w += d.w * vp.w;
-        d.x *= qv.x; d.y *= qv.y; d.z *= qv.z; d.w *= qv.w;
-      } else {
-        float4 s2 = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (p > 0.f) {
-          const uint64_t e = (uint64_t)m * xld + mid + 4 * c;
-          s2 = drop_scale4(seed, e, p, inv_keep);
-        }
-        float4 t2 = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          t2.x += ds[g] * w2[g].x; t2.y += ds[g] * w2[g].y; t2.z += ds[g] * w2[g].z; t2.w += ds[g] * w2[g].w;
-          dw2[g].x += ds[g] * rq.x * s2.x; dw2[g].y += ds[g] * rq.y * s2.y; dw2[g].z += ds[g] * rq.z * s2.z; dw2[g].w += ds[g] * rq.w * s2.w;
-        }
-        dq.x += qv.x > 0.f ? t2.x * s2.x : 0.f; dq.y += qv.y > 0.f ? t2.y * s2.y : 0.f;
-        dq.z += qv.z > 0.f ? t2.z * s2.z : 0.f; dq.w += qv.w > 0.f ? t2.w * s2.w : 0.f;
-      }
-      st4<XB>(xrow, c, d);
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      reinterpret_cast<float4*>(dwx_part + (part * G + g) * xld)[c] = dw[g];
-      if (mode == 2) reinterpret_cast<float4*>(dwx_part + (part * G + g) * xld + mid)[c] = dw2[g];
-    }
-    reinterpret_cast<float4*>(dq_part + part * mid)[c] = dq;
   }
 }
 
@@ -1520,68 +1218,6 @@ int vqa_lstm_cell_bwd(const float* gates, const float* c_in, const float* c_out,
   hipLaunchKernelGGL(lstm_cell_bwd_kernel, dim3(grid_for((int64_t)B * H, 256)), dim3(256), 0, STREAM, gates, c_in,
                      c_out, q_len, t, dh, dc, dgates, B, H);
   return check_hip(hipGetLastError(), "lstm_cell_bwd launch");
-}
-
-int vqa_att_score_fwd(const void* xs, int xs_is_bf16, const float* wx, int wx_ld, const float* bx, float* score, int B,
-                      int P, int mid, int G, float p, uint64_t seed, const float* qcat, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
-  VQA_REQUIRE(xs && wx && bx && score && mid % 4 == 0 && wx_ld % 4 == 0 && wx_ld >= (qcat ? 2 * mid : mid),
-              "vqa_att_score_fwd: bad args");
-  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
-  const int64_t M = (int64_t)B * P;
-  const bool quads = (reinterpret_cast<uintptr_t>(xs) & 15) == 0;
-  const float ik = keep_scale(p);
-  if (xs_is_bf16 && !qcat && mid % 8 == 0 && mid <= 1024 && quads) {
-    with_int14(G, [&](auto g) {
-      hipLaunchKernelGGL((att_score_fwd_bf16_kernel<decltype(g)::value>), dim3(grid_for(M, 8)), dim3(256), 0, STREAM,
-                         static_cast<const uint16_t*>(xs), wx, wx_ld, bx, score, M, P, mid, p, ik, seed);
-      return 0;
-    });
-  } else if (!xs_is_bf16 && !qcat && G <= 2 && mid % 256 == 0 && mid <= 1024 && quads) {
-    with_flag(G == 2, [&](auto two) {               // the rows kernel exists for one and two glimpses only
-      return with_int14(mid / 256, [&](auto it) {
-        hipLaunchKernelGGL((att_score_fwd_rows_kernel<decltype(two)::value ? 2 : 1, decltype(it)::value>), dim3(grid_for(M, 4)),
-                           dim3(256), 0, STREAM, static_cast<const float*>(xs), wx, wx_ld, bx, score, M, P, p, ik, seed);
-        return 0;
-      });
-    });
-  } else {
-    with_int14(G, [&](auto g) {
-      return with_flag(xs_is_bf16 != 0, [&](auto bf16) {
-        hipLaunchKernelGGL((att_score_fwd_kernel<decltype(g)::value, decltype(bf16)::value>), dim3(grid_for(M, 4)), dim3(256), 0,
-                           STREAM, xs, wx, wx_ld, bx, score, M, P, mid, p, ik, seed, qcat);
-        return 0;
-      });
-    });
-  }
-  return check_hip(hipGetLastError(), "att_score_fwd launch");
-}
-
-int vqa_att_row_splits(int P) {
-  int rs = (P + 127) / 128;
-  return rs < 1 ? 1 : (rs > 8 ? 8 : rs);
-}
-
-int vqa_att_score_bwd(const float* dscore, const float* wx, int wx_ld, void* xs_inout, int xs_is_bf16, float* dwx_part,
-                      float* dq_part, int B, int P, int mid, int G, float p, uint64_t seed, int mode,
-                      const float* vprime, const float* qp, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
-  VQA_REQUIRE(dscore && wx && xs_inout && dwx_part && dq_part && mid % 4 == 0 && wx_ld % 4 == 0,
-              "vqa_att_score_bwd: bad args");
-  VQA_REQUIRE(mode >= 0 && mode <= 2 && (mode != 1 || (vprime && qp)) && (mode != 2 || qp) &&
-                  wx_ld >= (mode == 2 ? 2 * mid : mid),
-              "vqa_att_score_bwd: mode %d needs its operands (vprime/qp) and a matching wx_ld", mode);
-  const int RS = vqa_att_row_splits(P);
-  VQA_REQUIRE(G >= 1 && G <= 4, "glimpses=%d unsupported (1..4)", G);
-  return with_int14(G, [&](auto g) {
-    return with_flag(xs_is_bf16 != 0, [&](auto bf16) {
-      hipLaunchKernelGGL((att_score_bwd_kernel<decltype(g)::value, decltype(bf16)::value>), dim3(B, RS), dim3(256), 0, STREAM,
-                         dscore, wx, wx_ld, xs_inout, dwx_part, dq_part, P, mid, RS, p, keep_scale(p), seed, mode, vprime, qp);
-      return check_hip(hipGetLastError(), "att_score_bwd launch");
-    });
-  });
 }
 
 // vqa_att_apply_fwd and vqa_att_apply_bwd take the checks of their gather forms: what used to reach a launch with undefined

@@ -486,7 +486,7 @@ class Engine:
 
     # ------------------------------------------------------------------ many questions per image (inference)
     # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder, the question encoder, q_lin and the
-    # classifier are the forward's own stages; the attention stage runs on ONE v' per image (csrc/att_grouped.hip).
+    # classifier are the forward's own stages; the attention stage runs on ONE v' per image (csrc/att_score.hip).
     @_device_current("v")
     def encode_images(self, P: Dict[str, Tensor], v: Tensor, with_vprime: bool = True):
         """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid] or None (with_vprime=False), (gh, gw))."""
@@ -557,7 +557,7 @@ class Engine:
     # ------------------------------------------------------------------ training through grouped image features
     # fp32 / fp32x3.  Question b looks at image img[b]; order / offsets group the questions by image.  The question encoder,
     # q_lin and the classifier are the forward's own stages on B questions; the attention stage runs on one v' per image
-    # (csrc/att_grouped.hip) and its backward sums the image-side gradients over the questions of an image.  One schedule
+    # (csrc/att_score.hip) and its backward sums the image-side gradients over the questions of an image.  One schedule
     # (_forward_grouped / backward_grouped) with two image sides:
     #
     # forward_shared: v holds every image ONCE and the image encoder runs on those N images, as a part of the graph.

@@ -273,7 +273,11 @@ int vqa_att_score_fwd(const void* xs, int xs_is_bf16 /* the bf16 path stores x a
  *   xs      <- gradient w.r.t. v' (what the v_conv dW / dX GEMMs consume)
  *   dq_part[b*RS+rs][mid]      partial sums of the gradient w.r.t. q' (RS = vqa_att_row_splits(P))
  *   dwx_part[b*RS+rs][G][xld]  partial sums of the x_conv weight gradient, xld = mid (2*mid for '|')
- * '*' needs vprime = the raw v' (aux output of the forward GEMM) and qp = q'; '|' needs qp. */
+ * '*' needs vprime = the raw v' (aux output of the forward GEMM) and qp = q'; '|' needs qp.
+ * Both entry points return VQA_ERR_INVALID, before any HIP call, for: G outside 1..4, a null pointer (those the mode
+ * needs included), B < 0, P < 1, mid < 4 or not a multiple of 4, wx_ld not a multiple of 4 or below the channels of x,
+ * p outside [0, 1), a mode outside 0..2, and a wx / qcat / qp / vprime / dwx_part / dq_part that is not 16-byte aligned.
+ * B = 0 returns VQA_OK without a launch.  The alignment of xs selects the forward's kernel and is no error. */
 int vqa_att_row_splits(int P);
 int vqa_att_score_bwd(const float* dscore, const float* wx, int wx_ld, void* xs_inout, int xs_is_bf16, float* dwx_part,
                       float* dq_part, int B, int P, int mid, int G, float p, uint64_t seed, int mode,

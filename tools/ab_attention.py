@@ -107,19 +107,30 @@ def score_cases(out, gen):
                 dwx_part, dq_part, _ = ops.att_score_bwd(dscore, wx, xs, B, P, p, 12, mode=mode, vprime=vprime, qp=qp)
                 tag = f"score bwd {dt} mode{mode} mid{mid} G{G} p{p}"
                 out[f"{tag} xs"], out[f"{tag} dwx_part"], out[f"{tag} dq_part"] = xs, dwx_part, dq_part
+    # two row splits with more than 256 column chunks (a second trip of the chunk walk); three splits, four glimpses
+    for B, P, mid, G in ((2, 130, 1028, 1), (1, 257, 256, 4)):
+        for mode in (0, 1, 2):
+            xld = 2 * mid if mode == 2 else mid
+            wx, vprime, qp, dscore = randn(gen, G, xld), randn(gen, B * P, mid), randn(gen, B, mid), randn(gen, B, G, P)
+            for p in (0.0, 0.3):
+                xs = randn(gen, B * P, mid).relu_()
+                dwx_part, dq_part, _ = ops.att_score_bwd(dscore, wx, xs, B, P, p, 12, mode=mode, vprime=vprime, qp=qp)
+                tag = f"score bwd fp32 B{B} P{P} mode{mode} mid{mid} G{G} p{p}"
+                out[f"{tag} xs"], out[f"{tag} dwx_part"], out[f"{tag} dq_part"] = xs, dwx_part, dq_part
 
 
 def grouped_cases(out, gen):
-    N, B, P, G, M = 3, 7, 70, 2, 4
+    N, B, P, M = 3, 7, 70, 4
     img, order, offsets = grouping(gen, B, N + 1)                   # the fourth image is the unasked one
     N += 1
     qrow = torch.randint(0, M, (B,), generator=gen).to(torch.int32).to(DEV)
-    for mid in (256, 20):
+    # mid 256: the register kernels ('+', '*'); 20, 1280 (two positions per wave) and 2052 (one): the general kernels
+    for mid, G in ((256, 2), (20, 2), (256, 1), (20, 1), (256, 3), (256, 4), (20, 4), (1280, 2), (2052, 1)):
         for mode in (0, 1, 2):
             xld = 2 * mid if mode == 2 else mid
             vprime, qp, qtab = randn(gen, N * P, mid), randn(gen, B, mid), randn(gen, M, mid)
             wx, bx, dscore = randn(gen, G, xld), randn(gen, G), randn(gen, B, G, P)
-            tag = f"grouped mid{mid} mode{mode}"
+            tag = f"grouped mid{mid} mode{mode}" if G == 2 else f"grouped mid{mid} G{G} mode{mode}"
             out[f"{tag} fwd"] = ops.att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N, B, P, mode)
             out[f"{tag} pairs fwd"] = ops.att_score_grouped_pairs_fwd(vprime, qtab, qrow, wx, bx, order, offsets, N, B, P, mode)
             for p in (0.0, 0.3):
@@ -189,6 +200,7 @@ def time_entry_points():
     xs, wx, bx = randn(gen, B * P, mid).relu_(), randn(gen, G, mid), randn(gen, G)
     xs16 = xs.to(torch.bfloat16)
     dv_in, norm = randn(gen, B * P, C), randn(gen, B * P).abs_() + 0.5
+    vprime, qp = randn(gen, N * P, mid), randn(gen, B, mid)         # the grouped score forms: 32 images x 8 questions
     runs = {
         "att_apply_fwd": lambda: ops.att_apply_fwd(score, vn, comb, G * C),
         "att_apply_bwd (no dvn)": lambda: ops.att_apply_bwd(dout, G * C, probs, vn, rowsum=rowsum, want_dvn=False),
@@ -197,6 +209,8 @@ def time_entry_points():
         "att_score_fwd fp32": lambda: ops.att_score_fwd(xs, wx, bx, B, P, p, 1),
         "att_score_fwd bf16": lambda: ops.att_score_fwd(xs16, wx, bx, B, P, p, 1),
         "att_score_bwd fp32": lambda: ops.att_score_bwd(probs, wx, xs, B, P, p, 1),
+        "att_score_grouped_drop_fwd": lambda: ops.att_score_grouped_drop_fwd(vprime, qp, wx, bx, order, offsets, N, B, P, 0, p, 1),
+        "att_score_grouped_bwd": lambda: ops.att_score_grouped_bwd(probs, vprime, qp, wx, order, offsets, N, B, P, 0, p, 1),
         "l2norm_bwd_joined": lambda: ops.l2norm_bwd_joined(dout, G * C, probs, dv_in, p, 2, vn, norm, 0.0, 3),
     }
     print(f"library {_lib.LIB_PATH}")
