@@ -124,6 +124,7 @@ PROTOTYPES = {
                             f32p, i64, i32, i32, i32, i32, f32p, f32p, i64, i32, vp]),
     "vqa_gemm_plan": (i32, [i32, i32, i32, i32, i32, i32, i64, C.POINTER(i32), i32]),
     "vqa_gemm_tall_bf16_supported": (i32, [i32, i32, i32, i32, i32]),
+    "vqa_gemm_tall_bf16_plan": (i32, [i32, i32, i32, C.POINTER(i32), i32]),
     "vqa_gemm_tall_bf16": (i32, [vp, i64, vp, i64, vp, i64, i32, i32, i32, f32p, i64, i32, i32, i32, i32, vp]),
     "vqa_conv_pack_weights_bf16": (i32, [f32p, vp, vp, i32, i32, i32, vp]),
     "vqa_conv3x3_relu_pool_fwd_bf16": (i32, [vp, vp, f32p, vp, i32, u8p, i32, i32, i32, i32, i32, i32, i32, vp]),

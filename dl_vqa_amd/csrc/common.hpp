@@ -86,6 +86,7 @@ struct Knobs {
   int wgrad_192;          // VQA_WGRAD_192 0/1
   int wgrad_384;          // VQA_WGRAD_384 0/1
   int conv_chunk;         // VQA_CONV_CHUNK: images per conv launch (tests)
+  int tall_bm;            // VQA_TALL_BM: 128 = the tall bf16 GEMM on 128 x 128 tiles; anything else: 256 x 128
 };
 const Knobs& knobs();
 

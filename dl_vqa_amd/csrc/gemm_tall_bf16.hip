@@ -269,6 +269,21 @@ int vqa_gemm_tall_bf16_supported(int M, int N, int K, int rg_div, int has_rowgro
   return 1;
 }
 
+/* The launch geometry of vqa_gemm_tall_bf16 for a shape under the VQA_TALL_BM knob in force, as the launcher computes it (it
+ * calls this); no HIP call is made.  out[0..4] = tile height (256, or 128 under VQA_TALL_BM=128), tiles_m, tiles_n, grid
+ * (workgroups: min(tiles, 65536 / tile height)), nk (k-stages of 64); n_out >= 5. */
+int vqa_gemm_tall_bf16_plan(int M, int N, int K, int32_t* out, int n_out) {
+  VQA_REQUIRE(M > 0 && N > 0 && K > 0 && N % TG_BN == 0 && K % TG_BK == 0 && out && n_out >= 5,
+              "vqa_gemm_tall_bf16_plan: bad args (M=%d N=%d K=%d n_out=%d)", M, N, K, n_out);
+  const int bm = knobs().tall_bm == 128 ? 128 : 256;
+  const int tiles_m = (M + bm - 1) / bm, tiles_n = N / TG_BN;
+  const int64_t tiles = (int64_t)tiles_m * tiles_n;
+  const int slots = 65536 / bm;                  // 1024 waves' worth of rows: one 8-wave or two 4-wave workgroups per CU
+  const int32_t v[5] = {bm, tiles_m, tiles_n, (int32_t)(tiles < slots ? tiles : slots), K / TG_BK};
+  for (int i = 0; i < 5; ++i) out[i] = v[i];
+  return VQA_OK;
+}
+
 int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
                        const float* rowgroup, int64_t rg_ld, int rg_div, int rg_op, int relu, int tag, vqa_stream_t stream) {
   VQA_REQUIRE(A && W && C, "vqa_gemm_tall_bf16: null operand");
@@ -278,6 +293,9 @@ int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, v
               (long long)ldw, (long long)ldc);
   VQA_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(C) & 15) == 0, "vqa_gemm_tall_bf16: operands must be 16-byte aligned");
+  // the row-group table is read 16 bytes (four columns) at a time
+  VQA_REQUIRE(!rowgroup || (rg_ld >= N && rg_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(rowgroup) & 15) == 0),
+              "vqa_gemm_tall_bf16: rowgroup must be 16-byte aligned with rg_ld >= N, a multiple of 4 (rg_ld=%lld)", (long long)rg_ld);
   TgParams P{};
   P.A = static_cast<const char*>(A); P.A_end = P.A + (int64_t)M * lda * 2; P.lda = lda;
   P.W = static_cast<const char*>(W); P.ldw = ldw;
@@ -285,7 +303,9 @@ int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, v
   P.rg = rowgroup; P.rg_ld = rg_ld; P.rg_div = rg_div > 0 ? rg_div : 1; P.rg_op = rg_op; P.relu = relu;
   P.rg_groups = (M + P.rg_div - 1) / P.rg_div;
   P.M = M; P.N = N; P.K = K;
-  P.tiles_n = N / TG_BN; P.nk = K / TG_BK;
+  int32_t plan[5];                                       // tile height, tiles_m, tiles_n, grid, nk
+  if (int rc = vqa_gemm_tall_bf16_plan(M, N, K, plan, 5)) return rc;
+  P.tiles_m = plan[1]; P.tiles_n = plan[2]; P.nk = plan[4];
   {
     const char* e = getenv("VQA_TALL_DBG");
     P.dbg = e ? atoi(e) : 0;
@@ -295,12 +315,9 @@ int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, v
   ProfScope prof(VQA_K_GEMM, s);
   // 256 x 128 tiles, one workgroup of eight waves per CU (1.68 ms at 1.49 M x 1024 x 256); VQA_TALL_BM=128: 128 x 128 tiles on two
   // workgroups of four waves per CU (1.82 ms: the two do not hide each other's phases, and W is fetched twice as often)
-  static const int bm256 = [] { const char* e = getenv("VQA_TALL_BM"); return e && atoi(e) == 128 ? 0 : 1; }();
-  return with_flag(bm256 != 0, [&](auto tall) {
+  return with_flag(plan[0] == 256, [&](auto tall) {
     constexpr int WM = decltype(tall)::value ? 4 : 2;      // a workgroup: 64 * WM rows, 128 * WM threads, 1024 / WM of them resident
-    P.tiles_m = (M + 64 * WM - 1) / (64 * WM);
-    const int tiles = P.tiles_m * P.tiles_n, slots = 1024 / WM;
-    return launch_kernel(gemm_tall_bf16_kernel<WM>, {"attr(gemm_tall_bf16)", "gemm_tall_bf16 launch"}, dim3(tiles < slots ? tiles : slots),
+    return launch_kernel(gemm_tall_bf16_kernel<WM>, {"attr(gemm_tall_bf16)", "gemm_tall_bf16 launch"}, dim3(plan[3]),
                          128 * WM, TgCfg<WM>::LDS, s, P);
   });
 }

@@ -98,6 +98,7 @@ static void read_knobs_locked() {
   g_knobs.wgrad_192 = env_int("VQA_WGRAD_192");
   g_knobs.wgrad_384 = env_int("VQA_WGRAD_384");
   g_knobs.conv_chunk = env_int("VQA_CONV_CHUNK");
+  g_knobs.tall_bm = env_int("VQA_TALL_BM");
   g_knobs_read = true;
 }
 const Knobs& knobs() {

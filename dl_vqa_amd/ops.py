@@ -803,6 +803,18 @@ def gemm_tall_bf16_supported(M: int, N: int, K: int, rg_div: int = 0, has_rowgro
     return bool(_lib.load().vqa_gemm_tall_bf16_supported(M, N, K, rg_div, int(has_rowgroup)))
 
 
+GEMM_TALL_PLAN_FIELDS = ("BM", "tiles_m", "tiles_n", "grid", "nk")
+
+
+def gemm_tall_bf16_plan(M: int, N: int, K: int) -> dict:
+    """The launch geometry of vqa_gemm_tall_bf16 for this shape under the VQA_TALL_BM knob in force, from the query its launcher
+    calls (vqa_gemm_tall_bf16_plan); makes no HIP call.  grid: workgroups; workgroup w walks tiles w, w + grid, ..."""
+    import ctypes
+    out = (ctypes.c_int32 * len(GEMM_TALL_PLAN_FIELDS))()
+    call("vqa_gemm_tall_bf16_plan", M, N, K, out, len(out))
+    return dict(zip(GEMM_TALL_PLAN_FIELDS, out))
+
+
 def gemm_tall_bf16(A: torch.Tensor, W: torch.Tensor, C: torch.Tensor, M: int, N: int, K: int, *, rowgroup=None, rg_div=1,
                    rg_op=0, relu=False, tag=0) -> torch.Tensor:
     """C [M,N] bf16 = act(A [M,K] . W [N,K]^T (+|*) rowgroup[row // rg_div]) on persistent 256 x 128 tiles (short K)."""

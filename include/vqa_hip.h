@@ -33,8 +33,8 @@ extern "C" {
  * version 8 that way, vqa_softmax_topk after them, and the two entry points of cached question features
  * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that, then image preprocessing (vqa_preprocess_supported,
  * vqa_preprocess_images), then the two entry points of training on cached image features (vqa_gather_rows_drop,
- * vqa_att_apply_gather_dscore), then the plan query vqa_gemm_plan -- a caller built against the earlier version-8 header finds every prototype it knows
- * unchanged. */
+ * vqa_att_apply_gather_dscore), then the plan query vqa_gemm_plan, then the tall GEMM's own query vqa_gemm_tall_bf16_plan -- a caller
+ * built against the earlier version-8 header finds every prototype it knows unchanged. */
 #define VQA_ABI_VERSION 8
 
 #define VQA_OK 0
@@ -513,9 +513,16 @@ int vqa_gemm_plan(int engine, int M, int N, int K, int transA, int transB, int64
 
 /* Tall bf16 GEMM with a short reduction (csrc/gemm_tall_bf16.hip): C[M][N] = act(A[M][K] . W[N][K]^T (+|*) rowgroup), bf16
  * result -- the v_conv forward of the bf16 path (models/model.py:173,187-193: M = B * positions, N = mid, K = image
- * features).  Persistent 256 x 128 tiles, LDS-DMA staging across tile boundaries, 16-byte stores.  Operands as
- * vqa_gemm_bf16 with transA = 0, transB = 1; rowgroup (optional) [M / rg_div][N] fp32, rg_op 0 = add, 1 = multiply. */
+ * features).  Persistent 256 x 128 tiles (128 x 128 under VQA_TALL_BM=128, a knob that vqa_reload_knobs re-reads), stages
+ * prefetched through registers across tile boundaries, 16-byte stores.  Operands as vqa_gemm_bf16 with transA = 0,
+ * transB = 1; rowgroup (optional) [ceil(M / rg_div)][N] fp32, rg_op 0 = add, 1 = multiply.  The row-group table is read 16
+ * bytes at a time: with a rowgroup, rg_ld >= N, rg_ld % 4 == 0 and a 16-byte aligned rowgroup pointer are required
+ * (VQA_ERR_INVALID otherwise).
+ * vqa_gemm_tall_bf16_plan: the launch geometry for a shape (N % 128 == 0, K % 64 == 0) under the knob in force, as the launcher
+ * computes it (it calls this query); no HIP call is made.  out[0..4] = tile height, tiles_m, tiles_n, grid (workgroups), nk
+ * (k-stages of 64); n_out >= 5. */
 int vqa_gemm_tall_bf16_supported(int M, int N, int K, int rg_div, int has_rowgroup);
+int vqa_gemm_tall_bf16_plan(int M, int N, int K, int32_t* out, int n_out);
 int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
                        const float* rowgroup, int64_t rg_ld, int rg_div, int rg_op, int relu, int tag, vqa_stream_t stream);
 

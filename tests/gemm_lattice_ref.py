@@ -1,5 +1,6 @@
-"""Exact-arithmetic operands, a float64 closed-form reference and the case table for vqa_gemm, vqa_gemm_x3 and vqa_gemm_bf16.
-No GPU; the only use of the HIP library is by tests/test_gemm_lattice_ref_cpu.py, which asks it for each case's plan.
+"""Exact-arithmetic operands, a float64 closed-form reference and the case table for vqa_gemm, vqa_gemm_x3, vqa_gemm_bf16 and
+vqa_gemm_tall_bf16.  No GPU; the only use of the HIP library is by tests/test_gemm_lattice_ref_cpu.py, which asks it for each
+case's plan.
 
 Operands live on a dyadic lattice of bf16 values (A: integers in [-4, 4], B: multiples of 0.5 in [-2, 2] with about a third
 zero, biases and row-group terms: multiples of 0.5 in [-2, 2], C0 of `accumulate`: integers in [-8, 8]).  assert_exact bounds
@@ -26,7 +27,7 @@ from collections import namedtuple
 
 import torch
 
-F32, X3, BF16 = "vqa_gemm", "vqa_gemm_x3", "vqa_gemm_bf16"
+F32, X3, BF16, TALL = "vqa_gemm", "vqa_gemm_x3", "vqa_gemm_bf16", "vqa_gemm_tall_bf16"
 LIMIT = float(2 ** 21)           # with unit 0.25: 23 bits
 LIMIT_X3 = float(2 ** 24)        # plane lattices: unit 1
 LEAD, TAIL, GUARD_ROWS = 16, 64, 2
@@ -35,9 +36,10 @@ NAN = float("nan")
 # rg_div 0: no row-group term.  nbias: 0, 1 or 2 bias vectors.
 Epi = namedtuple("Epi", "rg_div rg_op nbias relu accumulate aux", defaults=(0, 0, 0, False, False, False))
 # knobs: ((name, value), ...) of VQA_* variables; plan: the fields of ops.gemm_plan the case is listed for;
-# c_bf16: bf16 result; ldc: None = N + 3; c_off: elements added to C's aligned start; lattice: see operands()
-Case = namedtuple("Case", "group engine M N K transA transB knobs epi c_bf16 plan lattice ldc c_off",
-                  defaults=(False, True, (), Epi(), False, None, "std", None, 0))
+# c_bf16: bf16 result; ldc: None = N + 3; c_off: elements added to C's aligned start; lattice: see operands();
+# why: the mechanism a case of the tall engine is there for (tall_cases)
+Case = namedtuple("Case", "group engine M N K transA transB knobs epi c_bf16 plan lattice ldc c_off why",
+                  defaults=(False, True, (), Epi(), False, None, "std", None, 0, ""))
 LAYOUTS = [(False, True), (False, False), (True, True), (True, False)]
 
 
@@ -94,15 +96,16 @@ def product(lattice, M, N, K):
 
 
 def extras(c):
-    """bias1, bias2 [N], rowgroup [M / rg_div][N], C0 [M][N] of a case (None where the case has none)"""
+    """bias1, bias2 [N], rowgroup [ceil(M / rg_div)][N], C0 [M][N] of a case (None where the case has none); only the tall
+    engine's cases have a partial last group"""
     e = c.epi
     g = torch.Generator().manual_seed(c.M * 31 + c.N * 7 + e.rg_div)
     b1 = _half_steps(g, -2, 2, (c.N,)) if e.nbias >= 1 else None
     b2 = _half_steps(g, -2, 2, (c.N,)) if e.nbias >= 2 else None
     rg = None
     if e.rg_div:
-        assert c.M % e.rg_div == 0, "M is a multiple of rg_div"
-        rg = _half_steps(g, -2, 2, (c.M // e.rg_div, c.N), nonzero=e.rg_op == 1)
+        assert c.M % e.rg_div == 0 or c.engine == TALL, "M is a multiple of rg_div"
+        rg = _half_steps(g, -2, 2, (-(-c.M // e.rg_div), c.N), nonzero=e.rg_op == 1)
     c0 = torch.randint(-8, 9, (c.M, c.N), generator=g).double() if e.accumulate else None
     return b1, b2, rg, c0
 
@@ -198,7 +201,7 @@ def bf16_stats(t):
 
 # ------------------------------------------------------------------------------------------------ poisoned storage
 def quantum(c):
-    return 8 if c.engine == BF16 else 4
+    return 8 if c.engine in (BF16, TALL) else 4
 
 
 def roundup(n, q):
@@ -230,6 +233,8 @@ def outside(flat, rows, cols, ld, lead=LEAD):
 
 def leading_dims(c):
     """(lda, ldb, ldc, rg_ld): every one longer than the row it holds"""
+    if c.engine == TALL:                                     # multiples of 8 / 8 / 8 / 4, as the entry point asks
+        return c.K + 8, c.K + 16, c.N + 8, c.N + 8
     q = quantum(c)
     lda = roundup(c.M if c.transA else c.K, q) + q
     ldb = roundup(c.K if c.transB else c.N, q) + q
@@ -390,6 +395,79 @@ def x3_cases():
             out.append(Case("x3walk", X3, 3254, 2042, 40, tA, tB, _pers(p) if p == 0 else (), Epi(nbias=1),
                             plan=dict(BM=192, BN=128, tiles_m=17, tiles_n=16, splits=1, persistent=p)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the tall bf16 engine
+TALL128 = (("VQA_TALL_BM", "128"),)
+
+
+def tall_cases():
+    """vqa_gemm_tall_bf16 (csrc/gemm_tall_bf16.hip) on the std16 lattice, A [M][K] . W [N][K]^T, bf16 C.  `plan` holds the fields
+    of ops.gemm_tall_bf16_plan the case is listed for, `why` names its mechanism (tests/test_gemm_lattice_ref_cpu.py asserts
+    it from the plan).  256-row tiles run on min(tiles, 256) workgroups, 128-row tiles (VQA_TALL_BM=128) on min(tiles, 512);
+    workgroup w walks tiles w, w + grid, ... and prefetches across the seams; the row-group table of a tile is loaded at
+    k-stage nk - 3 and stored at nk - 2, so K = 192 (nk = 3) is the minimum lead."""
+    def case(why, M, N, K, rg_div=0, rg_op=0, relu=True, knobs=(), **plan):
+        return Case("tall", TALL, M, N, K, False, True, knobs, Epi(rg_div, rg_op, 0, relu), True, dict(plan, nk=K // 64), "std16",
+                    why=why)
+    one = dict(BM=256, tiles_m=8, tiles_n=8, grid=64)
+    seam = dict(tiles_m=34, tiles_n=8, grid=256)
+    return [
+        # one tile per workgroup
+        case("nk1", 2048, 1024, 64, **one),
+        case("nk1", 2048, 1024, 64, relu=False, **one),
+        case("nk2", 2048, 1024, 128, **one),
+        case("group-per-tile", 2048, 1024, 192, 256, 0, **one),
+        case("one-group", 2048, 1024, 192, 2048, 1, relu=False, **one),
+        # 272 tiles on 256 workgroups: 16 take a second tile, whose table is loaded in its first stage
+        case("seam", 8700, 1024, 192, 300, 1, BM=256, **seam),
+        # the training shape class: 13 images of 26 x 26 positions
+        case("train", 8788, 1024, 256, 676, 0, relu=False, BM=256, tiles_m=35, tiles_n=8, grid=256),
+        case("train", 8788, 1024, 256, 676, 0, BM=256, tiles_m=35, tiles_n=8, grid=256),
+        # 15 images of 54 x 54 positions
+        case("three-tiles", 43740, 384, 512, 2916, 1, BM=256, tiles_m=171, tiles_n=3, grid=256),
+        case("odd-grid", 17000, 128, 64, relu=False, BM=256, tiles_m=67, tiles_n=1, grid=67),
+        case("odd-grid", 17000, 128, 192, 1000, 0, BM=256, tiles_m=67, tiles_n=1, grid=67),
+        case("partial-group", 8700, 1024, 256, 512, 0, BM=256, **seam),
+        case("long-k", 2048, 1024, 1024, 1024, 0, relu=False, **one),
+        # 128-row tiles
+        case("seam", 8700, 1024, 192, 300, 1, knobs=TALL128, BM=128, tiles_m=68, tiles_n=8, grid=512),
+        case("odd-grid", 17000, 128, 192, 1000, 0, knobs=TALL128, BM=128, tiles_m=133, tiles_n=1, grid=133),
+        case("nk1", 2048, 1024, 64, knobs=TALL128, BM=128, tiles_m=16, tiles_n=8, grid=128),
+    ]
+
+
+def tall_cases_both_heights():
+    """tall_cases(), and every 256-row case that is not already listed under VQA_TALL_BM=128 once more on 128-row tiles (the
+    geometry restated here: 512 slots); the GPU file runs these, so every case is judged under both tile heights"""
+    listed = tall_cases()
+    have = {(c.M, c.N, c.K, c.epi) for c in listed if c.knobs}
+    out = list(listed)
+    for c in listed:
+        if not c.knobs and (c.M, c.N, c.K, c.epi) not in have:
+            tm, tn = -(-c.M // 128), c.N // 128
+            out.append(c._replace(knobs=TALL128, plan=dict(BM=128, tiles_m=tm, tiles_n=tn, grid=min(tm * tn, 512), nk=c.K // 64)))
+    return out
+
+
+def tall_wrong_forms(c):
+    """What four plausible bugs of the tall engine would compute for a case, in float64 before the bf16 rounding (the last one:
+    after it): the row-group row taken as row // 256 (the tile, not the group), the last 64 of K left out, ReLU applied before
+    the row-group term, and truncation to bf16 instead of round-to-nearest-even.  The CPU test shows that each differs from the
+    expected output, so the case can see the bug."""
+    A, B = operands(c.lattice, c.M, c.N, c.K)
+    e, (_, _, rg, _) = c.epi, extras(c)
+    prod = product(c.lattice, c.M, c.N, c.K)
+    term = lambda v, gx: v * gx if e.rg_op else v + gx
+    act = lambda v: torch.clamp_min(v, 0.0) if e.relu else v
+    rows = torch.arange(c.M)
+    tile_row = rg[torch.clamp(rows // 256, max=rg.shape[0] - 1)]
+    want = expected(c)[1]
+    trunc = (want.to(torch.float32).view(torch.int32) & -65536).view(torch.float32).to(torch.bfloat16)
+    return {"group = row // 256": rne_bf16(act(term(prod, tile_row))),
+            "last 64 of K dropped": rne_bf16(act(term(A[:, :c.K - 64] @ B[:c.K - 64], rg[rows // e.rg_div]))),
+            "ReLU before the row-group term": rne_bf16(term(act(prod), rg[rows // e.rg_div])),
+            "truncation to bf16": trunc}
 
 
 @functools.lru_cache(maxsize=None)

@@ -192,6 +192,31 @@ def l2norm_ref(pooled, mask, dvn=None):
     return vn.detach(), nrm.detach()[:, 0], x.grad
 
 
+def l2norm_join_ref(probs, dout, dv_in, mask_v):
+    """d loss / d vn as vqa_l2norm_bwd_joined joins it: dvn[b*P+p] = sum_g probs[b,g,p] * dout[b, g*C:(g+1)*C] (the
+    softmax-weighted sum's branch) + mask_v * dv_in (the branch through the dropout in front of the image projection).
+    probs [B,G,P], dout [B, G*C], dv_in and mask_v [B*P, C] (mask_v None: no dropout).  Float64."""
+    probs, dout, dv_in = _d(probs), _d(dout), _d(dv_in)
+    B, G, P = probs.shape
+    C = dv_in.shape[1]
+    dvn = torch.einsum("bgp,bgc->bpc", probs, dout.reshape(B, G, C)).reshape(B * P, C)
+    return dvn + (dv_in if mask_v is None else dv_in * _d(mask_v))
+
+
+def l2norm_join_autograd(pooled, mask, score, dout, dv_in, mask_v):
+    """d loss / d pooled by autograd through the whole stage: vn = normalise(mask * pooled), out = sum_p softmax(score) * vn,
+    v_drop = mask_v * vn, loss = sum(out * dout) + sum(v_drop * dv_in).  Float64; returns (probs, d pooled)."""
+    x = _d(pooled).requires_grad_(True)
+    u = x if mask is None else x * _d(mask)
+    vn = u / (u.norm(p=2, dim=1, keepdim=True) + 1e-12)
+    B, G, P = score.shape
+    pr = torch.softmax(_d(score), dim=-1)
+    out = torch.einsum("bgp,bpc->bgc", pr, vn.reshape(B, P, -1)).reshape(B, -1)
+    vd = vn if mask_v is None else vn * _d(mask_v)
+    ((out * _d(dout)).sum() + (vd * _d(dv_in)).sum()).backward()
+    return pr.detach(), x.grad
+
+
 # ----------------------------------------------------------------------------- tanh(dropout(embedding))
 def embed_tanh_ref(q, emb, mask, dx=None):
     """x [T, B, E] = tanh(mask[b, t, :] * emb[q[b, t]]), mask over the logical [B, T, E] tensor; row 0 is the padding

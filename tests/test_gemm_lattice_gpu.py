@@ -1,4 +1,5 @@
-"""vqa_gemm, vqa_gemm_x3 and vqa_gemm_bf16 bit for bit, in every plan the train step runs, on operands whose arithmetic is exact.
+"""vqa_gemm, vqa_gemm_x3, vqa_gemm_bf16 and vqa_gemm_tall_bf16 bit for bit, in every plan the train step runs, on operands whose
+arithmetic is exact.
 
 tests/gemm_lattice_ref.py draws the operands from a dyadic lattice of bf16 values on which every partial sum, split-K slab and
 epilogue step is an fp32 value, so each fp32 output must EQUAL the float64 closed form and each bf16 output its
@@ -65,8 +66,8 @@ def knobs(monkeypatch):
 class Tally:
     """Exact comparisons of one case; prints the case's [lattice] line and fails after it if anything differed."""
 
-    def __init__(self, c, plan):
-        self.c, self.plan, self.n, self.bad, self.where = c, plan, 0, 0, []
+    def __init__(self, c, plan, plan_text=None):
+        self.c, self.plan, self.n, self.bad, self.where, self.plan_text = c, plan, 0, 0, [], plan_text
 
     def eq(self, name, got, want):
         """got == want element for element (-0 equals +0, NaN equals nothing); a float64 reference is narrowed to got's type"""
@@ -92,8 +93,9 @@ class Tally:
 
     def done(self):
         p = self.plan
-        print(f"[lattice] {L.case_id(self.c)}: {p['BM']}x{p['BN']} tiles {p['tiles_m']}x{p['tiles_n']} nk {p['nk']} splits {p['splits']}x"
-              f"{p['ks_per_split']} order {p['order']} persistent {p['persistent']} wide {p['wide']}; compared {self.n} mismatches {self.bad}")
+        text = self.plan_text or (f"{p['BM']}x{p['BN']} tiles {p['tiles_m']}x{p['tiles_n']} nk {p['nk']} splits {p['splits']}x"
+                                  f"{p['ks_per_split']} order {p['order']} persistent {p['persistent']} wide {p['wide']}")
+        print(f"[lattice] {L.case_id(self.c)}: {text}; compared {self.n} mismatches {self.bad}")
         assert self.bad == 0 and not self.where, "\n".join(self.where)
 
 
@@ -231,3 +233,37 @@ def test_x3_persistent_workgroups_walk_several_tiles(ops, knobs, c):
     """272 tiles on the persistent kernel's 256 workgroups (16 of them take a second tile), and one tile per workgroup"""
     assert c.plan["tiles_m"] * c.plan["tiles_n"] == 272
     run(ops, knobs, c)
+
+
+# ----------------------------------------------------------------------------- the tall bf16 engine
+@pytest.mark.parametrize("c", L.tall_cases_both_heights(), ids=ids(L.tall_cases_both_heights()))
+def test_tall_bf16(ops, knobs, c):
+    """vqa_gemm_tall_bf16, every case on 256-row and (VQA_TALL_BM=128) on 128-row tiles: one tile per workgroup with one, two and three
+    k-stages, tile seams with the row-group table's minimum lead, tiles that span two row groups, a partial last group, a last
+    row tile partly past M, three tiles per workgroup, a grid that is no multiple of 8, with and without ReLU.  Every bf16
+    output equals the round-to-nearest-even of the float64 result; the pad columns of C and the guard rows after row M - 1
+    keep their NaN bits."""
+    knobs(c.knobs)
+    M, N, K, e = c.M, c.N, c.K, c.epi
+    assert ops.gemm_tall_bf16_supported(M, N, K, e.rg_div, bool(e.rg_div))
+    plan = ops.gemm_tall_bf16_plan(M, N, K)
+    assert {k: plan[k] for k in c.plan} == c.plan, (L.case_id(c), c.plan, plan)
+    A, B = L.operands(c.lattice, M, N, K)
+    rg = L.extras(c)[2]
+    want = L.expected(c)[1]
+    lda, ldw, ldc, rg_ld = L.leading_dims(c)
+    Ad = L.stored(A, M, K, lda, BF16).to(DEV)
+    Wd = L.stored(B.t().contiguous(), N, K, ldw, BF16).to(DEV)
+    rgd = None if rg is None else L.body(L.stored(rg, rg.shape[0], N, rg_ld, F32).to(DEV), rg.shape[0], N, rg_ld)
+    assert rgd is None or (rgd.shape[0] == -(-M // e.rg_div) and rgd.stride(0) == rg_ld > N and rgd.data_ptr() % 16 == 0)
+    C_cpu = L.stored(None, M, N, ldc, BF16)
+    Cd = C_cpu.to(DEV)
+    a, w, cv = L.body(Ad, M, K, lda), L.body(Wd, N, K, ldw), L.body(Cd, M, N, ldc)
+    assert a.stride(0) == lda and w.stride(0) == ldw and cv.stride(0) == ldc
+    assert a.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and cv.data_ptr() % 16 == 0
+    ops.gemm_tall_bf16(a, w, cv, M, N, K, rowgroup=rgd, rg_div=e.rg_div or 1, rg_op=e.rg_op, relu=e.relu)
+    torch.cuda.synchronize()
+    t = Tally(c, plan, f"{plan['BM']}-row tiles {plan['tiles_m']}x{plan['tiles_n']} grid {plan['grid']} nk {plan['nk']}")
+    t.eq("C", L.body(Cd, M, N, ldc), want)
+    t.untouched("C", L.outside(Cd, M, N, ldc), L.outside(C_cpu, M, N, ldc))
+    t.done()

@@ -210,3 +210,148 @@ def test_the_table_covers_every_kernel_of_the_three_engines(knob):
     missing = [cell for cell in want if cell not in cells]
     assert not missing, missing
     assert len(want) == 28 + 17 + 12 + 35 + 2 + 6 + 4
+
+
+# ----------------------------------------------------------------------------- the tall bf16 engine
+def tall_plan(c):
+    from dl_vqa_amd import ops
+    return ops.gemm_tall_bf16_plan(c.M, c.N, c.K)
+
+
+def test_tall_cases_are_exact_and_exercise_the_bf16_rounding():
+    """With K <= 512, sum |a| |b| max|rg| <= 2^15 (2^15 + 2 at K = 1024, added): far below 2^21, so the float64 result is the only
+    correct fp32 value and its round-to-nearest-even the only correct bf16 output -- and that rounding is at work: at least 3 % of
+    the expected values are no bf16 values and at least 1000 are exact ties, in every case."""
+    ids = [L.case_id(c) for c in L.tall_cases()]
+    assert len(set(ids)) == len(ids) == 16
+    for c in L.tall_cases():
+        assert c.lattice == "std16" and c.c_bf16 and L.assert_exact(c) <= 2.0 ** 15 + 2
+        A, B = L.operands(c.lattice, c.M, c.N, c.K)
+        assert float(A.abs().max()) == 16 and float(B.abs().max()) == 2 and L.on_lattice(B, 0.5)
+        want = L.expected(c)[1]
+        assert torch.equal(L.rne_bf16(want), want.to(torch.bfloat16))
+        unrep, ties = L.bf16_stats(want)
+        print(f"[lattice] {L.case_id(c)}: {100 * unrep:.1f} % of the outputs are no bf16 values, {ties} exact ties")
+        assert unrep >= 0.03 and ties >= 1000, (L.case_id(c), unrep, ties)
+        assert bool((want < 0).any()) == (not c.epi.relu)             # without ReLU negative outputs must survive
+        lda, ldw, ldc, rg_ld = L.leading_dims(c)
+        assert (lda, ldw, ldc, rg_ld) == (c.K + 8, c.K + 16, c.N + 8, c.N + 8)
+
+
+def test_tall_partial_last_row_group():
+    c = next(c for c in L.tall_cases() if c.why == "partial-group")
+    rg = L.extras(c)[2]
+    assert c.M % c.epi.rg_div == 508 and rg.shape == (17, c.N)
+    want = L.expected(c)[1]
+    prod = L.product(c.lattice, c.M, c.N, c.K)
+    assert torch.equal(want[16 * 512:], torch.clamp_min(prod[16 * 512:] + rg[16], 0.0))
+
+
+def test_tall_plan_query_and_its_knob(knob):
+    """vqa_gemm_tall_bf16_plan is what the launcher calls; VQA_TALL_BM is a knob like the others: re-read by vqa_reload_knobs,
+    and anything but 128 keeps the 256-row tiles."""
+    from dl_vqa_amd import _lib, ops
+    knob(())
+    assert ops.gemm_tall_bf16_plan(8788, 1024, 256) == dict(BM=256, tiles_m=35, tiles_n=8, grid=256, nk=4)
+    knob(L.TALL128)
+    assert ops.gemm_tall_bf16_plan(8788, 1024, 256) == dict(BM=128, tiles_m=69, tiles_n=8, grid=512, nk=4)
+    for other in ("256", "64", "0", "", "x"):
+        knob((("VQA_TALL_BM", other),))
+        assert ops.gemm_tall_bf16_plan(8788, 1024, 256)["BM"] == 256, other
+    knob(())
+    assert ops.gemm_tall_bf16_plan(2048, 1024, 64)["grid"] == 64
+    for bad in ((0, 128, 64), (256, 100, 64), (256, 128, 96)):
+        with pytest.raises(_lib.VqaHipError, match="vqa_gemm_tall_bf16_plan: bad args"):
+            ops.gemm_tall_bf16_plan(*bad)
+
+
+def _tiles_spanning_two_groups(c, p):
+    return sum(1 for mt in range(p["tiles_m"])
+               if mt * p["BM"] // c.epi.rg_div != (min((mt + 1) * p["BM"], c.M) - 1) // c.epi.rg_div)
+
+
+def test_every_tall_case_reaches_the_mechanism_it_is_listed_for(knob):
+    """From the launch geometry the launcher itself uses: tiles against grid, tiles per workgroup, the XCD swizzle's remainder,
+    the k-stage count against the row-group table's lead, and where the group boundaries fall in the tiles."""
+    from dl_vqa_amd import ops
+    seen = set()
+    for c in L.tall_cases():
+        knob(c.knobs)
+        p = tall_plan(c)
+        assert {k: p[k] for k in c.plan} == c.plan, (L.case_id(c), c.plan, p)
+        e = c.epi
+        assert ops.gemm_tall_bf16_supported(c.M, c.N, c.K, e.rg_div, bool(e.rg_div)), L.case_id(c)
+        bm, tiles, grid, nk = p["BM"], p["tiles_m"] * p["tiles_n"], p["grid"], p["nk"]
+        per_wg = -(-tiles // grid)
+        assert grid == min(tiles, 65536 // bm) and (not e.rg_div or (e.rg_div >= 256 and nk >= 3))
+        if c.why == "nk1":           # the prologue's second load is already the next tile, or past the end
+            assert nk == 1 and tiles == grid and not e.rg_div
+        elif c.why == "nk2":
+            assert nk == 2 and tiles == grid and not e.rg_div
+        elif c.why == "group-per-tile":      # the smallest nk with a table; every boundary on a tile seam
+            assert nk == 3 and tiles == grid and e.rg_div == bm and _tiles_spanning_two_groups(c, p) == 0
+        elif c.why == "one-group":
+            assert nk == 3 and tiles == grid and e.rg_div == c.M and e.rg_op == 1
+        elif c.why == "seam":        # a second tile whose table load falls in its first stage; a last row tile partly past M
+            assert nk == 3 and tiles > grid and per_wg == 2 and tiles % grid == (16 if bm == 256 else 32) and e.rg_op == 1
+            assert _tiles_spanning_two_groups(c, p) > (p["tiles_m"] // 2 if bm == 256 else p["tiles_m"] // 3)
+            assert 0 < p["tiles_m"] * bm - c.M < bm
+        elif c.why == "train":
+            assert (c.M, e.rg_div, nk, tiles, grid) == (13 * 676, 676, 4, 280, 256) and per_wg == 2 and 0 < p["tiles_m"] * bm - c.M < bm
+        elif c.why == "three-tiles":
+            assert tiles == 513 and grid == 256 and per_wg == 3 and tiles % grid == 1 and p["tiles_n"] & (p["tiles_n"] - 1)
+            assert c.M == 15 * e.rg_div and e.rg_op == 1 and nk == 8
+        elif c.why == "odd-grid":    # xcd_swizzle with a remainder; one column tile
+            assert p["tiles_n"] == 1 and tiles == grid and grid % 8 != 0 and nk in (1, 3) and (nk == 1) == (e.rg_div == 0)
+        elif c.why == "partial-group":
+            assert c.M % e.rg_div != 0 and tiles > grid and nk == 4
+        elif c.why == "long-k":
+            assert nk == 16 and tiles == grid and e.rg_div == 1024
+        else:
+            raise AssertionError(c.why)
+        seen.add((c.why, bm))
+    assert {w for w, bm in seen if bm == 256} == {"nk1", "nk2", "group-per-tile", "one-group", "seam", "train", "three-tiles",
+                                                  "odd-grid", "partial-group", "long-k"}
+    assert {w for w, bm in seen if bm == 128} == {"seam", "odd-grid", "nk1"}
+    assert {c.epi.relu for c in L.tall_cases() if c.why == "train"} == {False, True}
+    # the GPU file runs every case under both tile heights; the restated 128-row geometry is the query's
+    both = L.tall_cases_both_heights()
+    assert len(both) == 26 and len({L.case_id(c) for c in both}) == 26 and sum(1 for c in both if c.knobs) == 13
+    for c in both[16:]:
+        knob(c.knobs)
+        assert tall_plan(c) == c.plan, (L.case_id(c), c.plan, tall_plan(c))
+    assert {c.epi.relu for c in L.tall_cases() if c.why == "nk1" and not c.knobs} == {False, True}
+
+
+@pytest.mark.parametrize("why", ["seam", "train"])
+def test_tall_cases_can_see_four_plausible_bugs(why):
+    """The expected bf16 output of the seam case and of the training-shape case differs from what each wrong form would store."""
+    for c in [c for c in L.tall_cases() if c.why == why and not c.knobs]:
+        want = L.rne_bf16(L.expected(c)[1])
+        wrong = L.tall_wrong_forms(c)
+        assert len(wrong) == 4
+        for name, got in wrong.items():
+            n = int((got != want).sum())
+            print(f"[lattice] {L.case_id(c)}: '{name}' differs in {n} of {want.numel()} elements")
+            if name == "ReLU before the row-group term" and not c.epi.relu:
+                assert n == 0                                     # no ReLU: the same thing; the ReLU case of the pair tells
+            else:
+                assert n >= 1000, (L.case_id(c), name, n)
+        # row // 256 is the right group only while the two agree: in the first 256 rows, and nowhere once they have drifted apart
+        rows = (wrong["group = row // 256"] != want).any(1)
+        assert 0 < int(rows.sum()) < c.M
+
+
+def test_tall_row_group_arguments_are_refused_before_any_hip_call():
+    """The table is read 16 bytes at a time: rg_ld >= N, rg_ld % 4 == 0 and a 16-byte aligned rowgroup, or VQA_ERR_INVALID.
+    The pointers are never dereferenced on the host, and a refusal comes before the first HIP call."""
+    from dl_vqa_amd import _lib
+    lib = _lib.load()
+    M, N, K = 2048, 1024, 192
+    base = 1 << 20
+
+    def rc(rg, rg_ld):
+        return lib.vqa_gemm_tall_bf16(base, K, base, K, base, N, M, N, K, rg, rg_ld, 256, 0, 1, 0, None)
+    for rg, rg_ld in ((base, N - 4), (base, N + 2), (base + 4, N)):
+        assert rc(rg, rg_ld) == 1, (rg, rg_ld)
+        assert b"rowgroup must be 16-byte aligned" in lib.vqa_last_error()

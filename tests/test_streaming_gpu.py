@@ -10,7 +10,8 @@ Tolerances: the reference is float64, so the whole error is the kernel's.  A res
 gets max|err| / max|ref| <= 4 * 2^-24 * sqrt(n) (tol_sum); where tests/test_kernels_gpu.py already holds the same
 kernel to a looser bound that one is used (3e-6 scores and probabilities, 1e-5 attention backward, 2e-5 two chained
 reductions).  Masking, copies and single fp32 operations are compared for equality.  A bf16 output may differ by one
-bf16 rounding of the fp32 value: |got - ref| <= 2^-8 |ref| + 1e-6 max|ref|, for every element.
+bf16 rounding of the fp32 value: |got - ref| <= 2^-8 |ref| + T max|ref|, for every element, with T = 1e-6 or, in the
+L2-norm section, the fp32 tolerance of the same case.
 """
 import math
 
@@ -47,14 +48,14 @@ def check(name, got, ref, tol):
     assert e <= tol, f"{name}: {e} > {tol}"
 
 
-def check_bf16(name, got, ref):
-    """one bf16 rounding of the fp32 value, element-wise, no element exempt"""
+def check_bf16(name, got, ref, T=1e-6):
+    """one bf16 rounding of the fp32 value on top of its own error T (relative to max|ref|), element-wise, no element exempt"""
     got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
     assert bool(torch.isfinite(got).all()), f"{name}: unwritten / non-finite elements"
-    bound = 2.0 ** -8 * ref.abs() + 1e-6 * float(ref.abs().max())
+    bound = 2.0 ** -8 * ref.abs() + T * float(ref.abs().max())
     excess = float(((got - ref).abs() - bound).max())
-    worst = float(((got - ref).abs() / (ref.abs() + 1e-6 * float(ref.abs().max()))).max())
-    print(f"[parity] {name}: max |err| / (|ref| + 1e-6 max|ref|) = {worst:.3e} (tol 2^-8 = {2.0 ** -8:.1e})")
+    worst = float(((got - ref).abs() / bound.clamp_min(1e-300)).max())
+    print(f"[parity] {name}: max |err| / (2^-8 |ref| + {T:.1e} max|ref|) = {worst:.3e} (tol 1)")
     assert excess <= 0.0, f"{name}: an element is {excess} outside one bf16 rounding"
 
 
@@ -542,3 +543,127 @@ def test_sum_parts_shapes(batch, parts, cols):
     ops.sum_parts(part.to(DEV), out, batch, parts, cols)
     torch.cuda.synchronize()
     check(f"sum_parts {batch, parts, cols}", out, part.double().reshape(batch, parts, cols).sum(1), tol_sum(parts))
+
+
+# ----------------------------------------------------------------------------- i. L2 norm: every output mode against float64
+SEED_V = 0xC0FFEE1234ABCDEF   # the dropout in front of the image projection; SEED is the image dropout
+GUARD = 64                    # NaN elements before and after every output
+INV_EPS32 = float(np.float32(1.0) / np.float32(1e-12))          # 1 / (0 + 1e-12) as the kernels evaluate it
+
+L2_SHAPES = [
+    # (B, Hp, Wp, C, G, bf16 row-major output too, a pooled row of zeros)
+    (3, 5, 7, 16, 1, True, True),      # four active lanes; row pairs that straddle an image; 105 rows: the last pair clamps
+    (3, 5, 7, 48, 3, True, True),      # three channel blocks: c >> 2 and c & 3 both vary
+    (2, 3, 3, 256, 4, True, False),    # every lane active
+    (2, 3, 3, 272, 2, True, False),    # the two-pass form with a second trip of 4 lanes; 17 blocks
+    (1, 7, 5, 512, 4, True, False),
+    (97, 26, 26, 16, 2, False, False),     # 65 572 rows > 2 x 32 768 waves: the register form strides
+    (49, 26, 26, 272, 1, False, False),    # 33 124 rows > 32 768 waves: the two-pass form strides
+]
+
+
+def _guarded(n, dtype):
+    """a NaN buffer of n elements between two NaN guards: (flat, the view to hand to the kernel)"""
+    flat = torch.full((n + 2 * GUARD,), NAN, dtype=dtype, device=DEV)
+    return flat, flat[GUARD:GUARD + n]
+
+
+def _guards_intact(name, flat, n):
+    ints = flat.view(torch.int32 if flat.dtype == torch.float32 else torch.int16)
+    want = torch.full((1,), NAN, dtype=flat.dtype).view(ints.dtype).item()
+    assert bool((ints[:GUARD] == want).all()) and bool((ints[GUARD + n:] == want).all()), f"{name}: a guard element was written"
+
+
+def _l2_judge(name, got, ref, ref_zero, zero_row, T, bf16):
+    """every row but the all-zero one against the float64 gradient in the max norm of those rows; the all-zero row on its
+    own, relative to its own maximum, against dvn * (1 / (0 + 1e-12)) with the quotient evaluated in fp32"""
+    got = got.detach().double().cpu()
+    assert bool(torch.isfinite(got).all()), f"{name}: unwritten / non-finite elements"
+    keep = torch.ones(got.shape[0], dtype=torch.bool)
+    parts = [(name, got, ref)]
+    if zero_row is not None:
+        keep[zero_row] = False
+        parts = [(name, got[keep], ref[keep]), (name + " all-zero row", got[zero_row], ref_zero)]
+    for n, a, b in parts:
+        if bf16:
+            check_bf16(n, a, b, T)
+        else:
+            check(n, a, b, T)
+
+
+@pytest.mark.parametrize("B,Hp,Wp,C,G,rowmajor_bf16,zero", L2_SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}-C{s[3]}-G{s[4]}" for s in L2_SHAPES])
+@pytest.mark.parametrize("p_v,p", [(0.0, 0.0), (0.3, 0.3)])
+def test_l2norm_bwd_every_output_mode(p_v, p, B, Hp, Wp, C, G, rowmajor_bf16, zero):
+    """vqa_l2norm_bwd and vqa_l2norm_bwd_joined with the fp32, the bf16 and the channel-blocked bf16 output against float64:
+    dvn = sum_g probs * dout + mask_v * dv_in (tests/streaming_ref.py; for the plain entry point that sum rounded to fp32 is
+    the input), pushed through autograd of u / (|u| + 1e-12), u = mask * pooled.  Masks are R.mask_tensor's; vn and norm are
+    the float64 forward rounded to fp32.  fp32: 5e-6 of max|ref| (plain), + tol_sum(G + 1) for the join's G + 1-term sum;
+    bf16: |got - ref| <= 2^-8 |ref| + T max|ref| for every element, T the fp32 tolerance.  Outputs lie between NaN guards,
+    dout has NaN pad columns, the channel-blocked output is un-blocked with tests/conv_lattice_ref.py's from_c16."""
+    from tests.conv_lattice_ref import from_c16
+    P = Hp * Wp
+    rows = B * P
+    g = torch.Generator().manual_seed(rows * 7 + C + G)
+    pooled = torch.randn(rows, C, generator=g)
+    zero_row = P + 1 if zero else None
+    if zero:
+        pooled[zero_row] = 0.0
+    probs = torch.softmax(torch.randn(B, G, P, generator=g) * 2, dim=-1)
+    ld = G * C + 8
+    dout = torch.full((B, ld), NAN)
+    dout[:, :G * C] = torch.randn(B, G * C, generator=g)
+    dv_in = torch.randn(rows, C, generator=g)
+    mask, mask_v = R.mask_tensor(SEED, (rows, C), p), R.mask_tensor(SEED_V, (rows, C), p_v)
+    vn, norm = R.l2norm_ref(pooled, mask)
+    assert not zero or (float(norm[zero_row]) == 0.0 and float(vn[zero_row].abs().max()) == 0.0)
+    dvn = R.l2norm_join_ref(probs, dout[:, :G * C], dv_in, mask_v)
+    dvn32 = dvn.to(torch.float32)
+    m1 = 1.0 if mask is None else mask.double()
+    refs = {"joined": (R.l2norm_ref(pooled, mask, dvn)[2], dvn, 5e-6 + tol_sum(G + 1)),
+            "plain": (R.l2norm_ref(pooled, mask, dvn32)[2], dvn32.double(), 5e-6)}
+    vn_d, norm_d, dout_d, probs_d, dv_in_d, dvn_d = dev(vn, torch.float32), dev(norm, torch.float32), dev(dout), dev(probs), dev(dv_in), dev(dvn32)
+    modes = [(0, "fp32"), (2, "c16")] + ([(1, "bf16")] if rowmajor_bf16 else [])
+    for entry, (ref, a, T) in refs.items():
+        ref_zero = None if not zero else (a * INV_EPS32 * m1)[zero_row]
+        for mode, mname in modes:
+            flat, out = _guarded(rows * C, torch.float32 if mode == 0 else torch.bfloat16)
+            if entry == "joined":
+                _raw("vqa_l2norm_bwd_joined", dout_d, ld, probs_d, G, dv_in_d, p_v, SEED_V, vn_d, norm_d, out, mode, rows, P, C, p, SEED)
+            else:
+                _raw("vqa_l2norm_bwd", dvn_d, vn_d, norm_d, out, mode, rows, P, C, p, SEED)
+            torch.cuda.synchronize()
+            name = f"l2norm_bwd {entry} {mname} {B, Hp, Wp, C, G} p_v={p_v} p={p}"
+            _guards_intact(name, flat, rows * C)
+            got = out.view(rows, C) if mode != 2 else from_c16(out.view(B, C // 16, Hp, Wp, 16)).reshape(rows, C)
+            _l2_judge(name, got, ref, ref_zero, zero_row, T, mode != 0)
+    assert bool(torch.isnan(dout_d[:, G * C:]).all())
+
+
+@pytest.mark.parametrize("rows,C", [(37, 272), (4 * 32768 + 3, 8)])
+@pytest.mark.parametrize("p2", [0.3, 0.0])
+def test_l2norm_fwd_second_output(p2, rows, C):
+    """vqa_l2norm_fwd's second output vdrop = dropout_{p2}(vn), fp32 and bf16, in the two-pass form and in the register form past
+    the grid cap, against float64 mask2 * vn; p2 = 0 copies vn.  fp32: 2e-6, the bound vn is held to; bf16: one rounding on top."""
+    p = 0.3
+    g = torch.Generator().manual_seed(rows + C + 1)
+    u = torch.randn(rows, C, generator=g)
+    mask, mask2 = R.mask_tensor(SEED, (rows, C), p), R.mask_tensor(SEED_V, (rows, C), p2)
+    vn_ref, norm_ref = R.l2norm_ref(u, mask)
+    want = vn_ref if mask2 is None else vn_ref * mask2.double()
+    ud = dev(u)
+    for dtype, is_bf16 in ((torch.float32, 0), (torch.bfloat16, 1)):
+        vn, norm = nan_like(rows, C), nan_like(rows)
+        flat, vd = _guarded(rows * C, dtype)
+        _raw("vqa_l2norm_fwd", ud, vn, norm, rows, C, p, SEED, vd, is_bf16, p2, SEED_V)
+        torch.cuda.synchronize()
+        name = f"l2norm_fwd vdrop {'bf16' if is_bf16 else 'fp32'} {rows, C} p2={p2}"
+        _guards_intact(name, flat, rows * C)
+        check(f"{name}: vn", vn, vn_ref, 2e-6)
+        check(f"{name}: norm", norm, norm_ref, 2e-6)
+        if is_bf16:
+            check_bf16(name, vd.view(rows, C), want, 2e-6)
+        else:
+            check(name, vd.view(rows, C), want, 2e-6)
+        if p2 > 0:
+            dropped = (mask2 == 0)
+            assert 0.25 < float(dropped.float().mean()) < 0.35 and bool((vd.view(rows, C).cpu()[dropped] == 0).all())

@@ -143,3 +143,37 @@ def test_adam_reference_scales_the_gradient():
     f = lambda s: float(np.float32(s))
     O.adam_step(p2, gr * 0.5, m2, v2, 1, f(1e-3), f(0.9), f(0.999), f(1e-8))
     assert torch.equal(p, p2) and torch.equal(m, m2) and torch.equal(v, v2)
+
+
+@pytest.mark.parametrize("p_v,p", [(0.0, 0.0), (0.3, 0.3)])
+def test_l2norm_join_closed_form_equals_autograd_through_the_stage(p_v, p):
+    """The gradient vqa_l2norm_bwd_joined joins in closed form (weighted-sum branch + dropout branch), pushed through the
+    normalisation, is autograd through softmax-weighted sum + dropout + normalise."""
+    B, P, C, G = 2, 5, 8, 3
+    g = torch.Generator().manual_seed(3)
+    pooled = torch.randn(B * P, C, generator=g).double()
+    score = torch.randn(B, G, P, generator=g).double()
+    dout = torch.randn(B, G * C, generator=g).double()
+    dv_in = torch.randn(B * P, C, generator=g).double()
+    mask = R.mask_tensor(0x1122334455667788, (B * P, C), p)
+    mask_v = R.mask_tensor(0x8877665544332211, (B * P, C), p_v)
+    probs, want = R.l2norm_join_autograd(pooled, mask, score, dout, dv_in, mask_v)
+    dvn = R.l2norm_join_ref(probs, dout, dv_in, mask_v)
+    got = R.l2norm_ref(pooled, mask, dvn)[2]
+    assert R.rel_err(got, want) < 1e-13
+    # the two branches are both there: either alone is a different gradient
+    for part in (R.l2norm_join_ref(probs, dout, torch.zeros_like(dv_in), mask_v), R.l2norm_join_ref(torch.zeros_like(probs), dout, dv_in, mask_v)):
+        assert R.rel_err(R.l2norm_ref(pooled, mask, part)[2], want) > 1e-2
+    if p > 0:
+        assert float((mask == 0).float().mean()) > 0.1 and bool((got[mask == 0] == 0).all())
+
+
+def test_l2norm_all_zero_row_in_float64():
+    """A pooled row of zeros: vn = 0, norm = 0, and the gradient is dvn / 1e-12 -- what the kernels are held to on that row."""
+    g = torch.Generator().manual_seed(4)
+    pooled = torch.randn(3, 8, generator=g).double()
+    pooled[1] = 0
+    dvn = torch.randn(3, 8, generator=g).double()
+    vn, nrm, d = R.l2norm_ref(pooled, None, dvn)
+    assert float(vn[1].abs().max()) == 0 and float(nrm[1]) == 0
+    assert R.rel_err(d[1], dvn[1] * 1e12) < 1e-12
