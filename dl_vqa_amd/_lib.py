@@ -144,6 +144,7 @@ PROTOTYPES = {
     "vqa_pconv_wgrad": (i32, [vp, u8p, vp, f32p, f32p, i32, i32, i32, i32, i32, f32p, i64, i32, vp]),
     "vqa_pconv_dgrad": (i32, [vp, u8p, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_adam": (i32, [f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, i32, f32, vp]),
+    "vqa_adam_segments": (i32, [f32p, f32p, f32p, f32p, i64, vp, i32, f32, vp]),      # segs: a HOST array of AdamSegment
 }
 
 K_GEMM, K_CONV_FWD, K_CONV_DGRAD, K_CONV_WGRAD = 0, 1, 2, 3
@@ -155,6 +156,15 @@ class LstmDir(C.Structure):
     """vqa_lstm_dir_t (include/vqa_hip.h): one direction of an LSTM sequence, device pointers as integers."""
     _fields_ = [("w_hh", vp), ("xg", vp), ("gates", vp), ("Hs", vp), ("Cs", vp), ("c_final", vp),
                 ("dgates", vp), ("dh", vp), ("dc", vp), ("reverse", i32)]
+
+
+class AdamSegment(C.Structure):
+    """vqa_adam_segment (include/vqa_hip.h): one range [begin, end) of the flat buffer with its own Adam settings and step."""
+    _fields_ = [("begin", i64), ("end", i64), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32),
+                ("weight_decay", f32), ("step", i32), ("decoupled", i32)]
+
+
+ADAM_MAX_SEGMENTS = 64      # VQA_ADAM_MAX_SEGMENTS
 
 
 class VqaHipError(RuntimeError):

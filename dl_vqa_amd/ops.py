@@ -979,3 +979,31 @@ def scale_by(x, scalar_dev):
 def adam(param, grad, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     call("vqa_adam", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, beta1, beta2, eps,
          step, grad_scale, stream())
+
+
+ADAM_SEGMENT_FIELDS = ("begin", "end", "lr", "beta1", "beta2", "eps", "weight_decay", "step", "decoupled")
+
+
+def adam_segment_table(segments):
+    """The host array vqa_adam_segments reads, from a list of segments: each a tuple in the order of ADAM_SEGMENT_FIELDS
+    (beta1 onwards may be left out: 0.9, 0.999, 1e-8, no decay, step 1, not decoupled) or a dict with those keys."""
+    defaults = dict(beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, step=1, decoupled=0)
+    table = (_lib.AdamSegment * len(segments))()
+    for row, s in zip(table, segments):
+        if not isinstance(s, dict):
+            s = dict(zip(ADAM_SEGMENT_FIELDS, s))
+        unknown = set(s) - set(ADAM_SEGMENT_FIELDS)
+        if unknown or not {"begin", "end", "lr"} <= set(s):
+            raise ValueError(f"adam_segments: a segment needs begin, end, lr and may have {ADAM_SEGMENT_FIELDS[3:]}; got {sorted(s)}")
+        s = {**defaults, **s}
+        row.begin, row.end, row.step, row.decoupled = int(s["begin"]), int(s["end"]), int(s["step"]), int(bool(s["decoupled"]))
+        row.lr, row.beta1, row.beta2, row.eps, row.weight_decay = s["lr"], s["beta1"], s["beta2"], s["eps"], s["weight_decay"]
+    return table
+
+
+def adam_segments(param, grad, exp_avg, exp_avg_sq, segments, grad_scale=1.0):
+    """Adam / AdamW over the listed ranges of the flat buffers in ONE launch (vqa_adam_segments); every range has its own
+    step, lr, betas, eps and weight decay, and what no range covers is not touched.  `segments`: see adam_segment_table."""
+    table = adam_segment_table(segments)
+    call("vqa_adam_segments", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), table, len(table),
+         grad_scale, stream())

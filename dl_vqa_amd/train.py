@@ -16,6 +16,7 @@ from typing import Optional
 import torch
 
 from . import ops
+from ._lib import ADAM_MAX_SEGMENTS as MAX_ADAM_SEGMENTS     # what one launch carries in its arguments
 from .model import validate_question_lengths
 
 
@@ -147,16 +148,96 @@ def update_learning_rate(optimizer, iteration, initial_lr):
         param_group["lr"] = lr
 
 
+_GROUP_KEYS = ("params", "lr_scale", "weight_decay", "decoupled", "frozen", "betas", "eps")
+
+
+def _matches(name: str, spec: str) -> bool:
+    """A group's `params` entry names a parameter ("text.embedding.weight") or a prefix of dotted names ("image", "text.embedding")."""
+    return name == spec or name.startswith(spec + ".")
+
+
 class FusedAdam:
     """torch.optim.Adam(model.parameters(), lr) defaults (betas 0.9/0.999, eps 1e-8, no weight decay)
-    as ONE kernel over the model's flat parameter / gradient buffers."""
+    as ONE kernel over the model's flat parameter / gradient buffers.
 
-    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    ``groups=None`` (the default) is that optimiser: one group, one global step count, ``ops.adam`` over the whole buffer.
+
+    ``groups=[{...}, ...]`` gives torch.optim.Adam's parameter groups, still as one launch per step (``ops.adam_segments``
+    walks a table of ranges of the flat buffer).  Each dict has ``params`` -- a parameter name, a prefix of dotted names
+    such as ``"image"`` or ``"text.embedding"``, or a list of those, matched against ``model.named_parameters()`` -- and
+    optionally ``lr_scale`` (1.0), ``weight_decay`` (0.0), ``decoupled`` (False: L2 decay as torch.optim.Adam; True:
+    torch.optim.AdamW), ``frozen`` (False), ``betas`` and ``eps`` (the constructor's).  A parameter matched by two groups and
+    an entry that matches nothing raise ValueError; parameters matched by no group form a last group with the constructor's
+    values.  There is no amsgrad.
+
+    ``param_groups[k]["lr"]`` is the schedule's rate, the same in every group, because the reference's
+    ``update_learning_rate`` writes one value into all of them (train.py:31-35); what differs per group lives in
+    ``lr_scale`` and the rate a group's parameters are updated with is ``lr * lr_scale``.
+
+    Every parameter has its own step number, as in torch: it advances in exactly the steps that update the parameter -- it
+    has a gradient and its group is not frozen -- so a parameter that joins late (``unfreeze``) starts its bias correction
+    at step 1.  Parameters that are not updated are not listed in the table: the kernel neither reads nor writes them.
+    ``state_dict()`` is torch.optim.Adam's, with a state entry only for parameters that have been updated."""
+
+    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, *, groups=None):
         self.model = model
-        self.param_groups = [{"lr": lr, "betas": betas, "eps": eps}]
         self.step_count = 0
         self.exp_avg = None
         self.exp_avg_sq = None
+        self.grouped = groups is not None
+        if not self.grouped:
+            self.param_groups = [{"lr": lr, "betas": betas, "eps": eps}]
+            return
+        names = [n for n, _ in model.named_parameters()]
+        owner = {}
+        self.param_groups = []
+        for k, spec in enumerate(groups):
+            unknown = set(spec) - set(_GROUP_KEYS)
+            if unknown or "params" not in spec:
+                raise ValueError(f"FusedAdam: group {k} needs 'params' and may set {_GROUP_KEYS[1:]}; got {sorted(spec)}")
+            entries = (spec["params"],) if isinstance(spec["params"], str) else tuple(spec["params"])
+            members = []
+            for e in entries:
+                hit = [n for n in names if _matches(n, e)]
+                if not hit:
+                    raise ValueError(f"FusedAdam: group {k}: {e!r} matches no parameter")
+                for n in hit:
+                    if n in owner:
+                        raise ValueError(f"FusedAdam: parameter {n} is matched by group {owner[n]} and by group {k}")
+                    owner[n] = k
+                members += hit
+            self.param_groups.append({
+                "lr": lr, "betas": tuple(spec.get("betas", betas)), "eps": spec.get("eps", eps),
+                "weight_decay": float(spec.get("weight_decay", 0.0)), "lr_scale": float(spec.get("lr_scale", 1.0)),
+                "frozen": bool(spec.get("frozen", False)), "decoupled": bool(spec.get("decoupled", False)),
+                "spec": entries, "params": [n for n in names if n in members]})
+        rest = [n for n in names if n not in owner]
+        if rest:
+            self.param_groups.append({"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": 0.0, "lr_scale": 1.0,
+                                      "frozen": False, "decoupled": False, "spec": (), "params": rest})
+        self.steps = {n: 0 for n in names}       # per parameter: the number of updates it has had
+
+    def _require_groups(self, what):
+        if not self.grouped:
+            raise RuntimeError(f"FusedAdam.{what} needs parameter groups: build the optimiser with groups=[...]")
+
+    def _set_frozen(self, prefix, value):
+        self._require_groups("freeze / unfreeze")
+        spec = (prefix,) if isinstance(prefix, str) else tuple(prefix)
+        hit = [g for g in self.param_groups if g["spec"] == spec]
+        if not hit:
+            raise ValueError(f"FusedAdam: no group was built with params={prefix!r} "
+                             f"(groups: {[list(g['spec']) for g in self.param_groups if g['spec']]})")
+        hit[0]["frozen"] = value
+
+    def freeze(self, prefix):
+        """Stop updating the group that was built with params=prefix (the same as param_groups[k]["frozen"] = True): its
+        values, moments and step numbers stay as they are, whether or not its parameters get gradients."""
+        self._set_frozen(prefix, True)
+
+    def unfreeze(self, prefix):
+        """Update that group again; its parameters go on from their own step numbers (from 1 if they never were updated)."""
+        self._set_frozen(prefix, False)
 
     def _state(self):
         flat_p, flat_g, _ = self.model.flat_buffers()
@@ -199,7 +280,54 @@ class FusedAdam:
                 flat_g[o:o + k].view(p.shape).copy_(p.grad)
         return missing
 
+    def _segments(self, flat_g):
+        """The table of one grouped step: a segment per parameter that is updated -- it has a gradient and its group is not
+        frozen -- over its padded slot [offset, offset + ceil64(numel)) (the pad is zero in every buffer and stays zero under
+        Adam with or without decay), sorted by offset, neighbours with equal settings and step merged.  Gradients that
+        autograd keeps outside the flat buffer are copied into their slots (_gather_grads's rule); the slots of parameters
+        that are not updated are left alone.  Returns (segments, names of the updated parameters)."""
+        _, _, offsets = self.model.flat_buffers()
+        named = dict(self.model.named_parameters())
+        if all(p.grad is None for p in named.values()):
+            raise RuntimeError("FusedAdam.step: no parameter has a gradient: run backward first")
+        base = flat_g.data_ptr()
+        slots, updated = [], []
+        for g in self.param_groups:
+            if g["frozen"]:
+                continue
+            for n in g["params"]:
+                p = named[n]
+                if p.grad is None:
+                    continue
+                o, k = offsets[n]
+                if p.grad.data_ptr() != base + 4 * o or not p.grad.is_contiguous():
+                    flat_g[o:o + k].view(p.shape).copy_(p.grad)
+                settings = (g["lr"] * g["lr_scale"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                            self.steps[n] + 1, int(g["decoupled"]))
+                slots.append((o, o + (k + 63) // 64 * 64, settings))
+                updated.append(n)
+        if not slots:
+            raise RuntimeError("FusedAdam.step: no parameter has a gradient: every parameter with one is in a frozen group")
+        slots.sort(key=lambda s: s[0])
+        segments = []
+        for begin, end, settings in slots:
+            if segments and segments[-1][1] == begin and segments[-1][2:] == settings:
+                segments[-1] = (segments[-1][0], end) + settings
+            else:
+                segments.append((begin, end) + settings)
+        if len(segments) > MAX_ADAM_SEGMENTS:
+            raise RuntimeError(f"FusedAdam.step: {len(segments)} segments with different settings or steps; one launch "
+                               f"carries {MAX_ADAM_SEGMENTS}")
+        return segments, updated
+
     def step(self, grad_scale: float = 1.0):
+        if self.grouped:
+            flat_p, flat_g = self._state()
+            segments, updated = self._segments(flat_g)
+            ops.adam_segments(flat_p, flat_g, self.exp_avg, self.exp_avg_sq, segments, grad_scale)
+            for n in updated:
+                self.steps[n] += 1
+            return
         flat_p, flat_g = self._state()
         missing = self._gather_grads(flat_g)
         g = self.param_groups[0]
@@ -219,7 +347,58 @@ class FusedAdam:
 
     # checkpoint format of torch.optim.Adam, so `optimizer_state` in model.pth interchanges
     # (utils/train_logger.py:95-112, train.py:56-57)
+    def _grouped_state_dict(self):
+        """torch.optim.Adam's format: a param_groups entry per group with `params` as indices into named_parameters(), and
+        state[i] only for parameters that have been updated (step >= 1), each with its own step.  `lr` is the schedule's
+        rate; lr_scale, frozen and decoupled ride along (torch keeps keys it does not know).  torch.optim.Adam built with the
+        same grouping loads the result (AdamW for groups with decoupled=True); it knows no lr_scale, so whoever hands the
+        dict to torch multiplies each group's lr by its lr_scale."""
+        self._state()
+        _, _, offsets = self.model.flat_buffers()
+        named = list(self.model.named_parameters())
+        index = {n: i for i, (n, _) in enumerate(named)}
+        state = {}
+        for i, (n, p) in enumerate(named):
+            if self.steps[n] >= 1:
+                o, k = offsets[n]
+                state[i] = {"step": torch.tensor(float(self.steps[n])),
+                            "exp_avg": self.exp_avg[o:o + k].view(p.shape).clone(),
+                            "exp_avg_sq": self.exp_avg_sq[o:o + k].view(p.shape).clone()}
+        groups = [{"lr": g["lr"], "betas": g["betas"], "eps": g["eps"], "weight_decay": g["weight_decay"], "amsgrad": False,
+                   "lr_scale": g["lr_scale"], "frozen": g["frozen"], "decoupled": g["decoupled"],
+                   "params": [index[n] for n in g["params"]]} for g in self.param_groups]
+        return {"state": state, "param_groups": groups}
+
+    def _load_grouped_state_dict(self, sd):
+        self._state()
+        _, _, offsets = self.model.flat_buffers()
+        names = [n for n, _ in self.model.named_parameters()]
+        index = {n: i for i, n in enumerate(names)}
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError(f"FusedAdam.load_state_dict: {len(sd['param_groups'])} groups for an optimiser with "
+                             f"{len(self.param_groups)}")
+        for k, (g, saved) in enumerate(zip(self.param_groups, sd["param_groups"])):
+            if list(saved["params"]) != [index[n] for n in g["params"]]:
+                raise ValueError(f"FusedAdam.load_state_dict: group {k} holds other parameters than the optimiser's group {k}")
+        for g, saved in zip(self.param_groups, sd["param_groups"]):
+            g.update(lr=saved["lr"], betas=tuple(saved["betas"]), eps=saved["eps"],
+                     weight_decay=float(saved.get("weight_decay", 0.0)), lr_scale=float(saved.get("lr_scale", 1.0)),
+                     frozen=bool(saved.get("frozen", False)), decoupled=bool(saved.get("decoupled", False)))
+        for i, n in enumerate(names):
+            o, k = offsets[n]
+            st = sd["state"].get(i)
+            if st is None:                      # never updated: no moments, step 0
+                self.exp_avg[o:o + k].zero_()
+                self.exp_avg_sq[o:o + k].zero_()
+                self.steps[n] = 0
+            else:
+                self.exp_avg[o:o + k].copy_(st["exp_avg"].reshape(-1))
+                self.exp_avg_sq[o:o + k].copy_(st["exp_avg_sq"].reshape(-1))
+                self.steps[n] = int(float(st["step"]))
+
     def state_dict(self):
+        if self.grouped:
+            return self._grouped_state_dict()
         flat_p, _ = self._state()
         _, _, offsets = self.model.flat_buffers()
         state = {}
@@ -236,6 +415,8 @@ class FusedAdam:
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
+        if self.grouped:
+            return self._load_grouped_state_dict(sd)
         self._state()
         _, _, offsets = self.model.flat_buffers()
         names = [n for n, _ in self.model.named_parameters()]

@@ -33,7 +33,8 @@ extern "C" {
  * version 8 that way, vqa_softmax_topk after them, and the two entry points of cached question features
  * (vqa_att_score_grouped_pairs_fwd, vqa_gather_rows) after that, then image preprocessing (vqa_preprocess_supported,
  * vqa_preprocess_images), then the two entry points of training on cached image features (vqa_gather_rows_drop,
- * vqa_att_apply_gather_dscore), then the plan query vqa_gemm_plan, then the tall GEMM's own query vqa_gemm_tall_bf16_plan -- a caller
+ * vqa_att_apply_gather_dscore), then the plan query vqa_gemm_plan, then the tall GEMM's own query vqa_gemm_tall_bf16_plan, then
+ * Adam over a table of segments (vqa_adam_segments, with the struct vqa_adam_segment) -- a caller
  * built against the earlier version-8 header finds every prototype it knows unchanged. */
 #define VQA_ABI_VERSION 8
 
@@ -638,6 +639,32 @@ int vqa_gemm_x3(const float* A, int64_t lda, int transA, const float* B, int64_t
 /* ---- optimiser: torch.optim.Adam defaults over one flat buffer (train.py:55,80) ------------- */
 int vqa_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
              float beta1, float beta2, float eps, int step, float grad_scale, vqa_stream_t stream);
+
+/* ---- optimiser with parameter groups: Adam / AdamW over a table of segments of the flat buffer ----
+ * One launch updates every listed range [begin, end) with that segment's own step number (bias correction), learning
+ * rate, betas, eps and weight decay; elements outside every segment are neither read nor written.  `segs` is a HOST
+ * array: it travels to the kernel by value in the launch arguments (no allocation, no upload, no sync).
+ *   weight_decay == 0: the arithmetic of vqa_adam expression for expression -- the segment holds the bits vqa_adam
+ *     gives on that slice with that lr and step; no decay term is evaluated (0 * p would change signed zeros and
+ *     non-finite values);
+ *   weight_decay > 0, decoupled == 0 (torch.optim.Adam): the gradient is grad * grad_scale + weight_decay * param;
+ *   weight_decay > 0, decoupled == 1 (torch.optim.AdamW): param is first multiplied by 1 - lr * weight_decay.
+ * VQA_ERR_INVALID, before any HIP call, for: a null or not 16-byte aligned pointer, n < 1, n_segs outside
+ * 1..VQA_ADAM_MAX_SEGMENTS, a segment with begin or end no multiple of 4, begin < 0, begin >= end or end > n, segments that are
+ * not sorted and disjoint (begin below the previous end), step < 1, weight_decay < 0 (or NaN), decoupled outside 0/1.
+ * The grid is capped at VQA_ADAM_SEGMENTS_MAX_BLOCKS workgroups of 256 lanes, one float4 per lane: a longer walk
+ * (more than VQA_ADAM_SEGMENTS_MAX_BLOCKS * 1024 floats from the first begin to the last end) strides. */
+#define VQA_ADAM_MAX_SEGMENTS 64
+#define VQA_ADAM_SEGMENTS_MAX_BLOCKS 2048
+typedef struct {
+  int64_t begin, end;   /* [begin, end) in elements of the flat buffer; both multiples of 4 */
+  float lr, beta1, beta2, eps, weight_decay;
+  int step;             /* >= 1: this segment's own step number (bias correction) */
+  int decoupled;        /* 0: L2 as torch.optim.Adam; 1: torch.optim.AdamW */
+} vqa_adam_segment;
+int vqa_adam_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                      const vqa_adam_segment* segs /* HOST array */, int n_segs, float grad_scale,
+                      vqa_stream_t stream);
 
 #ifdef __cplusplus
 }
