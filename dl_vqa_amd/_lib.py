@@ -145,6 +145,7 @@ PROTOTYPES = {
     "vqa_pconv_dgrad": (i32, [vp, u8p, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_adam": (i32, [f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, i32, f32, vp]),
     "vqa_adam_segments": (i32, [f32p, f32p, f32p, f32p, i64, vp, i32, f32, vp]),      # segs: a HOST array of AdamSegment
+    "vqa_conv3x3_x3_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), i32]),
 }
 
 K_GEMM, K_CONV_FWD, K_CONV_DGRAD, K_CONV_WGRAD = 0, 1, 2, 3

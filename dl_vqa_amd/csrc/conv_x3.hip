@@ -437,6 +437,25 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::THREADS / 256) void conv_wgrad_x
   store_acc_tiles<Cfg>(acc, slab + (int64_t)tc.split * pa.KI * Co, Co, pa.KI, Co, m0, n0, wm, wn, lane);
 }
 
+// The tiling of one forward / dgrad launch: asked by the launchers and by vqa_conv3x3_x3_plan.  One workgroup per CU: nothing
+// else covers a tile's prologue and epilogue, so more than 256 tiles are walked persistently (VQA_PERSISTENT=0 selects one
+// workgroup per tile).
+struct X3Tiles { int bm, bn, waves, tiles_m, tiles_n; bool persistent; };
+template <class Cfg>
+static X3Tiles x3_tiles(int rows, int cols) {
+  X3Tiles t{Cfg::BM, Cfg::BN, Cfg::THREADS / 64, (rows + Cfg::BM - 1) / Cfg::BM, (cols + Cfg::BN - 1) / Cfg::BN, false};
+  t.persistent = knobs().persistent != 0 && t.tiles_m * t.tiles_n > 256;
+  return t;
+}
+// forward: rows = the four conv pixels of every window; dgrad: rows = input pixels
+template <class Cfg>
+static X3Tiles fwd_x3_tiles(const ConvGeom& g) { return x3_tiles<Cfg>(4 * g.B * g.Hp * g.Wp, g.Co); }
+template <class Cfg>
+static X3Tiles dgrad_x3_tiles(const ConvGeom& g) { return x3_tiles<Cfg>(g.B * g.H * g.W, g.CiP); }
+// which tile a layer runs: 192 x 128 for more than 64 output columns, else 256 x 64 (dgrad: the 16-wave one)
+static bool fwd_x3_wide(int Co) { return Co > 64; }
+static bool dgrad_x3_wide(int CiP) { return CiP > 64; }
+
 // XP / DP: the activation / pooled-gradient operand is x3-packed (the *x loaders) or fp32 (the conv.hip loaders, split in
 // the kernel); OP: the pooled output is written packed
 template <class Cfg, bool XP, bool OP>
@@ -447,14 +466,11 @@ static int launch_fwd_x3(const void* x, const void* wf, const float* bias, void*
   const int nWin = g.B * g.Hp * g.Wp, K = 9 * g.CiP;
   typename AL::Params pa{static_cast<decltype(AL::Params::x)>(x), g.H, g.W, g.CiP, g.Hp, g.Wp, g.stride, nWin, K};
   typename PlainCx<Cfg::NVB, Cfg::LT>::Params pb{wf, g.Co, g.Co, K, (int64_t)K * g.Co};
-  const int tiles_m = (4 * nWin + Cfg::BM - 1) / Cfg::BM, tiles_n = (g.Co + Cfg::BN - 1) / Cfg::BN;
-  // one workgroup per CU: nothing else covers a tile's prologue and epilogue, so the tiles are walked persistently
-  // (VQA_PERSISTENT=0 selects one workgroup per tile)
-  const int tiles = tiles_m * tiles_n;
-  return launch_tiles(knobs().persistent != 0 && tiles > 256, conv_fwd_x3_persistent_kernel<Cfg, AL, OP>,
+  const X3Tiles t = fwd_x3_tiles<Cfg>(g);
+  return launch_tiles(t.persistent, conv_fwd_x3_persistent_kernel<Cfg, AL, OP>,
                       {"attr(conv_fwd_x3_p)", "conv_fwd_x3_persistent launch"}, 256, conv_fwd_x3_kernel<Cfg, AL, OP>,
-                      {"attr(conv_fwd_x3)", "conv_fwd_x3 launch"}, tiles, Cfg::THREADS, SL::BYTES, s, pa, pb, bias, pooled,
-                      amax, g.Co, tiles_m, tiles_n, K / BK);
+                      {"attr(conv_fwd_x3)", "conv_fwd_x3 launch"}, t.tiles_m * t.tiles_n, Cfg::THREADS, SL::BYTES, s, pa, pb,
+                      bias, pooled, amax, g.Co, t.tiles_m, t.tiles_n, K / BK);
 }
 
 template <class Cfg, bool DP>
@@ -465,12 +481,11 @@ static int launch_dgrad_x3(const void* dp, const uint8_t* am, const void* wd, fl
   const int rows = g.B * g.H * g.W, K = 9 * g.Co;
   typename AL::Params pa{static_cast<decltype(AL::Params::dp)>(dp), am, g.H, g.W, g.Hp, g.Wp, g.Co, g.stride, rows, K};
   typename PlainCx<Cfg::NVB, Cfg::LT>::Params pb{wd, g.CiP, g.CiP, K, (int64_t)K * g.CiP};
-  const int tiles_m = (rows + Cfg::BM - 1) / Cfg::BM, tiles_n = (g.CiP + Cfg::BN - 1) / Cfg::BN;
-  const int tiles = tiles_m * tiles_n;
-  return launch_tiles(knobs().persistent != 0 && tiles > 256 /* see launch_fwd_x3 */,
-                      conv_dgrad_x3_persistent_kernel<Cfg, AL>, {"attr(conv_dgrad_x3_p)", "conv_dgrad_x3_persistent launch"},
-                      256, conv_dgrad_x3_kernel<Cfg, AL>, {"attr(conv_dgrad_x3)", "conv_dgrad_x3 launch"}, tiles,
-                      Cfg::THREADS, SL::BYTES, s, pa, pb, dx, g.CiP, tiles_m, tiles_n, K / BK);
+  const X3Tiles t = dgrad_x3_tiles<Cfg>(g);
+  return launch_tiles(t.persistent, conv_dgrad_x3_persistent_kernel<Cfg, AL>,
+                      {"attr(conv_dgrad_x3_p)", "conv_dgrad_x3_persistent launch"}, 256, conv_dgrad_x3_kernel<Cfg, AL>,
+                      {"attr(conv_dgrad_x3)", "conv_dgrad_x3 launch"}, t.tiles_m * t.tiles_n, Cfg::THREADS, SL::BYTES, s, pa, pb,
+                      dx, g.CiP, t.tiles_m, t.tiles_n, K / BK);
 }
 
 static WgradPlan plan_wgrad_x3(const ConvGeom& g) {
@@ -623,7 +638,7 @@ int vqa_conv3x3_relu_pool_fwd_x3(const void* x, int x_packed, const void* wf, co
             static_cast<const char*>(x) + c.xo * (x_packed ? 6 : 4), wf, bias,
             static_cast<char*>(pooled) + c.po * (pooled_packed ? 6 : 4), argmax + c.po, c.g, s);
       };
-      return Co > 64 ? go(CfgX{}) : go(CfgXn{});
+      return fwd_x3_wide(Co) ? go(CfgX{}) : go(CfgXn{});
     });
   });
 }
@@ -640,7 +655,7 @@ int vqa_conv3x3_dgrad_x3(const void* dpooled, int dp_packed, const uint8_t* argm
         return launch_dgrad_x3<decltype(cfg), decltype(dpk)::value>(
             static_cast<const char*>(dpooled) + c.po * (dp_packed ? 6 : 4), argmax + c.po, wd, dx + c.xo, c.g, s);
       };
-      return CiP > 64 ? go(CfgXd{}) : go(CfgXnd{});
+      return dgrad_x3_wide(CiP) ? go(CfgXd{}) : go(CfgXnd{});
     });
   });
 }
@@ -678,6 +693,33 @@ int vqa_conv3x3_wgrad_x3(const void* x, int x_packed, const float* dpooled, cons
         if (!dbias) return (int)VQA_OK;
         return launch_bias_grad(dpooled, argmax, dbias, nullptr, (int64_t)B * g1.Hp * g1.Wp, Co, bias_parts, s);
       });
+}
+
+int vqa_conv3x3_x3_plan(int pass, int B, int H, int W, int CiP, int Co, int stride, int32_t* out, int n_out) {
+  VQA_REQUIRE(pass >= 0 && pass <= 2 && B > 0 && out && n_out >= 11,
+              "vqa_conv3x3_x3_plan: bad args (pass=%d B=%d n_out=%d)", pass, B, n_out);
+  VQA_REQUIRE(CiP > 0 && Co > 0 && (stride == 1 || stride == 2) && !no_windows(B, H, W, stride),
+              "vqa_conv3x3_x3_plan: bad args (H=%d W=%d CiP=%d Co=%d stride=%d)", H, W, CiP, Co, stride);
+  const int chunk = x3_chunk(B, H, W, CiP, Co, stride);
+  VQA_REQUIRE(chunk > 0, "vqa_conv3x3_x3_plan: one %dx%dx%d image reaches 4 GiB", H, W, CiP);
+  const ConvGeom g = make_geom(B < chunk ? B : chunk, H, W, CiP, Co, stride);      // the first launch of the walk
+  if (int rc = check_geom("vqa_conv3x3_x3_plan", g)) return rc;
+  VQA_REQUIRE(x3_conv_ok(CiP, Co, g.Wp), "vqa_conv3x3_x3_plan: needs CiP, Co multiples of %d and 2*Wp >= %d (CiP=%d Co=%d Wp=%d)", BK,
+              BK, CiP, Co, g.Wp);
+  const int launches = (B + chunk - 1) / chunk;
+  if (pass == 2) {
+    const WgradPlan p = plan_wgrad_x3(g);
+    const int32_t v[11] = {CfgXw::BM, CfgXw::BN, CfgXw::THREADS / 64, p.tiles_m, p.tiles_n, 0, chunk, launches, p.nk, p.splits,
+                           p.ks_per_split};
+    for (int i = 0; i < 11; ++i) out[i] = v[i];
+    return VQA_OK;
+  }
+  const X3Tiles t = pass == 0 ? (fwd_x3_wide(Co) ? fwd_x3_tiles<CfgX>(g) : fwd_x3_tiles<CfgXn>(g))
+                              : (dgrad_x3_wide(CiP) ? dgrad_x3_tiles<CfgXd>(g) : dgrad_x3_tiles<CfgXnd>(g));
+  const int nk = 9 * (pass == 0 ? CiP : Co) / BK;
+  const int32_t v[11] = {t.bm, t.bn, t.waves, t.tiles_m, t.tiles_n, t.persistent, chunk, launches, nk, 1, nk};
+  for (int i = 0; i < 11; ++i) out[i] = v[i];
+  return VQA_OK;
 }
 
 }  // extern "C"

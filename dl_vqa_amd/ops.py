@@ -222,6 +222,22 @@ def conv_x3_supported(H: int, W: int, CiP: int, Co: int, stride: int) -> bool:
     return bool(_lib.load().vqa_conv3x3_x3_supported(H, W, CiP, Co, stride))
 
 
+CONV_X3_PASSES = {"forward": 0, "dgrad": 1, "wgrad": 2}
+CONV_X3_PLAN_FIELDS = ("BM", "BN", "waves", "tiles_m", "tiles_n", "persistent", "chunk", "launches", "nk", "splits", "ks_per_split")
+
+
+def conv_x3_plan(pass_: str, B: int, H: int, W: int, CiP: int, Co: int, stride: int = 1) -> dict:
+    """What conv_fwd / conv_dgrad / conv_wgrad with x3=True run for this layer and batch (pass_: "forward", "dgrad" or
+    "wgrad") under the VQA_* knobs in force, from the host functions the launchers use (vqa_conv3x3_x3_plan); makes no HIP
+    call.  `tiles` = tiles_m * tiles_n of the first launch; chunk: images per launch."""
+    import ctypes
+    out = (ctypes.c_int32 * len(CONV_X3_PLAN_FIELDS))()
+    call("vqa_conv3x3_x3_plan", CONV_X3_PASSES[pass_], B, H, W, CiP, Co, stride, out, len(out))
+    plan = dict(zip(CONV_X3_PLAN_FIELDS, out))
+    plan["tiles"] = plan["tiles_m"] * plan["tiles_n"]
+    return plan
+
+
 def conv_fwd(x: torch.Tensor, wf: torch.Tensor, bias: torch.Tensor, stride: int = 1, tag: int = 0, x3: bool = False,
              out_packed: bool = False):
     """x NHWC [B,H,W,CiP] -> (pooled [B,Hp,Wp,Co], argmax uint8 same shape).  x3: fp32 on the bf16 matrix cores

@@ -35,8 +35,10 @@ extern "C" {
  * vqa_preprocess_images), then the two entry points of training on cached image features (vqa_gather_rows_drop,
  * vqa_att_apply_gather_dscore), then the plan query vqa_gemm_plan, then the tall GEMM's own query vqa_gemm_tall_bf16_plan, then
  * Adam over a table of segments (vqa_adam_segments, with the struct vqa_adam_segment) -- a caller
- * built against the earlier version-8 header finds every prototype it knows unchanged. */
-#define VQA_ABI_VERSION 8
+ * built against the earlier version-8 header finds every prototype it knows unchanged.
+ * Version 9 adds the plan query of the fp32x3 conv entry points (vqa_conv3x3_x3_plan), appended at the end; every
+ * version-8 prototype is unchanged. */
+#define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
 #define VQA_ERR_INVALID 1 /* bad argument (shape, alignment, null pointer) */
@@ -665,6 +667,15 @@ typedef struct {
 int vqa_adam_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                       const vqa_adam_segment* segs /* HOST array */, int n_segs, float grad_scale,
                       vqa_stream_t stream);
+
+/* ---- the plan of the fp32x3 conv entry points ------------------------------------------------
+ * What vqa_conv3x3_relu_pool_fwd_x3 (pass 0), vqa_conv3x3_dgrad_x3 (pass 1) and vqa_conv3x3_wgrad_x3 (pass 2) run for a layer
+ * and batch under the VQA_* knobs in force, from the host functions their launchers call; no HIP call is made.  A batch is
+ * walked in launches of `chunk` images; the tiles are those of the first launch (min(B, chunk) images).
+ * out[0..10] = BM, BN, waves per workgroup, tiles_m, tiles_n, persistent (0: one workgroup per tile, 1: 256 workgroups walk the
+ * tiles; always 0 for pass 2), chunk, launches, nk (K-steps of 32), splits, ks_per_split (pass 0 and 1: 1 and nk); n_out >= 11.
+ * VQA_ERR_INVALID for a pass outside 0..2, a null out, a short n_out and every layer vqa_conv3x3_x3_supported refuses. */
+int vqa_conv3x3_x3_plan(int pass, int B, int H, int W, int CiP, int Co, int stride, int32_t* out, int n_out);
 
 #ifdef __cplusplus
 }

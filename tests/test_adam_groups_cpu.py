@@ -26,7 +26,7 @@ def test_symbol_is_declared_bound_and_exported():
     text = open(os.path.join(ROOT, "include", "vqa_hip.h")).read()
     head = text[:re.search(r"^#define\s+VQA_ABI_VERSION", text, flags=re.M).start()]
     assert "vqa_adam_segments" in head                      # listed with the other append-only additions
-    assert _lib.header_abi_version() == 8
+    assert _lib.header_abi_version() == 9
     assert "vqa_adam_segments" in _lib.PROTOTYPES and hasattr(lib, "vqa_adam_segments")
     assert ctypes.sizeof(_lib.AdamSegment) == 48            # two int64, five floats, two ints, padded to 8 bytes
     assert int(re.search(r"^#define\s+VQA_ADAM_MAX_SEGMENTS\s+(\d+)", text, flags=re.M).group(1)) == _lib.ADAM_MAX_SEGMENTS == 64

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import conv_lattice_ref as L
+from tests import gemm_lattice_ref as G
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -73,8 +74,8 @@ def poisoned(*shape, dtype=F32):
 class Tally:
     """Exact comparisons of one case; prints the case's [lattice] line and fails after it if anything differed."""
 
-    def __init__(self, family, key, note=""):
-        self.family, self.key, self.note, self.n, self.bad, self.where = family, key, note, 0, 0, []
+    def __init__(self, family, key, note="", lattice="bf16"):
+        self.family, self.key, self.note, self.lattice, self.n, self.bad, self.where = family, key, note, lattice, 0, 0, []
 
     def eq(self, name, got, want):
         """got (device, any kernel output type) == want; a float64 reference is narrowed to got's type by round-to-nearest-even"""
@@ -93,9 +94,9 @@ class Tally:
                               f"got {got[tuple(first)].item()} want {want[tuple(first)].item()}")
 
     def done(self):
-        s = L.cached_stats(*self.key)
+        s = L.cached_stats(*self.key, lattice=self.lattice)
         n = s["windows"]
-        print(f"[lattice] {self.family} B,Ci,H,W,Co,ks,stride={self.key}{self.note}: windows {n} tied {round(s['tied'] * n)} "
+        print(f"[lattice] {self.family} lattice={self.lattice} B,Ci,H,W,Co,ks,stride={self.key}{self.note}: windows {n} tied {round(s['tied'] * n)} "
               f"zero-max {round(s['zero_max'] * n)} compared {self.n} mismatches {self.bad}")
         assert self.bad == 0 and not self.where, "\n".join(self.where)
 
@@ -257,26 +258,46 @@ def test_first_block_persistent_kernels_take_a_second_item(ops):
 
 
 # ----------------------------------------------------------------------------- fp32 on the bf16 matrix cores (x3)
-@pytest.mark.parametrize("shape", L.X3_CASES, ids=str)
-def test_fp32x3(ops, shape):
-    """The exact three-way bf16 split of a lattice value is (value, 0, 0): the six partial products are exact too.  fp32 and
-    x3-packed input, plain and packed output, dgrad from the fp32 and from the packed pooled gradient, wgrad with and
-    without the packed pooled gradient, the bias gradient of x3_pack_pooled_grad; bytes and values equal the reference's, and
-    those of the fp32 MFMA kernels run beside them."""
+def x3_plans(ops, shape):
+    """ops.conv_x3_plan of the three passes: what the launchers decide for this layer and batch under the knobs in force"""
+    B, H, W, Ci, Co, stride = shape
+    return {p: ops.conv_x3_plan(p, B, H, W, Ci, Co, stride) for p in ("forward", "dgrad", "wgrad")}
+
+
+def run_x3(ops, shape, lattice="bf16", note=""):
+    """fp32 and x3-packed input, plain and packed output, dgrad from the fp32 and from the packed pooled gradient, wgrad with
+    and without the packed pooled gradient, the bias gradient of x3_pack_pooled_grad; bytes and values equal the reference's,
+    and those of the fp32 MFMA kernels run beside them in all three passes -- on a plane lattice these are fp32-exact,
+    order-free values whose mid and lo planes are not zero: "fp32x3 = fp32", bit for bit.  The split and every packed tensor
+    (x3_split of the packed weights; x3_pack of x, dy and the fp32 pooled output; the pooled tensor the packed epilogue
+    writes; the packed gradient of x3_pack_pooled_grad) are compared PLANE BY PLANE with x3_planes: the sum of the planes
+    alone would not notice a swapped mid and lo plane."""
     B, H, W, Ci, Co, stride = shape
     assert ops.conv_x3_supported(H, W, Ci, Co, stride) and not ops.conv_x3_supported(*L.X3_NOT_ADMITTED)
     k = L.key(*shape)
-    case, ref = L.cached(*k)
+    case, ref = L.cached(*k, lattice=lattice)
     pooled_r, amax_r, dx_r = nhwc_ref(ref)
-    t = Tally("fp32x3", k)
+    t = Tally("fp32x3", k, note, lattice)
     xd, bd, dyd, am = dev(L.nhwc(case.x)), dev(case.b), dev(L.nhwc(case.dy)), amax_r.to(DEV)
     wf, wd = ops.conv_pack_weights(dev(case.w), Ci)
     wfx, wdx = ops.x3_split(wf), ops.x3_split(wd)
+    torch.cuda.synchronize()
+    for name, planes, packed in (("wf", wfx, wf), ("wd", wdx, wd)):
+        for i, want in enumerate(G.x3_planes(packed.cpu().double())):
+            t.eq(f"x3_split({name}): plane {i}", planes[i].double(), want)
     xp, dyp = ops.x3_pack(xd), ops.x3_pack(dyd)
     t.eq("x3_pack(x), unpacked", L.x3_unpack(xp.cpu()), L.nhwc(case.x))
+    t.eq("x3_pack(x): planes", xp, L.x3_pack_planes(L.nhwc(case.x)))
+    t.eq("x3_pack(dy): planes", dyp, L.x3_pack_planes(L.nhwc(case.dy)))
+    t.eq("x3_pack(pooled): planes", ops.x3_pack(dev(pooled_r)), L.x3_pack_planes(pooled_r))
     p32, a32 = ops.conv_fwd(xd, wf, bd, stride)
     t.eq("fp32 MFMA: pooled", p32, pooled_r)
     t.eq("fp32 MFMA: bytes", a32, amax_r)
+    t.eq("fp32 MFMA: dX", ops.conv_dgrad(dyd, am, wd, xd.shape, stride), dx_r)
+    dw, db = poisoned(Co, Ci, 3, 3), poisoned(Co)
+    ops.conv_wgrad(xd, dyd, am, dw, db, stride)
+    t.eq("fp32 MFMA: dW", dw, ref.dw)
+    t.eq("fp32 MFMA: dbias", db, ref.db)
     for name, xin in (("fp32 in", xd), ("packed in", xp)):
         p, a = ops.conv_fwd(xin, wfx, bd, stride, x3=True)
         t.eq(f"{name}: pooled", p, pooled_r)
@@ -285,11 +306,14 @@ def test_fp32x3(ops, shape):
         torch.cuda.synchronize()
         assert not bool(torch.isnan(p.float()).any())
         t.eq(f"{name}: pooled packed, unpacked", L.x3_unpack(p.cpu()), pooled_r)
+        t.eq(f"{name}: pooled packed: planes", p, L.x3_pack_planes(pooled_r))
         t.eq(f"{name}: bytes (packed out)", a, amax_r)
     t.eq("dgrad from fp32 dP", ops.conv_dgrad(dyd, am, wdx, xd.shape, stride, x3=True), dx_r)
     t.eq("dgrad from packed dP", ops.conv_dgrad(dyp, am, wdx, xd.shape, stride, x3=True), dx_r)
     db_s = poisoned(Co)
-    t.eq("x3_pack_pooled_grad: packed dP, unpacked", L.x3_unpack(ops.x3_pack_pooled_grad(dyd, am, db_s).cpu()), L.nhwc(case.dy))
+    dyp_s = ops.x3_pack_pooled_grad(dyd, am, db_s)
+    t.eq("x3_pack_pooled_grad: packed dP, unpacked", L.x3_unpack(dyp_s.cpu()), L.nhwc(case.dy))
+    t.eq("x3_pack_pooled_grad: planes", dyp_s, L.x3_pack_planes(L.nhwc(case.dy)))
     t.eq("x3_pack_pooled_grad: dbias", db_s, ref.db)
     for name, xin, packed_dp in (("fp32 in", xd, None), ("packed in", xp, None), ("packed in, packed dP", xp, dyp),
                                  ("fp32 in, packed dP", xd, dyp)):
@@ -301,6 +325,59 @@ def test_fp32x3(ops, shape):
     ops.conv_wgrad(xp, dyd, am, dw, None, stride, x3=True, dpooled_packed=dyp)        # dbias not asked for
     t.eq("wgrad packed in, packed dP, no dbias: dW", dw, ref.dw)
     t.done()
+
+
+@pytest.mark.parametrize("shape", L.X3_CASES, ids=str)
+def test_fp32x3(ops, shape):
+    """The exact three-way bf16 split of a lattice value is (value, 0, 0): the six partial products are exact too, and five of
+    them are zero.  Everything run_x3 runs; test_fp32x3_planes feeds the other five."""
+    run_x3(ops, shape)
+
+
+# shape -> (forward tile, dgrad tile and waves)
+PLANE_TILES = {(2, 36, 36, 32, 64, 1): ((256, 64), (256, 64, 16)), (1, 36, 36, 96, 128, 1): ((192, 128), (192, 128, 8)),
+               (2, 37, 67, 32, 64, 2): ((256, 64), (256, 64, 16))}
+
+
+@pytest.mark.parametrize("lattice,shape", L.PLANE_CASES, ids=str)
+def test_fp32x3_planes(ops, lattice, shape):
+    """The plane lattices of tests/conv_lattice_ref.py: integers whose hi, mid and lo planes are occupied, every sum below 2^24,
+    the three dropped plane products exactly zero -- each of the six kept products (hh, hm, mh, mm, hl, lh) reaches the
+    result of each pass in some case here, and tests/test_conv_lattice_ref_cpu.py shows that leaving any one out changes at
+    least a tenth of what is compared ([coverage]).  Forward on 256 x 64 and dgrad on the 16-wave 256 x 64 tile (32 -> 64
+    channels), both on 192 x 128 (96 -> 128), asserted from the plan query; `iii` also at the stride-2 map."""
+    plans = x3_plans(ops, shape)
+    fwd, dgrad = PLANE_TILES[shape]
+    assert (plans["forward"]["BM"], plans["forward"]["BN"]) == fwd, plans["forward"]
+    assert (plans["dgrad"]["BM"], plans["dgrad"]["BN"], plans["dgrad"]["waves"]) == dgrad, plans["dgrad"]
+    assert all(p["persistent"] == 0 and p["launches"] == 1 and p["chunk"] == shape[0] for p in plans.values()), plans
+    run_x3(ops, shape, lattice, f" fwd {fwd[0]}x{fwd[1]} dgrad {dgrad[0]}x{dgrad[1]}/{dgrad[2]} waves")
+
+
+@pytest.mark.parametrize("persistent", [1, 0])
+@pytest.mark.parametrize("shape", L.X3_PERSISTENT_CASES, ids=str)
+def test_fp32x3_persistent_kernels(ops, knob, shape, persistent):
+    """More than 256 tiles: conv_fwd_x3_persistent_kernel and conv_dgrad_x3_persistent_kernel walk them on 256 workgroups (the
+    loaders run ahead into the next tile during the epilogue); under VQA_PERSISTENT=0 the same tiles run one per workgroup.
+    (4,114,114,96,128): forward 262, dgrad 271 tiles of 192 x 128; (6,114,114,64,64): forward 294, dgrad 305 tiles of 256 x 64.
+    The bf16-exact lattice (ties and zero maxima included): the same bits either way."""
+    if not persistent:
+        knob("VQA_PERSISTENT", "0")
+    plans = x3_plans(ops, shape)
+    tile = (192, 128) if shape[4] > 64 else (256, 64)
+    for p in ("forward", "dgrad"):
+        assert (plans[p]["BM"], plans[p]["BN"]) == tile and plans[p]["tiles"] > 256 and plans[p]["persistent"] == persistent, plans[p]
+    run_x3(ops, shape, note=f" tiles fwd {plans['forward']['tiles']} dgrad {plans['dgrad']['tiles']} persistent={persistent}")
+
+
+def test_fp32x3_batch_chunks_with_packed_operands(ops, knob):
+    """VQA_CONV_CHUNK=2 walks B = 5 as 2 + 2 + 1 images: the packed input, packed output and packed pooled gradient advance by
+    6 bytes per element from chunk to chunk, wgrad's chunks are further split-K slabs of one reduce.  Lattice `iii` (its dW
+    budget holds over the five images with fewer pooled gradients kept: conv_lattice_ref.PLANE_ARGS)."""
+    knob("VQA_CONV_CHUNK", "2")
+    plans = x3_plans(ops, L.X3_CHUNK_CASE)
+    assert all(p["chunk"] == 2 and p["launches"] == 3 for p in plans.values()), plans
+    run_x3(ops, L.X3_CHUNK_CASE, L.X3_CHUNK_LATTICE, " VQA_CONV_CHUNK=2")
 
 
 # ----------------------------------------------------------------------------- bf16 implicit GEMM

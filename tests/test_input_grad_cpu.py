@@ -48,12 +48,12 @@ def test_new_entry_points_in_header_prototypes_and_library():
     from dl_vqa_amd import _lib
     with open(_lib.HEADER_PATH) as f:
         header = f.read()
-    assert _lib.header_abi_version() == 8
+    assert _lib.header_abi_version() == 9
     for name in NEW_ENTRY_POINTS:
         assert re.search(r"\b" + name + r"\s*\(", header), name
         assert name in _lib.PROTOTYPES, name
     lib = _lib.load()
-    assert lib.vqa_abi_version() == 8
+    assert lib.vqa_abi_version() == 9
     for name in NEW_ENTRY_POINTS:
         assert hasattr(lib, name), name
     # the dedicated path's shape rule: the forward's, minus nothing

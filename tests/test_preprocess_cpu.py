@@ -227,7 +227,7 @@ def test_entry_points_in_header_prototypes_and_library():
     lib = _lib.load()
     for name in ("vqa_preprocess_images", "vqa_preprocess_supported"):
         assert re.search(r"\b%s\s*\(" % name, header) and name in _lib.PROTOTYPES and hasattr(lib, name)
-    assert lib.vqa_abi_version() == _lib.header_abi_version() == 8              # additions: the version stays
+    assert lib.vqa_abi_version() == _lib.header_abi_version() == 9              # 9 since vqa_conv3x3_x3_plan
     from dl_vqa_amd import preprocess as P
     m = re.search(r"typedef struct \{([^{}]*)\} vqa_pre_image_t;", header)
     fields = re.findall(r"\b(\w+)\s*[,;]", m.group(1))

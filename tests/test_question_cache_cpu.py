@@ -166,12 +166,12 @@ def test_new_entry_points_in_header_prototypes_and_library():
     build.build_library(verbose=False)
     with open(_lib.HEADER_PATH) as f:
         header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    assert _lib.header_abi_version() == 8
+    assert _lib.header_abi_version() == 9
     for name in NEW_ENTRY_POINTS:
         assert re.search(r"\b" + name + r"\s*\(", header), name
         assert name in _lib.PROTOTYPES, name
     lib = _lib.load()
-    assert lib.vqa_abi_version() == 8
+    assert lib.vqa_abi_version() == 9
     for name in NEW_ENTRY_POINTS:
         assert hasattr(lib, name), name
 

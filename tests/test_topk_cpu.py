@@ -18,7 +18,7 @@ def test_entry_point_in_header_prototypes_and_library():
     assert "vqa_softmax_topk" in _lib.PROTOTYPES
     lib = _lib.load()
     assert hasattr(lib, "vqa_softmax_topk")
-    assert lib.vqa_abi_version() == _lib.header_abi_version() == 8          # an addition: the version stays
+    assert lib.vqa_abi_version() == _lib.header_abi_version() == 9          # 9 since vqa_conv3x3_x3_plan
 
 
 def test_argument_validation_without_gpu():
