@@ -10,6 +10,7 @@ from __future__ import annotations
 import functools
 import inspect
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 from typing import Callable, Dict, Optional
 
@@ -29,6 +30,10 @@ def _site_seed(base: int, site: int) -> int:
 
 
 _SFX = ("", "_reverse")     # parameter-name suffix of LSTM direction d
+
+# what Engine.conv_routes decides for one conv block; both passes read it
+ConvRoute = namedtuple("ConvRoute", "kind x_shape Co src out dy dx x3 pdg pack_in need_wd")
+_OUT16 = {"nhwc32": torch.float32, "nhwc16": torch.bfloat16, "c16": torch.bfloat16}     # a bf16 block's out_dtype by route.out
 
 
 def _gemm(A, B, C, M, N, K, x3=False, **kw):
@@ -120,17 +125,56 @@ class Engine:
                                  f"of 64 after the first block (num_channels={self.channels}, stride={self.stride})")
         self._sides = {}        # the side stream of each device (_on_side_stream)
 
-    def _pconv_ok(self, H: int, W: int) -> bool:
-        """bf16 path: do the patch convolutions cover every block after the first for an H x W image?"""
-        if os.environ.get("VQA_PCONV", "1") == "0" or self.stride != 1:
-            return False
-        h, w = ops.conv_out_hw(H, W, 1)
-        for l in range(1, self.L):
-            ci, co = self.channels[l], self.channels[l + 1]
-            if not (ops.pconv_supported(h, w, ci, co, 1) and ci % 64 == 0 and ops.pconv_wgrad_supported(h, w, ci, co)):
-                return False
-            h, w = ops.conv_out_hw(h, w, 1)
-        return True
+    def conv_routes(self, v_shape, keep: bool, need_dx: bool = False):
+        """The kernel family of every conv block for an image batch of v_shape [B,C,H,W], decided once for both passes: one
+        ConvRoute per block (the table in DESIGN.md, "Conv routes").  Makes no launch and allocates nothing.
+        kind: convk (kernel_size != 3), conv0 (dedicated first block), pconv (bf16 patch), conv16 (bf16 implicit GEMM) or conv32
+        (fp32 implicit GEMM; x3: split kernels; pdg: patch backward-data; pack_in: x3-packs its own input, the producer could
+        not).  x_shape: the NHWC input.  Layouts nchw / nhwc32 / nhwc16 / x3 / c16: src and out of input and pooled output, dy
+        of the pooled gradient backward reads, dx of the input gradient it writes (None: none).  need_wd: forward packs the
+        backward-data weights (a pdg block the patch image instead; wds[l] is a tensor or None)."""
+        B, C, H, W = v_shape
+        L, ch, bf16 = self.L, self.channels, self.bf16
+        # the first block has a dedicated kernel that reads the NCHW image as is (K = 27 is too thin for the generic implicit
+        # GEMM), fp16 features included; otherwise the image is converted to NHWC4 once
+        fast0 = self.ks == 3 and ops.conv0_supported(C, H, W, ch[1], self.stride)
+        if bf16 and not fast0:
+            raise ValueError("the bf16 path needs the dedicated first-block kernel (3-channel NCHW image, "
+                             "W % 4 == 0, 32 or 64 output channels)")
+        shapes = [(B, H, W, C if fast0 else 4)]
+        for l in range(1, L):
+            H, W = ops.convk_out_hw(H, W, self.ks, self.stride)[2:]
+            shapes.append((B, H, W, ch[l]))
+        # bf16 path: blocks 1.. on the patch convolutions (csrc/conv_patch_bf16.hip: LDS-resident input patch, activations
+        # between the blocks channel-blocked) when EVERY block's shape has them; VQA_PCONV=0 keeps the implicit-GEMM kernels
+        # (A/B runs, parity tests of both)
+        use_pc = bf16 and os.environ.get("VQA_PCONV", "1") != "0" and all(
+            ops.pconv_supported(h, w, ci, co, 1) and ci % 64 == 0 and ops.pconv_wgrad_supported(h, w, ci, co)
+            for (_, h, w, ci), co in zip(shapes[1:], ch[2:]))
+        kinds = ["convk" if self.ks != 3 else "conv0" if l == 0 and fast0 else
+                 ("pconv" if use_pc else "conv16") if bf16 else "conv32" for l in range(L)]
+        x3 = [k == "conv32" and self._x3_layer(s, co) for k, s, co in zip(kinds, shapes, ch[1:])] + [False]
+        # fp32 backward-data of blocks 1.. on the patch kernel (csrc/conv_patch_f32.hip: the pre-pool gradient built in LDS once
+        # per K-slice instead of routed once per tap by the loaders); VQA_PDGRAD=0 keeps the implicit-GEMM kernel
+        # (measured at B = 256, 224 x 224: 64-channel input 3.96 -> 3.69 ms; 128-channel input 3.20 -> 3.32 ms, so blocks whose
+        # input has a multiple of 128 channels stay on the implicit-GEMM kernel unless VQA_PDGRAD=2 forces the patch kernel)
+        pdg_mode = os.environ.get("VQA_PDGRAD", "1")
+        routes = []
+        for l, (kind, s) in enumerate(zip(kinds, shapes)):
+            last, src = l == L - 1, routes[-1].out if l else "nchw" if fast0 else "nhwc32"
+            pdg = (kind == "conv32" and keep and l > 0 and not x3[l] and self.stride == 1 and pdg_mode != "0"
+                   and (s[3] % 128 != 0 or pdg_mode == "2") and ops.pconvf_supported(s[1], s[2], s[3], ch[l + 1]))
+            # fp32x3: a block whose successor runs on the split kernels writes its output x3-packed (split once per tensor by
+            # the producer's epilogue; forward and wgrad of the successor read that form).  bf16: fp32 out of the last block
+            # (the L2 normalisation consumes it)
+            out = ("x3" if x3[l + 1] and (x3[l] or kind == "conv0") else
+                   "nhwc32" if last or not bf16 else "c16" if use_pc else "nhwc16")
+            # the patch kernels read their pooled gradient channel-blocked as well; block 0 has an input gradient only on demand
+            dy = "c16" if kind == "pconv" else "nhwc16" if bf16 else "nhwc32"
+            dx = routes[-1].dy if l else src if need_dx else None
+            need_wd = keep and kind != "conv0" and not pdg and (kind != "conv32" or dx is not None)
+            routes.append(ConvRoute(kind, s, ch[l + 1], src, out, dy, dx, x3[l], pdg, x3[l] and src != "x3", need_wd))
+        return routes
 
     @staticmethod
     def _rows16(x: Tensor, ld: int, rows: int, cols: int, rows8: int) -> Tensor:
@@ -162,12 +206,6 @@ class Engine:
         """fp32x3 mode: the three v_conv products (rows = B * positions) run on the split GEMM when they are large
         enough to fill the chip with 192 x 128 tiles."""
         return self.x3_gemm and rows >= 192 * 64 and self.mid >= 128 and self.C >= 64
-
-    def _out_shape(self, x, l, fast0):
-        """NHWC shape of block l's pooled output for input activation x (the NCHW image for the dedicated first block)."""
-        B, H, W = (x.shape[0], x.shape[2], x.shape[3]) if (l == 0 and fast0) else ops.nhwc_shape(x)[:3]
-        Hp, Wp = ops.conv_out_hw(H, W, self.stride)
-        return (B, Hp, Wp, self.channels[l + 1])
 
     # ------------------------------------------------------------------ stream fork / join
     def _on_side_stream(self, dev, job, backward=False):
@@ -308,8 +346,8 @@ class Engine:
     def _encoder_saved(enc, norm, p_img, need_dx, v):
         """The saved fields of a schedule that ran _image_encoder on the image batch v: what the L2-norm backward and
         _conv_bwd read."""
-        return dict(acts=enc.acts, idxs=enc.idxs, wds=enc.wds, norm=norm, fast0=enc.fast0, use_pc=enc.use_pc, p_img=p_img,
-                    need_dx=need_dx, v_dtype=v.dtype, v_shape=tuple(v.shape))
+        return dict(routes=enc.routes, acts=enc.acts, idxs=enc.idxs, wds=enc.wds, norm=norm, fast0=enc.fast0, use_pc=enc.use_pc,
+                    p_img=p_img, need_dx=need_dx, v_dtype=v.dtype, v_shape=tuple(v.shape))
 
     def _question_encoder(self, P, x_emb, q_len, combined, l16):
         """LSTM over the embedded question x_emb [T,B,E] on the current stream; the final cell states land in combined[:, GC:].
@@ -348,70 +386,19 @@ class Engine:
 
     def _image_encoder(self, P, v, keep, need_dx=False):
         """conv + relu + pool x L (models/model.py:79-84) over the image v [B,C,S,S].  Returns a namespace: out (the last
-        pooled activation), fast0, use_pc and -- when `keep` -- what backward reads: acts (every block's input, then out),
-        idxs (arg-max bytes) and wds (backward-data weights) per block.  Nothing kept: an activation is dropped as soon
-        as the next block has consumed it."""
-        # the first block has a dedicated kernel that reads the NCHW image as is (K = 27 is too thin for the
-        # generic implicit GEMM); otherwise the image is converted to NHWC4 once
-        fast0 = self.ks == 3 and ops.conv0_supported(v.shape[1], v.shape[2], v.shape[3], self.channels[1], self.stride)
-        if v.dtype == torch.float16 and not fast0:
-            # the dedicated first-block kernels read the dataset's fp16 features as they are (widened where the LDS patch is
-            # staged); only shapes they do not cover take a widened copy through the generic NHWC path
-            v = ops.half_to_float(v)
-        x = v if fast0 else ops.nchw_to_nhwc4(v)
-        if self.bf16 and not fast0:
-            raise ValueError("the bf16 path needs the dedicated first-block kernel (3-channel NCHW image, "
-                             "W % 4 == 0, 32 or 64 output channels)")
-        # bf16 path: blocks 1.. on the patch convolutions (csrc/conv_patch_bf16.hip: LDS-resident input patch, activations
-        # between the blocks channel-blocked "C16") when every block's shape has them; VQA_PCONV=0 keeps the implicit-GEMM
-        # kernels (A/B runs, parity tests of both)
-        use_pc = self.bf16 and fast0 and self._pconv_ok(v.shape[2], v.shape[3])
-        # fp32 backward-data of blocks 1.. on the patch kernel (csrc/conv_patch_f32.hip: the pre-pool gradient built in LDS once
-        # per K-slice instead of routed once per tap by the loaders); VQA_PDGRAD=0 keeps the implicit-GEMM kernel
-        # (measured at B = 256, 224 x 224: 64-channel input 3.96 -> 3.69 ms; 128-channel input 3.20 -> 3.32 ms, so blocks whose
-        # input has a multiple of 128 channels stay on the implicit-GEMM kernel unless VQA_PDGRAD=2 forces the patch kernel)
-        pdg_mode = os.environ.get("VQA_PDGRAD", "1")
+        pooled activation), routes, fast0, use_pc and -- when `keep` -- what backward reads: acts (every block's input, then
+        out), idxs (arg-max bytes) and wds (backward-data weights or None) per block.  Nothing kept: an activation is dropped
+        as soon as the next block has consumed it."""
+        routes = self.conv_routes(tuple(v.shape), keep, need_dx)
+        x = v
+        if routes[0].src != "nchw":
+            # only shapes the dedicated first-block kernels do not cover take a (widened) NHWC4 copy through the generic path
+            x = ops.nchw_to_nhwc4(ops.half_to_float(v) if v.dtype == torch.float16 else v)
         acts, idxs, wds = [], [], []
-        for l in range(self.L):
+        for l, r in enumerate(routes):
             w, bias = P[f"image.conv{l}.weight"], P[f"image.conv{l}.bias"]
-            Co = w.shape[0]
-            assert Co == self.channels[l + 1]
-            # fp32x3: a block whose successor runs on the split kernels writes its output x3-packed (split once per
-            # tensor by the producer's epilogue; forward and wgrad of the successor read that form)
-            nxt_x3 = self.x3 and l + 1 < self.L and self._x3_layer(self._out_shape(x, l, fast0), self.channels[l + 2])
-            wd = None
-            if self.ks != 3:
-                wd = ops.convk_pack_weights(w, x.shape[3])
-                y, am = ops.convk_fwd(x, wd, bias, self.ks, self.stride, tag=l)
-            elif l == 0 and fast0:
-                y, am = ops.conv0_fwd(x, w, bias, out_dtype=torch.bfloat16 if self.bf16 else torch.float32,
-                                      bf16_mfma=self.bf16, out_packed=nxt_x3, out_c16=use_pc)
-            elif self.bf16:
-                # bf16 activations in, bf16 out (fp32 out of the last block: the L2 normalisation consumes it)
-                out_dtype = torch.float32 if l == self.L - 1 else torch.bfloat16
-                if use_pc:
-                    wf, wd = ops.pconv_pack_weights(w, need_wd=keep)
-                    y, am = ops.pconv_fwd(x, wf, bias, Co, out_dtype=out_dtype, tag=l)
-                else:
-                    wf, wd = ops.conv_pack_weights_bf16(w, x.shape[3], need_wd=keep)
-                    y, am = ops.conv_fwd_bf16(x, wf, bias, self.stride, out_dtype=out_dtype, tag=l)
-            else:
-                x_shape = ops.nhwc_shape(x)
-                x3 = self._x3_layer(x_shape, Co)
-                pdg = (keep and l > 0 and not x3 and self.stride == 1 and x.dim() == 4 and pdg_mode != "0"
-                       and (x_shape[3] % 128 != 0 or pdg_mode == "2")
-                       and ops.pconvf_supported(x_shape[1], x_shape[2], x_shape[3], Co))
-                # block 0 packs its backward-data weights only when the input gradient is wanted
-                wf, wd = ops.conv_pack_weights(w, x_shape[3], need_wd=(keep and (l > 0 or need_dx) and not pdg))
-                if pdg:
-                    wd = ("pconvf", ops.pconvf_pack_weights(w))
-                if x3:
-                    # operands are split once per tensor, not by every workgroup in every K-step: the weights here, the
-                    # input activation by its producer (or here, when the producer could not: it replaces the fp32 tensor)
-                    wf, wd = ops.x3_split(wf), (ops.x3_split(wd) if wd is not None else None)
-                    if x.dim() == 4:
-                        x = ops.x3_pack(x)
-                y, am = ops.conv_fwd(x, wf, bias, self.stride, tag=l, x3=x3, out_packed=x3 and nxt_x3)
+            assert w.shape[0] == r.Co
+            x, y, am, wd = getattr(self, f"_{r.kind}_fwd")(r, l, x, w, bias)
             if keep:
                 acts.append(x)
                 idxs.append(am)
@@ -420,7 +407,37 @@ class Engine:
             del y, am, wd       # nothing kept: only the block's output is alive while the next block runs
         if keep:
             acts.append(x)
-        return SimpleNamespace(out=x, acts=acts, idxs=idxs, wds=wds, fast0=fast0, use_pc=use_pc)
+        return SimpleNamespace(out=x, routes=routes, acts=acts, idxs=idxs, wds=wds, fast0=routes[0].kind == "conv0",
+                               use_pc=any(r.kind == "pconv" for r in routes))
+
+    # one forward per route kind: (the block's input as backward reads it again, pooled output, arg-max bytes, backward-data weights)
+    def _convk_fwd(self, r, l, x, w, bias):
+        wk = ops.convk_pack_weights(w, r.x_shape[3])
+        return (x, *ops.convk_fwd(x, wk, bias, self.ks, self.stride, tag=l), wk)
+
+    def _conv0_fwd(self, r, l, x, w, bias):
+        return (x, *ops.conv0_fwd(x, w, bias, out_dtype=torch.bfloat16 if self.bf16 else torch.float32, bf16_mfma=self.bf16,
+                                  out_packed=r.out == "x3", out_c16=r.out == "c16"), None)
+
+    def _pconv_fwd(self, r, l, x, w, bias):
+        wf, wd = ops.pconv_pack_weights(w, need_wd=r.need_wd)
+        return (x, *ops.pconv_fwd(x, wf, bias, r.Co, out_dtype=_OUT16[r.out], tag=l), wd)
+
+    def _conv16_fwd(self, r, l, x, w, bias):
+        wf, wd = ops.conv_pack_weights_bf16(w, r.x_shape[3], need_wd=r.need_wd)
+        return (x, *ops.conv_fwd_bf16(x, wf, bias, self.stride, out_dtype=_OUT16[r.out], tag=l), wd)
+
+    def _conv32_fwd(self, r, l, x, w, bias):
+        wf, wd = ops.conv_pack_weights(w, r.x_shape[3], need_wd=r.need_wd)
+        if r.pdg:
+            wd = ops.pconvf_pack_weights(w)
+        if r.x3:
+            # operands are split once per tensor, not by every workgroup in every K-step: the weights here, the
+            # input activation by its producer (or here, when the producer could not: it replaces the fp32 tensor)
+            wf, wd = ops.x3_split(wf), (ops.x3_split(wd) if wd is not None else None)
+            if r.pack_in:
+                x = ops.x3_pack(x)
+        return (x, *ops.conv_fwd(x, wf, bias, self.stride, tag=l, x3=r.x3, out_packed=r.out == "x3"), wd)
 
     def _q_lin_fwd(self, P, qf, p_att, seed):
         """q' = q_lin(drop(qf)) for the question features qf [B,Q] (leading dimension Dc).  Returns (q' [B,mid], the
@@ -889,7 +906,7 @@ class Engine:
         """L2-norm (+ dropout) backward, then the conv blocks from the last to the first.  Returns the image gradient
         (ctx.need_dx) or None."""
         sd = lambda site: _site_seed(ctx.seed, site)
-        c16_hw = tuple(ctx.idxs[-1].shape[2:4]) if self.bf16 and ctx.use_pc else None   # channel-blocked for the routed patches
+        c16_hw = tuple(ctx.idxs[-1].shape[2:4]) if ctx.routes[-1].dy == "c16" else None   # channel-blocked for the routed patches
         dP = ops.l2norm_bwd_joined(dcomb, self.Dc, ctx.probs, dv_in, ctx.p_att, sd(SITE_ATT_V), ctx.vn, ctx.norm, ctx.p_img,
                                    sd(SITE_IMAGE), out_dtype=torch.bfloat16 if self.bf16 else torch.float32, c16_hw=c16_hw)
         if c16_hw is None:
@@ -897,49 +914,43 @@ class Engine:
         return self._conv_bwd(P, ctx, dP, Gr)
 
     def _conv_bwd(self, P, ctx, dP, Gr):
-        """The conv blocks from the last to the first, from dP = d loss / d (the last pooled activation).  Returns the image
-        gradient (ctx.need_dx) or None."""
-        dv = None
-        for l in range(self.L - 1, -1, -1):
-            if self.ks != 3:
-                dP = ops.convk_bwd(ctx.acts[l], dP, ctx.idxs[l], ctx.wds[l], Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"],
-                                   self.ks, self.stride, need_dx=l > 0 or ctx.need_dx, tag=l)
-                continue
-            if l == 0 and ctx.fast0:
-                if self.bf16:
-                    ops.conv0_wgrad_bf16(ctx.acts[0], dP, ctx.idxs[0], Gr["image.conv0.weight"], Gr["image.conv0.bias"])
-                else:
-                    ops.conv0_wgrad(ctx.acts[0], dP, ctx.idxs[0], Gr["image.conv0.weight"], Gr["image.conv0.bias"])
-                if ctx.need_dx:
-                    # the image gradient straight from the pooled gradient, in the caller's NCHW layout and dtype (csrc/conv0_dgrad.hip);
-                    # the bf16 path's forward multiplies by the bf16-rounded weights, so its backward-data does as well
-                    dv = ops.conv0_dgrad(dP, ctx.idxs[0], P["image.conv0.weight"], ctx.v_shape, out_dtype=ctx.v_dtype,
-                                         round_w_bf16=self.bf16)
-                continue
-            if self.bf16 and ctx.use_pc:
-                # both kernels route the pre-pool gradient themselves (pooled gradient + arg-max bytes, C16); the block below
-                # gets its pooled gradient C16 again, the first block's weight gradient NHWC
-                Bx, _, Hx, Wx, _ = ctx.acts[l].shape
-                ops.pconv_wgrad(ctx.acts[l], dP, ctx.idxs[l], Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"], tag=l)
-                dP = ops.pconv_dgrad(dP, ctx.idxs[l], ctx.wds[l], (Bx, Hx, Wx, self.channels[l]), out_c16=l > 1, tag=l)
-                continue
-            if self.bf16:
-                ops.conv_wgrad_bf16(ctx.acts[l], dP, ctx.idxs[l], Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"],
-                                    self.stride, tag=l)
-                dP = ops.conv_dgrad_bf16(dP, ctx.idxs[l], ctx.wds[l], ctx.acts[l].shape, self.stride, tag=l)
-                continue
-            x_shape = ops.nhwc_shape(ctx.acts[l])
-            x3 = self._x3_layer(x_shape, dP.shape[3])
-            # fp32x3: the pooled gradient is split once (x3-packed) for its two readers, wgrad and dgrad
-            # (one pass: it also sums the bias gradient)
-            dPp = ops.x3_pack_pooled_grad(dP, ctx.idxs[l], Gr[f"image.conv{l}.bias"]) if x3 else None
-            ops.conv_wgrad(ctx.acts[l], dP, ctx.idxs[l], Gr[f"image.conv{l}.weight"],
-                           None if x3 else Gr[f"image.conv{l}.bias"], self.stride, tag=l, x3=x3, dpooled_packed=dPp)
-            if l > 0 and isinstance(ctx.wds[l], tuple):
-                dP = ops.pconvf_dgrad(dP, ctx.idxs[l], ctx.wds[l][1], x_shape, tag=l)
-            elif l > 0 or ctx.need_dx:
-                dP = ops.conv_dgrad(dPp if x3 else dP, ctx.idxs[l], ctx.wds[l], x_shape, self.stride, tag=l, x3=x3)
-        if ctx.need_dx and dv is None:
+        """The conv blocks from the last to the first, each as its route says (ctx.routes), from dP = d loss / d (the last
+        pooled activation).  Returns the image gradient (ctx.need_dx) or None."""
+        for l, r in reversed(list(enumerate(ctx.routes))):
+            dP = getattr(self, f"_{r.kind}_bwd")(r, l, ctx, dP, Gr[f"image.conv{l}.weight"], Gr[f"image.conv{l}.bias"],
+                                                 P[f"image.conv{l}.weight"])
+        if ctx.routes[0].dx == "nhwc32":
             # generic first block (NHWC4 input): drop the pad channel, back to the caller's NCHW layout and dtype
-            dv = ops.nhwc_to_nchw(dP, ctx.v_shape[1], out_dtype=ctx.v_dtype)
-        return dv
+            return ops.nhwc_to_nchw(dP, ctx.v_shape[1], out_dtype=ctx.v_dtype)
+        return dP
+
+    # one backward per route kind: writes the block's weight and bias gradients dw, db; returns its input gradient in layout r.dx
+    def _convk_bwd(self, r, l, ctx, dP, dw, db, w):
+        return ops.convk_bwd(ctx.acts[l], dP, ctx.idxs[l], ctx.wds[l], dw, db, self.ks, self.stride, need_dx=r.dx is not None,
+                             tag=l)
+
+    def _conv0_bwd(self, r, l, ctx, dP, dw, db, w):
+        (ops.conv0_wgrad_bf16 if self.bf16 else ops.conv0_wgrad)(ctx.acts[0], dP, ctx.idxs[0], dw, db)
+        # the image gradient straight from the pooled gradient, in the caller's NCHW layout and dtype (csrc/conv0_dgrad.hip);
+        # the bf16 path's forward multiplies by the bf16-rounded weights, so its backward-data does as well
+        return ops.conv0_dgrad(dP, ctx.idxs[0], w, ctx.v_shape, out_dtype=ctx.v_dtype, round_w_bf16=self.bf16) if r.dx else None
+
+    def _pconv_bwd(self, r, l, ctx, dP, dw, db, w):
+        # both kernels route the pre-pool gradient themselves (pooled gradient + arg-max bytes, C16); a patch block below
+        # gets its pooled gradient C16 again, the first block's weight gradient NHWC
+        ops.pconv_wgrad(ctx.acts[l], dP, ctx.idxs[l], dw, db, tag=l)
+        return ops.pconv_dgrad(dP, ctx.idxs[l], ctx.wds[l], r.x_shape, out_c16=r.dx == "c16", tag=l)
+
+    def _conv16_bwd(self, r, l, ctx, dP, dw, db, w):
+        ops.conv_wgrad_bf16(ctx.acts[l], dP, ctx.idxs[l], dw, db, self.stride, tag=l)
+        return ops.conv_dgrad_bf16(dP, ctx.idxs[l], ctx.wds[l], r.x_shape, self.stride, tag=l)
+
+    def _conv32_bwd(self, r, l, ctx, dP, dw, db, w):
+        # fp32x3: the pooled gradient is split once (x3-packed) for its two readers, wgrad and dgrad
+        # (one pass: it also sums the bias gradient)
+        dPp = ops.x3_pack_pooled_grad(dP, ctx.idxs[l], db) if r.x3 else None
+        ops.conv_wgrad(ctx.acts[l], dP, ctx.idxs[l], dw, None if r.x3 else db, self.stride, tag=l, x3=r.x3, dpooled_packed=dPp)
+        if r.pdg:
+            return ops.pconvf_dgrad(dP, ctx.idxs[l], ctx.wds[l], r.x_shape, tag=l)
+        if r.dx:
+            return ops.conv_dgrad(dPp if r.x3 else dP, ctx.idxs[l], ctx.wds[l], r.x_shape, self.stride, tag=l, x3=r.x3)
