@@ -146,6 +146,13 @@ PROTOTYPES = {
     "vqa_adam": (i32, [f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, i32, f32, vp]),
     "vqa_adam_segments": (i32, [f32p, f32p, f32p, f32p, i64, vp, i32, f32, vp]),      # segs: a HOST array of AdamSegment
     "vqa_conv3x3_x3_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), i32]),
+    # float16 image-feature caches: the fp32 entry points' argument lists, the cache operand a void pointer
+    "vqa_float_to_half": (i32, [f32p, vp, i64, vp]),
+    "vqa_gather_rows_drop_f16": (i32, [vp, vp, f32p, i32, i32, i64, f32, u64, vp]),
+    "vqa_att_apply_gather_fwd_f16": (i32, [f32p, vp, vp, f32p, f32p, i64, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_apply_gather_dscore_f16": (i32, [f32p, i64, f32p, vp, vp, f32p, f32p, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_score_grouped_fwd_f16": (i32, [vp, f32p, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_score_grouped_pairs_fwd_f16": (i32, [vp, f32p, vp, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
 }
 
 K_GEMM, K_CONV_FWD, K_CONV_DGRAD, K_CONV_WGRAD = 0, 1, 2, 3

@@ -22,6 +22,7 @@
 // table [M][mid] of distinct questions; everything else is still indexed by b.  Only the row address changes: the operation
 // order above is the same, so the scores equal the PAIRS = false kernels' on the expanded qp[qrow], bit for bit.
 #include "common.hpp"
+#include "cache_load.hpp"
 
 namespace vqa {
 
@@ -378,6 +379,24 @@ __device__ __forceinline__ void att_tile_to_lds(const float* vprime, float* tile
   for (; i < n4; i += 256) dst[i] = src[i];
 }
 
+// The same walk over a float16 v' (a float16 image-feature cache, cache_load.hpp): a quad of halves is one 8-byte load,
+// widened here -- the one place v' enters the grouped forward kernels -- so the LDS tile is fp32 either way and everything
+// behind it is the same code.  (An overload, not a template over both: the fp32 loader above keeps its code.)
+__device__ __forceinline__ void att_tile_to_lds(const __half* vprime, float* tile, int64_t row0, int rows, int mid) {
+  const __half* src = vprime + row0 * mid;
+  float4* dst = reinterpret_cast<float4*>(tile);
+  const int n4 = rows * (mid >> 2);
+  int i = threadIdx.x;
+  for (; i + 768 < n4; i += 1024) {          // four loads in flight per thread
+    float4 t[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t[u] = load_quad(src, i + 256 * u);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) dst[i + 256 * u] = t[u];
+  }
+  for (; i < n4; i += 256) dst[i] = load_quad(src, i);
+}
+
 // the question range of image n, clamped to [0, B] (a malformed offsets array then reads nothing out of bounds)
 __device__ __forceinline__ void att_group_range(const int* offsets, int n, int B, int& k0, int& k1) {
   k0 = offsets[n];
@@ -397,8 +416,9 @@ __device__ __forceinline__ int att_q_row(const int* qrow, int b, int B, int M) {
 
 // '+' / '*', mid = 256 * IT <= 1024: x_conv weights and the question's q' row in registers, 4 positions per wave.
 // grid (ceil(P/16), N), 256 threads, 16 * mid floats of dynamic LDS.
-template <int G, int IT, bool MUL, bool DROP, bool PAIRS>
-__global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vprime, const float* qp, const int* qrow, int M,
+// VT: v' is fp32, or fp16 for a float16 image-feature cache (vqa_att_score_grouped_fwd_f16 / _pairs_fwd_f16: inference, DROP = false)
+template <int G, int IT, bool MUL, bool DROP, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_score_grouped_kernel(const VT* vprime, const float* qp, const int* qrow, int M,
                                                                 const float* wx, int wx_ld, const float* bx, const int* order,
                                                                 const int* offsets, float* score, int B, int P, float p,
                                                                 float inv_keep, uint64_t seed) {
@@ -488,8 +508,8 @@ __global__ __launch_bounds__(256) void att_score_grouped_kernel(const float* vpr
 
 // Any mid % 4 == 0 and every mode: the channel walk is a run-time loop (weights and q' re-read through L1 per position),
 // `pw` positions per wave (the tile is 4 * pw rows).  Same per-lane operation order as the kernel above.
-template <int G, bool DROP, bool PAIRS>
-__global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const float* vprime, const float* qp, const int* qrow,
+template <int G, bool DROP, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const VT* vprime, const float* qp, const int* qrow,
                                                                         int M, const float* wx, int wx_ld, const float* bx,
                                                                         const int* order, const int* offsets, float* score, int B,
                                                                         int P, int mid, int pw, int mode, float p, float inv_keep,
@@ -778,6 +798,41 @@ static int grouped_fwd(const char* who, const float* vprime, const float* qp, co
   return check_hip(hipGetLastError(), "att_score_grouped_fwd launch");
 }
 
+// the two inference entry points on a float16 v' (a float16 image-feature cache): grouped_fwd's checks, path choice, grid and
+// LDS size; the tile loader reads a quad of halves as 8 bytes, so v' is 8-byte aligned where the fp32 form asks for 16
+static int grouped_fwd_f16(const char* who, const void* vprime_f16, const float* qp, const int32_t* qrow, int M, const float* wx,
+                           int wx_ld, const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                           int P, int mid, int G, int mode, hipStream_t s) {
+  const int rc = att_score_check(who, true, vprime_f16 && qp && wx && bx && score, order && offsets, N, B, P, mid, wx_ld, G, mode,
+                                 0.f, bits(qp, wx));
+  if (rc) return rc;
+  VQA_REQUIRE((bits(vprime_f16) & 7) == 0, "%s: vprime must be 8-byte aligned", who);
+  if (B == 0) return VQA_OK;
+  const __half* vprime = static_cast<const __half*>(vprime_f16);
+  const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
+  const dim3 grid((P + TP - 1) / TP, N);
+  const size_t lds = (size_t)TP * mid * 4;
+  with_int14(G, [&](auto g) {
+    return with_flag(qrow != nullptr, [&](auto pairs) {
+      constexpr int kG = decltype(g)::value;
+      constexpr bool kPairs = decltype(pairs)::value;
+      if (pw)
+        hipLaunchKernelGGL((att_score_grouped_general_kernel<kG, false, kPairs, __half>), grid, dim3(256), lds, s, vprime, qp, qrow, M,
+                           wx, wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, 0.f, 1.f, (uint64_t)0);
+      else
+        with_int14(mid / 256, [&](auto it) {
+          return with_flag(mode == 1, [&](auto mul) {
+            hipLaunchKernelGGL((att_score_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, false, kPairs, __half>), grid,
+                               dim3(256), lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, 0.f, 1.f, (uint64_t)0);
+            return 0;
+          });
+        });
+      return 0;
+    });
+  });
+  return check_hip(hipGetLastError(), "att_score_grouped_fwd_f16 launch");
+}
+
 extern "C" {
 
 // The plain forms take the checks of their grouped forms (att_score_check): what used to reach a launch with undefined
@@ -914,6 +969,26 @@ int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const fl
   });
 #undef GROUPED_BWD_GENERAL
   return check_hip(hipGetLastError(), "att_score_grouped_bwd launch");
+}
+
+int vqa_att_score_grouped_fwd_f16(const void* vprime_f16, const float* qp, const float* wx, int wx_ld, const float* bx,
+                                  const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P, int mid, int G,
+                                  int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  return grouped_fwd_f16("vqa_att_score_grouped_fwd_f16", vprime_f16, qp, nullptr, 0, wx, wx_ld, bx, order, offsets, score, N, B, P,
+                         mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_score_grouped_pairs_fwd_f16(const void* vprime_f16, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                        const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                                        int M, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_score_grouped_pairs_fwd_f16: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_score_grouped_pairs_fwd_f16: M=%d question rows (>= 1)", M);
+  return grouped_fwd_f16("vqa_att_score_grouped_pairs_fwd_f16", vprime_f16, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, N, B,
+                         P, mid, G, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

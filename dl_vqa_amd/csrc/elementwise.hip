@@ -3,6 +3,7 @@
 // All are HBM-bound streaming kernels: 16-byte per-lane accesses, wave64 shuffles for reductions.
 #include <hip/hip_fp16.h>
 #include "common.hpp"
+#include "cache_load.hpp"
 
 namespace vqa {
 
@@ -550,9 +551,10 @@ __device__ __forceinline__ void att_softmax_to_lds(const float* score, float* pr
 // grid (B, ceil(C/64)); dynamic LDS: G*P + 16 + 16*G*64 floats.  Sum order per channel: positions pg, pg+16, ... within
 // a group, then the 16 groups in order.
 // b = the sample (score / probs / out row), n = the image whose vn rows it weights: n == b in vqa_att_apply_fwd,
-// n = img[b] in vqa_att_apply_gather_fwd (several questions per image)
-template <int G>
-__device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* score, const float* vn, float* probs, float* out,
+// n = img[b] in vqa_att_apply_gather_fwd (several questions per image).  VT: vn's element type (cache_load.hpp); a lane's
+// four channels are one 16-byte load of fp32 or one 8-byte load of fp16, everything else is the same code.
+template <int G, class VT>
+__device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* score, const VT* vn, float* probs, float* out,
                                                       int64_t out_ld, int P, int C, int b, int n) {
   float* pr = sm;            // [G][P]
   float* red = sm + G * P;   // [16]
@@ -566,12 +568,12 @@ __device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* sc
 #pragma unroll
   for (int g = 0; g < G; ++g) acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (c < C) {
-    const float* vb = vn + (int64_t)n * P * C + c;
+    const VT* vb = vn + (int64_t)n * P * C + c;
     int i = pg;
     for (; i + 48 < P; i += 64) {
       float4 v[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(vb + (int64_t)(i + 16 * u) * C);
+      for (int u = 0; u < 4; ++u) v[u] = load_quad(vb + (int64_t)(i + 16 * u) * C, 0);
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -581,7 +583,7 @@ __device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* sc
         }
     }
     for (; i < P; i += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(vb + (int64_t)i * C);
+      const float4 v = load_quad(vb + (int64_t)i * C, 0);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         const float w = pr[g * P + i];
@@ -617,8 +619,8 @@ __global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, con
 }
 
 // grid (B, ceil(C/64)), 256 threads = 4 position groups x 64 channels; dynamic LDS: G*P + 16 + 4*G*64 floats
-template <int G>
-__device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score, const float* vn, float* probs, float* out,
+template <int G, class VT>
+__device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score, const VT* vn, float* probs, float* out,
                                                    int64_t out_ld, int P, int C, int b, int n) {
   float* pr = sm;            // [G][P]
   float* red = sm + G * P;   // [16]
@@ -632,9 +634,9 @@ __device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score
 #pragma unroll
   for (int g = 0; g < G; ++g) acc[g] = 0.f;
   if (c < C) {
-    const float* vb = vn + (int64_t)n * P * C + c;
+    const VT* vb = vn + (int64_t)n * P * C + c;
     for (int i = pg; i < P; i += 4) {
-      const float v = vb[(int64_t)i * C];
+      const float v = load_one(vb, (int64_t)i * C);
 #pragma unroll
       for (int g = 0; g < G; ++g) acc[g] += pr[g * P + i] * v;
     }
@@ -663,19 +665,31 @@ __global__ void att_apply_fwd_kernel(const float* score, const float* vn, const 
   att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
 }
 
+// vqa_att_apply_gather_fwd_f16: the two GATHER kernels above on a float16 vn (V4: C % 4 == 0 and vn 8-byte aligned)
+template <int G, bool V4>
+__global__ void att_apply_gather_fwd_f16_kernel(const float* score, const __half* vn, const int* img, float* probs, float* out,
+                                                int64_t out_ld, int P, int C, int N) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int n = img[blockIdx.x];
+  if ((unsigned)n >= (unsigned)N) return;
+  if (V4) att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
+  else att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
+}
+
 // pass 1: one wave per (b,p): dprob -> dscore buffer, dvn row written
 // One (sample b, position pp) row against the image row `v` that b weights there: dprob[b][g][pp] = <v, dout[b][g]> and
 // (d != null) d[c] = sum_g probs[b][g][pp] * dout[b][g*C + c].  v: row b*P + pp in vqa_att_apply_bwd, row img[b]*P + pp in
-// vqa_att_apply_gather_bwd -- the (sample, image) form, as in att_apply_fwd_body.
-template <int G>
-__device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dout_ld, const float* probs, const float4* v,
+// vqa_att_apply_gather_bwd -- the (sample, image) form, as in att_apply_fwd_body.  v: the row's first element, fp32 or fp16
+// (cache_load.hpp), read a channel quad at a time.
+template <int G, class VT>
+__device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dout_ld, const float* probs, const VT* v,
                                                   float4* d, float* dprob, int64_t b, int pp, int P, int C, int lane) {
   const int nch = C >> 2;
   float pr[G], acc[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) { pr[g] = probs[(b * G + g) * P + pp]; acc[g] = 0.f; }
   for (int c = lane; c < nch; c += 64) {
-    const float4 x = v[c];
+    const float4 x = load_quad(v, c);
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -709,8 +723,27 @@ __global__ void att_apply_bwd_rows_kernel(const float* dout, int64_t dout_ld, co
       n = n < 0 ? 0 : (n >= N ? N - 1 : n);               // a malformed index reads nothing out of bounds
       vm = (int64_t)n * P + pp;
     }
-    att_apply_bwd_row<G>(dout, dout_ld, probs, reinterpret_cast<const float4*>(vn + vm * C),
-                         dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr, dprob, b, pp, P, C, lane);
+    att_apply_bwd_row<G>(dout, dout_ld, probs, vn + vm * C, dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr, dprob, b, pp,
+                         P, C, lane);
+  }
+}
+
+// vqa_att_apply_gather_dscore_f16: the GATHER rows kernel above on a float16 vn.  Nobody wants a gradient of a cache, so dvn
+// is always null -- but it stays a run-time argument, as in the kernel above: the row body then compiles to the arithmetic
+// (the same fused multiply-adds) of the fp32 instantiation, which a body specialised for d == null does not.
+template <int G>
+__global__ void att_apply_gather_rows_f16_kernel(const float* dout, int64_t dout_ld, const float* probs, const __half* vn,
+                                                 const int* img, int N, float* dprob, float* dvn, int64_t M, int P, int C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t m = wave; m < M; m += nwaves) {
+    const int64_t b = m / P;
+    const int pp = (int)(m - b * P);
+    int n = img[b];
+    n = n < 0 ? 0 : (n >= N ? N - 1 : n);                 // a malformed index reads nothing out of bounds
+    att_apply_bwd_row<G>(dout, dout_ld, probs, vn + ((int64_t)n * P + pp) * C, dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr,
+                         dprob, b, pp, P, C, lane);
   }
 }
 
@@ -948,10 +981,11 @@ __global__ void gather_rows_kernel(const float* src, int64_t src_ld, const int* 
 // dropped in one pass, the mask indexed by the BANK row (64-bit flat index), zeros for a row index outside [0, M).  Rows are
 // long (one image's features), so the flat range n * row_len is spread over a capped grid; a thread divides once and then
 // walks (row, column) by the grid stride split on the host into (step_j, step_c) = divmod(stride, width).  VEC: one float4
-// per thread and iteration (row_len % 4 == 0, so a row start is a multiple of 4 for drop_scale4).
-template <bool VEC>
-__global__ void gather_rows_drop_kernel(const float* src, const int* rows, float* dst, int n, int M, int64_t row_len,
-                                        int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
+// per thread and iteration (row_len % 4 == 0, so a row start is a multiple of 4 for drop_scale4).  VT: the bank's element
+// type (cache_load.hpp); dst is fp32 either way, and the mask multiplies the widened value.
+template <bool VEC, class VT>
+__device__ __forceinline__ void gather_rows_drop_body(const VT* src, const int* rows, float* dst, int n, int M, int64_t row_len,
+                                                      int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
   const int64_t rw = VEC ? row_len >> 2 : row_len;
   const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t j = first / rw, c = first - j * rw;
@@ -962,7 +996,7 @@ __global__ void gather_rows_drop_kernel(const float* src, const int* rows, float
     if (VEC) {
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (in) {
-        v = reinterpret_cast<const float4*>(src + s)[c];
+        v = load_quad(src + s, c);
         if (p > 0.f) {
           const float4 ds_ = drop_scale4(seed, (uint64_t)(s + 4 * c), p, inv_keep);
           v.x *= ds_.x; v.y *= ds_.y; v.z *= ds_.z; v.w *= ds_.w;
@@ -972,7 +1006,7 @@ __global__ void gather_rows_drop_kernel(const float* src, const int* rows, float
     } else {
       float v = 0.f;
       if (in) {
-        v = src[s + c];
+        v = load_one(src, s + c);
         if (p > 0.f) v *= drop_scale(seed, (uint64_t)(s + c), p, inv_keep);
       }
       dst[d + c] = v;
@@ -981,6 +1015,19 @@ __global__ void gather_rows_drop_kernel(const float* src, const int* rows, float
     c += step_c;
     if (c >= rw) { c -= rw; ++j; }
   }
+}
+
+template <bool VEC>
+__global__ void gather_rows_drop_kernel(const float* src, const int* rows, float* dst, int n, int M, int64_t row_len,
+                                        int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
+  gather_rows_drop_body<VEC>(src, rows, dst, n, M, row_len, step_j, step_c, p, inv_keep, seed);
+}
+
+// vqa_gather_rows_drop_f16: a float16 bank
+template <bool VEC>
+__global__ void gather_rows_drop_f16_kernel(const __half* src, const int* rows, float* dst, int n, int M, int64_t row_len,
+                                            int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
+  gather_rows_drop_body<VEC>(src, rows, dst, n, M, row_len, step_j, step_c, p, inv_keep, seed);
 }
 
 // fp16 -> fp32, 8 values (16 bytes in, 32 bytes out) per thread and iteration
@@ -994,6 +1041,23 @@ __global__ void half_to_float_kernel(const __half* x, float* y, int64_t n) {
     reinterpret_cast<float4*>(y)[2 * i + 1] = make_float4(c.x, c.y, d.x, d.y);
   }
   if (blockIdx.x == 0 && threadIdx.x < n - 8 * n8) y[8 * n8 + threadIdx.x] = __half2float(x[8 * n8 + threadIdx.x]);
+}
+
+// fp32 -> fp16, round to nearest even (v_cvt_f16_f32: overflow to +-inf, NaN stays NaN, subnormal results kept): the mirror
+// of half_to_float_kernel, 8 values (32 bytes in, 16 bytes out) per thread and iteration
+__global__ void float_to_half_kernel(const float* x, __half* y, int64_t n) {
+  const int64_t n8 = n / 8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
+    uint4 raw;
+    __half2* h = reinterpret_cast<__half2*>(&raw);
+    h[0] = __halves2half2(__float2half(a.x), __float2half(a.y));
+    h[1] = __halves2half2(__float2half(a.z), __float2half(a.w));
+    h[2] = __halves2half2(__float2half(b.x), __float2half(b.y));
+    h[3] = __halves2half2(__float2half(b.z), __float2half(b.w));
+    reinterpret_cast<uint4*>(y)[i] = raw;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < n - 8 * n8) y[8 * n8 + threadIdx.x] = __float2half(x[8 * n8 + threadIdx.x]);
 }
 
 __global__ void scale_by_kernel(float* x, int64_t n, const float* s) {
@@ -1159,6 +1223,37 @@ static int att_apply_bwd_launch(const float* dout, int64_t dout_ld, const float*
                          probs, order, offsets, dvn, Mn, B, P, C);
       return check_hip(hipGetLastError(), "att_apply_gather_dvn launch");
     });
+  if (rc) return rc;
+  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, s, probs, dscore, P, dscore_rowsum);
+  return check_hip(hipGetLastError(), "softmax_bwd launch");
+}
+
+// The float16-vn forms (a float16 image-feature cache): the gather forward and the dscore half of the gather backward, the
+// same grids, blocks and LDS sizes.  The forward's quad kernel needs whole quads of channels and an 8-byte aligned vn.
+static int att_apply_gather_fwd_f16_launch(const float* score, const __half* vn, const int32_t* img, float* probs, float* out,
+                                           int64_t out_ld, int N, int B, int P, int C, int G, hipStream_t s) {
+  if (B == 0) return VQA_OK;
+  const dim3 grid(B, (C + 63) / 64);
+  const size_t lds = att_apply_fwd_lds(G, P);
+  return with_int14(G, [&](auto g) {
+    return with_flag(C % 4 == 0 && (reinterpret_cast<uintptr_t>(vn) & 7) == 0, [&](auto v4) {
+      hipLaunchKernelGGL((att_apply_gather_fwd_f16_kernel<decltype(g)::value, decltype(v4)::value>), grid, dim3(256), lds, s, score,
+                         vn, img, probs, out, out_ld, P, C, N);
+      return check_hip(hipGetLastError(), "att_apply_gather_fwd_f16 launch");
+    });
+  });
+}
+
+static int att_apply_gather_dscore_f16_launch(const float* dout, int64_t dout_ld, const float* probs, const __half* vn,
+                                              const int32_t* img, float* dscore, float* dscore_rowsum, int N, int B, int P, int C,
+                                              int G, hipStream_t s) {
+  if (B == 0) return VQA_OK;
+  const int64_t M = (int64_t)B * P;
+  const int rc = with_int14(G, [&](auto g) {
+    hipLaunchKernelGGL(att_apply_gather_rows_f16_kernel<decltype(g)::value>, dim3(grid_for(M, 4)), dim3(256), 0, s, dout, dout_ld,
+                       probs, vn, img, N, dscore, (float*)nullptr, M, P, C);
+    return check_hip(hipGetLastError(), "att_apply_gather_rows_f16 launch");
+  });
   if (rc) return rc;
   hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, s, probs, dscore, P, dscore_rowsum);
   return check_hip(hipGetLastError(), "softmax_bwd launch");
@@ -1427,6 +1522,64 @@ int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t strea
   hipLaunchKernelGGL(half_to_float_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, STREAM,
                      static_cast<const __half*>(x_f16), y, n);
   return check_hip(hipGetLastError(), "half_to_float launch");
+}
+
+// ---- float16 image-feature caches: the converter and the cache readers of this file on a half operand
+int vqa_float_to_half(const float* x, void* y_f16, int64_t n, vqa_stream_t stream) {
+  VQA_REQUIRE(x && y_f16 && n >= 0, "vqa_float_to_half: bad args");
+  VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_f16 % 16) == 0, "vqa_float_to_half: pointers must be 16-byte aligned");
+  if (n == 0) return VQA_OK;
+  hipLaunchKernelGGL(float_to_half_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, STREAM, x, static_cast<__half*>(y_f16), n);
+  return check_hip(hipGetLastError(), "float_to_half launch");
+}
+
+int vqa_gather_rows_drop_f16(const void* src_f16, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
+                             uint64_t seed, vqa_stream_t stream) {
+  VQA_REQUIRE(src_f16 && rows && dst, "vqa_gather_rows_drop_f16: null pointer");
+  VQA_REQUIRE(n >= 0 && M >= 1 && row_len >= 1, "vqa_gather_rows_drop_f16: n=%d, M=%d, row_len=%lld out of range", n, M,
+              (long long)row_len);
+  VQA_REQUIRE(p >= 0.f && p < 1.f, "vqa_gather_rows_drop_f16: p=%g outside [0, 1)", (double)p);
+  VQA_REQUIRE((reinterpret_cast<uintptr_t>(src_f16) & 1) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0,
+              "vqa_gather_rows_drop_f16: src must be 2-byte and dst 4-byte aligned");
+  if (n == 0) return VQA_OK;
+  const __half* src = static_cast<const __half*>(src_f16);
+  // the quad path: 8-byte loads of the bank, 16-byte stores
+  const bool vec = row_len % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 7) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  const int64_t rw = vec ? row_len / 4 : row_len;
+  const int grid = grid_for((int64_t)n * rw, 256);
+  const int64_t stride = (int64_t)grid * 256;
+  if (vec)
+    hipLaunchKernelGGL(gather_rows_drop_f16_kernel<true>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
+                       stride / rw, stride % rw, p, keep_scale(p), seed);
+  else
+    hipLaunchKernelGGL(gather_rows_drop_f16_kernel<false>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
+                       stride / rw, stride % rw, p, keep_scale(p), seed);
+  return check_hip(hipGetLastError(), "gather_rows_drop_f16 launch");
+}
+
+int vqa_att_apply_gather_fwd_f16(const float* score, const void* vn_f16, const int32_t* img, float* probs, float* out,
+                                 int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
+  const int rc = att_apply_check("vqa_att_apply_gather_fwd_f16", false, score && vn_f16 && probs && out, img, N, B, P, C, G, out_ld,
+                                 0);
+  if (rc) return rc;
+  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & 1) == 0, "vqa_att_apply_gather_fwd_f16: vn must be 2-byte aligned");
+  return att_apply_gather_fwd_f16_launch(score, static_cast<const __half*>(vn_f16), img, probs, out, out_ld, N, B, P, C, G, STREAM);
+}
+
+int vqa_att_apply_gather_dscore_f16(const float* dout, int64_t dout_ld, const float* probs, const void* vn_f16,
+                                    const int32_t* img, float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G,
+                                    vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
+  const int rc = att_apply_check("vqa_att_apply_gather_dscore_f16", true, dout && probs && vn_f16 && dscore, img, N, B, P, C, G,
+                                 dout_ld, quad_bits(dout, nullptr, nullptr));
+  if (rc) return rc;
+  // the rows kernel reads a quad of halves as 8 bytes where the fp32 form reads 16
+  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & 7) == 0, "vqa_att_apply_gather_dscore_f16: vn must be 8-byte aligned");
+  return att_apply_gather_dscore_f16_launch(dout, dout_ld, probs, static_cast<const __half*>(vn_f16), img, dscore, dscore_rowsum, N,
+                                            B, P, C, G, STREAM);
 }
 
 int vqa_scale_by(float* x, int64_t n, const float* scalar, vqa_stream_t stream) {

@@ -505,9 +505,12 @@ class Engine:
     # Eval mode, fp32 / fp32x3, nothing kept for a backward.  The image encoder, the question encoder, q_lin and the
     # classifier are the forward's own stages; the attention stage runs on ONE v' per image (csrc/att_score.hip).
     @_device_current("v")
-    def encode_images(self, P: Dict[str, Tensor], v: Tensor, with_vprime: bool = True):
-        """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid] or None (with_vprime=False), (gh, gw))."""
+    def encode_images(self, P: Dict[str, Tensor], v: Tensor, with_vprime: bool = True, dtype: torch.dtype = torch.float32):
+        """v [N,C,S,S] fp32 / fp16 -> (vn [N,Pn,C], v' = v_conv(vn) [N*Pn, mid] or None (with_vprime=False), (gh, gw)).
+        dtype float16: both are computed in fp32 as always -- v' from the fp32 vn -- and each is then rounded once
+        (ops.to_half); the fp32 temporaries live for this call only."""
         assert not self.bf16, "encode_images: fp32 / fp32x3 only"
+        assert dtype in (torch.float32, torch.float16), dtype
         assert v.is_cuda and v.dtype in (torch.float32, torch.float16) and v.dim() == 4, \
             "v must be a float32 (or the dataset's float16) CUDA tensor [N,C,S,S]"
         x = self._image_encoder(P, v.contiguous(), keep=False).out
@@ -518,6 +521,9 @@ class Engine:
         if with_vprime:
             vprime = torch.empty(N * Pn, self.mid, dtype=torch.float32, device=v.device)
             ops.gemm(vn, P["attention.v_conv.weight"], vprime, N * Pn, self.mid, C, tag=21, x3=self._x3_gemm(N * Pn))
+        if dtype == torch.float16:
+            vn = ops.to_half(vn)
+            vprime = ops.to_half(vprime) if vprime is not None else None
         return vn.view(N, Pn, C), vprime, (gh, gw)
 
     @_device_current("feats", _cache_device)
@@ -607,7 +613,8 @@ class Engine:
         """vn [M,Pn,C]; rows [n_u], order [B], offsets [n_u+1], img [B]: device int32 (model.compact_image_index and the image
         index itself).  Returns (logits [B,A], ctx or None)."""
         assert not self.bf16, "forward_features: fp32 / fp32x3 only"
-        assert vn.is_cuda and vn.dtype == torch.float32 and vn.dim() == 3 and vn.is_contiguous() and vn.shape[2] == self.C
+        assert vn.is_cuda and vn.dtype in (torch.float32, torch.float16) and vn.dim() == 3 and vn.is_contiguous() \
+            and vn.shape[2] == self.C                   # a float16 bank is read natively: the gather and the weighted sum widen it
         side = lambda p_img, p_att: self._bank_rows(vn, rows, p_att, seed)
         return self._forward_grouped(P, side, vn.device, q, q_len, order, offsets, img, training, seed, keep, bad_tokens)
 

@@ -208,12 +208,24 @@ def _ranked(out, k: int):
     return TopAnswers(idx.long(), prob)
 
 
+def _check_cache_dtype(what: str, dtype):
+    """ValueError unless dtype is a storage format of ImageFeatures."""
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: dtype must be torch.float32 or torch.float16 (the storage formats of image features), "
+                         f"got {dtype!r}")
+
+
 class ImageFeatures:
     """What VqaNet.encode_images returns and VqaNet.answer reads: the L2-normalised image features `vn` [N, P, C], their
     attention projection `vprime` = v_conv(vn) [N*P, mid], the grid (gh, gw) with P = gh * gw, and N.  A plain holder of
     CUDA tensors; it can be kept across many answer() calls, as long as the weights it was computed from stay the same.
     `vprime` is None for features encoded with with_vprime=False: a bank for VqaNet.forward_features, which reads `vn`
-    alone (v' is 4x the size of vn in the reference's configuration and is recomputed there from the trained v_conv)."""
+    alone (v' is 4x the size of vn in the reference's configuration and is recomputed there from the trained v_conv).
+
+    Storage format (`dtype`): torch.float32, or torch.float16 = the fp32 features with each tensor rounded once to nearest
+    even (encode_images(dtype=torch.float16), or .to(torch.float16)): half the bytes held and half the bytes every reader
+    moves.  Every consumer widens on load and computes in fp32, so it gives, bit for bit, what it gives on the fp32 holder
+    .to(torch.float32) of the same values; against the unrounded fp32 features the answers differ by that one rounding."""
     __slots__ = ("vn", "vprime", "grid", "N", "_model", "_flat_ptr")
 
     def __init__(self, vn, vprime, grid, model):
@@ -221,11 +233,33 @@ class ImageFeatures:
         self._model = weakref.ref(model)
         self._flat_ptr = model._flat_param.data_ptr()     # a re-flattened model (moved, new storage) no longer matches
 
+    @property
+    def dtype(self):
+        """The storage format of vn (and of vprime, where there is one): torch.float32 or torch.float16."""
+        return self.vn.dtype
+
+    def to(self, dtype):
+        """These features in the other storage format, as a new holder of the same model and grid (self for the same dtype).
+        float32 -> float16 rounds both tensors once, with the library's converter (ops.to_half: to nearest even, as
+        .half()); float16 -> float32 widens (ops.half_to_float), which is exact.  ValueError for any other dtype."""
+        _check_cache_dtype("ImageFeatures.to", dtype)
+        if dtype == self.dtype:
+            return self
+        with torch.cuda.device(self.vn.device):
+            convert = ops.to_half if dtype == torch.float16 else ops.half_to_float
+            out = ImageFeatures.__new__(ImageFeatures)
+            out.vn = convert(self.vn.contiguous()) if self.vn.numel() else self.vn.to(dtype)
+            out.vprime = None if self.vprime is None else (
+                convert(self.vprime.contiguous()) if self.vprime.numel() else self.vprime.to(dtype))
+        out.grid, out.N, out._model, out._flat_ptr = self.grid, self.N, self._model, self._flat_ptr
+        return out
+
     @classmethod
     def cat(cls, parts):
         """Concatenate features of the same model and grid along N (a data set encoded in chunks): rows keep the order of
         `parts`.  vprime is concatenated when every part has one, otherwise the result has none.  TypeError for anything
-        that is not an ImageFeatures, ValueError for an empty list or differing grids / feature widths, RuntimeError for
+        that is not an ImageFeatures, ValueError for an empty list, differing grids / feature widths or mixed storage
+        formats (the result keeps the parts' common dtype), RuntimeError for
         parts of different models (or of a model whose parameters moved between two encode_images calls)."""
         parts = list(parts)
         if not parts:
@@ -244,6 +278,9 @@ class ImageFeatures:
             if f.grid != first.grid or f.vn.shape[1:] != first.vn.shape[1:] or f.vn.device != first.vn.device:
                 raise ValueError(f"ImageFeatures.cat: grids / feature shapes differ ({first.grid} {tuple(first.vn.shape[1:])} "
                                  f"and {f.grid} {tuple(f.vn.shape[1:])})")
+            if f.dtype != first.dtype:
+                raise ValueError(f"ImageFeatures.cat: the parts have different storage formats ({first.dtype} and {f.dtype}); "
+                                 "convert them with .to(dtype) first")
         vn = torch.cat([f.vn for f in parts], dim=0)
         vprime = torch.cat([f.vprime for f in parts], dim=0) if all(f.vprime is not None for f in parts) else None
         out = cls(vn, vprime, first.grid, model)
@@ -685,7 +722,9 @@ class VqaNet(nn.Module):
         buffer are not written, and FusedAdam skips them.  Outside a grad context it returns the same logits and keeps
         nothing.  Only feats.vn is read: v' = v_conv(vn) is recomputed every step from the current v_conv.weight, so
         in-place optimiser steps never make feats stale for THIS call (they do for answer(), see encode_images).  feats
-        must belong to this model instance and its current parameter storage, as for answer().
+        must belong to this model instance and its current parameter storage, as for answer().  A float16 bank
+        (feats.dtype == torch.float16) is read as it is -- the gather and the weighted sum widen on load -- and gives the
+        logits and gradients of the fp32 bank holding the same values, bit for bit.
 
         Dropout in train mode: image.drop (models/model.py:84) is NOT applied -- the features are the encoder's eval-mode
         output; that is what frozen means here.  attention.drop on v (model.py:185) draws one mask per feature ROW of the
@@ -742,9 +781,16 @@ class VqaNet(nn.Module):
                                "forward_features: vn only); encode them with with_vprime=True to answer from them")
 
     @torch.no_grad()
-    def encode_images(self, v, with_vprime: bool = True) -> ImageFeatures:
+    def encode_images(self, v, with_vprime: bool = True, dtype: torch.dtype = torch.float32) -> ImageFeatures:
         """The image-only part of the forward, once per image: conv blocks, L2 normalisation and v' = v_conv(vn).
         v [N,3,S,S] fp32 or fp16, CUDA.  Eval mode, compute_dtype fp32 or fp32x3; no autograd graph.
+
+        dtype: the storage format of the result, torch.float32 (default) or torch.float16; anything else is a ValueError,
+        raised before any device work.  float16 holds exactly encode_images(v).vn.half() and .vprime.half(): everything is
+        computed in fp32 as for the default -- v' from the fp32 vn, not from the rounded one -- and each tensor is rounded
+        once, to nearest even.  Half the memory, for an answer cache and for a training bank alike; answer, predict,
+        answer_pairs, predict_pairs and forward_features read it as it is (see ImageFeatures).  The fp32 temporaries are
+        this call's, so encoding in chunks keeps them at chunk size.
 
         with_vprime=False skips the v_conv product and leaves feats.vprime None: a bank for forward_features, which reads
         vn alone (chunks are joined by ImageFeatures.cat).  answer / predict / answer_pairs raise RuntimeError on it.
@@ -753,12 +799,13 @@ class VqaNet(nn.Module):
         or of a model whose parameters have moved to new storage, but it cannot see weights that changed IN PLACE (FusedAdam
         steps the flat parameter buffer through raw pointers; load_state_dict copies into it): re-encode after an
         optimiser step or load_state_dict."""
+        _check_cache_dtype("VqaNet.encode_images", dtype)
         self._check_inference("encode_images")
         self._ensure_flat()
         _need_cuda("encode_images", v.is_cuda)
         if v.dtype not in (torch.float32, torch.float16):
             v = v.float()
-        vn, vprime, grid = self._engine.encode_images(self._param_dict(), v.detach(), with_vprime=bool(with_vprime))
+        vn, vprime, grid = self._engine.encode_images(self._param_dict(), v.detach(), with_vprime=bool(with_vprime), dtype=dtype)
         return ImageFeatures(vn, vprime, grid, self)
 
     @torch.no_grad()

@@ -35,6 +35,13 @@ def _chk(t: torch.Tensor, dtype=torch.float32):
     assert t.is_cuda and t.dtype == dtype, (t.device, t.dtype)
 
 
+def _cache_suffix(t: torch.Tensor) -> str:
+    """The entry-point suffix for an image-feature cache operand (vn, v', a bank): fp32, or float16 read natively by the
+    *_f16 entry points.  Every other operand of those calls stays fp32."""
+    assert t.is_cuda and t.dtype in (torch.float32, torch.float16), (t.device, t.dtype)
+    return "_f16" if t.dtype == torch.float16 else ""
+
+
 def _gemm(name: str, c_kind: tuple, A, B, C, M, N, K, transA, transB, lda, ldb, ldc, bias1, bias2, rowgroup, rg_div, rg_op, relu,
           accumulate, aux, tag) -> torch.Tensor:
     """The call of vqa_gemm / vqa_gemm_x3 / vqa_gemm_bf16: leading dimensions default to the stored row length, the workspace
@@ -546,9 +553,10 @@ def _grouped_score_head(vprime, qp, wx, order, offsets, N: int, B: int, P: int, 
 def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
     """Scores [B, G, P] of B questions against N images from ONE v' [N*P, mid] per image: order / offsets (device int32,
     model.group_by_image) list the questions of image n as order[offsets[n]:offsets[n+1]].  mode 0 '+', 1 '*', 2 '|'
-    (wx [G, 2*mid])."""
+    (wx [G, 2*mid]).  vprime is fp32 or float16 (a float16 cache: the same scores as from vprime.float(), bit for bit)."""
+    _chk(qp)
     G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, B)
-    call("vqa_att_score_grouped_fwd", ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
+    call("vqa_att_score_grouped_fwd" + _cache_suffix(vprime), ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
          N, B, P, mid, G, mode, stream())
     return score
 
@@ -560,7 +568,7 @@ def att_score_grouped_pairs_fwd(vprime, qp, qrow, wx, bx, order, offsets, N: int
     _chk(qrow, torch.int32), _chk(qp)
     assert qrow.numel() == B
     G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, M)
-    call("vqa_att_score_grouped_pairs_fwd", ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets),
+    call("vqa_att_score_grouped_pairs_fwd" + _cache_suffix(vprime), ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets),
          ptr(score), N, B, M, P, mid, G, mode, stream())
     return score
 
@@ -584,15 +592,16 @@ def gather_rows(src, rows, dst, cols: Optional[int] = None):
 def gather_rows_drop(src, rows, p: float, seed: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[j] = dropout_{p, seed}(src)[rows[j]] without forming the dropped src: src [M, ...] is a contiguous fp32 bank of
     rows, rows device int32 [n]; the mask of element i of bank row r is drop_scale(seed, r * row_len + i) (64-bit), the one
-    dropout(src, p, seed) applies.  p = 0 copies; an index outside [0, M) gives a row of zeros.  Returns [n, ...]."""
-    _chk(src), _chk(rows, torch.int32)
+    dropout(src, p, seed) applies.  p = 0 copies; an index outside [0, M) gives a row of zeros.  Returns [n, ...], fp32.
+    A float16 bank is widened as it is read: the same bits as from src.float()."""
+    _chk(rows, torch.int32)
     assert src.is_contiguous()
     M, n = src.shape[0], rows.numel()
     row_len = src.numel() // M
     if out is None:
         out = torch.empty((n,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
     assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.numel() == n * row_len
-    call("vqa_gather_rows_drop", ptr(src), ptr(rows), ptr(out), n, M, row_len, p, seed, stream())
+    call("vqa_gather_rows_drop" + _cache_suffix(src), ptr(src), ptr(rows), ptr(out), n, M, row_len, p, seed, stream())
     return out
 
 
@@ -606,19 +615,20 @@ def _apply_gather_head(probs, vn, img):
 
 def att_apply_gather_dscore(dout, dout_ld, probs, vn, img, rowsum=None):
     """The dscore half of att_apply_gather_bwd (same device code, same bits), for a vn nobody wants a gradient of: vn
-    [N, P, C] may be a large bank, only the rows img[b] (device int32 [B]) are read."""
+    [N, P, C] may be a large bank, fp32 or float16, only the rows img[b] (device int32 [B]) are read."""
     B, G, P, N, C = _apply_gather_head(probs, vn, img)
     dscore = torch.empty_like(probs)
-    call("vqa_att_apply_gather_dscore", ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(dscore), ptr(rowsum), N, B, P, C, G,
+    call("vqa_att_apply_gather_dscore" + _cache_suffix(vn), ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(dscore), ptr(rowsum), N, B, P, C, G,
          stream())
     return dscore
 
 
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
-    """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C]."""
+    """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C], fp32 or
+    float16."""
     B, G, P, N, C = _apply_gather_head(score, vn, img)
     probs = torch.empty_like(score)
-    call("vqa_att_apply_gather_fwd", ptr(score), ptr(vn), ptr(img), ptr(probs), ptr(out), out_ld, N, B, P, C, G, stream())
+    call("vqa_att_apply_gather_fwd" + _cache_suffix(vn), ptr(score), ptr(vn), ptr(img), ptr(probs), ptr(out), out_ld, N, B, P, C, G, stream())
     return probs
 
 
@@ -743,6 +753,19 @@ def half_to_float(x: torch.Tensor) -> torch.Tensor:
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     call("vqa_half_to_float", ptr(x), ptr(y), x.numel(), stream())
     return y
+
+
+def to_half(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 -> float16 on the device, layout unchanged: round to nearest even, overflow to +-inf, NaN kept, subnormals kept
+    (what torch's .half() gives).  The one rounding of a float16 image-feature cache.  out: a contiguous float16 tensor of
+    x's element count to write into."""
+    _chk(x)
+    assert x.is_contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float16 and out.is_contiguous() and out.numel() == x.numel()
+    call("vqa_float_to_half", ptr(x), ptr(out), x.numel(), stream())
+    return out
 
 
 # ---------------------------------------------------------------------------- image preprocessing (csrc/preprocess.hip)

@@ -124,7 +124,9 @@ def run_batch_features(model, batch_data, max_answers, feats, image_index, batch
     rows) stands in for the images and question b looks at row image_index[b] (a host list or an integer tensor of B
     entries in [0, N)).  batch_data is the loader's 7-tuple; its v entry is ignored and may be None.  Same fused loss and
     score; the loss is divided by the number of QUESTIONS.  No convolution runs, and the image.* parameters get no gradient
-    (VqaNet.forward_features, which also states the dropout semantics)."""
+    (VqaNet.forward_features, which also states the dropout semantics).  The bank may be stored as float16
+    (encode_images(..., dtype=torch.float16): half the memory); the step is then, bit for bit, the step on the fp32 bank
+    holding the same values."""
     _v, q, a_indices, a_values, a_length, idx, q_len = batch_data
     n_index = len(image_index) if not torch.is_tensor(image_index) else image_index.numel()
     if n_index != q.shape[0]:

@@ -37,7 +37,9 @@ extern "C" {
  * Adam over a table of segments (vqa_adam_segments, with the struct vqa_adam_segment) -- a caller
  * built against the earlier version-8 header finds every prototype it knows unchanged.
  * Version 9 adds the plan query of the fp32x3 conv entry points (vqa_conv3x3_x3_plan), appended at the end; every
- * version-8 prototype is unchanged. */
+ * version-8 prototype is unchanged.  The entry points of float16 image-feature caches joined version 9 the append-only way
+ * (vqa_float_to_half, vqa_gather_rows_drop_f16, vqa_att_apply_gather_fwd_f16, vqa_att_apply_gather_dscore_f16,
+ * vqa_att_score_grouped_fwd_f16, vqa_att_score_grouped_pairs_fwd_f16). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -676,6 +678,35 @@ int vqa_adam_segments(float* param, const float* grad, float* exp_avg, float* ex
  * tiles; always 0 for pass 2), chunk, launches, nk (K-steps of 32), splits, ks_per_split (pass 0 and 1: 1 and nk); n_out >= 11.
  * VQA_ERR_INVALID for a pass outside 0..2, a null out, a short n_out and every layer vqa_conv3x3_x3_supported refuses. */
 int vqa_conv3x3_x3_plan(int pass, int B, int H, int W, int CiP, int Co, int stride, int32_t* out, int n_out);
+
+/* ---- float16 image-feature caches ---------------------------------------------------------------
+ * The cached image features (vn, and v' = v_conv(vn)) may be stored as IEEE half: the fp32 tensor rounded ONCE, to nearest
+ * even, overflow to +-inf, NaN kept, subnormals kept (vqa_float_to_half).  Each reader below is the device code of the entry
+ * point it is named after with the cache operand's load widened on the fly (exact), so it returns, bit for bit, what the fp32
+ * entry point returns on an fp32 tensor holding the same values; every other operand is fp32 and checked as there.
+ * A quad of halves is one 8-byte load, so the half operand needs 8-byte alignment where the fp32 form needs 16.
+ *   vqa_float_to_half: y[i] = half(x[i]); x and y 16-byte aligned; n == 0 returns VQA_OK without a launch.
+ *   vqa_gather_rows_drop_f16: src is a half bank [M][row_len], dst fp32.  The quad path (8-byte loads, 16-byte stores) needs
+ *     row_len % 4 == 0, src 8-byte and dst 16-byte aligned; anything else takes the scalar path, same bits.
+ *   vqa_att_apply_gather_fwd_f16: vn is half [N][P][C].  C % 4 != 0 or a vn that is not 8-byte aligned runs the scalar kernel.
+ *   vqa_att_apply_gather_dscore_f16: vn is half; C % 4 == 0, dout_ld % 4 == 0, dout 16-byte and vn 8-byte aligned
+ *     (VQA_ERR_INVALID otherwise, as the fp32 form refuses what it cannot read as quads).
+ *   vqa_att_score_grouped_fwd_f16 / vqa_att_score_grouped_pairs_fwd_f16: v' is half [N*P][mid], 8-byte aligned; it is widened
+ *     while its tile is staged in LDS (the tile stays fp32).  Inference forms only: training recomputes v' in fp32. */
+int vqa_float_to_half(const float* x, void* y_f16, int64_t n, vqa_stream_t stream);
+int vqa_gather_rows_drop_f16(const void* src_f16, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
+                             uint64_t seed, vqa_stream_t stream);
+int vqa_att_apply_gather_fwd_f16(const float* score, const void* vn_f16, const int32_t* img, float* probs, float* out,
+                                 int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream);
+int vqa_att_apply_gather_dscore_f16(const float* dout, int64_t dout_ld, const float* probs, const void* vn_f16,
+                                    const int32_t* img, float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G,
+                                    vqa_stream_t stream);
+int vqa_att_score_grouped_fwd_f16(const void* vprime_f16, const float* qp, const float* wx, int wx_ld, const float* bx,
+                                  const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P, int mid, int G,
+                                  int mode, vqa_stream_t stream);
+int vqa_att_score_grouped_pairs_fwd_f16(const void* vprime_f16, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                        const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                                        int M, int P, int mid, int G, int mode, vqa_stream_t stream);
 
 #ifdef __cplusplus
 }
