@@ -764,73 +764,45 @@ static int with_drop_or_pairs(bool drop, bool pairs, F&& f) {
   return pairs ? f(Flag<false>{}, Flag<true>{}) : with_flag(drop, [&](auto d) { return f(d, Flag<false>{}); });
 }
 
-// the three grouped forward entry points: p == 0 runs the DROP = false kernels, the inference entry point's code; qrow != NULL
-// (inference only, p == 0, seed == 0) runs their PAIRS instantiations over the q' table qp [M][mid]
-static int grouped_fwd(const char* who, const float* vprime, const float* qp, const int32_t* qrow, int M, const float* wx,
+// the grouped forward entry points: p == 0 runs the DROP = false kernels, the inference entry point's code; qrow != NULL
+// (inference only, p == 0, seed == 0) runs their PAIRS instantiations over the q' table qp [M][mid].  VT = __half: the two
+// inference entry points on a float16 v' (a float16 image-feature cache, p == 0): no DROP kernel is instantiated for it, and
+// the tile loader reads a quad of halves as 8 bytes, so v' is 8-byte aligned where the fp32 form asks for 16
+template <class VT>
+static int grouped_fwd(const char* who, const VT* vprime, const float* qp, const int32_t* qrow, int M, const float* wx,
                        int wx_ld, const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B, int P,
                        int mid, int G, int mode, float p, uint64_t seed, hipStream_t s) {
+  constexpr bool f32 = std::is_same<VT, float>::value;
   const int rc = att_score_check(who, true, vprime && qp && wx && bx && score, order && offsets, N, B, P, mid, wx_ld, G, mode, p,
-                                 bits(vprime, qp, wx));
+                                 f32 ? bits(vprime, qp, wx) : bits(qp, wx));
   if (rc) return rc;
+  VQA_REQUIRE((bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
   if (B == 0) return VQA_OK;
   const float ik = keep_scale(p);
   const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
   const dim3 grid((P + TP - 1) / TP, N);
   const size_t lds = (size_t)TP * mid * 4;
   with_int14(G, [&](auto g) {
-    return with_drop_or_pairs(p > 0.f, qrow != nullptr, [&](auto drop, auto pairs) {
+    auto launch = [&](auto drop, auto pairs) {
       constexpr int kG = decltype(g)::value;
       constexpr bool kDrop = decltype(drop)::value, kPairs = decltype(pairs)::value;
       if (pw)
-        hipLaunchKernelGGL((att_score_grouped_general_kernel<kG, kDrop, kPairs>), grid, dim3(256), lds, s, vprime, qp, qrow, M, wx,
-                           wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, p, ik, seed);
+        hipLaunchKernelGGL((att_score_grouped_general_kernel<kG, kDrop, kPairs, VT>), grid, dim3(256), lds, s, vprime, qp, qrow, M,
+                           wx, wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, p, ik, seed);
       else
         with_int14(mid / 256, [&](auto it) {
           return with_flag(mode == 1, [&](auto mul) {
-            hipLaunchKernelGGL((att_score_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, kDrop, kPairs>), grid,
+            hipLaunchKernelGGL((att_score_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, kDrop, kPairs, VT>), grid,
                                dim3(256), lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, p, ik, seed);
             return 0;
           });
         });
       return 0;
-    });
+    };
+    if constexpr (f32) return with_drop_or_pairs(p > 0.f, qrow != nullptr, launch);
+    else return with_flag(qrow != nullptr, [&](auto pairs) { return launch(Flag<false>{}, pairs); });
   });
   return check_hip(hipGetLastError(), "att_score_grouped_fwd launch");
-}
-
-// the two inference entry points on a float16 v' (a float16 image-feature cache): grouped_fwd's checks, path choice, grid and
-// LDS size; the tile loader reads a quad of halves as 8 bytes, so v' is 8-byte aligned where the fp32 form asks for 16
-static int grouped_fwd_f16(const char* who, const void* vprime_f16, const float* qp, const int32_t* qrow, int M, const float* wx,
-                           int wx_ld, const float* bx, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
-                           int P, int mid, int G, int mode, hipStream_t s) {
-  const int rc = att_score_check(who, true, vprime_f16 && qp && wx && bx && score, order && offsets, N, B, P, mid, wx_ld, G, mode,
-                                 0.f, bits(qp, wx));
-  if (rc) return rc;
-  VQA_REQUIRE((bits(vprime_f16) & 7) == 0, "%s: vprime must be 8-byte aligned", who);
-  if (B == 0) return VQA_OK;
-  const __half* vprime = static_cast<const __half*>(vprime_f16);
-  const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
-  const dim3 grid((P + TP - 1) / TP, N);
-  const size_t lds = (size_t)TP * mid * 4;
-  with_int14(G, [&](auto g) {
-    return with_flag(qrow != nullptr, [&](auto pairs) {
-      constexpr int kG = decltype(g)::value;
-      constexpr bool kPairs = decltype(pairs)::value;
-      if (pw)
-        hipLaunchKernelGGL((att_score_grouped_general_kernel<kG, false, kPairs, __half>), grid, dim3(256), lds, s, vprime, qp, qrow, M,
-                           wx, wx_ld, bx, order, offsets, score, B, P, mid, pw, mode, 0.f, 1.f, (uint64_t)0);
-      else
-        with_int14(mid / 256, [&](auto it) {
-          return with_flag(mode == 1, [&](auto mul) {
-            hipLaunchKernelGGL((att_score_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, false, kPairs, __half>), grid,
-                               dim3(256), lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, B, P, 0.f, 1.f, (uint64_t)0);
-            return 0;
-          });
-        });
-      return 0;
-    });
-  });
-  return check_hip(hipGetLastError(), "att_score_grouped_fwd_f16 launch");
 }
 
 extern "C" {
@@ -976,8 +948,8 @@ int vqa_att_score_grouped_fwd_f16(const void* vprime_f16, const float* qp, const
                                   int mode, vqa_stream_t stream) {
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
-  return grouped_fwd_f16("vqa_att_score_grouped_fwd_f16", vprime_f16, qp, nullptr, 0, wx, wx_ld, bx, order, offsets, score, N, B, P,
-                         mid, G, mode, (hipStream_t)stream);
+  return grouped_fwd("vqa_att_score_grouped_fwd_f16", static_cast<const __half*>(vprime_f16), qp, nullptr, 0, wx, wx_ld, bx, order,
+                     offsets, score, N, B, P, mid, G, mode, 0.f, 0, (hipStream_t)stream);
 }
 
 int vqa_att_score_grouped_pairs_fwd_f16(const void* vprime_f16, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
@@ -987,8 +959,8 @@ int vqa_att_score_grouped_pairs_fwd_f16(const void* vprime_f16, const float* qp,
   ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
   VQA_REQUIRE(qrow, "vqa_att_score_grouped_pairs_fwd_f16: null qrow");
   VQA_REQUIRE(M >= 1, "vqa_att_score_grouped_pairs_fwd_f16: M=%d question rows (>= 1)", M);
-  return grouped_fwd_f16("vqa_att_score_grouped_pairs_fwd_f16", vprime_f16, qp, qrow, M, wx, wx_ld, bx, order, offsets, score, N, B,
-                         P, mid, G, mode, (hipStream_t)stream);
+  return grouped_fwd("vqa_att_score_grouped_pairs_fwd_f16", static_cast<const __half*>(vprime_f16), qp, qrow, M, wx, wx_ld, bx,
+                     order, offsets, score, N, B, P, mid, G, mode, 0.f, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,10 @@ namespace vqa {
 
 // quad c of the row that starts at p (elements 4*c .. 4*c + 3) as a float4: one 16-byte load of fp32 (p 16-byte aligned), one
 // 8-byte load of fp16 (p 8-byte aligned)
+// That alignment, host side: a launcher takes its quad kernel for a pointer with (address & (kQuadAlign<VT> - 1)) == 0, and
+// an entry point whose kernel has no scalar form requires it.
+template <class VT>
+constexpr uintptr_t kQuadAlign = 4 * sizeof(VT);
 template <class I>
 __device__ __forceinline__ float4 load_quad(const float* p, I c) { return reinterpret_cast<const float4*>(p)[c]; }
 template <class I>

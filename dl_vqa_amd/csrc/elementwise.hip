@@ -1,9 +1,7 @@
-// Memory-bound stages of the VQA hot path: dropout, L2-norm, embedding+tanh, LSTM cell, attention
-// softmax / weighted sum, soft-target cross entropy, reductions, Adam.
+// Memory-bound stages of the VQA hot path: dropout, L2-norm, embedding+tanh, LSTM cell, soft-target cross entropy,
+// reductions.  (The attention softmax / weighted sum: att_apply.hip; row gathers and fp16 converters: gather.hip; Adam: adam.hip.)
 // All are HBM-bound streaming kernels: 16-byte per-lane accesses, wave64 shuffles for reductions.
-#include <hip/hip_fp16.h>
 #include "common.hpp"
-#include "cache_load.hpp"
 
 namespace vqa {
 
@@ -512,295 +510,6 @@ __global__ void lstm_cell_bwd_kernel(const float* gates, const float* c_in, cons
   }
 }
 
-// ------------------------------------------------------------------ softmax over positions + weighted sum
-__device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  v = is_max ? wave_max(v) : wave_sum(v);
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, red[i]) : r + red[i];
-  return r;
-}
-
-// Softmax over the P positions of every glimpse into LDS (and to `probs` from the first channel block).
-template <int G>
-__device__ __forceinline__ void att_softmax_to_lds(const float* score, float* probs, float* pr, float* red, int b, int P,
-                                                   bool write) {
-  const int tid = threadIdx.x;
-  for (int g = 0; g < G; ++g) {
-    const float* s = score + ((int64_t)b * G + g) * P;
-    float mx = -INFINITY;
-    for (int i = tid; i < P; i += blockDim.x) mx = fmaxf(mx, s[i]);
-    mx = block_reduce(mx, red, true);
-    float sum = 0.f;
-    for (int i = tid; i < P; i += blockDim.x) { const float e = expf(s[i] - mx); pr[g * P + i] = e; sum += e; }
-    sum = block_reduce(sum, red, false);
-    const float inv = 1.f / sum;
-    for (int i = tid; i < P; i += blockDim.x) {
-      const float v = pr[g * P + i] * inv;
-      pr[g * P + i] = v;
-      if (write) probs[((int64_t)b * G + g) * P + i] = v;
-    }
-  }
-}
-
-// C % 4 == 0: 256 threads = 16 position groups x 16 channel quads, 16-byte loads, four positions in flight per thread
-// (the scalar form below runs at 26 % of the HBM rate: one 4-byte load per FMA pair, 169 dependent iterations).
-// grid (B, ceil(C/64)); dynamic LDS: G*P + 16 + 16*G*64 floats.  Sum order per channel: positions pg, pg+16, ... within
-// a group, then the 16 groups in order.
-// b = the sample (score / probs / out row), n = the image whose vn rows it weights: n == b in vqa_att_apply_fwd,
-// n = img[b] in vqa_att_apply_gather_fwd (several questions per image).  VT: vn's element type (cache_load.hpp); a lane's
-// four channels are one 16-byte load of fp32 or one 8-byte load of fp16, everything else is the same code.
-template <int G, class VT>
-__device__ __forceinline__ void att_apply_fwd_v4_body(float* sm, const float* score, const VT* vn, float* probs, float* out,
-                                                      int64_t out_ld, int P, int C, int b, int n) {
-  float* pr = sm;            // [G][P]
-  float* red = sm + G * P;   // [16]
-  float* part = red + 16;    // [16][G][64]
-  const int tid = threadIdx.x;
-  att_softmax_to_lds<G>(score, probs, pr, red, b, P, blockIdx.y == 0);
-  __syncthreads();
-  const int cq = tid & 15, pg = tid >> 4;
-  const int c = blockIdx.y * 64 + cq * 4;
-  float4 acc[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c < C) {
-    const VT* vb = vn + (int64_t)n * P * C + c;
-    int i = pg;
-    for (; i + 48 < P; i += 64) {
-      float4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = load_quad(vb + (int64_t)(i + 16 * u) * C, 0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const float w = pr[g * P + i + 16 * u];
-          acc[g].x += w * v[u].x; acc[g].y += w * v[u].y; acc[g].z += w * v[u].z; acc[g].w += w * v[u].w;
-        }
-    }
-    for (; i < P; i += 16) {
-      const float4 v = load_quad(vb + (int64_t)i * C, 0);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const float w = pr[g * P + i];
-        acc[g].x += w * v.x; acc[g].y += w * v.y; acc[g].z += w * v.z; acc[g].w += w * v.w;
-      }
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) *reinterpret_cast<float4*>(part + (pg * G + g) * 64 + cq * 4) = acc[g];
-  __syncthreads();
-  // 64 * G outputs, one per thread (G <= 4)
-  for (int o = tid; o < 64 * G; o += 256) {
-    const int g = o >> 6, cl = o & 63;
-    float v = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v += part[(k * G + g) * 64 + cl];
-    if (blockIdx.y * 64 + cl < C) out[(int64_t)b * out_ld + g * C + blockIdx.y * 64 + cl] = v;
-  }
-}
-
-// GATHER (vqa_att_apply_gather_fwd): n = img[b], and a sample whose index is outside [0, N) is left unwritten (block-uniform
-// exit).  Otherwise n = b, and img / N are not read.
-template <int G, bool GATHER>
-__global__ void att_apply_fwd_v4_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
-                                        int64_t out_ld, int P, int C, int N) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  int n = blockIdx.x;
-  if (GATHER) {
-    n = img[blockIdx.x];
-    if ((unsigned)n >= (unsigned)N) return;
-  }
-  att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
-}
-
-// grid (B, ceil(C/64)), 256 threads = 4 position groups x 64 channels; dynamic LDS: G*P + 16 + 4*G*64 floats
-template <int G, class VT>
-__device__ __forceinline__ void att_apply_fwd_body(float* sm, const float* score, const VT* vn, float* probs, float* out,
-                                                   int64_t out_ld, int P, int C, int b, int n) {
-  float* pr = sm;            // [G][P]
-  float* red = sm + G * P;   // [16]
-  float* part = red + 16;    // [4][G][64]
-  const int tid = threadIdx.x;
-  att_softmax_to_lds<G>(score, probs, pr, red, b, P, blockIdx.y == 0);
-  __syncthreads();
-  const int cl = tid & 63, pg = tid >> 6;
-  const int c = blockIdx.y * 64 + cl;
-  float acc[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) acc[g] = 0.f;
-  if (c < C) {
-    const VT* vb = vn + (int64_t)n * P * C + c;
-    for (int i = pg; i < P; i += 4) {
-      const float v = load_one(vb, (int64_t)i * C);
-#pragma unroll
-      for (int g = 0; g < G; ++g) acc[g] += pr[g * P + i] * v;
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) part[(pg * G + g) * 64 + cl] = acc[g];
-  __syncthreads();
-  if (pg == 0 && c < C) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float v = part[g * 64 + cl] + part[(G + g) * 64 + cl] + part[(2 * G + g) * 64 + cl] + part[(3 * G + g) * 64 + cl];
-      out[(int64_t)b * out_ld + g * C + c] = v;
-    }
-  }
-}
-
-template <int G, bool GATHER>
-__global__ void att_apply_fwd_kernel(const float* score, const float* vn, const int* img, float* probs, float* out,
-                                     int64_t out_ld, int P, int C, int N) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  int n = blockIdx.x;
-  if (GATHER) {
-    n = img[blockIdx.x];
-    if ((unsigned)n >= (unsigned)N) return;
-  }
-  att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
-}
-
-// vqa_att_apply_gather_fwd_f16: the two GATHER kernels above on a float16 vn (V4: C % 4 == 0 and vn 8-byte aligned)
-template <int G, bool V4>
-__global__ void att_apply_gather_fwd_f16_kernel(const float* score, const __half* vn, const int* img, float* probs, float* out,
-                                                int64_t out_ld, int P, int C, int N) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int n = img[blockIdx.x];
-  if ((unsigned)n >= (unsigned)N) return;
-  if (V4) att_apply_fwd_v4_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
-  else att_apply_fwd_body<G>(sm, score, vn, probs, out, out_ld, P, C, blockIdx.x, n);
-}
-
-// pass 1: one wave per (b,p): dprob -> dscore buffer, dvn row written
-// One (sample b, position pp) row against the image row `v` that b weights there: dprob[b][g][pp] = <v, dout[b][g]> and
-// (d != null) d[c] = sum_g probs[b][g][pp] * dout[b][g*C + c].  v: row b*P + pp in vqa_att_apply_bwd, row img[b]*P + pp in
-// vqa_att_apply_gather_bwd -- the (sample, image) form, as in att_apply_fwd_body.  v: the row's first element, fp32 or fp16
-// (cache_load.hpp), read a channel quad at a time.
-template <int G, class VT>
-__device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dout_ld, const float* probs, const VT* v,
-                                                  float4* d, float* dprob, int64_t b, int pp, int P, int C, int lane) {
-  const int nch = C >> 2;
-  float pr[G], acc[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) { pr[g] = probs[(b * G + g) * P + pp]; acc[g] = 0.f; }
-  for (int c = lane; c < nch; c += 64) {
-    const float4 x = load_quad(v, c);
-    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float4 go = reinterpret_cast<const float4*>(dout + b * dout_ld + (int64_t)g * C)[c];
-      acc[g] += x.x * go.x + x.y * go.y + x.z * go.z + x.w * go.w;
-      o.x += pr[g] * go.x; o.y += pr[g] * go.y; o.z += pr[g] * go.z; o.w += pr[g] * go.w;
-    }
-    if (d) d[c] = o;       // d == null: vqa_l2norm_bwd_joined recomputes this branch where it is consumed
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const float s = wave_sum(acc[g]);
-    if (lane == 0) dprob[(b * G + g) * P + pp] = s;
-  }
-}
-
-// GATHER (vqa_att_apply_gather_bwd, several questions per image): sample b weighted the rows of image img[b] of vn [N][P][C];
-// dvn is null there -- the per-image sum is the kernel below.
-template <int G, bool GATHER>
-__global__ void att_apply_bwd_rows_kernel(const float* dout, int64_t dout_ld, const float* probs, const float* vn,
-                                          const int* img, int N, float* dprob, float* dvn, int64_t M, int P, int C) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t m = wave; m < M; m += nwaves) {
-    const int64_t b = m / P;
-    const int pp = (int)(m - b * P);
-    int64_t vm = m;
-    if (GATHER) {
-      int n = img[b];
-      n = n < 0 ? 0 : (n >= N ? N - 1 : n);               // a malformed index reads nothing out of bounds
-      vm = (int64_t)n * P + pp;
-    }
-    att_apply_bwd_row<G>(dout, dout_ld, probs, vn + vm * C, dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr, dprob, b, pp,
-                         P, C, lane);
-  }
-}
-
-// vqa_att_apply_gather_dscore_f16: the GATHER rows kernel above on a float16 vn.  Nobody wants a gradient of a cache, so dvn
-// is always null -- but it stays a run-time argument, as in the kernel above: the row body then compiles to the arithmetic
-// (the same fused multiply-adds) of the fp32 instantiation, which a body specialised for d == null does not.
-template <int G>
-__global__ void att_apply_gather_rows_f16_kernel(const float* dout, int64_t dout_ld, const float* probs, const __half* vn,
-                                                 const int* img, int N, float* dprob, float* dvn, int64_t M, int P, int C) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t m = wave; m < M; m += nwaves) {
-    const int64_t b = m / P;
-    const int pp = (int)(m - b * P);
-    int n = img[b];
-    n = n < 0 ? 0 : (n >= N ? N - 1 : n);                 // a malformed index reads nothing out of bounds
-    att_apply_bwd_row<G>(dout, dout_ld, probs, vn + ((int64_t)n * P + pp) * C, dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr,
-                         dprob, b, pp, P, C, lane);
-  }
-}
-
-// Several questions per image: the weighted-sum branch of d loss / d vn summed per IMAGE, one wave per image row (n, pp):
-// dvn[n][pp][c] = sum over the questions b = order[offsets[n] .. offsets[n+1]) in that order, g ascending inside a question,
-// of probs[b][g][pp] * dout[b][g*C + c] -- the row body's sum for one question.  Every row of dvn is written, zeros for an
-// image nobody asks about.
-template <int G>
-__global__ void att_apply_gather_dvn_kernel(const float* dout, int64_t dout_ld, const float* probs, const int* order,
-                                            const int* offsets, float* dvn, int64_t M, int B, int P, int C) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int nch = C >> 2;
-  for (int64_t m = wave; m < M; m += nwaves) {
-    const int64_t n = m / P;
-    const int pp = (int)(m - n * P);
-    int k0 = offsets[n], k1 = offsets[n + 1];
-    k0 = k0 < 0 ? 0 : k0;
-    k1 = k1 > B ? B : k1;
-    float4* d = reinterpret_cast<float4*>(dvn + m * C);
-    for (int c = lane; c < nch; c += 64) {
-      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int k = k0; k < k1; ++k) {
-        const int64_t b = order[k];
-        if ((uint64_t)b >= (uint64_t)B) continue;
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const float pr = probs[(b * G + g) * P + pp];
-          const float4 go = reinterpret_cast<const float4*>(dout + b * dout_ld + (int64_t)g * C)[c];
-          o.x += pr * go.x; o.y += pr * go.y; o.z += pr * go.z; o.w += pr * go.w;
-        }
-      }
-      d[c] = o;
-    }
-  }
-}
-// pass 2: block per (b,g): dscore = probs * (dprob - sum_p probs*dprob), in place on dprob
-// rowsum (optional) [B*G]: sum_p dscore of the block's row -- the per-sample part of the x_conv bias gradient
-__global__ void softmax_bwd_kernel(const float* probs, float* dscore, int P, float* rowsum) {
-  __shared__ float red[16];
-  const int64_t base = (int64_t)blockIdx.x * P;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < P; i += blockDim.x) s += probs[base + i] * dscore[base + i];
-  s = block_reduce(s, red, false);
-  float t = 0.f;
-  for (int i = threadIdx.x; i < P; i += blockDim.x) {
-    const float d = probs[base + i] * (dscore[base + i] - s);
-    dscore[base + i] = d;
-    t += d;
-  }
-  if (rowsum) {
-    t = block_reduce(t, red, false);
-    if (threadIdx.x == 0) rowsum[blockIdx.x] = t;
-  }
-}
-
 // ------------------------------------------------------------------ soft-target CE + VQA score
 __global__ void softce_kernel(const float* logits, int64_t ld, const int64_t* a_idx, const int64_t* a_val, int kmax,
                               int A, float inv_batch, float* loss_rows, float* score_rows, float* dlogits, int64_t dld) {
@@ -956,191 +665,6 @@ __global__ void add2d_kernel(const float* a, int64_t lda, const float* b, int64_
   }
 }
 
-// dst[b][0:cols] = src[rows[b]][0:cols], zeros for a row index outside [0, M); VEC: one float4 per thread and iteration
-template <bool VEC>
-__global__ void gather_rows_kernel(const float* src, int64_t src_ld, const int* rows, float* dst, int64_t dst_ld, int B, int M,
-                                   int cols) {
-  const int cw = VEC ? cols >> 2 : cols;
-  const int64_t n = (int64_t)B * cw;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = i / cw;
-    const int c = (int)(i - b * cw);
-    const int r = rows[b];
-    const bool in = (unsigned)r < (unsigned)M;
-    if (VEC) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (in) v = reinterpret_cast<const float4*>(src + (int64_t)r * src_ld)[c];
-      reinterpret_cast<float4*>(dst + b * dst_ld)[c] = v;
-    } else {
-      dst[b * dst_ld + c] = in ? src[(int64_t)r * src_ld + c] : 0.f;
-    }
-  }
-}
-
-// dst[j][0:row_len] = src[rows[j]][0:row_len] * drop_scale(seed, rows[j]*row_len + i): rows of a large bank compacted and
-// dropped in one pass, the mask indexed by the BANK row (64-bit flat index), zeros for a row index outside [0, M).  Rows are
-// long (one image's features), so the flat range n * row_len is spread over a capped grid; a thread divides once and then
-// walks (row, column) by the grid stride split on the host into (step_j, step_c) = divmod(stride, width).  VEC: one float4
-// per thread and iteration (row_len % 4 == 0, so a row start is a multiple of 4 for drop_scale4).  VT: the bank's element
-// type (cache_load.hpp); dst is fp32 either way, and the mask multiplies the widened value.
-template <bool VEC, class VT>
-__device__ __forceinline__ void gather_rows_drop_body(const VT* src, const int* rows, float* dst, int n, int M, int64_t row_len,
-                                                      int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
-  const int64_t rw = VEC ? row_len >> 2 : row_len;
-  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t j = first / rw, c = first - j * rw;
-  while (j < n) {
-    const int r = rows[j];
-    const bool in = (unsigned)r < (unsigned)M;
-    const int64_t s = (int64_t)r * row_len, d = j * row_len;
-    if (VEC) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (in) {
-        v = load_quad(src + s, c);
-        if (p > 0.f) {
-          const float4 ds_ = drop_scale4(seed, (uint64_t)(s + 4 * c), p, inv_keep);
-          v.x *= ds_.x; v.y *= ds_.y; v.z *= ds_.z; v.w *= ds_.w;
-        }
-      }
-      reinterpret_cast<float4*>(dst + d)[c] = v;
-    } else {
-      float v = 0.f;
-      if (in) {
-        v = load_one(src, s + c);
-        if (p > 0.f) v *= drop_scale(seed, (uint64_t)(s + c), p, inv_keep);
-      }
-      dst[d + c] = v;
-    }
-    j += step_j;
-    c += step_c;
-    if (c >= rw) { c -= rw; ++j; }
-  }
-}
-
-template <bool VEC>
-__global__ void gather_rows_drop_kernel(const float* src, const int* rows, float* dst, int n, int M, int64_t row_len,
-                                        int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
-  gather_rows_drop_body<VEC>(src, rows, dst, n, M, row_len, step_j, step_c, p, inv_keep, seed);
-}
-
-// vqa_gather_rows_drop_f16: a float16 bank
-template <bool VEC>
-__global__ void gather_rows_drop_f16_kernel(const __half* src, const int* rows, float* dst, int n, int M, int64_t row_len,
-                                            int64_t step_j, int64_t step_c, float p, float inv_keep, uint64_t seed) {
-  gather_rows_drop_body<VEC>(src, rows, dst, n, M, row_len, step_j, step_c, p, inv_keep, seed);
-}
-
-// fp16 -> fp32, 8 values (16 bytes in, 32 bytes out) per thread and iteration
-__global__ void half_to_float_kernel(const __half* x, float* y, int64_t n) {
-  const int64_t n8 = n / 8;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint4 raw = reinterpret_cast<const uint4*>(x)[i];
-    const __half2* h = reinterpret_cast<const __half2*>(&raw);
-    const float2 a = __half22float2(h[0]), b = __half22float2(h[1]), c = __half22float2(h[2]), d = __half22float2(h[3]);
-    reinterpret_cast<float4*>(y)[2 * i] = make_float4(a.x, a.y, b.x, b.y);
-    reinterpret_cast<float4*>(y)[2 * i + 1] = make_float4(c.x, c.y, d.x, d.y);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < n - 8 * n8) y[8 * n8 + threadIdx.x] = __half2float(x[8 * n8 + threadIdx.x]);
-}
-
-// fp32 -> fp16, round to nearest even (v_cvt_f16_f32: overflow to +-inf, NaN stays NaN, subnormal results kept): the mirror
-// of half_to_float_kernel, 8 values (32 bytes in, 16 bytes out) per thread and iteration
-__global__ void float_to_half_kernel(const float* x, __half* y, int64_t n) {
-  const int64_t n8 = n / 8;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 a = reinterpret_cast<const float4*>(x)[2 * i], b = reinterpret_cast<const float4*>(x)[2 * i + 1];
-    uint4 raw;
-    __half2* h = reinterpret_cast<__half2*>(&raw);
-    h[0] = __halves2half2(__float2half(a.x), __float2half(a.y));
-    h[1] = __halves2half2(__float2half(a.z), __float2half(a.w));
-    h[2] = __halves2half2(__float2half(b.x), __float2half(b.y));
-    h[3] = __halves2half2(__float2half(b.z), __float2half(b.w));
-    reinterpret_cast<uint4*>(y)[i] = raw;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < n - 8 * n8) y[8 * n8 + threadIdx.x] = __float2half(x[8 * n8 + threadIdx.x]);
-}
-
-__global__ void scale_by_kernel(float* x, int64_t n, const float* s) {
-  const float k = *s;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) x[i] *= k;
-}
-
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, int64_t n, float step_size, float beta1,
-                            float beta2, float eps, float inv_sqrt_bc2, float grad_scale) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gr = g[i] * grad_scale;
-    const float mi = beta1 * m[i] + (1.f - beta1) * gr;
-    const float vi = beta2 * v[i] + (1.f - beta2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-    p[i] -= step_size * (mi / denom);
-  }
-}
-
-// ---------------------------------------------------------------- Adam over a table of segments (vqa_adam_segments)
-// A segment as the kernel reads it: bounds in float4 units, the host's bias-corrected scalars (as vqa_adam computes them),
-// mode 0 = no decay (adam_kernel's arithmetic), 1 = L2 decay, 2 = decoupled decay (keep = 1 - lr * weight_decay).
-struct AdamSeg {
-  int64_t q0, q1;
-  float step_size, beta1, beta2, eps, inv_sqrt_bc2, wd, keep;
-  int mode;
-};
-struct AdamSegTable { AdamSeg s[VQA_ADAM_MAX_SEGMENTS]; };      // 3 KiB of the 4 KiB a launch may pass by value
-
-// One element.  MODE 0 is adam_kernel's arithmetic, expression for expression and rounding for rounding: left to itself the
-// compiler contracts the same expressions differently inside a float4 body (beta2 * v + t * gr becomes one packed fma here,
-// a multiply and an add there), so contraction is off in this function and the three fused operations adam_kernel's code
-// has -- the first moment, the denominator, the final update -- are written as fmaf.  tests/test_adam_groups_gpu.py holds the
-// two kernels to the same bits.  The decay terms exist only in MODE 1 / 2.
-template <int MODE>
-__device__ __forceinline__ void adam_seg_elem(float& p, float g, float& m, float& v, const AdamSeg& s, float grad_scale) {
-#pragma clang fp contract(off)
-  float pi = p;
-  float gr = g * grad_scale;
-  if (MODE == 1) gr = gr + s.wd * pi;
-  if (MODE == 2) pi = pi * s.keep;
-  const float mi = fmaf(1.f - s.beta1, gr, s.beta1 * m);
-  const float vi = s.beta2 * v + (1.f - s.beta2) * gr * gr;
-  m = mi; v = vi;
-  const float denom = fmaf(sqrtf(vi), s.inv_sqrt_bc2, s.eps);
-  p = fmaf(-s.step_size, mi / denom, pi);
-}
-template <int MODE>
-__device__ __forceinline__ void adam_seg_quad(float4& p, const float4& g, float4& m, float4& v, const AdamSeg& s, float grad_scale) {
-  adam_seg_elem<MODE>(p.x, g.x, m.x, v.x, s, grad_scale);
-  adam_seg_elem<MODE>(p.y, g.y, m.y, v.y, s, grad_scale);
-  adam_seg_elem<MODE>(p.z, g.z, m.z, v.z, s, grad_scale);
-  adam_seg_elem<MODE>(p.w, g.w, m.w, v.w, s, grad_scale);
-}
-
-// One lane owns a float4 and walks [first q0, last q1) with the grid's stride.  The table arrives by value; it is copied to LDS
-// with a loop whose index is the same in every lane (a per-lane index into the argument would move it to scratch) and the lanes
-// index the LDS copy.  The walk of a lane only moves forward, so its segment cursor does too: one 16-byte LDS read of the bounds
-// per float4 while the lane stays inside a segment.  A float4 in a gap costs no global access.
-__global__ __launch_bounds__(256) void adam_segments_kernel(float* p, const float* g, float* m, float* v, const AdamSegTable tab,
-                                                             int n_segs, float grad_scale) {
-  __shared__ AdamSeg seg[VQA_ADAM_MAX_SEGMENTS];
-  for (int s = 0; s < n_segs; ++s)
-    if (threadIdx.x == 0) seg[s] = tab.s[s];
-  __syncthreads();
-  const int64_t q_end = seg[n_segs - 1].q1, stride = (int64_t)gridDim.x * blockDim.x;
-  int s = 0;
-  for (int64_t q = seg[0].q0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < q_end; q += stride) {
-    while (q >= seg[s].q1) ++s;                     // q < q_end = the last q1: s stays below n_segs
-    if (q < seg[s].q0) continue;                    // between two segments
-    const AdamSeg sg = seg[s];
-    float4 pq = reinterpret_cast<const float4*>(p)[q];
-    const float4 gq = reinterpret_cast<const float4*>(g)[q];
-    float4 mq = reinterpret_cast<const float4*>(m)[q], vq = reinterpret_cast<const float4*>(v)[q];
-    if (sg.mode == 0) adam_seg_quad<0>(pq, gq, mq, vq, sg, grad_scale);
-    else if (sg.mode == 1) adam_seg_quad<1>(pq, gq, mq, vq, sg, grad_scale);
-    else adam_seg_quad<2>(pq, gq, mq, vq, sg, grad_scale);
-    reinterpret_cast<float4*>(m)[q] = mq;
-    reinterpret_cast<float4*>(v)[q] = vq;
-    reinterpret_cast<float4*>(p)[q] = pq;
-  }
-}
-
 }  // namespace vqa
 
 using namespace vqa;
@@ -1156,107 +680,6 @@ static void l2norm_bwd_launch(const float* dvn, const float* vn, const float* no
                      keep_scale(p), seed, positions, dout, dout_ld, probs, dv_in, p_v, keep_scale(p_v), seed_v)
   if (mode == 2) L2B(2); else if (mode == 1) L2B(1); else L2B(0);
 #undef L2B
-}
-
-// ---------------------------------------------------------------- softmax + weighted sum: the host side of vqa_att_apply_*
-// dynamic LDS of both forward kernels (the scalar one uses less of it): probs [G][P], 16 reduction slots, part [16][G][64]
-static size_t att_apply_fwd_lds(int G, int P) { return ((size_t)G * P + 16 + 16 * G * 64) * 4; }
-
-static uintptr_t quad_bits(const void* a, const void* b, const void* c) {
-  return reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
-}
-
-// What the five entry points check, before any HIP call (`who` names the caller in the messages).  backward: the kernels
-// read dout / vn and write dvn as float4, so C and the leading dimension are multiples of 4 and `quads` (quad_bits of those
-// pointers, a null one counts as aligned) is 16-byte aligned.  pointers / indices: the form's data pointers and its
-// img / order / offsets are all there (true for a form without indices).  N: 1 for a form without an image count.
-static int att_apply_check(const char* who, bool backward, bool pointers, bool indices, int N, int B, int P, int C, int G,
-                           int64_t ld, uintptr_t quads) {
-  VQA_REQUIRE(G >= 1 && G <= 4, "%s: glimpses=%d unsupported (1..4)", who, G);
-  VQA_REQUIRE(pointers, "%s: null pointer", who);
-  VQA_REQUIRE(indices, "%s: null pointer among img / order / offsets", who);
-  const bool widths = backward ? C >= 4 && C % 4 == 0 && ld % 4 == 0 : C >= 1;
-  VQA_REQUIRE(N >= 1 && B >= 0 && P >= 1 && widths && ld >= (int64_t)G * C, "%s: N=%d, B=%d, P=%d, C=%d%s, %s=%lld out of range",
-              who, N, B, P, C, backward ? " (a multiple of 4)" : "", backward ? "dout_ld" : "out_ld", (long long)ld);
-  VQA_REQUIRE(backward || att_apply_fwd_lds(G, P) <= 64 * 1024, "%s: G*P=%d too large for LDS", who, G * P);
-  VQA_REQUIRE((quads & 15) == 0, "%s: dout, vn and dvn must be 16-byte aligned", who);
-  return VQA_OK;
-}
-
-// img == null: sample b weights its own image (vqa_att_apply_fwd), N is not read.  The 16-byte kernels need whole quads
-// of channels and an aligned vn; anything else runs the scalar ones.
-static int att_apply_fwd_launch(const float* score, const float* vn, const int32_t* img, float* probs, float* out,
-                                int64_t out_ld, int N, int B, int P, int C, int G, hipStream_t s) {
-  if (B == 0) return VQA_OK;
-  const dim3 grid(B, (C + 63) / 64);
-  const size_t lds = att_apply_fwd_lds(G, P);
-  return with_int14(G, [&](auto g) {
-    return with_flags(C % 4 == 0 && (reinterpret_cast<uintptr_t>(vn) & 15) == 0, img != nullptr, [&](auto v4, auto gather) {
-      if (decltype(v4)::value)
-        hipLaunchKernelGGL((att_apply_fwd_v4_kernel<decltype(g)::value, decltype(gather)::value>), grid, dim3(256), lds, s, score,
-                           vn, img, probs, out, out_ld, P, C, N);
-      else
-        hipLaunchKernelGGL((att_apply_fwd_kernel<decltype(g)::value, decltype(gather)::value>), grid, dim3(256), lds, s, score,
-                           vn, img, probs, out, out_ld, P, C, N);
-      return check_hip(hipGetLastError(), "att_apply_fwd launch");
-    });
-  });
-}
-
-// img == null: the plain form, whose rows kernel writes dvn [B][P][C] itself (dvn == null: nobody wants it).  With img the
-// rows kernel leaves dvn alone, and order / offsets (with dvn [N][P][C]) add the per-image sum; then the softmax backward.
-static int att_apply_bwd_launch(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
-                                const int32_t* order, const int32_t* offsets, float* dscore, float* dvn, float* dscore_rowsum,
-                                int N, int B, int P, int C, int G, hipStream_t s) {
-  if (B == 0) return VQA_OK;
-  const int64_t M = (int64_t)B * P, Mn = (int64_t)N * P;
-  int rc = with_int14(G, [&](auto g) {
-    return with_flag(img != nullptr, [&](auto gather) {
-      hipLaunchKernelGGL((att_apply_bwd_rows_kernel<decltype(g)::value, decltype(gather)::value>), dim3(grid_for(M, 4)), dim3(256),
-                         0, s, dout, dout_ld, probs, vn, img, N, dscore, decltype(gather)::value ? nullptr : dvn, M, P, C);
-      return check_hip(hipGetLastError(), "att_apply_bwd_rows launch");
-    });
-  });
-  if (rc == VQA_OK && order)
-    rc = with_int14(G, [&](auto g) {
-      hipLaunchKernelGGL(att_apply_gather_dvn_kernel<decltype(g)::value>, dim3(grid_for(Mn, 4)), dim3(256), 0, s, dout, dout_ld,
-                         probs, order, offsets, dvn, Mn, B, P, C);
-      return check_hip(hipGetLastError(), "att_apply_gather_dvn launch");
-    });
-  if (rc) return rc;
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, s, probs, dscore, P, dscore_rowsum);
-  return check_hip(hipGetLastError(), "softmax_bwd launch");
-}
-
-// The float16-vn forms (a float16 image-feature cache): the gather forward and the dscore half of the gather backward, the
-// same grids, blocks and LDS sizes.  The forward's quad kernel needs whole quads of channels and an 8-byte aligned vn.
-static int att_apply_gather_fwd_f16_launch(const float* score, const __half* vn, const int32_t* img, float* probs, float* out,
-                                           int64_t out_ld, int N, int B, int P, int C, int G, hipStream_t s) {
-  if (B == 0) return VQA_OK;
-  const dim3 grid(B, (C + 63) / 64);
-  const size_t lds = att_apply_fwd_lds(G, P);
-  return with_int14(G, [&](auto g) {
-    return with_flag(C % 4 == 0 && (reinterpret_cast<uintptr_t>(vn) & 7) == 0, [&](auto v4) {
-      hipLaunchKernelGGL((att_apply_gather_fwd_f16_kernel<decltype(g)::value, decltype(v4)::value>), grid, dim3(256), lds, s, score,
-                         vn, img, probs, out, out_ld, P, C, N);
-      return check_hip(hipGetLastError(), "att_apply_gather_fwd_f16 launch");
-    });
-  });
-}
-
-static int att_apply_gather_dscore_f16_launch(const float* dout, int64_t dout_ld, const float* probs, const __half* vn,
-                                              const int32_t* img, float* dscore, float* dscore_rowsum, int N, int B, int P, int C,
-                                              int G, hipStream_t s) {
-  if (B == 0) return VQA_OK;
-  const int64_t M = (int64_t)B * P;
-  const int rc = with_int14(G, [&](auto g) {
-    hipLaunchKernelGGL(att_apply_gather_rows_f16_kernel<decltype(g)::value>, dim3(grid_for(M, 4)), dim3(256), 0, s, dout, dout_ld,
-                       probs, vn, img, N, dscore, (float*)nullptr, M, P, C);
-    return check_hip(hipGetLastError(), "att_apply_gather_rows_f16 launch");
-  });
-  if (rc) return rc;
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(B * G), dim3(256), 0, s, probs, dscore, P, dscore_rowsum);
-  return check_hip(hipGetLastError(), "softmax_bwd launch");
 }
 
 extern "C" {
@@ -1379,57 +802,6 @@ int vqa_lstm_cell_bwd(const float* gates, const float* c_in, const float* c_out,
   return check_hip(hipGetLastError(), "lstm_cell_bwd launch");
 }
 
-// vqa_att_apply_fwd and vqa_att_apply_bwd take the checks of their gather forms: what used to reach a launch with undefined
-// results (out_ld / dout_ld < G*C, P < 1, a dout, vn or dvn that the backward cannot read as float4, G outside 1..4) is
-// VQA_ERR_INVALID, and B == 0 is VQA_OK without a launch.  Every argument set that was valid runs the kernels it ran, on the
-// same grid, block and LDS size; a vn that is not 16-byte aligned now takes the forward's scalar kernels.
-int vqa_att_apply_fwd(const float* score, const float* vn, float* probs, float* out, int64_t out_ld, int B, int P,
-                      int C, int G, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_fwd", false, score && vn && probs && out, true, 1, B, P, C, G, out_ld, 0);
-  return rc ? rc : att_apply_fwd_launch(score, vn, nullptr, probs, out, out_ld, 0, B, P, C, G, STREAM);
-}
-
-int vqa_att_apply_gather_fwd(const float* score, const float* vn, const int32_t* img, float* probs, float* out,
-                             int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_gather_fwd", false, score && vn && probs && out, img, N, B, P, C, G, out_ld, 0);
-  return rc ? rc : att_apply_fwd_launch(score, vn, img, probs, out, out_ld, N, B, P, C, G, STREAM);
-}
-
-int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, float* dscore,
-                      float* dvn, float* dscore_rowsum, int B, int P, int C, int G, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_bwd", true, dout && probs && vn && dscore, true, 1, B, P, C, G, dout_ld,
-                                 quad_bits(dout, vn, dvn));
-  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, nullptr, nullptr, nullptr, dscore, dvn, dscore_rowsum, 0, B, P,
-                                        C, G, STREAM);
-}
-
-int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
-                             const int32_t* order, const int32_t* offsets, float* dscore, float* dvn, float* dscore_rowsum,
-                             int N, int B, int P, int C, int G, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_gather_bwd", true, dout && probs && vn && dscore && dvn, img && order && offsets,
-                                 N, B, P, C, G, dout_ld, quad_bits(dout, vn, dvn));
-  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, order, offsets, dscore, dvn, dscore_rowsum, N, B, P, C, G,
-                                        STREAM);
-}
-
-int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
-                                float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_gather_dscore", true, dout && probs && vn && dscore, img, N, B, P, C, G, dout_ld,
-                                 quad_bits(dout, vn, nullptr));
-  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, nullptr, nullptr, dscore, nullptr, dscore_rowsum, N, B, P,
-                                        C, G, STREAM);
-}
-
 int vqa_softce_fwd_bwd(const float* logits, int64_t ld, const int64_t* a_idx, const int64_t* a_val, int kmax, int B,
                        int A, float inv_batch, float* loss_rows, float* score_rows, float* dlogits, int64_t dld,
                        vqa_stream_t stream) {
@@ -1476,170 +848,6 @@ int vqa_add2d(const float* a, int64_t lda, const float* b, int64_t ldb, float* y
   hipLaunchKernelGGL(add2d_kernel, dim3(grid_for(rows * cols, 256)), dim3(256), 0, STREAM, a, lda, b, ldb, y, ldy,
                      rows, cols);
   return check_hip(hipGetLastError(), "add2d launch");
-}
-
-int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float* dst, int64_t dst_ld, int B, int M, int cols,
-                    vqa_stream_t stream) {
-  VQA_REQUIRE(src && rows && dst, "vqa_gather_rows: null pointer");
-  VQA_REQUIRE(B >= 0 && M >= 1 && cols >= 1, "vqa_gather_rows: B=%d, M=%d, cols=%d out of range", B, M, cols);
-  VQA_REQUIRE(src_ld >= cols && dst_ld >= cols, "vqa_gather_rows: src_ld=%lld and dst_ld=%lld must be >= cols=%d",
-              (long long)src_ld, (long long)dst_ld, cols);
-  if (B == 0) return VQA_OK;
-  const bool vec = cols % 4 == 0 && src_ld % 4 == 0 && dst_ld % 4 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(grid_for((int64_t)B * (cols / 4), 256)), dim3(256), 0, STREAM, src, src_ld,
-                       rows, dst, dst_ld, B, M, cols);
-  else
-    hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(grid_for((int64_t)B * cols, 256)), dim3(256), 0, STREAM, src, src_ld, rows,
-                       dst, dst_ld, B, M, cols);
-  return check_hip(hipGetLastError(), "gather_rows launch");
-}
-
-int vqa_gather_rows_drop(const float* src, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
-                         uint64_t seed, vqa_stream_t stream) {
-  VQA_REQUIRE(src && rows && dst, "vqa_gather_rows_drop: null pointer");
-  VQA_REQUIRE(n >= 0 && M >= 1 && row_len >= 1, "vqa_gather_rows_drop: n=%d, M=%d, row_len=%lld out of range", n, M,
-              (long long)row_len);
-  VQA_REQUIRE(p >= 0.f && p < 1.f, "vqa_gather_rows_drop: p=%g outside [0, 1)", (double)p);
-  if (n == 0) return VQA_OK;
-  const bool vec = row_len % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-  const int64_t rw = vec ? row_len / 4 : row_len;
-  const int grid = grid_for((int64_t)n * rw, 256);
-  const int64_t stride = (int64_t)grid * 256;
-  if (vec)
-    hipLaunchKernelGGL(gather_rows_drop_kernel<true>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
-                       stride / rw, stride % rw, p, keep_scale(p), seed);
-  else
-    hipLaunchKernelGGL(gather_rows_drop_kernel<false>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
-                       stride / rw, stride % rw, p, keep_scale(p), seed);
-  return check_hip(hipGetLastError(), "gather_rows_drop launch");
-}
-
-int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t stream) {
-  VQA_REQUIRE(x_f16 && y && n > 0, "vqa_half_to_float: bad args");
-  VQA_REQUIRE(((uintptr_t)x_f16 % 16) == 0 && ((uintptr_t)y % 16) == 0, "vqa_half_to_float: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(half_to_float_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, STREAM,
-                     static_cast<const __half*>(x_f16), y, n);
-  return check_hip(hipGetLastError(), "half_to_float launch");
-}
-
-// ---- float16 image-feature caches: the converter and the cache readers of this file on a half operand
-int vqa_float_to_half(const float* x, void* y_f16, int64_t n, vqa_stream_t stream) {
-  VQA_REQUIRE(x && y_f16 && n >= 0, "vqa_float_to_half: bad args");
-  VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_f16 % 16) == 0, "vqa_float_to_half: pointers must be 16-byte aligned");
-  if (n == 0) return VQA_OK;
-  hipLaunchKernelGGL(float_to_half_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, STREAM, x, static_cast<__half*>(y_f16), n);
-  return check_hip(hipGetLastError(), "float_to_half launch");
-}
-
-int vqa_gather_rows_drop_f16(const void* src_f16, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
-                             uint64_t seed, vqa_stream_t stream) {
-  VQA_REQUIRE(src_f16 && rows && dst, "vqa_gather_rows_drop_f16: null pointer");
-  VQA_REQUIRE(n >= 0 && M >= 1 && row_len >= 1, "vqa_gather_rows_drop_f16: n=%d, M=%d, row_len=%lld out of range", n, M,
-              (long long)row_len);
-  VQA_REQUIRE(p >= 0.f && p < 1.f, "vqa_gather_rows_drop_f16: p=%g outside [0, 1)", (double)p);
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(src_f16) & 1) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0,
-              "vqa_gather_rows_drop_f16: src must be 2-byte and dst 4-byte aligned");
-  if (n == 0) return VQA_OK;
-  const __half* src = static_cast<const __half*>(src_f16);
-  // the quad path: 8-byte loads of the bank, 16-byte stores
-  const bool vec = row_len % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 7) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
-  const int64_t rw = vec ? row_len / 4 : row_len;
-  const int grid = grid_for((int64_t)n * rw, 256);
-  const int64_t stride = (int64_t)grid * 256;
-  if (vec)
-    hipLaunchKernelGGL(gather_rows_drop_f16_kernel<true>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
-                       stride / rw, stride % rw, p, keep_scale(p), seed);
-  else
-    hipLaunchKernelGGL(gather_rows_drop_f16_kernel<false>, dim3(grid), dim3(256), 0, STREAM, src, rows, dst, n, M, row_len,
-                       stride / rw, stride % rw, p, keep_scale(p), seed);
-  return check_hip(hipGetLastError(), "gather_rows_drop_f16 launch");
-}
-
-int vqa_att_apply_gather_fwd_f16(const float* score, const void* vn_f16, const int32_t* img, float* probs, float* out,
-                                 int64_t out_ld, int N, int B, int P, int C, int G, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_FWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_gather_fwd_f16", false, score && vn_f16 && probs && out, img, N, B, P, C, G, out_ld,
-                                 0);
-  if (rc) return rc;
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & 1) == 0, "vqa_att_apply_gather_fwd_f16: vn must be 2-byte aligned");
-  return att_apply_gather_fwd_f16_launch(score, static_cast<const __half*>(vn_f16), img, probs, out, out_ld, N, B, P, C, G, STREAM);
-}
-
-int vqa_att_apply_gather_dscore_f16(const float* dout, int64_t dout_ld, const float* probs, const void* vn_f16,
-                                    const int32_t* img, float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G,
-                                    vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
-  const int rc = att_apply_check("vqa_att_apply_gather_dscore_f16", true, dout && probs && vn_f16 && dscore, img, N, B, P, C, G,
-                                 dout_ld, quad_bits(dout, nullptr, nullptr));
-  if (rc) return rc;
-  // the rows kernel reads a quad of halves as 8 bytes where the fp32 form reads 16
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & 7) == 0, "vqa_att_apply_gather_dscore_f16: vn must be 8-byte aligned");
-  return att_apply_gather_dscore_f16_launch(dout, dout_ld, probs, static_cast<const __half*>(vn_f16), img, dscore, dscore_rowsum, N,
-                                            B, P, C, G, STREAM);
-}
-
-int vqa_scale_by(float* x, int64_t n, const float* scalar, vqa_stream_t stream) {
-  VQA_REQUIRE(x && scalar && n > 0, "vqa_scale_by: bad args");
-  hipLaunchKernelGGL(scale_by_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM, x, n, scalar);
-  return check_hip(hipGetLastError(), "scale_by launch");
-}
-
-int vqa_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-             float beta2, float eps, int step, float grad_scale, vqa_stream_t stream) {
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ADAM, (hipStream_t)stream);
-  VQA_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "vqa_adam: bad args");
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq, n,
-                     step_size, beta1, beta2, eps, inv_sqrt_bc2, grad_scale);
-  return check_hip(hipGetLastError(), "adam launch");
-}
-
-int vqa_adam_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                      const vqa_adam_segment* segs, int n_segs, float grad_scale, vqa_stream_t stream) {
-  VQA_REQUIRE(param && grad && exp_avg && exp_avg_sq && segs, "vqa_adam_segments: null pointer");
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-                reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
-              "vqa_adam_segments: param, grad, exp_avg and exp_avg_sq must be 16-byte aligned");
-  VQA_REQUIRE(n >= 1 && n_segs >= 1 && n_segs <= VQA_ADAM_MAX_SEGMENTS, "vqa_adam_segments: n=%lld, n_segs=%d out of range (1..%d segments)",
-              (long long)n, n_segs, VQA_ADAM_MAX_SEGMENTS);
-  AdamSegTable tab;
-  memset(&tab, 0, sizeof(tab));
-  int64_t prev_end = 0;
-  for (int i = 0; i < n_segs; ++i) {
-    const vqa_adam_segment& s = segs[i];
-    VQA_REQUIRE(s.begin % 4 == 0 && s.end % 4 == 0, "vqa_adam_segments: segment %d [%lld, %lld) is not aligned to 4 elements", i,
-                (long long)s.begin, (long long)s.end);
-    VQA_REQUIRE(s.begin >= 0 && s.begin < s.end && s.end <= n, "vqa_adam_segments: segment %d [%lld, %lld) out of range (n=%lld)", i,
-                (long long)s.begin, (long long)s.end, (long long)n);
-    VQA_REQUIRE(s.begin >= prev_end, "vqa_adam_segments: segment %d [%lld, %lld) overlaps or precedes segment %d (sorted, disjoint)",
-                i, (long long)s.begin, (long long)s.end, i - 1);
-    VQA_REQUIRE(s.step >= 1, "vqa_adam_segments: segment %d has step=%d (>= 1)", i, s.step);
-    VQA_REQUIRE(s.weight_decay >= 0.f && (s.decoupled == 0 || s.decoupled == 1),
-                "vqa_adam_segments: segment %d has weight_decay=%g, decoupled=%d", i, (double)s.weight_decay, s.decoupled);
-    prev_end = s.end;
-    const double bc1 = 1.0 - pow((double)s.beta1, s.step), bc2 = 1.0 - pow((double)s.beta2, s.step);
-    AdamSeg& d = tab.s[i];
-    d.q0 = s.begin / 4;
-    d.q1 = s.end / 4;
-    d.step_size = (float)((double)s.lr / bc1);
-    d.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    d.beta1 = s.beta1; d.beta2 = s.beta2; d.eps = s.eps; d.wd = s.weight_decay;
-    d.keep = (float)(1.0 - (double)s.lr * (double)s.weight_decay);
-    d.mode = s.weight_decay == 0.f ? 0 : (s.decoupled ? 2 : 1);
-  }
-  set_launch_tag(-1);
-  ProfScope prof(VQA_K_ADAM, (hipStream_t)stream);
-  const int64_t quads = tab.s[n_segs - 1].q1 - tab.s[0].q0;
-  hipLaunchKernelGGL(adam_segments_kernel, dim3(grid_for(quads, 256, VQA_ADAM_SEGMENTS_MAX_BLOCKS)), dim3(256), 0, STREAM, param, grad,
-                     exp_avg, exp_avg_sq, tab, n_segs, grad_scale);
-  return check_hip(hipGetLastError(), "adam_segments launch");
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Float64 CPU references for the streaming (HBM-bound) kernels of csrc/elementwise.hip.
+"""Float64 CPU references for the streaming (HBM-bound) kernels of csrc/elementwise.hip and the units split from it
+(att_apply.hip, gather.hip, adam.hip).
 
 Nothing here touches the GPU or the HIP library: the dropout masks are recomputed from the counter-based hash of
 csrc/common.hpp in numpy (keep_scale), every operator is plain float64 torch, and the attention-score backward exists

@@ -1,5 +1,5 @@
-"""GPU parity of the streaming (HBM-bound) kernels of csrc/elementwise.hip against float64, in every mode, at the
-tails and past the grid cap.
+"""GPU parity of the streaming (HBM-bound) kernels of csrc/elementwise.hip and the units split from it (att_apply.hip,
+gather.hip, adam.hip) against float64, in every mode, at the tails and past the grid cap.
 
 The references are tests/streaming_ref.py (float64, CPU).  Every dropout mask is data from keep_scale -- the numpy
 restatement of the counter-based hash -- never the output of a kernel, so the element index a fused kernel uses is

@@ -116,6 +116,16 @@ def main():
     run("sq4096_nt", 2.0 * S ** 3, lambda: ops.gemm(a, bm, cm, S, S, S))
     run("sq4096_nn", 2.0 * S ** 3, lambda: ops.gemm(a, bm, cm, S, S, S, transB=False, lda=S, ldb=S))
     run("sq4096_tn", 2.0 * S ** 3, lambda: ops.gemm(a, bm, cm, S, S, S, transA=True, transB=False, lda=S, ldb=S))
+    # two small streaming kernels of the loss head (no MFMA work: read the milliseconds), for an A/B of two builds (VQA_LIB)
+    A, G = 3000, 2
+    logits = torch.randn(B, A, device=dev)
+    a_idx = torch.randint(0, A + 1, (B, 10), device=dev)
+    a_val = torch.randint(1, 11, (B, 10), device=dev)
+    dl = torch.empty_like(logits)
+    run("softce", 0.0, lambda: ops.softce(logits, A, a_idx, a_val, A, 1.0 / B, dl, A))
+    ds = torch.randn(B, G, P, device=dev)
+    dbx = torch.empty(G, device=dev)
+    run("sum_bgp", 0.0, lambda: ops.sum_bgp(ds, dbx))
     tot = sum(r[1] for r in res)
     print(f"sum of listed kernels: {tot:.3f} ms")
 
