@@ -816,8 +816,15 @@ class Engine:
         # bf16 path: both on bf16 MFMA, dx' already is bf16 (written in place over x)
         v_op, wv_op = (ctx.v16.view(B * Pn, C), ctx.wv16) if self.bf16 else (ctx.v_in, P["attention.v_conv.weight"])
         gx3 = self._x3_gemm(B * Pn)
-        _gemm(dxpre, v_op, Gr["attention.v_conv.weight"], mid, C, B * Pn, transA=True, transB=False, lda=mid, ldb=C, tag=44,
-              x3=gx3)
+        # the bf16 GEMM takes K in multiples of 8: of an odd batch (B * Pn = 3 * 676, ...) it gets the first rows8 rows, and
+        # the fp32 GEMM adds the last 1..7, widened to fp32 -- the products are exact either way, the accumulation fp32
+        rows8 = B * Pn // 8 * 8 if self.bf16 else B * Pn
+        if rows8:
+            _gemm(dxpre, v_op, Gr["attention.v_conv.weight"], mid, C, rows8, transA=True, transB=False, lda=mid, ldb=C, tag=44,
+                  x3=gx3)
+        if rows8 != B * Pn:
+            _gemm(ops.to_f32(dxpre[rows8:]), ops.to_f32(v_op[rows8:]), Gr["attention.v_conv.weight"], mid, C, B * Pn - rows8,
+                  transA=True, transB=False, lda=mid, ldb=C, accumulate=rows8 > 0, tag=44)
         dv_in = new(B * Pn, C)
         _gemm(dxpre, wv_op, dv_in, B * Pn, C, mid, transB=False, lda=mid, ldb=C, tag=45, x3=gx3)
         self._q_lin_bwd(P, ctx, dqp, dcomb, Gr)

@@ -376,6 +376,70 @@ def test_bf16_module_patch_conv_path_matches_bf16_oracle(pconv, monkeypatch):
         assert e < 2e-2, (k, e)
 
 
+def _train_step_against_bf16_oracle(name, cfg, V, A, B, S, T, seeds, tol_logits, tol_grad):
+    """One train-mode forward + backward of VqaNet(compute_dtype="bf16") with the oracle's soft cross-entropy, against
+    O.loss_and_grads(bf16=True) under the same dropout masks: logits and loss within tol_logits (absolute) and the logits
+    closer to the bf16 oracle than half the bf16-to-fp32 distance; every gradient within tol_grad of its largest entry, the
+    error printed per parameter.  Returns (ctx, O)."""
+    from oracle import vqa_oracle as O
+    from dl_vqa_amd import VqaNet
+    from dl_vqa_amd.train import soft_ce_loss_and_score
+    from tests.hip_masks import hip_masks
+    torch.manual_seed(seeds[0])
+    m = VqaNet(cfg, V, compute_dtype="bf16").to(DEV).train()
+    sd = {k: t.detach().cpu().clone() for k, t in m.state_dict().items()}
+    v, q, a_idx, a_val, _, _, ql = O.synthetic_batch(B, S, T, V, A, seed=seeds[1])
+    torch.manual_seed(9)
+    y = m(v.to(DEV), q.to(DEV), ql.to(DEV))
+    loss, _ = soft_ce_loss_and_score(y, a_idx.to(DEV), a_val.to(DEV))
+    loss.backward()
+    torch.cuda.synchronize()
+    ctx = m._last_ctx
+    masks = hip_masks(m._engine, ctx.seed, B, T, ctx.acts[-1].shape[1], DEV)
+    y_ref, loss_ref, g_ref = O.loss_and_grads(sd, cfg, v, q, ql, a_idx, a_val, masks=masks, bf16=True)
+    y_f32, _, g_f32 = O.loss_and_grads(sd, cfg, v, q, ql, a_idx, a_val, masks=masks)
+    err = float((y.detach().cpu() - y_ref).abs().max())
+    dist = float((y_f32 - y_ref).abs().max())
+    print(f"[parity-bf16] {name} logits |err| vs bf16 oracle {err:.3e}; bf16 vs fp32 oracle {dist:.3e}")
+    assert err < tol_logits and err < 0.5 * dist
+    assert abs(float(loss.detach()) - float(loss_ref)) < tol_logits
+    for k, p in m.named_parameters():
+        ref = g_ref[k]
+        scale = max(float(ref.abs().max()), 1e-12)
+        if k == "attention.x_conv.bias":
+            assert float(p.grad.abs().max()) < 1e-6
+            continue
+        e = float((p.grad.cpu() - ref).abs().max()) / scale
+        d = float((g_f32[k] - ref).abs().max()) / scale
+        print(f"[parity-bf16] {name} grad {k}: vs bf16 oracle {e:.3e}; bf16 vs fp32 oracle {d:.3e}")
+        assert e < tol_grad, (k, e)
+    return ctx, O
+
+
+def test_bf16_module_odd_rows_matches_bf16_oracle():
+    """An odd batch: the shape of test_bf16_module_patch_conv_path_matches_bf16_oracle with B = 3, so B * P = 108 rows, 4 past a
+    multiple of 8.  The v_conv weight gradient contracts over those rows; the bf16 GEMM takes the first 104 and the fp32 GEMM
+    adds the last 4 (engine.py, _attention_bwd) -- this step used to raise from the bf16 GEMM's argument check.  The
+    tolerances of test_bf16_module_matches_bf16_oracle."""
+    cfg = bf16_cfg("+", 0.3)
+    cfg["image"]["num_channels"] = [3, 64, 128, 256]
+    ctx, _ = _train_step_against_bf16_oracle("module (odd rows, B * P = 108)", cfg, 50, 24, 3, 68, 6, (4, 8), 5e-5, 2e-2)
+    assert ctx.B * ctx.Pn == 108
+
+
+def test_bf16_module_lstm_side_products_at_step_widths():
+    """The bf16 LSTM-side products (xg, dW_hh, dW_ih, dx on vqa_gemm_bf16) at the widths the train step has -- H = 1024,
+    E = 300 padded to 304 -- with T * B = 56, a multiple of 8, so lstm16 is on: every other test at H = 1024 has T * B = 28
+    and keeps them in fp32.  The bounds of test_bf16_configs3_bench_architecture, which has the same widths: logits 5e-4
+    absolute and less than half the bf16-to-fp32 distance, gradients 5e-2 of the largest entry.  The tight bounds on these
+    products are tests/test_step_links_gpu.py's."""
+    from tests.golden_util import full_cfg
+    ctx, O = _train_step_against_bf16_oracle("module (lstm16 at H = 1024, T * B = 56)", full_cfg(1000), 3000, 1000, 4, 68, 14,
+                                             (13, 9), 5e-4, 5e-2)
+    assert O.lstm16_ok(1024, 56)
+    assert ctx.x16 is not None and ctx.x16.dtype == torch.bfloat16 and tuple(ctx.x16.shape) == (56, 304)
+
+
 def test_bf16_four_block_448_matches_bf16_oracle():
     """A DEEPER network than the one benchmarked (448x448 images, FOUR conv blocks 64/128/256/512 -> a 26x26 grid,
     Hq=Ha=Hc=1024, T=14, A=1000) at B=2 in train mode with shared dropout masks: the bf16 kernels at a 512-channel block
