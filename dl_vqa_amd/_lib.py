@@ -153,6 +153,9 @@ PROTOTYPES = {
     "vqa_att_apply_gather_dscore_f16": (i32, [f32p, i64, f32p, vp, vp, f32p, f32p, i32, i32, i32, i32, i32, vp]),
     "vqa_att_score_grouped_fwd_f16": (i32, [vp, f32p, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_att_score_grouped_pairs_fwd_f16": (i32, [vp, f32p, vp, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
+    # image dropout on a bank of cached image features
+    "vqa_gather_rows_drop_norm": (i32, [f32p, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),
+    "vqa_gather_rows_drop_norm_f16": (i32, [vp, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),
 }
 
 K_GEMM, K_CONV_FWD, K_CONV_DGRAD, K_CONV_WGRAD = 0, 1, 2, 3

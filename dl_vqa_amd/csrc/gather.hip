@@ -73,6 +73,117 @@ __global__ void gather_rows_drop_kernel(const VT* src, const int* rows, float* d
   gather_rows_drop_body<VEC>(src, rows, dst, n, M, row_len, step_j, step_c, p, inv_keep, seed);
 }
 
+// Image dropout on rows of a bank of L2-normalised features: for feature row (j, pos) of the n * P asked
+// ones, u = src[rows[j]][pos][:] * drop_scale(seed, bank index), vn_out = u / (|u| + 1e-12) -- the operations of
+// l2norm_fwd_kernel (elementwise.hip) on a gathered row, the mask indexed by the BANK row (64-bit) -- and, where vdrop_out
+// is given, vdrop_out = vn_out * drop_scale(seed2, bank index).  One wave per feature row of C floats; zeros in both
+// outputs for a row index outside [0, M).  REG: C <= 256, a lane keeps its quad in registers and a wave has four feature
+// rows in flight (one pass over memory); otherwise the general form reads a row twice.  VT: the bank's element type.
+template <bool REG, class VT>
+__global__ void gather_rows_drop_norm_kernel(const VT* src, const int* rows, float* vn_out, float* vdrop_out, int n, int M, int P,
+                                             int C, float p, float inv_keep, uint64_t seed, float p2, float inv_keep2,
+                                             uint64_t seed2) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int nch = C >> 2;
+  const int64_t frows = (int64_t)n * P;            // feature rows of the output
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (REG) {
+    constexpr int R = 4;
+    const int c = lane;
+    const bool cok = c < nch;
+    for (int64_t f0 = R * wave; f0 < frows; f0 += R * nwaves) {
+      float4 u[R];
+      int64_t s[R];                                // first element of the bank's feature row, -1: nothing to read
+      int64_t j = f0 / P;                          // one division a group: (j, pos) then walks the R consecutive rows
+      int pos = (int)(f0 - j * P);
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        s[k] = -1;
+        if (f0 + k < frows) {
+          const int r = rows[j];
+          if ((unsigned)r < (unsigned)M) s[k] = ((int64_t)r * P + pos) * C;
+        }
+        u[k] = (cok && s[k] >= 0) ? load_quad(src + s[k], c) : zero4;
+        if (++pos == P) { pos = 0; ++j; }
+      }
+      float ss[R];
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        if (p > 0.f && s[k] >= 0) {
+          const float4 ds_ = drop_scale4(seed, (uint64_t)(s[k] + 4 * c), p, inv_keep);
+          u[k].x *= ds_.x; u[k].y *= ds_.y; u[k].z *= ds_.z; u[k].w *= ds_.w;
+        }
+        ss[k] = 0.f;
+        ss[k] += u[k].x * u[k].x + u[k].y * u[k].y + u[k].z * u[k].z + u[k].w * u[k].w;
+      }
+#pragma unroll
+      for (int k = 0; k < R; ++k) ss[k] = wave_sum(ss[k]);
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const int64_t f = f0 + k;
+        if (f >= frows) break;
+        if (!cok) continue;
+        const float inv = 1.0f / (sqrtf(ss[k]) + 1e-12f);
+        const float4 o = make_float4(u[k].x * inv, u[k].y * inv, u[k].z * inv, u[k].w * inv);
+        reinterpret_cast<float4*>(vn_out + f * C)[c] = o;
+        if (vdrop_out) {
+          float4 d = o;
+          if (p2 > 0.f && s[k] >= 0) {
+            const float4 ds_ = drop_scale4(seed2, (uint64_t)(s[k] + 4 * c), p2, inv_keep2);
+            d.x *= ds_.x; d.y *= ds_.y; d.z *= ds_.z; d.w *= ds_.w;
+          }
+          reinterpret_cast<float4*>(vdrop_out + f * C)[c] = d;
+        }
+      }
+    }
+    return;
+  }
+  for (int64_t f = wave; f < frows; f += nwaves) {
+    const int64_t j = f / P;
+    const int r = rows[j];
+    float4* dst = reinterpret_cast<float4*>(vn_out + f * C);
+    float4* dst2 = vdrop_out ? reinterpret_cast<float4*>(vdrop_out + f * C) : nullptr;
+    if ((unsigned)r >= (unsigned)M) {              // wave-uniform
+      for (int c = lane; c < nch; c += 64) {
+        dst[c] = zero4;
+        if (dst2) dst2[c] = zero4;
+      }
+      continue;
+    }
+    const int64_t s = ((int64_t)r * P + (f - j * P)) * C;
+    float ss = 0.f;
+    for (int c = lane; c < nch; c += 64) {
+      float4 u = load_quad(src + s, c);
+      if (p > 0.f) {
+        const float4 ds_ = drop_scale4(seed, (uint64_t)(s + 4 * c), p, inv_keep);
+        u.x *= ds_.x; u.y *= ds_.y; u.z *= ds_.z; u.w *= ds_.w;
+      }
+      ss += u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w;
+    }
+    ss = wave_sum(ss);
+    const float inv = 1.0f / (sqrtf(ss) + 1e-12f);
+    for (int c = lane; c < nch; c += 64) {
+      float4 u = load_quad(src + s, c);
+      if (p > 0.f) {
+        const float4 ds_ = drop_scale4(seed, (uint64_t)(s + 4 * c), p, inv_keep);
+        u.x *= ds_.x; u.y *= ds_.y; u.z *= ds_.z; u.w *= ds_.w;
+      }
+      const float4 o = make_float4(u.x * inv, u.y * inv, u.z * inv, u.w * inv);
+      dst[c] = o;
+      if (dst2) {
+        float4 d = o;
+        if (p2 > 0.f) {
+          const float4 ds_ = drop_scale4(seed2, (uint64_t)(s + 4 * c), p2, inv_keep2);
+          d.x *= ds_.x; d.y *= ds_.y; d.z *= ds_.z; d.w *= ds_.w;
+        }
+        dst2[c] = d;
+      }
+    }
+  }
+}
+
 // fp16 -> fp32, 8 values (16 bytes in, 32 bytes out) per thread and iteration
 __global__ void half_to_float_kernel(const __half* x, float* y, int64_t n) {
   const int64_t n8 = n / 8;
@@ -133,6 +244,31 @@ static int gather_rows_drop(const char* who, const VT* src, const int32_t* rows,
   });
 }
 
+// vqa_gather_rows_drop_norm and vqa_gather_rows_drop_norm_f16.  Quads only (there is no scalar kernel): every check is made
+// here, before any HIP call.  One wave per feature row, four waves a workgroup; the register form takes four rows a wave.
+template <class VT>
+static int gather_rows_drop_norm(const char* who, const VT* src, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M,
+                                 int P, int C, float p, uint64_t seed, float p2, uint64_t seed2, hipStream_t s) {
+  const uintptr_t sb = reinterpret_cast<uintptr_t>(src), ob = reinterpret_cast<uintptr_t>(vn_out),
+                  db = reinterpret_cast<uintptr_t>(vdrop_out);
+  VQA_REQUIRE(src && rows && vn_out, "%s: null pointer", who);
+  VQA_REQUIRE(n >= 0 && M >= 1 && P >= 1, "%s: n=%d, M=%d, P=%d out of range", who, n, M, P);
+  VQA_REQUIRE(C >= 4 && C % 4 == 0, "%s: C=%d must be a positive multiple of 4", who, C);
+  VQA_REQUIRE(p >= 0.f && p < 1.f, "%s: p=%g outside [0, 1)", who, (double)p);
+  VQA_REQUIRE(!vdrop_out || (p2 >= 0.f && p2 < 1.f), "%s: p2=%g outside [0, 1)", who, (double)p2);
+  VQA_REQUIRE((sb & (kQuadAlign<VT> - 1)) == 0, "%s: src must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  VQA_REQUIRE((ob & 15) == 0 && (db & 15) == 0, "%s: vn_out and vdrop_out must be 16-byte aligned", who);
+  if (n == 0) return VQA_OK;
+  if (!vdrop_out) { p2 = 0.f; seed2 = 0; }
+  const bool reg = C <= 256;
+  const int grid = grid_for((int64_t)n * P, reg ? 16 : 4);
+  return with_flag(reg, [&](auto r) {
+    hipLaunchKernelGGL((gather_rows_drop_norm_kernel<decltype(r)::value, VT>), dim3(grid), dim3(256), 0, s, src, rows, vn_out,
+                       vdrop_out, n, M, P, C, p, keep_scale(p), seed, p2, keep_scale(p2), seed2);
+    return check_hip(hipGetLastError(), "gather_rows_drop_norm launch");
+  });
+}
+
 extern "C" {
 
 int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float* dst, int64_t dst_ld, int B, int M, int cols,
@@ -178,6 +314,18 @@ int vqa_float_to_half(const float* x, void* y_f16, int64_t n, vqa_stream_t strea
 int vqa_gather_rows_drop_f16(const void* src_f16, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
                              uint64_t seed, vqa_stream_t stream) {
   return gather_rows_drop("vqa_gather_rows_drop_f16", static_cast<const __half*>(src_f16), rows, dst, n, M, row_len, p, seed, STREAM);
+}
+
+// ---- image dropout on a bank of normalised features
+int vqa_gather_rows_drop_norm(const float* src, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M, int P, int C,
+                              float p, uint64_t seed, float p2, uint64_t seed2, vqa_stream_t stream) {
+  return gather_rows_drop_norm("vqa_gather_rows_drop_norm", src, rows, vn_out, vdrop_out, n, M, P, C, p, seed, p2, seed2, STREAM);
+}
+
+int vqa_gather_rows_drop_norm_f16(const void* src_f16, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M, int P,
+                                  int C, float p, uint64_t seed, float p2, uint64_t seed2, vqa_stream_t stream) {
+  return gather_rows_drop_norm("vqa_gather_rows_drop_norm_f16", static_cast<const __half*>(src_f16), rows, vn_out, vdrop_out, n, M,
+                               P, C, p, seed, p2, seed2, STREAM);
 }
 
 }  // extern "C"

@@ -590,8 +590,9 @@ class Engine:
     # forward_features: the image encoder is frozen: `vn` [M,Pn,C] is a bank of its eval-mode outputs (encode_images).  Only the
     # n_u DISTINCT asked rows are touched: rows (ascending) names them, order / offsets group the questions by their slot in
     # rows.  No kernel's grid or byte count depends on M.  v' is recomputed from the current v_conv weight every step.
-    # Dropout: SITE_IMAGE is not applied; SITE_ATT_V draws per BANK row (logical tensor [M, gh, gw, C]); the question-side
-    # sites draw per question as forward_shared does.
+    # Dropout: SITE_IMAGE is not applied unless image dropout is asked for (a slot index: then it draws per BANK row like
+    # SITE_ATT_V, and the asked rows are renormalised after it); SITE_ATT_V draws per BANK row (logical tensor [M, gh, gw, C]);
+    # the question-side sites draw per question as forward_shared does.
     @_device_current("v")
     def forward_shared(self, P: Dict[str, Tensor], v: Tensor, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor,
                        img: Tensor, training: bool, seed: int, keep: bool, bad_tokens: Optional[Tensor] = None,
@@ -609,14 +610,18 @@ class Engine:
     @_device_current("vn")
     def forward_features(self, P: Dict[str, Tensor], vn: Tensor, q: Tensor, q_len: Tensor, rows: Tensor, order: Tensor,
                          offsets: Tensor, img: Tensor, training: bool, seed: int, keep: bool,
-                         bad_tokens: Optional[Tensor] = None):
+                         bad_tokens: Optional[Tensor] = None, slot: Optional[Tensor] = None):
         """vn [M,Pn,C]; rows [n_u], order [B], offsets [n_u+1], img [B]: device int32 (model.compact_image_index and the image
-        index itself).  Returns (logits [B,A], ctx or None)."""
+        index itself).  slot [B] (device int32, rows[slot[b]] == img[b]) asks for image dropout: where its rate is above 0
+        (train mode, image.dropout > 0) the weighted sum reads the dropped, renormalised rows at slot[b] instead of the bank at
+        img[b]; None, or a rate of 0, is the schedule without it.  Returns (logits [B,A], ctx or None)."""
         assert not self.bf16, "forward_features: fp32 / fp32x3 only"
         assert vn.is_cuda and vn.dtype in (torch.float32, torch.float16) and vn.dim() == 3 and vn.is_contiguous() \
             and vn.shape[2] == self.C                   # a float16 bank is read natively: the gather and the weighted sum widen it
-        side = lambda p_img, p_att: self._bank_rows(vn, rows, p_att, seed)
-        return self._forward_grouped(P, side, vn.device, q, q_len, order, offsets, img, training, seed, keep, bad_tokens)
+        drop = slot is not None and self._rates(training)[1] > 0
+        side = lambda p_img, p_att: self._bank_rows(vn, rows, p_img if drop else 0.0, p_att, seed)
+        return self._forward_grouped(P, side, vn.device, q, q_len, order, offsets, slot if drop else img, training, seed, keep,
+                                     bad_tokens)
 
     def _encoded_images(self, P, v, keep, need_dx, p_img, p_att, seed):
         """forward_shared's image side: the image encoder on the N images, image dropout + L2 normalisation, attention.drop(v)
@@ -632,10 +637,19 @@ class Engine:
         own = dict(encoded=True, pooled=enc.out, **self._encoder_saved(enc, norm, p_img, need_dx, v))
         return vn.view(N, gh * gw, C), v_in, N, own
 
-    def _bank_rows(self, vn, rows, p_att, seed):
+    def _bank_rows(self, vn, rows, p_img, p_att, seed):
         """forward_features' image side: the asked rows of the bank vn [M,Pn,C], compacted, with attention.drop(v) indexed by
         the bank row.  Returns (vn: the weighted sum reads the bank itself, undropped; v_in [n_u,Pn,C]; n_u; the schedule's own
-        saved fields)."""
+        saved fields).  p_img > 0 (image dropout asked for): image.drop and the renormalisation on the compacted rows in the
+        same pass, both masks indexed by the bank row; what comes back as vn is then vn_d [n_u,Pn,C], which
+        the weighted sum reads at a question's slot in rows."""
+        if p_img > 0:
+            if p_att > 0:
+                vn_d, v_in = ops.gather_rows_drop_norm(vn, rows, p_img, _site_seed(seed, SITE_IMAGE),
+                                                       drop2=(p_att, _site_seed(seed, SITE_ATT_V)))
+            else:
+                vn_d = v_in = ops.gather_rows_drop_norm(vn, rows, p_img, _site_seed(seed, SITE_IMAGE))
+            return vn_d, v_in, rows.numel(), dict(encoded=False, rows=rows)
         v_in = ops.gather_rows_drop(vn, rows, p_att, _site_seed(seed, SITE_ATT_V))
         return vn, v_in, rows.numel(), dict(encoded=False, rows=rows)
 

@@ -436,16 +436,21 @@ class _VqaSharedFunction(torch.autograd.Function):
         return _node_backward(ctx, dlogits, 6, ctx.model._engine.backward_grouped)
 
 
+def _slot_of(index):
+    """The slot view of forward_features' uploaded index (rows, order, offsets, img[, slot]): there with image dropout."""
+    return index[4] if len(index) > 4 else None
+
+
 class _VqaFeaturesFunction(torch.autograd.Function):
     """Autograd node of one VqaNet.forward_features call: the image encoder is not part of the graph.  vn is the bank's
-    feature tensor (no gradient), index the device int32 views (rows [n_u], order [B], offsets [n_u+1], image index [B]) of
-    _upload_index.  Every parameter is an input, so that gradient storage follows _VqaFunction's rules through the same
-    helper; the image.* parameters get None."""
+    feature tensor (no gradient), index the device int32 views (rows [n_u], order [B], offsets [n_u+1], image index [B] and,
+    with image dropout, slot [B]) of _upload_index.  Every parameter is an input, so that gradient storage follows
+    _VqaFunction's rules through the same helper; the image.* parameters get None."""
 
     @staticmethod
     def forward(ctx, model, vn, q, q_len, seed, index, *params):
         return _node_forward(ctx, model, lambda P: model._engine.forward_features(
-            P, vn, q, q_len, *index, model.training, seed, keep=True, bad_tokens=model._token_counter(q)))
+            P, vn, q, q_len, *index[:4], model.training, seed, keep=True, bad_tokens=model._token_counter(q), slot=_slot_of(index)))
 
     @staticmethod
     def backward(ctx, dlogits):
@@ -707,7 +712,7 @@ class VqaNet(nn.Module):
         return logits
 
     # ------------------------------------------------------------------ training on cached image features
-    def forward_features(self, feats, q, q_len, image_index):
+    def forward_features(self, feats, q, q_len, image_index, image_dropout=False):
         """forward_shared() with the image encoder frozen and run beforehand: feats is an ImageFeatures of this model
         (encode_images, possibly with_vprime=False, possibly an ImageFeatures.cat of chunks) with N rows, and question b
         (q[b], q_len[b]) looks at row image_index[b].  Returns logits [B, A].  No convolution runs here, forward or
@@ -726,17 +731,30 @@ class VqaNet(nn.Module):
         (feats.dtype == torch.float16) is read as it is -- the gather and the weighted sum widen on load -- and gives the
         logits and gradients of the fp32 bank holding the same values, bit for bit.
 
-        Dropout in train mode: image.drop (models/model.py:84) is NOT applied -- the features are the encoder's eval-mode
-        output; that is what frozen means here.  attention.drop on v (model.py:185) draws one mask per feature ROW of the
-        bank: the logical tensor is [feats.N, gh, gw, C], element (n, p, c) at flat index (n*P + p)*C + c with n the row in
-        feats, not the slot in the batch -- forward_shared's convention for the same images in the same order, so with
-        image.dropout = 0 the two calls are the same function of the seed.  Every question-side site (text, attention.drop
+        Dropout in train mode: with image_dropout=False (the default) image.drop (models/model.py:84) is NOT applied -- the
+        features are the encoder's eval-mode output.  image_dropout=True applies it at the configured rate, from the bank
+        alone: the reference drops first and L2-normalises second (model.py:55-56), normalisation is scale-invariant, so the
+        asked rows are masked and renormalised, m*vn / |m*vn| = m*pooled / |m*pooled|, in the pass that gathers them -- what
+        the train-mode encoder would give for that mask, up to how the 1e-12 guard of the norm scales (immaterial unless the
+        kept part of a feature row has a norm near 1e-12; an all-zero kept part gives zeros either way).  The mask is drawn
+        per feature ROW of the bank, logical tensor [feats.N, gh, gw, C] at the image site, as attention.drop's below:
+        forward_shared's convention for the same images in the same order, so with image_dropout=True
+        forward_features(encode_images(v), ...) and forward_shared(v, ...) are the same function of the seed for the non-image
+        parameters, up to rounding.  In eval mode, or with image.dropout = 0, True runs exactly what False runs.
+        image_dropout must be a bool (ValueError otherwise, before any device work).  The image.* gradients stay None.
+
+        attention.drop on v (model.py:185) draws one mask per feature ROW of the bank: the logical tensor is
+        [feats.N, gh, gw, C], element (n, p, c) at flat index (n*P + p)*C + c with n the row in feats, not the slot in the
+        batch -- forward_shared's convention for the same images in the same order, so with image.dropout = 0 the two calls
+        are the same function of the seed.  Every question-side site (text, attention.drop
         on q and on x, both classifier sites) draws per question exactly as forward_shared does.  One seed is drawn per
-        training forward, none in eval mode.
+        training forward, none in eval mode, with or without image_dropout.
 
         NotImplementedError for compute_dtype "bf16" and for a model wrapped by dl_vqa_amd.distributed.DataParallel,
         TypeError for a feats that is not an ImageFeatures, RuntimeError for CPU tensors or foreign features, ValueError
         for wrong ranks, a wrong image_index count or an empty batch."""
+        if not isinstance(image_dropout, bool):
+            raise ValueError(f"VqaNet.forward_features: image_dropout must be a bool, got {image_dropout!r}")
         self._check_grouped_training("forward_features", "on cached image features")
         if not isinstance(feats, ImageFeatures):
             raise TypeError("VqaNet.forward_features: feats must come from VqaNet.encode_images (or ImageFeatures.cat)")
@@ -747,22 +765,24 @@ class VqaNet(nn.Module):
         self._check_owned("forward_features", feats, "image", "encode_images")
         B, N = q.shape[0], feats.N
         img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
-        rows, _slot, order, offsets = compact_image_index(img, N)
+        rows, slot, order, offsets = compact_image_index(img, N)
         if order.numel() != B:
             raise ValueError(f"VqaNet.forward_features: {order.numel()} image_index entries for {B} questions")
         if N == 0 or B == 0:
             raise ValueError(f"VqaNet.forward_features: an empty batch ({N} feature rows, {B} questions)")
         self._validate_tokens(q)
         validate_question_lengths(q_len, q.shape[1])
-        index = _upload_index(feats.vn.device, rows, order, offsets, img)
+        # image dropout at a rate above 0: the weighted sum then reads the dropped rows at a question's slot in `rows`
+        drop = image_dropout and self.training and self._engine.p_image > 0
+        index = _upload_index(feats.vn.device, rows, order, offsets, img, *((slot,) if drop else ()))
         seed = self._next_seed() if self.training else 0
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for n, p in zip(self._names, self._params)
                                                     if n not in self._image_names)
         if need_grad:
             logits = _VqaFeaturesFunction.apply(self, feats.vn, q, q_len, seed, index, *self._params)
         else:
-            logits, _ = self._engine.forward_features(self._param_dict(), feats.vn, q, q_len, *index, self.training, seed,
-                                                      keep=False, bad_tokens=self._token_counter(q))
+            logits, _ = self._engine.forward_features(self._param_dict(), feats.vn, q, q_len, *index[:4], self.training, seed,
+                                                      keep=False, bad_tokens=self._token_counter(q), slot=_slot_of(index))
         self._after_forward_tokens(q)
         return logits
 

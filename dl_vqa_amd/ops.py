@@ -605,6 +605,27 @@ def gather_rows_drop(src, rows, p: float, seed: int, out: Optional[torch.Tensor]
     return out
 
 
+def gather_rows_drop_norm(src, rows, p: float, seed: int, drop2=None):
+    """Image dropout on the asked rows of a bank of L2-normalised features: vn_d[j] = l2norm(dropout_{p, seed}(src)[rows[j]]),
+    every feature row of C channels renormalised after the mask (vqa_l2norm_fwd's operations), without forming the dropped
+    bank.  src [M, P, C] contiguous, fp32 or float16 (widened as it is read: the bits of src.float()); rows device int32 [n];
+    masks are indexed by the BANK row (64-bit), as gather_rows_drop's.  drop2 = (p2, seed2): also return
+    v_in = dropout_{p2, seed2}(.)[rows] of vn_d, written in the same pass.  An index outside [0, M) gives zeros.  Returns
+    vn_d [n, P, C] fp32, or (vn_d, v_in)."""
+    _chk(rows, torch.int32)
+    assert src.dim() == 3 and src.is_contiguous()
+    (M, P, C), n = src.shape, rows.numel()
+    vn_d = torch.empty(n, P, C, dtype=torch.float32, device=src.device)
+    name = "vqa_gather_rows_drop_norm" + _cache_suffix(src)
+    if drop2 is None:
+        call(name, ptr(src), ptr(rows), ptr(vn_d), None, n, M, P, C, p, seed, 0.0, 0, stream())
+        return vn_d
+    p2, seed2 = drop2
+    v_in = torch.empty_like(vn_d)
+    call(name, ptr(src), ptr(rows), ptr(vn_d), ptr(v_in), n, M, P, C, p, seed, p2, seed2, stream())
+    return vn_d, v_in
+
+
 def _apply_gather_head(probs, vn, img):
     """What the att_apply_gather_* wrappers check: (B, G, P, N, C) of probs-shaped [B, G, P], vn [N, P, C], img int32 [B]."""
     (B, G, P), N, C = probs.shape, vn.shape[0], vn.shape[-1]

@@ -119,14 +119,21 @@ def run_batch_shared(model, batch_data, max_answers, image_index, batch_divisor:
     return soft_ce_loss_and_score(y_hat, a_indices, a_values, batch_divisor)
 
 
-def run_batch_features(model, batch_data, max_answers, feats, image_index, batch_divisor: Optional[int] = None):
+def run_batch_features(model, batch_data, max_answers, feats, image_index, batch_divisor: Optional[int] = None,
+                       image_dropout=False):
     """run_batch_shared with the image encoder frozen and run beforehand: `feats` (VqaNet.encode_images, a bank of N feature
     rows) stands in for the images and question b looks at row image_index[b] (a host list or an integer tensor of B
     entries in [0, N)).  batch_data is the loader's 7-tuple; its v entry is ignored and may be None.  Same fused loss and
     score; the loss is divided by the number of QUESTIONS.  No convolution runs, and the image.* parameters get no gradient
     (VqaNet.forward_features, which also states the dropout semantics).  The bank may be stored as float16
     (encode_images(..., dtype=torch.float16): half the memory); the step is then, bit for bit, the step on the fp32 bank
-    holding the same values."""
+    holding the same values.
+
+    image_dropout=True (a bool; ValueError otherwise) applies image.drop at the configured rate to the asked rows, which are
+    renormalised after it: the head then trains on what run_batch_shared gives it with image.* frozen, instead of on
+    features that image.drop never touched (VqaNet.forward_features).  The default leaves the step as it was."""
+    if not isinstance(image_dropout, bool):
+        raise ValueError(f"run_batch_features: image_dropout must be a bool, got {image_dropout!r}")
     _v, q, a_indices, a_values, a_length, idx, q_len = batch_data
     n_index = len(image_index) if not torch.is_tensor(image_index) else image_index.numel()
     if n_index != q.shape[0]:
@@ -137,7 +144,7 @@ def run_batch_features(model, batch_data, max_answers, feats, image_index, batch
     a_values = a_values.to(dev, non_blocking=True)
     validate_question_lengths(q_len, q.shape[1])
     q_len = q_len.to(dev, non_blocking=True)
-    y_hat = model.forward_features(feats, q, q_len, image_index)
+    y_hat = model.forward_features(feats, q, q_len, image_index, image_dropout)
     return soft_ce_loss_and_score(y_hat, a_indices, a_values, batch_divisor)
 
 

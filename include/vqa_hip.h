@@ -39,7 +39,9 @@ extern "C" {
  * Version 9 adds the plan query of the fp32x3 conv entry points (vqa_conv3x3_x3_plan), appended at the end; every
  * version-8 prototype is unchanged.  The entry points of float16 image-feature caches joined version 9 the append-only way
  * (vqa_float_to_half, vqa_gather_rows_drop_f16, vqa_att_apply_gather_fwd_f16, vqa_att_apply_gather_dscore_f16,
- * vqa_att_score_grouped_fwd_f16, vqa_att_score_grouped_pairs_fwd_f16). */
+ * vqa_att_score_grouped_fwd_f16, vqa_att_score_grouped_pairs_fwd_f16), and after them the two of image dropout on a bank of
+ * cached image features (vqa_gather_rows_drop_norm, vqa_gather_rows_drop_norm_f16; declared with the entry points of training
+ * on cached image features). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -386,6 +388,26 @@ int vqa_gather_rows_drop(const float* src, const int32_t* rows, float* dst, int 
  * N >= 1; dout and vn 16-byte aligned.  B == 0 returns without a launch. */
 int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
                                 float* dscore, float* dscore_rowsum, int N, int B, int P, int C, int G, vqa_stream_t stream);
+
+/* ---- image dropout on a bank of cached image features -------------------------------
+ * src is a bank [M][P][C] of L2-normalised features, fp32 (vqa_gather_rows_drop_norm) or IEEE half (.._f16, widened on load:
+ * the bits of the fp32 form on the same values); rows is device int32 [n].  For j < n, pos < P, c < C, with r = rows[j] and the
+ * 64-bit bank index e = (r*P + pos)*C + c:
+ *   u         = src[e] * keep(seed, e) / (1 - p)            the mask vqa_dropout(p, seed) applies to the whole bank
+ *   nrm       = sqrt(sum over c of u^2)                     of the C channels of (j, pos)
+ *   vn_out    [(j*P + pos)*C + c] = u * (1 / (nrm + 1e-12f))    the operations of vqa_l2norm_fwd
+ *   vdrop_out [(j*P + pos)*C + c] = vn_out[..] * keep(seed2, e) / (1 - p2)
+ * Normalisation is scale-invariant, so on a bank that holds vn = pooled / (|pooled| + 1e-12) this is image.drop followed by
+ * the L2 normalisation of the same pooled features, up to how the 1e-12 guard scales; a feature row whose kept part is all
+ * zero gives zeros.  vdrop_out is optional: null writes vn_out alone, and p2 and seed2 are then ignored.  A rows[j] outside
+ * [0, M) writes zeros to both outputs.  p = 0 renormalises a row (not a bit-exact copy).
+ * VQA_ERR_INVALID, before any HIP call, for: a null src, rows or vn_out; n < 0; M < 1; P < 1; C < 4 or C % 4 != 0; p (or, with
+ * vdrop_out, p2) outside [0, 1); a src that is not 16-byte (half: 8-byte) aligned; an output that is not 16-byte aligned.
+ * n == 0 returns VQA_OK without a launch.  One wave per feature row, no LDS; neither the grid nor the bytes moved depend on M. */
+int vqa_gather_rows_drop_norm(const float* src, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M, int P, int C,
+                              float p, uint64_t seed, float p2, uint64_t seed2, vqa_stream_t stream);
+int vqa_gather_rows_drop_norm_f16(const void* src_f16, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M, int P,
+                                  int C, float p, uint64_t seed, float p2, uint64_t seed2, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
