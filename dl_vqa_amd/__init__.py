@@ -15,9 +15,11 @@ cached image features (``encode_images(v, with_vprime=False)``, ``ImageFeatures.
 convolution runs in the step, and only the bank rows a batch asks about are touched (``compact_image_index``).
 ``preprocess_images`` turns decoded RGB images of any sizes into the ``v [N,3,S,S]`` all of these start from -- the reference's
 resize, centre crop, normalisation and fp16 cast (preprocessing/preprocess_images.py), bit for bit, in one kernel launch.
+``VqaNet.explain`` / ``explain_pairs`` are ``answer`` / ``answer_pairs`` with a gradient x input map per question
+(``Attribution``): why an answer, at the normalised feature layer, from the same caches and without a convolution.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
-           "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index"]
+           "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution"]

@@ -153,6 +153,16 @@ PROTOTYPES = {
     "vqa_att_apply_gather_dscore_f16": (i32, [f32p, i64, f32p, vp, vp, f32p, f32p, i32, i32, i32, i32, i32, vp]),
     "vqa_att_score_grouped_fwd_f16": (i32, [vp, f32p, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_att_score_grouped_pairs_fwd_f16": (i32, [vp, f32p, vp, f32p, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
+    # gradient x input attribution from cached image features (bound before the last two: tests pin what the table ends with)
+    "vqa_att_attr_apply_gather": (i32, [f32p, i64, f32p, f32p, vp, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_attr_apply_gather_f16": (i32, [f32p, i64, f32p, vp, vp, f32p, f32p, f32p, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_attr_score_grouped_path": (i32, [i32, i32]),
+    "vqa_att_attr_score_grouped": (i32, [f32p, f32p, f32p, f32p, f32p, i32, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_attr_score_grouped_pairs": (i32, [f32p, f32p, f32p, f32p, vp, f32p, i32, vp, vp, f32p, i32, i32, i32, i32, i32, i32,
+                                               i32, vp]),
+    "vqa_att_attr_score_grouped_f16": (i32, [f32p, f32p, vp, f32p, f32p, i32, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_attr_score_grouped_pairs_f16": (i32, [f32p, f32p, vp, f32p, vp, f32p, i32, vp, vp, f32p, i32, i32, i32, i32, i32,
+                                                   i32, i32, vp]),
     # image dropout on a bank of cached image features
     "vqa_gather_rows_drop_norm": (i32, [f32p, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),
     "vqa_gather_rows_drop_norm_f16": (i32, [vp, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),

@@ -1,6 +1,7 @@
 // The second half of the attention stage: softmax over positions + weighted sum of the image features, forward and
 // backward -- the vqa_att_apply_* entry points, plain, gathered (several questions per image) and on a float16
-// image-feature cache.  The scores it starts from: att_score.hip.  HBM-bound streaming kernels, as in elementwise.hip.
+// image-feature cache; and the dscore backward that also writes r1, the weighted-sum path of the gradient x input map
+// (vqa_att_attr_apply_gather).  The scores it starts from: att_score.hip.  HBM-bound streaming kernels, as in elementwise.hip.
 #include <hip/hip_fp16.h>
 #include "common.hpp"
 #include "cache_load.hpp"
@@ -153,9 +154,12 @@ __global__ void att_apply_fwd_kernel(const float* score, const VT* vn, const int
 // (d != null) d[c] = sum_g probs[b][g][pp] * dout[b][g*C + c].  v: row b*P + pp in vqa_att_apply_bwd, row img[b]*P + pp in
 // vqa_att_apply_gather_bwd -- the (sample, image) form, as in att_apply_fwd_body.  v: the row's first element, fp32 or fp16
 // (cache_load.hpp), read a channel quad at a time.
-template <int G, class VT>
+// ATTR (vqa_att_attr_apply_gather): also r1[b][pp] = sum_g probs[b][g][pp] * dprob[b][g][pp], g ascending, from the same
+// wave sums before the softmax backward overwrites them -- the weighted-sum path of the gradient x input map.
+template <int G, class VT, bool ATTR = false>
 __device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dout_ld, const float* probs, const VT* v,
-                                                  float4* d, float* dprob, int64_t b, int pp, int P, int C, int lane) {
+                                                  float4* d, float* dprob, int64_t b, int pp, int P, int C, int lane,
+                                                  float* r1) {
   const int nch = C >> 2;
   float pr[G], acc[G];
 #pragma unroll
@@ -171,11 +175,14 @@ __device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dou
     }
     if (d) d[c] = o;       // d == null: vqa_l2norm_bwd_joined recomputes this branch where it is consumed
   }
+  float r = 0.f;
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const float s = wave_sum(acc[g]);
     if (lane == 0) dprob[(b * G + g) * P + pp] = s;
+    if (ATTR) r += pr[g] * s;
   }
+  if (ATTR && lane == 0) r1[b * P + pp] = r;
 }
 
 // GATHER (vqa_att_apply_gather_bwd, several questions per image): sample b weighted the rows of image img[b] of vn [N][P][C];
@@ -183,9 +190,11 @@ __device__ __forceinline__ void att_apply_bwd_row(const float* dout, int64_t dou
 // only) dvn is always null: nobody wants a gradient of a cache.  It stays a run-time argument all the same: the row body
 // then compiles to the arithmetic (the same fused multiply-adds) of the fp32 instantiation, which a body specialised for
 // d == null does not.
-template <int G, bool GATHER, class VT = float>
+// ATTR (GATHER only): the row body also writes r1 [B][P] (null and not read otherwise); dvn is null at run time there as well.
+template <int G, bool GATHER, class VT = float, bool ATTR = false>
 __global__ void att_apply_bwd_rows_kernel(const float* dout, int64_t dout_ld, const float* probs, const VT* vn,
-                                          const int* img, int N, float* dprob, float* dvn, int64_t M, int P, int C) {
+                                          const int* img, int N, float* dprob, float* dvn, int64_t M, int P, int C,
+                                          float* r1) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -198,8 +207,8 @@ __global__ void att_apply_bwd_rows_kernel(const float* dout, int64_t dout_ld, co
       n = n < 0 ? 0 : (n >= N ? N - 1 : n);               // a malformed index reads nothing out of bounds
       vm = (int64_t)n * P + pp;
     }
-    att_apply_bwd_row<G>(dout, dout_ld, probs, vn + vm * C, dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr, dprob, b, pp,
-                         P, C, lane);
+    att_apply_bwd_row<G, VT, ATTR>(dout, dout_ld, probs, vn + vm * C, dvn ? reinterpret_cast<float4*>(dvn + m * C) : nullptr, dprob,
+                                   b, pp, P, C, lane, r1);
   }
 }
 
@@ -325,13 +334,19 @@ static int att_apply_fwd_launch(const float* score, const VT* vn, const int32_t*
 template <class VT>
 static int att_apply_bwd_launch(const float* dout, int64_t dout_ld, const float* probs, const VT* vn, const int32_t* img,
                                 const int32_t* order, const int32_t* offsets, float* dscore, float* dvn, float* dscore_rowsum,
-                                int N, int B, int P, int C, int G, hipStream_t s) {
+                                int N, int B, int P, int C, int G, hipStream_t s, float* r1 = nullptr) {
   if (B == 0) return VQA_OK;
   const int64_t M = (int64_t)B * P, Mn = (int64_t)N * P;
   int rc = with_int14(G, [&](auto g) {
+    if (r1) {                                             // the attribution form: a dscore form that also writes r1
+      hipLaunchKernelGGL((att_apply_bwd_rows_kernel<decltype(g)::value, true, VT, true>), dim3(grid_for(M, 4)), dim3(256), 0, s,
+                         dout, dout_ld, probs, vn, img, N, dscore, static_cast<float*>(nullptr), M, P, C, r1);
+      return check_hip(hipGetLastError(), "att_apply_bwd_rows (attribution) launch");
+    }
     return with_gather<VT>(img != nullptr, [&](auto gather) {
       hipLaunchKernelGGL((att_apply_bwd_rows_kernel<decltype(g)::value, decltype(gather)::value, VT>), dim3(grid_for(M, 4)),
-                         dim3(256), 0, s, dout, dout_ld, probs, vn, img, N, dscore, decltype(gather)::value ? nullptr : dvn, M, P, C);
+                         dim3(256), 0, s, dout, dout_ld, probs, vn, img, N, dscore, decltype(gather)::value ? nullptr : dvn, M, P, C,
+                         static_cast<float*>(nullptr));
       return check_hip(hipGetLastError(), "att_apply_bwd_rows launch");
     });
   });
@@ -397,6 +412,32 @@ int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float*
                                  quad_bits(dout, vn, nullptr));
   return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, nullptr, nullptr, dscore, nullptr, dscore_rowsum, N, B, P,
                                         C, G, STREAM);
+}
+
+// ---- gradient x input attribution: vqa_att_apply_gather_dscore's launches, the rows kernel writing r1 too
+int vqa_att_attr_apply_gather(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                              float* dscore, float* dscore_rowsum, float* r1, int N, int B, int P, int C, int G,
+                              vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
+  const int rc = att_apply_check("vqa_att_attr_apply_gather", true, dout && probs && vn && dscore && r1, img, N, B, P, C, G,
+                                 dout_ld, quad_bits(dout, vn, nullptr));
+  return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, nullptr, nullptr, dscore, nullptr, dscore_rowsum, N, B, P,
+                                        C, G, STREAM, r1);
+}
+
+int vqa_att_attr_apply_gather_f16(const float* dout, int64_t dout_ld, const float* probs, const void* vn_f16,
+                                  const int32_t* img, float* dscore, float* dscore_rowsum, float* r1, int N, int B, int P, int C,
+                                  int G, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
+  const int rc = att_apply_check("vqa_att_attr_apply_gather_f16", true, dout && probs && vn_f16 && dscore && r1, img, N, B, P, C,
+                                 G, dout_ld, quad_bits(dout, nullptr, nullptr));
+  if (rc) return rc;
+  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & (kQuadAlign<__half> - 1)) == 0,
+              "vqa_att_attr_apply_gather_f16: vn must be 8-byte aligned");
+  return att_apply_bwd_launch(dout, dout_ld, probs, static_cast<const __half*>(vn_f16), img, nullptr, nullptr, dscore, nullptr,
+                              dscore_rowsum, N, B, P, C, G, STREAM, r1);
 }
 
 // ---- float16 image-feature caches: the gather forward and the dscore backward on a half vn, the same

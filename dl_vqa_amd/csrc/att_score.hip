@@ -21,6 +21,8 @@
 // PAIRS (vqa_att_score_grouped_pairs_fwd, answers from cached question features): pair b reads the q' row qp[qrow[b]] of a
 // table [M][mid] of distinct questions; everything else is still indexed by b.  Only the row address changes: the operation
 // order above is the same, so the scores equal the PAIRS = false kernels' on the expanded qp[qrow], bit for bit.
+// Attribution (vqa_att_attr_score_grouped*, inference): the same ownership and walk turned to the gradient x input map of a
+// question -- see the section "grouped attribution" below.
 #include "common.hpp"
 #include "cache_load.hpp"
 
@@ -589,6 +591,152 @@ __global__ __launch_bounds__(256) void att_score_grouped_general_kernel(const VT
   }
 }
 
+// ------------------------------------------------------------------ grouped attribution (gradient x input at vn, inference)
+// R[b][p] = r1[b][p] + sum_m c[b][p][m] * s[b][p][m] * v'[n*P + p][m] with c = sum_g dscore[b][g][p] * wx[g][m] and s the
+// derivative of x = relu(v' (+|*) q') by v' (include/vqa_hip.h): the score path of the map, v_conv folded away because
+// vn . Wv^T is the cached v' itself.  The grouped forward's ownership and walk (a workgroup: a tile of positions of ONE
+// image in LDS, the image's questions streamed past it, lanes reduce over mid), with dscore where the forward has nothing
+// and r1 where it has the bias.  One quad's term, for every kernel and mode: c in g-ascending order, then
+// c.x*s.x*v.x + ... in x, y, z, w order; a lane sums its quads lane + 64*i in ascending i, then the wave butterfly.
+template <int G, int MODE>
+__device__ __forceinline__ float att_attr_quad(const float (&ds)[G], const float4 (&w)[G], const float4 v, const float4 q) {
+  float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int g = 0; g < G; ++g) { c.x += ds[g] * w[g].x; c.y += ds[g] * w[g].y; c.z += ds[g] * w[g].z; c.w += ds[g] * w[g].w; }
+  float4 s;
+  if (MODE == 0) {
+    s.x = v.x + q.x > 0.f ? 1.f : 0.f; s.y = v.y + q.y > 0.f ? 1.f : 0.f;
+    s.z = v.z + q.z > 0.f ? 1.f : 0.f; s.w = v.w + q.w > 0.f ? 1.f : 0.f;
+  } else if (MODE == 1) {
+    s.x = v.x * q.x > 0.f ? q.x : 0.f; s.y = v.y * q.y > 0.f ? q.y : 0.f;
+    s.z = v.z * q.z > 0.f ? q.z : 0.f; s.w = v.w * q.w > 0.f ? q.w : 0.f;
+  } else {
+    s.x = v.x > 0.f ? 1.f : 0.f; s.y = v.y > 0.f ? 1.f : 0.f; s.z = v.z > 0.f ? 1.f : 0.f; s.w = v.w > 0.f ? 1.f : 0.f;
+  }
+  return c.x * s.x * v.x + c.y * s.y * v.y + c.z * s.z * v.z + c.w * s.w * v.w;
+}
+
+// '+' / '*', mid = 256 * IT <= 1024: the grouped forward's register kernel with its operands -- x_conv weights and the
+// question's q' row in registers, 4 positions per wave, the next question's row in flight.  grid (ceil(P/16), N), 256
+// threads, 16 * mid floats of dynamic LDS.  Every asked (b, p) is written exactly once.
+template <int G, int IT, bool MUL, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_attr_score_grouped_kernel(const float* r1, const float* dscore, const VT* vprime,
+                                                                     const float* qp, const int* qrow, int M, const float* wx,
+                                                                     int wx_ld, const int* order, const int* offsets, float* out,
+                                                                     int B, int P) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  constexpr int mid = 256 * IT, PW = 4, TP = 16;
+  const int n = blockIdx.y, p0 = blockIdx.x * TP;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  if (k0 >= k1) return;                                   // nobody asks about this image
+  const int rows = min(TP, P - p0);
+  att_tile_to_lds(vprime, tile, (int64_t)n * P + p0, rows, mid);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float4 w[IT][G];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int g = 0; g < G; ++g) w[i][g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[lane + 64 * i];
+  __syncthreads();
+  const int pl = wave * PW;                               // first local position of this wave
+  if (pl >= rows) return;
+  float4 q[IT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  int b = order[k0];
+  const int r0 = att_q_row<PAIRS>(qrow, b, B, M);
+  bool ok = r0 >= 0;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) q[i] = reinterpret_cast<const float4*>(qp + (int64_t)r0 * mid)[lane + 64 * i];
+  }
+  for (int k = k0; k < k1; ++k) {
+    float4 qn[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) qn[i] = q[i];
+    int bn = -1;
+    bool okn = false;
+    if (k + 1 < k1) {
+      bn = order[k + 1];
+      const int rn = att_q_row<PAIRS>(qrow, bn, B, M);
+      okn = rn >= 0;
+      if (okn) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) qn[i] = reinterpret_cast<const float4*>(qp + (int64_t)rn * mid)[lane + 64 * i];
+      }
+    }
+    if (ok) {
+#pragma unroll
+      for (int j = 0; j < PW; ++j) {
+        if (pl + j < rows) {                              // wave-uniform
+          const int64_t pos = p0 + pl + j;
+          float ds[G];
+#pragma unroll
+          for (int g = 0; g < G; ++g) ds[g] = dscore[((int64_t)b * G + g) * P + pos];
+          float acc = 0.f;
+#pragma unroll
+          for (int i = 0; i < IT; ++i)
+            acc += att_attr_quad<G, MUL ? 1 : 0>(ds, w[i], reinterpret_cast<const float4*>(tile + (pl + j) * mid)[lane + 64 * i],
+                                                 q[i]);
+          acc = wave_sum(acc);
+          if (lane == 0) out[(int64_t)b * P + pos] = r1[(int64_t)b * P + pos] + acc;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < IT; ++i) q[i] = qn[i];
+    b = bn;
+    ok = okn;
+  }
+}
+
+// Any mid % 4 == 0 and every mode: the channel walk is a run-time loop (weights and q' re-read through L1 per position),
+// `pw` positions per wave (the tile is 4 * pw rows).  '|' reads the first mid columns of wx and no q'.
+template <int G, int MODE, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_attr_score_grouped_general_kernel(const float* r1, const float* dscore,
+                                                                             const VT* vprime, const float* qp, const int* qrow,
+                                                                             int M, const float* wx, int wx_ld, const int* order,
+                                                                             const int* offsets, float* out, int B, int P,
+                                                                             int mid, int pw) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  const int TP = 4 * pw;
+  const int n = blockIdx.y, p0 = blockIdx.x * TP;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  if (k0 >= k1) return;
+  const int rows = min(TP, P - p0);
+  att_tile_to_lds(vprime, tile, (int64_t)n * P + p0, rows, mid);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nq = mid >> 2;
+  for (int j = 0; j < pw; ++j) {
+    const int pl = wave * pw + j;
+    if (pl >= rows) break;
+    const int64_t pos = p0 + pl;
+    const float4* vrow = reinterpret_cast<const float4*>(tile + pl * mid);
+    for (int k = k0; k < k1; ++k) {
+      const int b = order[k];
+      const int r = att_q_row<PAIRS>(qrow, b, B, M);
+      if (r < 0) continue;
+      const float4* qv = MODE == 2 ? nullptr : reinterpret_cast<const float4*>(qp + (int64_t)r * mid);     // '|' reads no q'
+      float ds[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) ds[g] = dscore[((int64_t)b * G + g) * P + pos];
+      float acc = 0.f;
+      for (int c = lane; c < nq; c += 64) {
+        float4 w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[c];
+        const float4 q = MODE == 2 ? make_float4(0.f, 0.f, 0.f, 0.f) : qv[c];
+        acc += att_attr_quad<G, MODE>(ds, w, vrow[c], q);
+      }
+      acc = wave_sum(acc);
+      if (lane == 0) out[(int64_t)b * P + pos] = r1[(int64_t)b * P + pos] + acc;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ grouped backward (training through shared image features)
 // d loss / d v' (one row per IMAGE position, summed over the image's questions), d loss / d q' and the x_conv weight
 // gradient from dscore; x = relu(v' (+|*) q') is recomputed, never read.  With
@@ -805,6 +953,47 @@ static int grouped_fwd(const char* who, const VT* vprime, const float* qp, const
   return check_hip(hipGetLastError(), "att_score_grouped_fwd launch");
 }
 
+// the four attribution entry points: the grouped forward's checks, grid, LDS size and path choice (att_score_grouped_pw);
+// qrow != NULL runs the PAIRS instantiations over the q' table qp [M][mid]; '|' reads no q' (qp may be NULL there)
+template <class VT>
+static int grouped_attr(const char* who, const float* r1, const float* dscore, const VT* vprime, const float* qp,
+                        const int32_t* qrow, int M, const float* wx, int wx_ld, const int32_t* order, const int32_t* offsets,
+                        float* out, int N, int B, int P, int mid, int G, int mode, hipStream_t s) {
+  constexpr bool f32 = std::is_same<VT, float>::value;
+  const int rc = att_score_check(who, true, r1 && dscore && vprime && wx && out && (mode == 2 || qp), order && offsets, N, B, P,
+                                 mid, wx_ld, G, mode, 0.f, f32 ? bits(vprime, qp, wx) : bits(qp, wx));
+  if (rc) return rc;
+  VQA_REQUIRE((bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  if (B == 0) return VQA_OK;
+  const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
+  const dim3 grid((P + TP - 1) / TP, N);
+  const size_t lds = (size_t)TP * mid * 4;
+  // MODE is a template argument of the general kernel: a macro passes the constant
+#define GROUPED_ATTR_GENERAL(kMODE)                                                                                              \
+  hipLaunchKernelGGL((att_attr_score_grouped_general_kernel<kG, kMODE, kPairs, VT>), grid, dim3(256), lds, s, r1, dscore, vprime, \
+                     qp, qrow, M, wx, wx_ld, order, offsets, out, B, P, mid, pw)
+  with_int14(G, [&](auto g) {
+    return with_flag(qrow != nullptr, [&](auto pairs) {
+      constexpr int kG = decltype(g)::value;
+      constexpr bool kPairs = decltype(pairs)::value;
+      if (pw == 0)
+        with_int14(mid / 256, [&](auto it) {
+          return with_flag(mode == 1, [&](auto mul) {
+            hipLaunchKernelGGL((att_attr_score_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, kPairs, VT>), grid,
+                               dim3(256), lds, s, r1, dscore, vprime, qp, qrow, M, wx, wx_ld, order, offsets, out, B, P);
+            return 0;
+          });
+        });
+      else if (mode == 0) GROUPED_ATTR_GENERAL(0);
+      else if (mode == 1) GROUPED_ATTR_GENERAL(1);
+      else GROUPED_ATTR_GENERAL(2);
+      return 0;
+    });
+  });
+#undef GROUPED_ATTR_GENERAL
+  return check_hip(hipGetLastError(), "att_attr_score_grouped launch");
+}
+
 extern "C" {
 
 // The plain forms take the checks of their grouped forms (att_score_check): what used to reach a launch with undefined
@@ -961,6 +1150,50 @@ int vqa_att_score_grouped_pairs_fwd_f16(const void* vprime_f16, const float* qp,
   VQA_REQUIRE(M >= 1, "vqa_att_score_grouped_pairs_fwd_f16: M=%d question rows (>= 1)", M);
   return grouped_fwd("vqa_att_score_grouped_pairs_fwd_f16", static_cast<const __half*>(vprime_f16), qp, qrow, M, wx, wx_ld, bx,
                      order, offsets, score, N, B, P, mid, G, mode, 0.f, 0, (hipStream_t)stream);
+}
+
+// ---- gradient x input attribution
+int vqa_att_attr_score_grouped_path(int mode, int mid) { return att_score_grouped_pw(mode, mid); }
+
+int vqa_att_attr_score_grouped(const float* r1, const float* dscore, const float* vprime, const float* qp, const float* wx,
+                               int wx_ld, const int32_t* order, const int32_t* offsets, float* out, int N, int B, int P, int mid,
+                               int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  return grouped_attr("vqa_att_attr_score_grouped", r1, dscore, vprime, qp, nullptr, 0, wx, wx_ld, order, offsets, out, N, B, P,
+                      mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_attr_score_grouped_pairs(const float* r1, const float* dscore, const float* vprime, const float* qp,
+                                     const int32_t* qrow, const float* wx, int wx_ld, const int32_t* order, const int32_t* offsets,
+                                     float* out, int N, int B, int M, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_attr_score_grouped_pairs: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_attr_score_grouped_pairs: M=%d question rows (>= 1)", M);
+  return grouped_attr("vqa_att_attr_score_grouped_pairs", r1, dscore, vprime, qp, qrow, M, wx, wx_ld, order, offsets, out, N, B, P,
+                      mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_attr_score_grouped_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp, const float* wx,
+                                   int wx_ld, const int32_t* order, const int32_t* offsets, float* out, int N, int B, int P,
+                                   int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  return grouped_attr("vqa_att_attr_score_grouped_f16", r1, dscore, static_cast<const __half*>(vprime_f16), qp, nullptr, 0, wx,
+                      wx_ld, order, offsets, out, N, B, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_attr_score_grouped_pairs_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp,
+                                         const int32_t* qrow, const float* wx, int wx_ld, const int32_t* order,
+                                         const int32_t* offsets, float* out, int N, int B, int M, int P, int mid, int G, int mode,
+                                         vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_attr_score_grouped_pairs_f16: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_attr_score_grouped_pairs_f16: M=%d question rows (>= 1)", M);
+  return grouped_attr("vqa_att_attr_score_grouped_pairs_f16", r1, dscore, static_cast<const __half*>(vprime_f16), qp, qrow, M, wx,
+                      wx_ld, order, offsets, out, N, B, P, mid, G, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -532,6 +532,12 @@ class Engine:
         """B questions against the N encoded images of `feats` (vn, vprime): question b looks at image img[b]; order /
         offsets (device int32) group the questions by image.  Returns (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer: fp32 / fp32x3 only"
+        score, _qp, combined = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        return self._answer_tail(P, feats, score, img, combined)[:3]
+
+    def _answer_front(self, P, feats, q, q_len, order, offsets, bad_tokens):
+        """What answer and explain begin with.  Returns (score [B,G,Pn], q' [B,mid], the classifier-input buffer whose
+        question half the encoder has written)."""
         N, Pn, _ = feats.vn.shape
         # ---- question encoder and q_lin, eval mode, on the current stream (there are no convolutions to hide them under)
         txt, _ = self._question_front(P, q, q_len, feats.vn.device, 0.0, 0, bad_tokens, side=False)
@@ -539,17 +545,60 @@ class Engine:
         # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
         score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
                                           P["attention.x_conv.bias"], order, offsets, N, q.shape[0], Pn, self.att_mode)
-        return self._answer_tail(P, feats, score, img, txt.combined)
+        return score, qp, txt.combined
 
     def _answer_tail(self, P, feats, score, img, combined, cached=None):
-        """What answer and answer_pairs end with: softmax over positions + weighted sum of the image img[b]'s features into
-        combined[:, :GC], and the eval-mode classifier.  cached = (qf, qrow): answer_pairs' question half of the classifier
-        input (models/model.py:64), one cached row per pair; answer's encoder has written it.  Returns (logits, probs, score)."""
+        """What answer, answer_pairs, explain and explain_pairs end with: softmax over positions + weighted sum of the image
+        img[b]'s features into combined[:, :GC], and the eval-mode classifier.  cached = (qf, qrow): answer_pairs' question
+        half of the classifier input (models/model.py:64), one cached row per pair; answer's encoder has written it.
+        Returns (logits, probs, score, h1): h1 = relu(lin1(combined)), which only the explain calls read."""
         probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, self.Dc)
         if cached is not None:
             ops.gather_rows(*cached, combined[:, self.GC:], self.Q)
-        logits = self._classifier_fwd(P, combined, 0.0, 0, None)[0]
-        return logits, probs, score
+        logits, _c_in, h1, _h1d = self._classifier_fwd(P, combined, 0.0, 0, None)
+        return logits, probs, score, h1
+
+    # ------------------------------------------------------------------ gradient x input maps from cached features
+    # explain / explain_pairs are answer / answer_pairs with the tail kept: from (probs, h1, logits) the gradient of ONE logit
+    # per question is carried back to the classifier input (two small products, no parameter gradient), and two kernels turn
+    # it into R[b, p] = sum_c vn * d logit / d vn (include/vqa_hip.h) without forming the gradient tensor.
+    @_device_current("feats", _cache_device)
+    def explain(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
+                answers: Optional[Tensor] = None, bad_tokens: Optional[Tensor] = None):
+        """answer's arguments plus answers (device int32 [B], None: each question's arg-max).  Returns (maps [B,Pn],
+        answers int32 [B], logits [B,A])."""
+        assert not self.bf16, "explain: fp32 / fp32x3 only"
+        score, qp, combined = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        return self._explain_tail(P, feats, score, img, combined, None, qp, None, order, offsets, answers)
+
+    @_device_current("feats", _cache_device)
+    def explain_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor, qrow: Tensor,
+                      answers: Optional[Tensor] = None):
+        """answer_pairs' arguments plus answers, as explain."""
+        assert not self.bf16, "explain_pairs: fp32 / fp32x3 only"
+        score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
+        return self._explain_tail(P, feats, score, img, combined, (qfeats.qf, qrow), qfeats.qprime, qrow, order, offsets, answers)
+
+    def _explain_tail(self, P, feats, score, img, combined, cached, qp, qrow, order, offsets, answers):
+        """What explain and explain_pairs end with: _answer_tail, then the gradient of logit[b, answers[b]] back to the image
+        half of the classifier input, and the two attribution kernels.  qp: q' [B,mid], or explain_pairs' table read through
+        qrow.  Returns (maps [B,Pn], answers int32 [B], logits [B,A])."""
+        logits, probs, score, h1 = self._answer_tail(P, feats, score, img, combined, cached)
+        B, hid, GC, dev = img.numel(), self.hid, self.GC, feats.vn.device
+        N, Pn, _ = feats.vn.shape
+        if answers is None:                                # topk_answers' arg-max, on the device
+            answers = ops.softmax_topk(logits, 1)[0].view(B)
+        # d logit[b, a_b] / d h1 = W2[a_b, :] where h1 > 0 (a column outside [0, A): a zero row, hence a zero map)
+        dh = torch.empty(B, hid, dtype=torch.float32, device=dev)
+        ops.gather_rows(P["classifier.lin2.weight"], answers, dh)
+        ops.relu_drop_bwd(h1, dh, dh, 0.0, 0)
+        # d logit / d combined[:, :GC] = dh . W1[:, :GC]: the image half only, plain fp32 in every compute mode
+        dcomb = torch.empty(B, GC, dtype=torch.float32, device=dev)
+        ops.gemm(dh, P["classifier.lin1.weight"], dcomb, B, GC, hid, transB=False, lda=hid, ldb=self.Dc)
+        dscore, r1 = ops.att_attr_apply_gather(dcomb, GC, probs, feats.vn, img)
+        maps = ops.att_attr_score_grouped(r1, dscore, feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1), order,
+                                          offsets, N, B, Pn, self.att_mode, qrow=qrow)
+        return maps, answers, logits
 
     # ------------------------------------------------------------------ cached question features (inference)
     # The mirror image of encode_images / answer: the question encoder and q_lin run once per DISTINCT question, and
@@ -569,13 +618,17 @@ class Engine:
         looks at image img[b] with question qrow[b]; order / offsets (device int32) group the pairs by image.  Returns
         (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer_pairs: fp32 / fp32x3 only"
+        score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
+        return self._answer_tail(P, feats, score, img, combined, cached=(qfeats.qf, qrow))[:3]
+
+    def _pairs_front(self, P, feats, qfeats, order, offsets, img, qrow):
+        """What answer_pairs and explain_pairs begin with.  Returns (score [B,G,Pn], an empty classifier-input buffer)."""
         B = img.numel()
         N, Pn, _ = feats.vn.shape
         # ---- attention: scores from v' (one per image) and q' (one per distinct question)
         score = ops.att_score_grouped_pairs_fwd(feats.vprime, qfeats.qprime, qrow, P["attention.x_conv.weight"].view(self.G, -1),
                                                 P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode)
-        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=feats.vn.device)
-        return self._answer_tail(P, feats, score, img, combined, cached=(qfeats.qf, qrow))
+        return score, torch.empty(B, self.Dc, dtype=torch.float32, device=feats.vn.device)
 
     # ------------------------------------------------------------------ training through grouped image features
     # fp32 / fp32x3.  Question b looks at image img[b]; order / offsets group the questions by image.  The question encoder,

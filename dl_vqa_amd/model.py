@@ -126,6 +126,16 @@ def _upload_index(dev, *parts):
     return torch.split(torch.cat([p.to(torch.int32) for p in parts]).to(dev), [p.numel() for p in parts])
 
 
+def _upload_with_columns(dev, index, cols):
+    """_upload_index of the host index tensors `index`, together with the answer columns `cols` of explain / explain_pairs
+    where those are host data (the same single copy); CUDA columns become int32 on `dev`, None stays None.  Returns (the
+    device index tensors, the device columns or None)."""
+    if cols is None or cols.is_cuda:
+        return _upload_index(dev, *index), (cols if cols is None else cols.to(device=dev, dtype=torch.int32))
+    *index, cols = _upload_index(dev, *index, cols)
+    return tuple(index), cols
+
+
 def group_by_image(image_index, N: int):
     """Group questions by the image they ask about: image_index[b] in [0, N) -> (order int32 [B], offsets int32 [N+1]) on
     the host; the questions of image n are order[offsets[n]:offsets[n+1]], in their original order (a stable counting
@@ -159,6 +169,16 @@ class TopAnswers(NamedTuple):
     fp32 [B, k] (their softmax probabilities)."""
     indices: torch.Tensor
     probs: torch.Tensor
+
+
+class Attribution(NamedTuple):
+    """What VqaNet.explain / explain_pairs return: maps fp32 [B, gh, gw] -- the gradient x input map R[b, p] of each question
+    on the feature grid (signed, no upsampling, no normalisation) --, answers int64 [B] -- the answer column each map explains
+    (0-based, as TopAnswers.indices) -- and logits fp32 [B, A] -- what answer() / answer_pairs() return for the same
+    arguments, bit for bit."""
+    maps: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
 
 
 TOPK_MAX = 64     # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
@@ -840,30 +860,37 @@ class VqaNet(nn.Module):
         synchronises once.  Nothing is kept for a backward: _last_ctx, the gradient buffer and the dropout seed stream are
         left alone.  See encode_images for when `feats` has to be recomputed."""
         self._check_inference("answer")
+        q, q_len, index = self._answer_args("answer", feats, q, q_len, image_index)
+        B = q.shape[0]
+        if B == 0:
+            return self._no_answers(feats, return_attention)
+        eng = self._engine
+        logits, probs, _score = eng.answer(self._param_dict(), feats, q, q_len, *_upload_index(feats.vn.device, *index),
+                                           bad_tokens=self._token_counter(q))
+        self._after_forward_tokens(q)
+        if return_attention:
+            return logits, probs.view(B, eng.G, *feats.grid)
+        return logits
+
+    def _answer_args(self, what: str, feats, q, q_len, image_index):
+        """What answer() and explain() check after _check_inference, in answer()'s order.  Returns (q, q_len as tensors, the
+        host index tensors (order, offsets, img) of the questions grouped by image)."""
         self._ensure_flat()
         if not isinstance(feats, ImageFeatures):
-            raise TypeError("VqaNet.answer: feats must come from VqaNet.encode_images")
-        self._check_owned("answer", feats, "image", "encode_images")
-        self._need_vprime("answer", feats)
+            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
+        self._check_owned(what, feats, "image", "encode_images")
+        self._need_vprime(what, feats)
         q = torch.as_tensor(q)
         q_len = torch.as_tensor(q_len)
-        _check_question_ranks("VqaNet.answer", q, q_len)
+        _check_question_ranks(f"VqaNet.{what}", q, q_len)
         self._validate_tokens(q)
         validate_question_lengths(q_len, q.shape[1])
         B, N = q.shape[0], feats.N
         img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
         order, offsets = _group(img, N)
         if order.numel() != B:
-            raise ValueError(f"VqaNet.answer: {order.numel()} image_index entries for {B} questions")
-        if B == 0:
-            return self._no_answers(feats, return_attention)
-        eng = self._engine
-        logits, probs, _score = eng.answer(self._param_dict(), feats, q, q_len, *_upload_index(feats.vn.device, order, offsets, img),
-                                           bad_tokens=self._token_counter(q))
-        self._after_forward_tokens(q)
-        if return_attention:
-            return logits, probs.view(B, eng.G, *feats.grid)
-        return logits
+            raise ValueError(f"VqaNet.{what}: {order.numel()} image_index entries for {B} questions")
+        return q, q_len, (order, offsets, img)
 
     @torch.no_grad()
     def predict(self, feats: ImageFeatures, q, q_len, image_index, k: int = 1, return_attention: bool = False):
@@ -919,33 +946,39 @@ class VqaNet(nn.Module):
         moved parameters, or to another device than the other cache.  Nothing is kept for a backward: _last_ctx, the
         gradient buffer and the dropout seed stream are left alone."""
         self._check_inference("answer_pairs")
+        index = self._pairs_args("answer_pairs", feats, qfeats, image_index, question_index)
+        eng = self._engine
+        B = index[-1].numel()
+        if B == 0:
+            return self._no_answers(feats, return_attention)
+        logits, probs, _score = eng.answer_pairs(self._param_dict(), feats, qfeats, *_upload_index(feats.vn.device, *index))
+        if return_attention:
+            return logits, probs.view(B, eng.G, *feats.grid)
+        return logits
+
+    def _pairs_args(self, what: str, feats, qfeats, image_index, question_index):
+        """What answer_pairs() and explain_pairs() check after _check_inference, in answer_pairs()'s order.  Returns the host
+        index tensors (order, offsets, img, qidx) of the pairs grouped by image."""
         if not isinstance(feats, ImageFeatures):
-            raise TypeError("VqaNet.answer_pairs: feats must come from VqaNet.encode_images")
+            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
         if not isinstance(qfeats, QuestionFeatures):
-            raise TypeError("VqaNet.answer_pairs: qfeats must come from VqaNet.encode_questions")
+            raise TypeError(f"VqaNet.{what}: qfeats must come from VqaNet.encode_questions")
         N, M = feats.N, qfeats.M
         n_img, n_q = torch.as_tensor(image_index).numel(), torch.as_tensor(question_index).numel()
         if n_img != n_q:
-            raise ValueError(f"VqaNet.answer_pairs: {n_img} image_index entries for {n_q} question_index entries")
+            raise ValueError(f"VqaNet.{what}: {n_img} image_index entries for {n_q} question_index entries")
         img = _host_image_index(image_index, N)                      # each index: one copy to the host, reused below
         order, offsets = _group(img, N)
         qidx = _host_image_index(question_index, M, "question_index", "questions")
         self._ensure_flat()
-        self._check_owned("answer_pairs", feats, "image", "encode_images")
-        self._check_owned("answer_pairs", qfeats, "question", "encode_questions")
-        self._need_vprime("answer_pairs", feats)
+        self._check_owned(what, feats, "image", "encode_images")
+        self._check_owned(what, qfeats, "question", "encode_questions")
+        self._need_vprime(what, feats)
         dev = feats.vn.device
         if qfeats.qprime.device != dev:
-            raise RuntimeError(f"VqaNet.answer_pairs: the image features are on {dev} and the question features on "
+            raise RuntimeError(f"VqaNet.{what}: the image features are on {dev} and the question features on "
                                f"{qfeats.qprime.device}; encode both on the model's device")
-        eng = self._engine
-        B = qidx.numel()
-        if B == 0:
-            return self._no_answers(feats, return_attention)
-        logits, probs, _score = eng.answer_pairs(self._param_dict(), feats, qfeats, *_upload_index(dev, order, offsets, img, qidx))
-        if return_attention:
-            return logits, probs.view(B, eng.G, *feats.grid)
-        return logits
+        return order, offsets, img, qidx
 
     @torch.no_grad()
     def predict_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, k: int = 1,
@@ -955,3 +988,89 @@ class VqaNet(nn.Module):
         validated first; everything else is answer_pairs()'s."""
         k = _check_k("VqaNet.predict_pairs", k, self._engine.A)
         return _ranked(self.answer_pairs(feats, qfeats, image_index, question_index, return_attention=return_attention), k)
+
+    # ------------------------------------------------------------------ gradient x input maps from cached features
+    def _answer_columns(self, what: str, answers, B: int):
+        """The `answers` argument of explain / explain_pairs, judged on the host: None (each question's arg-max), a CUDA
+        integer tensor of B columns as it is, or host data as int32 [B] after its range check."""
+        if answers is None:
+            return None
+        cols = torch.as_tensor(answers).detach().reshape(-1)
+        if cols.is_floating_point() or cols.is_complex() or cols.dtype == torch.bool:
+            raise TypeError(f"VqaNet.{what}: answers must hold integer answer columns, got {cols.dtype}")
+        if cols.numel() != B:
+            raise ValueError(f"VqaNet.{what}: {cols.numel()} answers for {B} questions")
+        if cols.is_cuda:
+            return cols
+        A = self._engine.A
+        if B and (int(cols.min()) < 0 or int(cols.max()) >= A):
+            bad = int(cols.min()) if int(cols.min()) < 0 else int(cols.max())
+            raise IndexError(f"VqaNet.{what}: answers entry {bad} out of range [0, {A})")
+        return cols.to(torch.int32)
+
+    def _attribution(self, feats, out, B: int) -> Attribution:
+        """Attribution of the engine's (maps [B,P], answers int32 [B], logits), or the empty one for B == 0."""
+        eng, dev = self._engine, feats.vn.device
+        if out is None:
+            return Attribution(torch.empty(0, *feats.grid, dtype=torch.float32, device=dev),
+                               torch.empty(0, dtype=torch.int64, device=dev),
+                               torch.empty(0, eng.A, dtype=torch.float32, device=dev))
+        maps, cols, logits = out
+        return Attribution(maps.view(B, *feats.grid), cols.long(), logits)
+
+    @torch.no_grad()
+    def explain(self, feats: ImageFeatures, q, q_len, image_index, answers=None) -> Attribution:
+        """answer() with a gradient x input map per question: Attribution(maps fp32 [B, gh, gw], answers int64 [B], logits
+        fp32 [B, A]).  For question b about image n = image_index[b] and the answer column a_b = answers[b],
+
+            maps[b, p] = R[b, p] = sum_c vn[n, p, c] * d logits[b, a_b] / d vn[n, p, c]
+
+        on the feature grid: signed, not upsampled, not normalised.  R is the attribution AT THE NORMALISED FEATURE LAYER
+        (feats.vn, the output of the conv blocks after the L2 normalisation) WITH THE QUESTION HELD FIXED: it follows vn
+        along both of its paths to the logit -- the attention-weighted sum, and the attention scores through v_conv -- in
+        eval mode.  The conv blocks, the L2 normalisation and the question path (embedding, LSTM, q_lin, the question half
+        of the classifier input) are not part of it: nothing is attributed to pixels or to question tokens.  No convolution
+        and no v_conv product runs, and the gradient tensor itself is never formed (include/vqa_hip.h has the formulas).
+
+        answers=None explains each question's arg-max answer, chosen on the device in topk_answers' order (ties by the
+        smaller column): answers == predict(feats, q, q_len, image_index, k=1).indices[:, 0].  Otherwise answers is a list or
+        an integer tensor of B columns (0-based, as TopAnswers.indices).  Host data is checked: ValueError for a wrong count,
+        IndexError outside [0, A), TypeError for a non-integer dtype.  A CUDA tensor is taken as it is, without a copy to the
+        host: its count is checked, its values are not, and an entry outside [0, A) gives a map of zeros.
+
+        logits are answer()'s for the same arguments, bit for bit.  Everything else is answer()'s too: eval mode only
+        (RuntimeError in train mode), fp32 / fp32x3 (NotImplementedError for "bf16"), both judged before any device work;
+        the feature-ownership checks and image_index rules; fp32 and float16 caches (a float16 cache gives, bit for bit,
+        what feats.to(torch.float32) gives); B == 0 returns empty tensors.  Rows come back in the caller's order and do not
+        depend on how the batch is ordered or split.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad
+        and the dropout seed stream are left alone."""
+        self._check_inference("explain")
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError("VqaNet.explain: feats must come from VqaNet.encode_images")
+        cols = self._answer_columns("explain", answers, len(q))
+        q, q_len, index = self._answer_args("explain", feats, q, q_len, image_index)
+        B = q.shape[0]
+        if B == 0:
+            return self._attribution(feats, None, 0)
+        index, cols = _upload_with_columns(feats.vn.device, index, cols)
+        out = self._engine.explain(self._param_dict(), feats, q, q_len, *index, answers=cols, bad_tokens=self._token_counter(q))
+        self._after_forward_tokens(q)
+        return self._attribution(feats, out, B)
+
+    @torch.no_grad()
+    def explain_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
+                      answers=None) -> Attribution:
+        """explain() for B (image, question) pairs from the two caches, as answer_pairs() is to answer(): pair b looks at
+        image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  maps, answers
+        and the `answers` argument are explain()'s; logits are answer_pairs()'s for the same arguments, bit for bit; the index
+        rules, ownership checks and errors are answer_pairs()'s, with the `answers` checks of explain() judged first."""
+        self._check_inference("explain_pairs")
+        cols = self._answer_columns("explain_pairs", answers, torch.as_tensor(image_index).numel())
+        index = self._pairs_args("explain_pairs", feats, qfeats, image_index, question_index)
+        B = index[-1].numel()
+        if B == 0:
+            return self._attribution(feats, None, 0)
+        index, cols = _upload_with_columns(feats.vn.device, index, cols)
+        out = self._engine.explain_pairs(self._param_dict(), feats, qfeats, *index, answers=cols)
+        return self._attribution(feats, out, B)
+

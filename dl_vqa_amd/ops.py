@@ -644,6 +644,51 @@ def att_apply_gather_dscore(dout, dout_ld, probs, vn, img, rowsum=None):
     return dscore
 
 
+def att_attr_apply_gather(dout, dout_ld, probs, vn, img, rowsum=None):
+    """att_apply_gather_dscore (the same device code, the same dscore / rowsum bits) that also returns r1 [B, P] =
+    sum_g probs * (vn[img] . dout_g): the weighted-sum path of the gradient x input map (include/vqa_hip.h).  Returns
+    (dscore [B, G, P], r1 [B, P]); vn fp32 or float16."""
+    B, G, P, N, C = _apply_gather_head(probs, vn, img)
+    dscore = torch.empty_like(probs)
+    r1 = torch.empty(B, P, dtype=torch.float32, device=probs.device)
+    call("vqa_att_attr_apply_gather" + _cache_suffix(vn), ptr(dout), dout_ld, ptr(probs), ptr(vn), ptr(img), ptr(dscore), ptr(rowsum), ptr(r1),
+         N, B, P, C, G, stream())
+    return dscore, r1
+
+
+def att_attr_score_grouped_path(mode: int, mid: int) -> int:
+    """The kernel att_attr_score_grouped runs for (mode, mid): 0 = the register kernel, else the general kernel with that many
+    positions per wave."""
+    return _lib.load().vqa_att_attr_score_grouped_path(mode, mid)
+
+
+def att_attr_score_grouped(r1, dscore, vprime, qp, wx, order, offsets, N: int, B: int, P: int, mode: int, qrow=None, out=None):
+    """The gradient x input map R [B, P] = r1 + r2 (include/vqa_hip.h) from r1 [B, P], dscore [B, G, P] (att_attr_apply_gather),
+    ONE v' [N*P, mid] per image (fp32 or float16), q' and wx [G, xld]; order / offsets as att_score_grouped_fwd.  qrow (device
+    int32 [B]): the pairs form over a table qp [M, mid], bit-identical to the plain form on qp[qrow].  mode 2 ('|') reads no
+    q' (qp may be None).  out: written in place where a listed question has a row; rows of images nobody asks about and of
+    questions that are not listed are left as they are."""
+    G, xld, mid = _score_dims(wx, mode == 2)
+    _chk(order, torch.int32), _chk(offsets, torch.int32), _chk(r1), _chk(dscore)
+    M = qp.shape[0] if qp is not None else (B if qrow is None else 1)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid)
+    assert r1.shape == (B, P) and dscore.shape == (B, G, P) and r1.is_contiguous() and dscore.is_contiguous()
+    assert qp is None or (qp.dtype == torch.float32 and qp.shape == (M if qrow is not None else B, mid))
+    if out is None:
+        out = torch.empty(B, P, dtype=torch.float32, device=vprime.device)
+    assert out.shape == (B, P) and out.is_contiguous() and out.dtype == torch.float32
+    sfx = _cache_suffix(vprime)
+    if qrow is None:
+        call("vqa_att_attr_score_grouped" + sfx, ptr(r1), ptr(dscore), ptr(vprime), ptr(qp), ptr(wx), xld, ptr(order), ptr(offsets),
+             ptr(out), N, B, P, mid, G, mode, stream())
+    else:
+        _chk(qrow, torch.int32)
+        assert qrow.numel() == B
+        call("vqa_att_attr_score_grouped_pairs" + sfx, ptr(r1), ptr(dscore), ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(order),
+             ptr(offsets), ptr(out), N, B, M, P, mid, G, mode, stream())
+    return out
+
+
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C], fp32 or
     float16."""

@@ -41,7 +41,9 @@ extern "C" {
  * (vqa_float_to_half, vqa_gather_rows_drop_f16, vqa_att_apply_gather_fwd_f16, vqa_att_apply_gather_dscore_f16,
  * vqa_att_score_grouped_fwd_f16, vqa_att_score_grouped_pairs_fwd_f16), and after them the two of image dropout on a bank of
  * cached image features (vqa_gather_rows_drop_norm, vqa_gather_rows_drop_norm_f16; declared with the entry points of training
- * on cached image features). */
+ * on cached image features), and then the seven of gradient x input attribution (vqa_att_attr_apply_gather, vqa_att_attr_apply_gather_f16,
+ * vqa_att_attr_score_grouped_path, vqa_att_attr_score_grouped, vqa_att_attr_score_grouped_pairs, vqa_att_attr_score_grouped_f16,
+ * vqa_att_attr_score_grouped_pairs_f16; declared behind those of the cached-feature paths they extend). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -408,6 +410,55 @@ int vqa_gather_rows_drop_norm(const float* src, const int32_t* rows, float* vn_o
                               float p, uint64_t seed, float p2, uint64_t seed2, vqa_stream_t stream);
 int vqa_gather_rows_drop_norm_f16(const void* src_f16, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M, int P,
                                   int C, float p, uint64_t seed, float p2, uint64_t seed2, vqa_stream_t stream);
+
+/* ---- gradient x input attribution from cached image features (inference; csrc/att_apply.hip, csrc/att_score.hip) ----
+ * For question b about image n = img[b] and a chosen answer column a_b, the map at the L2-normalised features vn (eval mode,
+ * no dropout, the question held fixed):
+ *   R[b][p] = sum_c vn[n][p][c] * d logit[b][a_b] / d vn[n][p][c]
+ * vn reaches the logit through the weighted sum and through the scores via v' = v_conv(vn) = vn . Wv^T.  With
+ * dwv[b][g][c] = d logit[b][a_b] / d combined[b][g*C + c] (the caller's dout, row stride dout_ld):
+ *   t[b][g][p]      = vn[n][p][:] . dwv[b][g][:]
+ *   r1[b][p]        = sum_g probs[b][g][p] * t[b][g][p]
+ *   dscore[b][g][p] = probs[b][g][p] * (t[b][g][p] - sum_p' probs[b][g][p'] * t[b][g][p'])
+ *   c[b][p][m]      = sum_g dscore[b][g][p] * wx[g][m]                      ('|': the first mid columns of wx)
+ *   r2[b][p]        = sum_m c[b][p][m] * s[b][p][m] * v'[n][p][m]
+ *                     '+': s = [v' + q' > 0]     '*': s = [v' * q' > 0] * q'     '|': s = [v' > 0]
+ *   R[b][p]         = r1[b][p] + r2[b][p]
+ * r2 uses sum_c vn[p][c] * sum_m dv'[p][m] * Wv[m][c] = sum_m dv'[p][m] * v'[p][m]: nothing of shape [B][P][C] or [B][P][mid]
+ * is formed and v_conv does not run.
+ *   vqa_att_attr_apply_gather / _f16: vqa_att_apply_gather_dscore (/ _f16) -- the same arguments, limits and alignment rules,
+ *     the same device code and therefore the same dscore and dscore_rowsum bits -- that also writes r1 [B][P] (g ascending)
+ *     from t before the softmax backward overwrites it.
+ *   vqa_att_attr_score_grouped / _pairs / _f16 / _pairs_f16: out [B][P] = r1 + r2 from r1 [B][P], dscore [B][G][P], v'
+ *     [N*P][mid] (fp32, or half for a float16 cache, 8-byte aligned), q' [B][mid] (pairs: the table [M][mid] read through qrow
+ *     [B]; NULL allowed for '|', which reads no q') and wx [G][wx_ld].  The ownership, checks, limits and path choice of
+ *     vqa_att_score_grouped_fwd: a workgroup stages a tile of positions of ONE image in LDS and walks that image's questions;
+ *     no atomics; one summation order per (b, p) (a lane's channel quads lane*4 + 256*i in ascending i, x, y, z, w inside a
+ *     quad, then the wave butterfly) whatever the grouping.  Every (b, p) of a question listed in order / offsets is written
+ *     exactly once; rows of questions that are not listed, and every row when an image has no question, are left alone.  The
+ *     pairs form equals the plain form on qp[qrow], the half form the fp32 form on the widened v', bit for bit.
+ *   vqa_att_attr_score_grouped_path: the kernel those four run for (mode, mid) -- 0: the register kernel ('+' / '*', mid =
+ *     256 * IT <= 1024), else the general kernel with that many positions per wave (4, 2 or 1). */
+int vqa_att_attr_apply_gather(const float* dout, int64_t dout_ld, const float* probs, const float* vn, const int32_t* img,
+                              float* dscore, float* dscore_rowsum, float* r1, int N, int B, int P, int C, int G,
+                              vqa_stream_t stream);
+int vqa_att_attr_apply_gather_f16(const float* dout, int64_t dout_ld, const float* probs, const void* vn_f16,
+                                  const int32_t* img, float* dscore, float* dscore_rowsum, float* r1, int N, int B, int P, int C,
+                                  int G, vqa_stream_t stream);
+int vqa_att_attr_score_grouped_path(int mode, int mid);
+int vqa_att_attr_score_grouped(const float* r1, const float* dscore, const float* vprime, const float* qp, const float* wx,
+                               int wx_ld, const int32_t* order, const int32_t* offsets, float* out, int N, int B, int P, int mid,
+                               int G, int mode, vqa_stream_t stream);
+int vqa_att_attr_score_grouped_pairs(const float* r1, const float* dscore, const float* vprime, const float* qp,
+                                     const int32_t* qrow, const float* wx, int wx_ld, const int32_t* order, const int32_t* offsets,
+                                     float* out, int N, int B, int M, int P, int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_attr_score_grouped_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp, const float* wx,
+                                   int wx_ld, const int32_t* order, const int32_t* offsets, float* out, int N, int B, int P,
+                                   int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_attr_score_grouped_pairs_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp,
+                                         const int32_t* qrow, const float* wx, int wx_ld, const int32_t* order,
+                                         const int32_t* offsets, float* out, int N, int B, int M, int P, int mid, int G, int mode,
+                                         vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
