@@ -17,9 +17,12 @@ convolution runs in the step, and only the bank rows a batch asks about are touc
 resize, centre crop, normalisation and fp16 cast (preprocessing/preprocess_images.py), bit for bit, in one kernel launch.
 ``VqaNet.explain`` / ``explain_pairs`` are ``answer`` / ``answer_pairs`` with a gradient x input map per question
 (``Attribution``): why an answer, at the normalised feature layer, from the same caches and without a convolution.
+``VqaNet.explain_words`` carries the same gradient on to the question: one gradient x input value per token
+(``WordAttribution``), back through q_lin, the attention scores and the LSTM, with no parameter gradient formed.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
-           "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution"]
+           "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
+           "WordAttribution"]

@@ -22,7 +22,8 @@
 // table [M][mid] of distinct questions; everything else is still indexed by b.  Only the row address changes: the operation
 // order above is the same, so the scores equal the PAIRS = false kernels' on the expanded qp[qrow], bit for bit.
 // Attribution (vqa_att_attr_score_grouped*, inference): the same ownership and walk turned to the gradient x input map of a
-// question -- see the section "grouped attribution" below.
+// question -- see the section "grouped attribution" below.  vqa_att_attr_dq_grouped* (the gradient of one logit at q' through
+// the scores, for the per-token map): the grouped backward's body under DQ_ONLY -- see "grouped backward" below.
 #include "common.hpp"
 #include "cache_load.hpp"
 
@@ -65,15 +66,22 @@ __device__ __forceinline__ void st4(void* row, int c, float4 v) {
 // The backward of one quad of one row, for the plain and the grouped kernels alike.  With ds = dscore[b][:][p], x the quad
 // of relu(...) and sc its dropout scales:  dw[g] += ds[g] * x * sc  (the x_conv weight gradient);  returns
 // d = (x > 0) * sc * sum_g ds[g] * w[g], the gradient at the pre-activation.  What d becomes (dq', dv', the in-place
-// store, the '*' factors) differs per kernel and mode and stays at the call sites.
-template <int G>
+// store, the '*' factors) differs per kernel and mode and stays at the call sites.  DW = false (the attribution form
+// vqa_att_attr_dq_grouped, which wants d alone): the dw lines are not compiled; d is the same expression either way.
+template <int G, bool DW = true>
 __device__ __forceinline__ float4 att_score_bwd_dx(const float (&ds)[G], const float4 (&w)[G], const float4 x, const float4 sc,
                                                    float4 (&dw)[G]) {
   float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    t.x += ds[g] * w[g].x; t.y += ds[g] * w[g].y; t.z += ds[g] * w[g].z; t.w += ds[g] * w[g].w;
-    dw[g].x += ds[g] * x.x * sc.x; dw[g].y += ds[g] * x.y * sc.y; dw[g].z += ds[g] * x.z * sc.z; dw[g].w += ds[g] * x.w * sc.w;
+    if (DW) {
+      t.x += ds[g] * w[g].x; t.y += ds[g] * w[g].y; t.z += ds[g] * w[g].z; t.w += ds[g] * w[g].w;
+    } else {                                              // the fused multiply-adds hipcc contracts the line above to
+      t.x = fmaf(ds[g], w[g].x, t.x); t.y = fmaf(ds[g], w[g].y, t.y); t.z = fmaf(ds[g], w[g].z, t.z); t.w = fmaf(ds[g], w[g].w, t.w);
+    }
+    if (DW) {
+      dw[g].x += ds[g] * x.x * sc.x; dw[g].y += ds[g] * x.y * sc.y; dw[g].z += ds[g] * x.z * sc.z; dw[g].w += ds[g] * x.w * sc.w;
+    }
   }
   float4 d;
   d.x = x.x > 0.f ? t.x * sc.x : 0.f; d.y = x.y > 0.f ? t.y * sc.y : 0.f;
@@ -757,8 +765,16 @@ __global__ __launch_bounds__(256) void att_attr_score_grouped_general_kernel(con
 // `order`'s order, positions ascending, g ascending), whatever the grid.
 constexpr int BTP = 16;
 
-template <int G, int MODE, bool DROP>
-__device__ __forceinline__ void att_score_bwd_quad(const float* __restrict__ dscore, const float* __restrict__ vprime,
+//
+// DQ_ONLY (vqa_att_attr_dq_grouped / _f16, inference: the gradient of ONE logit at q' through the scores, for the per-token
+// map of VqaNet.explain_words): the same body with the dv' tile, the dw accumulators and their stores compiled out -- the
+// thread keeps its 16 float4 of v' and nothing else across the question walk, dvprime and dwx_part are never touched (NULL).
+// dq is the same sequence of operations on the same values, so dq_part equals the training form's at p = 0 bit for bit.
+// '+' / '*' only: for '|' the q' half adds the same constant to every position's score and softmax is shift-invariant, so
+// the gradient at q' of anything behind the softmax is identically zero -- there is no DQ_ONLY instantiation of MODE 2.
+// VT: v' is fp32, or fp16 for a float16 image-feature cache (cache_load.hpp; DQ_ONLY only): widened on load, same bits.
+template <int G, int MODE, bool DROP, bool DQ_ONLY = false, class VT = float>
+__device__ __forceinline__ void att_score_bwd_quad(const float* __restrict__ dscore, const VT* __restrict__ vprime,
                                                    const float* __restrict__ qp, const float* __restrict__ wx, int wx_ld,
                                                    const int* __restrict__ order, float* __restrict__ dvprime,
                                                    float* __restrict__ dq_part, float* __restrict__ dwx_part, int n, int tile,
@@ -775,12 +791,13 @@ __device__ __forceinline__ void att_score_bwd_quad(const float* __restrict__ dsc
     dw[g] = zero;
     dw2[g] = zero;
   }
-  float4 v[BTP], dv[BTP];
+  static_assert(!DQ_ONLY || (MODE != 2 && !DROP), "DQ_ONLY: '+' / '*', no dropout");
+  float4 v[BTP], dv[DQ_ONLY ? 1 : BTP];
 #pragma unroll
   for (int j = 0; j < BTP; ++j) {
     v[j] = zero;
-    dv[j] = zero;
-    if (j < rows && k0 < k1) v[j] = reinterpret_cast<const float4*>(vprime + ((int64_t)n * P + p0 + j) * mid)[c];
+    if constexpr (!DQ_ONLY) dv[j] = zero;
+    if (j < rows && k0 < k1) v[j] = load_quad(vprime + ((int64_t)n * P + p0 + j) * mid, c);
     if (MODE == 2) v[j] = relu4(v[j]);                    // '|': the v' half of x does not depend on the question
   }
   for (int k = k0; k < k1; ++k) {
@@ -799,8 +816,13 @@ __device__ __forceinline__ void att_score_bwd_quad(const float* __restrict__ dsc
         const float4 x = MODE == 2 ? v[j] : att_combine<MODE == 1>(v[j], q);
         float4 sc = make_float4(1.f, 1.f, 1.f, 1.f);
         if (DROP) sc = drop_scale4(seed, (uint64_t)m * xld + 4 * c, p, inv_keep);
-        const float4 d = att_score_bwd_dx<G>(ds, w, x, sc, dw);
-        if (MODE == 0) {
+        const float4 d = att_score_bwd_dx<G, !DQ_ONLY>(ds, w, x, sc, dw);
+        if constexpr (DQ_ONLY) {
+          if (MODE == 0) { dq.x += d.x; dq.y += d.y; dq.z += d.z; dq.w += d.w; }
+          else {                                          // as the training form's `dq += d * v` compiles: fused
+            dq.x = fmaf(d.x, v[j].x, dq.x); dq.y = fmaf(d.y, v[j].y, dq.y); dq.z = fmaf(d.z, v[j].z, dq.z); dq.w = fmaf(d.w, v[j].w, dq.w);
+          }
+        } else if (MODE == 0) {
           dq.x += d.x; dq.y += d.y; dq.z += d.z; dq.w += d.w;
           dv[j].x += d.x; dv[j].y += d.y; dv[j].z += d.z; dv[j].w += d.w;
         } else if (MODE == 1) {
@@ -816,14 +838,16 @@ __device__ __forceinline__ void att_score_bwd_quad(const float* __restrict__ dsc
     }
     reinterpret_cast<float4*>(dq_part + ((int64_t)b * NT + tile) * mid)[c] = dq;
   }
+  if constexpr (!DQ_ONLY) {
 #pragma unroll
-  for (int j = 0; j < BTP; ++j)
-    if (j < rows) reinterpret_cast<float4*>(dvprime + ((int64_t)n * P + p0 + j) * mid)[c] = dv[j];
-  const int64_t part = (int64_t)n * NT + tile;
+    for (int j = 0; j < BTP; ++j)
+      if (j < rows) reinterpret_cast<float4*>(dvprime + ((int64_t)n * P + p0 + j) * mid)[c] = dv[j];
+    const int64_t part = (int64_t)n * NT + tile;
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    reinterpret_cast<float4*>(dwx_part + (part * G + g) * xld)[c] = dw[g];
-    if (MODE == 2) reinterpret_cast<float4*>(dwx_part + (part * G + g) * xld + mid)[c] = dw2[g];
+    for (int g = 0; g < G; ++g) {
+      reinterpret_cast<float4*>(dwx_part + (part * G + g) * xld)[c] = dw[g];
+      if (MODE == 2) reinterpret_cast<float4*>(dwx_part + (part * G + g) * xld + mid)[c] = dw2[g];
+    }
   }
 }
 
@@ -857,6 +881,35 @@ __global__ __launch_bounds__(256) void att_score_grouped_bwd_general_kernel(cons
   for (int c = threadIdx.x; c < (mid >> 2); c += 256)
     att_score_bwd_quad<G, MODE, DROP>(dscore, vprime, qp, wx, wx_ld, order, dvprime, dq_part, dwx_part, n, tile, gridDim.x, rows,
                                       k0, k1, B, P, mid, c, p, inv_keep, seed);
+}
+
+// vqa_att_attr_dq_grouped / _f16: the two kernels above under DQ_ONLY -- same grid, same block, same ownership (16 positions
+// of one image per workgroup, one channel quad per thread), same dispatch (att_score_grouped_pw).  No LDS, no atomics.
+template <int G, int IT, bool MUL, class VT>
+__global__ __launch_bounds__(64 * IT) void att_attr_dq_grouped_kernel(const float* dscore, const VT* vprime, const float* qp,
+                                                                       const float* wx, int wx_ld, const int* order,
+                                                                       const int* offsets, float* dq_part, int B, int P) {
+  constexpr int mid = 256 * IT;
+  const int n = blockIdx.y, tile = blockIdx.x;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  att_score_bwd_quad<G, MUL ? 1 : 0, false, true, VT>(dscore, vprime, qp, wx, wx_ld, order, nullptr, dq_part, nullptr, n, tile,
+                                                      gridDim.x, min(BTP, P - tile * BTP), k0, k1, B, P, mid, threadIdx.x, 0.f,
+                                                      1.f, 0);
+}
+
+template <int G, int MODE, class VT>
+__global__ __launch_bounds__(256) void att_attr_dq_grouped_general_kernel(const float* dscore, const VT* vprime, const float* qp,
+                                                                          const float* wx, int wx_ld, const int* order,
+                                                                          const int* offsets, float* dq_part, int B, int P,
+                                                                          int mid) {
+  const int n = blockIdx.y, tile = blockIdx.x;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  const int rows = min(BTP, P - tile * BTP);
+  for (int c = threadIdx.x; c < (mid >> 2); c += 256)
+    att_score_bwd_quad<G, MODE, false, true, VT>(dscore, vprime, qp, wx, wx_ld, order, nullptr, dq_part, nullptr, n, tile,
+                                                 gridDim.x, rows, k0, k1, B, P, mid, c, 0.f, 1.f, 0);
 }
 
 }  // namespace vqa
@@ -992,6 +1045,44 @@ static int grouped_attr(const char* who, const float* r1, const float* dscore, c
   });
 #undef GROUPED_ATTR_GENERAL
   return check_hip(hipGetLastError(), "att_attr_score_grouped launch");
+}
+
+// the two entry points of d logit / d q' through the scores: the checks and limits of att_score_check, the grid and the
+// path choice of vqa_att_score_grouped_bwd.  '|' is refused: that gradient is identically zero (see att_score_bwd_quad)
+template <class VT>
+static int grouped_attr_dq(const char* who, const float* dscore, const VT* vprime, const float* qp, const float* wx, int wx_ld,
+                           const int32_t* order, const int32_t* offsets, float* dq_part, int N, int B, int P, int mid, int G,
+                           int mode, hipStream_t s) {
+  constexpr bool f32 = std::is_same<VT, float>::value;
+  VQA_REQUIRE(mode != 2,
+              "%s: mode 2 ('|') has no gradient to compute: the q' half adds the same constant to every position's score and "
+              "softmax is shift-invariant, so d logit / d q' through the scores is identically zero (modes 0 '+' and 1 '*' only)",
+              who);
+  const int rc = att_score_check(who, true, dscore && vprime && qp && wx && dq_part, order && offsets, N, B, P, mid, wx_ld, G,
+                                 mode, 0.f, (f32 ? bits(vprime, qp, wx) : bits(qp, wx)) | bits(dq_part));
+  if (rc) return rc;
+  VQA_REQUIRE((bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  if (B == 0) return VQA_OK;
+  const dim3 grid((P + BTP - 1) / BTP, N);                 // vqa_att_score_grouped_tiles(P)
+  with_int14(G, [&](auto g) {
+    constexpr int kG = decltype(g)::value;
+    if (att_score_grouped_pw(mode, mid) == 0)
+      with_int14(mid / 256, [&](auto it) {
+        return with_flag(mode == 1, [&](auto mul) {
+          hipLaunchKernelGGL((att_attr_dq_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, VT>), grid,
+                             dim3(64 * decltype(it)::value), 0, s, dscore, vprime, qp, wx, wx_ld, order, offsets, dq_part, B, P);
+          return 0;
+        });
+      });
+    else if (mode == 0)
+      hipLaunchKernelGGL((att_attr_dq_grouped_general_kernel<kG, 0, VT>), grid, dim3(256), 0, s, dscore, vprime, qp, wx, wx_ld,
+                         order, offsets, dq_part, B, P, mid);
+    else
+      hipLaunchKernelGGL((att_attr_dq_grouped_general_kernel<kG, 1, VT>), grid, dim3(256), 0, s, dscore, vprime, qp, wx, wx_ld,
+                         order, offsets, dq_part, B, P, mid);
+    return 0;
+  });
+  return check_hip(hipGetLastError(), "att_attr_dq_grouped launch");
 }
 
 extern "C" {
@@ -1194,6 +1285,25 @@ int vqa_att_attr_score_grouped_pairs_f16(const float* r1, const float* dscore, c
   VQA_REQUIRE(M >= 1, "vqa_att_attr_score_grouped_pairs_f16: M=%d question rows (>= 1)", M);
   return grouped_attr("vqa_att_attr_score_grouped_pairs_f16", r1, dscore, static_cast<const __half*>(vprime_f16), qp, qrow, M, wx,
                       wx_ld, order, offsets, out, N, B, P, mid, G, mode, (hipStream_t)stream);
+}
+
+// ---- gradient x input per question token: d logit / d q' through the scores
+int vqa_att_attr_dq_grouped(const float* dscore, const float* vprime, const float* qp, const float* wx, int wx_ld,
+                            const int32_t* order, const int32_t* offsets, float* dq_part, int N, int B, int P, int mid, int G,
+                            int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  return grouped_attr_dq("vqa_att_attr_dq_grouped", dscore, vprime, qp, wx, wx_ld, order, offsets, dq_part, N, B, P, mid, G, mode,
+                         (hipStream_t)stream);
+}
+
+int vqa_att_attr_dq_grouped_f16(const float* dscore, const void* vprime_f16, const float* qp, const float* wx, int wx_ld,
+                                const int32_t* order, const int32_t* offsets, float* dq_part, int N, int B, int P, int mid, int G,
+                                int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  return grouped_attr_dq("vqa_att_attr_dq_grouped_f16", dscore, static_cast<const __half*>(vprime_f16), qp, wx, wx_ld, order,
+                         offsets, dq_part, N, B, P, mid, G, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

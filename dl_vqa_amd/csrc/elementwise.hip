@@ -462,6 +462,64 @@ __global__ __launch_bounds__(256) void embed_tanh_bwd_binned_kernel(const int64_
   }
 }
 
+// Gradient x input per token slot (vqa_embed_attr; eval mode, no dropout): with e = emb[q[b][t]] the
+// embedding output before tanh, x = tanh(e) as the forward wrote it and dx = dx0 (+ dx1) the gradient of one logit at x,
+//   words[b][t] = sum_e emb[q[b][t]][e] * (1 - x[t][b][e]^2) * dx[t*B + b][e]
+// -- embed_tanh_bwd's element without the sum over the slots that share a token.  One wave per slot, slots walked by a
+// grid stride.  The summation order is a property of the slot, not of the grid: lane l adds the terms of its elements
+// 4*(l + 64*i) + k in ascending i and, inside a quad, k = 0, 1, 2, 3, each term rounded before it is added (no fused
+// multiply-add across the term and the sum); then the wave butterfly.  VEC reads the four operands' quads as 16-byte
+// loads, !VEC the same elements one by one: the same values in the same order, hence the same bits.  Every words[b][t] is
+// written: +0.0 for t >= q_len[b] and for a token id outside [0, V) (counted by the forward, a zero row there and here).
+__device__ __forceinline__ float embed_attr_add(float acc, float e, float x, float d) {
+#pragma clang fp contract(off)
+  const float g = 1.f - x * x;
+  const float term = e * g * d;
+  return acc + term;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void embed_attr_kernel(const int64_t* q, const float* emb, const float* x, const float* dx0,
+                                                         const float* dx1, const int64_t* q_len, float* words, int B, int T,
+                                                         int E, int V) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int nq = (E + 3) >> 2;                              // quads, the last one ragged when E % 4 != 0 (!VEC only)
+  for (int64_t s = wave; s < (int64_t)B * T; s += nwaves) {
+    const int b = (int)(s / T), t = (int)(s - (int64_t)b * T);
+    const int64_t tok = q[s];
+    float acc = 0.f;
+    if ((int64_t)t < q_len[b] && tok >= 0 && tok < V) {     // wave-uniform
+      const float* er = emb + tok * E;
+      const int64_t row = ((int64_t)t * B + b) * E;
+      const float *xr = x + row, *d0 = dx0 + row, *d1 = dx1 ? dx1 + row : nullptr;
+      for (int c = lane; c < nq; c += 64) {
+        if (VEC) {
+          const float4 e4 = reinterpret_cast<const float4*>(er)[c], x4 = reinterpret_cast<const float4*>(xr)[c];
+          float4 d4 = reinterpret_cast<const float4*>(d0)[c];
+          if (d1) {
+            const float4 o = reinterpret_cast<const float4*>(d1)[c];
+            d4.x += o.x; d4.y += o.y; d4.z += o.z; d4.w += o.w;
+          }
+          acc = embed_attr_add(acc, e4.x, x4.x, d4.x);
+          acc = embed_attr_add(acc, e4.y, x4.y, d4.y);
+          acc = embed_attr_add(acc, e4.z, x4.z, d4.z);
+          acc = embed_attr_add(acc, e4.w, x4.w, d4.w);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int i = 4 * c + k;
+            if (i < E) acc = embed_attr_add(acc, er[i], xr[i], d1 ? d0[i] + d1[i] : d0[i]);
+          }
+        }
+      }
+      acc = wave_sum(acc);
+    }
+    if (lane == 0) words[s] = acc;
+  }
+}
+
 // ------------------------------------------------------------------ LSTM cell
 __global__ void lstm_cell_fwd_kernel(const float* xg, const float* hg, const float* c_in, const float* h_in,
                                      const int64_t* q_len, int t, float* gates, float* c_out, float* h_out,
@@ -783,6 +841,22 @@ int vqa_embed_tanh_bwd(const int64_t* q, const float* x, const float* dx, float*
   hipLaunchKernelGGL(embed_tanh_bwd_binned_kernel, dim3(V), dim3(256), 0, STREAM, q, x, dx, demb, B, T, E, V, p, keep_scale(p), seed,
                      offsets, slots);
   return check_hip(hipGetLastError(), "embed_tanh_bwd(binned) launch");
+}
+
+int vqa_embed_attr(const int64_t* q, const float* emb, const float* x, const float* dx0, const float* dx1,
+                   const int64_t* q_len, float* words, int B, int T, int E, int V, vqa_stream_t stream) {
+  VQA_REQUIRE(q && emb && x && dx0 && q_len && words, "vqa_embed_attr: null pointer");
+  VQA_REQUIRE(B >= 0 && T >= 1 && E >= 1 && V >= 1, "vqa_embed_attr: B=%d, T=%d, E=%d, V=%d out of range", B, T, E, V);
+  if (B == 0) return VQA_OK;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(emb) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx0) |
+                      reinterpret_cast<uintptr_t>(dx1);
+  const dim3 grid(grid_for((int64_t)B * T, 4));             // four waves, four slots per workgroup
+  with_flag(E % 4 == 0 && (a & 15) == 0, [&](auto vec) {
+    hipLaunchKernelGGL((embed_attr_kernel<decltype(vec)::value>), grid, dim3(256), 0, STREAM, q, emb, x, dx0, dx1, q_len, words,
+                       B, T, E, V);
+    return 0;
+  });
+  return check_hip(hipGetLastError(), "embed_attr launch");
 }
 
 int vqa_lstm_cell_fwd(const float* xg, const float* hg, const float* c_in, const float* h_in, const int64_t* q_len,

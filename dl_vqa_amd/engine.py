@@ -532,12 +532,13 @@ class Engine:
         """B questions against the N encoded images of `feats` (vn, vprime): question b looks at image img[b]; order /
         offsets (device int32) group the questions by image.  Returns (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer: fp32 / fp32x3 only"
-        score, _qp, combined = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        return self._answer_tail(P, feats, score, img, combined)[:3]
+        score, _qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        return self._answer_tail(P, feats, score, img, txt.combined)[:3]
 
     def _answer_front(self, P, feats, q, q_len, order, offsets, bad_tokens):
-        """What answer and explain begin with.  Returns (score [B,G,Pn], q' [B,mid], the classifier-input buffer whose
-        question half the encoder has written)."""
+        """What answer, explain and explain_words begin with.  Returns (score [B,G,Pn], q' [B,mid], _question_front's
+        namespace: txt.combined is the classifier-input buffer whose question half the encoder has written, and the
+        recurrence state, which explain_words goes back through, stays alive with it)."""
         N, Pn, _ = feats.vn.shape
         # ---- question encoder and q_lin, eval mode, on the current stream (there are no convolutions to hide them under)
         txt, _ = self._question_front(P, q, q_len, feats.vn.device, 0.0, 0, bad_tokens, side=False)
@@ -545,7 +546,7 @@ class Engine:
         # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
         score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
                                           P["attention.x_conv.bias"], order, offsets, N, q.shape[0], Pn, self.att_mode)
-        return score, qp, txt.combined
+        return score, qp, txt
 
     def _answer_tail(self, P, feats, score, img, combined, cached=None):
         """What answer, answer_pairs, explain and explain_pairs end with: softmax over positions + weighted sum of the image
@@ -568,8 +569,8 @@ class Engine:
         """answer's arguments plus answers (device int32 [B], None: each question's arg-max).  Returns (maps [B,Pn],
         answers int32 [B], logits [B,A])."""
         assert not self.bf16, "explain: fp32 / fp32x3 only"
-        score, qp, combined = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        return self._explain_tail(P, feats, score, img, combined, None, qp, None, order, offsets, answers)
+        score, qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        return self._explain_tail(P, feats, score, img, txt.combined, None, qp, None, order, offsets, answers)
 
     @_device_current("feats", _cache_device)
     def explain_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor, qrow: Tensor,
@@ -579,10 +580,11 @@ class Engine:
         score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
         return self._explain_tail(P, feats, score, img, combined, (qfeats.qf, qrow), qfeats.qprime, qrow, order, offsets, answers)
 
-    def _explain_tail(self, P, feats, score, img, combined, cached, qp, qrow, order, offsets, answers):
-        """What explain and explain_pairs end with: _answer_tail, then the gradient of logit[b, answers[b]] back to the image
-        half of the classifier input, and the two attribution kernels.  qp: q' [B,mid], or explain_pairs' table read through
-        qrow.  Returns (maps [B,Pn], answers int32 [B], logits [B,A])."""
+    def _explain_tail(self, P, feats, score, img, combined, cached, qp, qrow, order, offsets, answers, tail=None):
+        """What explain, explain_pairs and explain_words end the image side with: _answer_tail, then the gradient of
+        logit[b, answers[b]] back to the image half of the classifier input, and the two attribution kernels.  qp: q'
+        [B,mid], or explain_pairs' table read through qrow.  Returns (maps [B,Pn], answers int32 [B], logits [B,A]).
+        tail: a dict that receives dh = d logit / d h1 [B,hid] and dscore [B,G,Pn], which explain_words carries on from."""
         logits, probs, score, h1 = self._answer_tail(P, feats, score, img, combined, cached)
         B, hid, GC, dev = img.numel(), self.hid, self.GC, feats.vn.device
         N, Pn, _ = feats.vn.shape
@@ -598,7 +600,55 @@ class Engine:
         dscore, r1 = ops.att_attr_apply_gather(dcomb, GC, probs, feats.vn, img)
         maps = ops.att_attr_score_grouped(r1, dscore, feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1), order,
                                           offsets, N, B, Pn, self.att_mode, qrow=qrow)
+        if tail is not None:
+            tail.update(dh=dh, dscore=dscore)
         return maps, answers, logits
+
+    # ------------------------------------------------------------------ gradient x input per question token
+    # explain_words is explain carried on to the other input: the same logit's gradient at the question half of the classifier
+    # input and, through the scores, at q' (one kernel, csrc/att_score.hip), back through q_lin and the recurrence to the
+    # embedding stage, where one kernel (csrc/elementwise.hip) turns it into words[b, t] = sum_e e * d logit / d e.  Data
+    # gradients only: no dW_hh, dW_ih, bias or embedding gradient is formed, nothing is written to a gradient buffer.
+    @_device_current("feats", _cache_device)
+    def explain_words(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
+                      answers: Optional[Tensor] = None, bad_tokens: Optional[Tensor] = None, stages: Optional[dict] = None):
+        """explain's arguments.  Returns (words [B,T], maps [B,Pn], answers int32 [B], logits [B,A]); maps, answers and
+        logits are explain's.  stages (a dict) receives dq_att [B,mid] = d logit / d q' through the scores (zeros for '|'),
+        attention_path (the launches made for that path: none for '|'), dqf [B,Q] = d logit / d (question features) and dx
+        [T,B,E] = d logit / d tanh(e), summed over the directions."""
+        assert not self.bf16, "explain_words: fp32 / fp32x3 only"
+        score, qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        tail = {}
+        maps, answers, logits = self._explain_tail(P, feats, score, img, txt.combined, None, qp, None, order, offsets, answers,
+                                                   tail)
+        B, T = txt.q.shape
+        N, Pn, _ = feats.vn.shape
+        E, H, Q, GC, mid, hid, dev = self.E, self.H, self.Q, self.GC, self.mid, self.hid, feats.vn.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        # d logit / d combined[:, GC:] = dh . W1[:, GC:]: the question half, a product of its own (the image half keeps
+        # explain's tiles, hence explain's bits)
+        dqf = new(B, Q)
+        ops.gemm(tail["dh"], P["classifier.lin1.weight"][:, GC:], dqf, B, Q, hid, transB=False, lda=hid, ldb=self.Dc)
+        # + d logit / d q' through the scores, back through q_lin.  '|': that path is identically zero (the q' half shifts every
+        # position's score by the same constant and softmax is shift-invariant): no kernel, no q_lin product
+        dq_att = None
+        if self.att_mode != 2:
+            dq_part, NT = ops.att_attr_dq_grouped(tail["dscore"], feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
+                                                  order, offsets, N, B, Pn, self.att_mode)
+            dq_att = ops.sum_parts(dq_part, new(B, mid), B, NT, mid)
+            ops.gemm(dq_att, P["attention.q_lin.weight"], dqf, B, Q, mid, transB=False, lda=mid, ldb=Q, accumulate=True, tag=47)
+        # back through time from dc_n = dqf[:, d*H:(d+1)*H], dh_n = 0, then dx_d = dgates_d . W_ih_d
+        dirs = self._recurrence_bwd(P, txt.lstm, txt.q_len, dqf, Q, B, T)
+        dx = []
+        for d, st in enumerate(dirs):
+            dx.append(ops.gemm(st["dgates"], P["text.lstm.weight_ih_l0" + _SFX[d]], new(T * B, E), T * B, E, 4 * H, transB=False,
+                               lda=4 * H, ldb=E, tag=53))
+        words = ops.embed_attr(txt.q, P["text.embedding.weight"], txt.x_emb, dx[0], dx[1] if self.ndir > 1 else None, txt.q_len)
+        if isinstance(stages, dict):
+            stages.update(dq_att=dq_att if dq_att is not None else torch.zeros(B, mid, dtype=torch.float32, device=dev),
+                          attention_path=("att_attr_dq_grouped", "sum_parts", "q_lin") if dq_att is not None else (),
+                          dqf=dqf, dx=(ops.add(dx[0], dx[1], new(T * B, E)) if self.ndir > 1 else dx[0]).view(T, B, E))
+        return words, maps, answers, logits
 
     # ------------------------------------------------------------------ cached question features (inference)
     # The mirror image of encode_images / answer: the question encoder and q_lin run once per DISTINCT question, and
@@ -921,18 +971,17 @@ class Engine:
                 ops.dropout(dq_in, ctx.p_att, sd(SITE_ATT_Q), out=dq_in)
             ops.add2d(dcomb[:, GC:], Dc, dq_in, Q, dcomb[:, GC:], Dc, B, Q)
 
-    def _question_bwd(self, P, ctx, dcomb, Gr):
-        """BPTT over the masked steps, the LSTM weight gradients of every direction and the embedding gradient, on the
-        current stream."""
-        B, T = ctx.B, ctx.T
-        E, H, Dc, GC = self.E, self.H, self.Dc, self.GC
-        dev = dcomb.device
+    def _recurrence_bwd(self, P, lstm, q_len, dqf, ld, B, T):
+        """Backward through time of every direction, on the current stream: from dc_n = dqf[:, d*H:(d+1)*H] (dqf: d / d
+        (question features) [B,Q], leading dimension ld) and dh_n = 0 to dgates [T][B][4H], kept in lstm[d]["dgates"].  The
+        recurrence half of _question_bwd, and all of it that explain_words runs; reads the forward's gates, Hs, Cs.  Returns the
+        per-direction dicts ops.lstm_seq_bwd takes."""
+        H, dev = self.H, dqf.device
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        # ---- the recurrence: dgates [T][B][4H] of every direction
         dirs = []
-        for d, st in enumerate(ctx.lstm):
+        for d, st in enumerate(lstm):
             dc = new(B, H)
-            ops.add2d(dcomb[:, GC + d * H:], Dc, None, 0, dc, H, B, H)
+            ops.add2d(dqf[:, d * H:], ld, None, 0, dc, H, B, H)
             dh = torch.zeros(B, H, dtype=torch.float32, device=dev)
             st["dgates"] = new(T, B, 4 * H)                   # kept alive until the streams have joined
             dirs.append(dict(w_hh=P["text.lstm.weight_hh_l0" + _SFX[d]], gates=st["gates"], Hs=st["Hs"], Cs=st["Cs"],
@@ -941,15 +990,26 @@ class Engine:
         if fused:
             # one call: the first cell backward + T-1 fused (dgates . W_hh -> next cell backward) launches,
             # every direction per launch, replayed as a cached hipGraph
-            ops.lstm_seq_bwd(dirs, ctx.q_len, B, T, H, use_graph=use_graph)
+            ops.lstm_seq_bwd(dirs, q_len, B, T, H, use_graph=use_graph)
         else:
             for st in dirs:
                 for n, (t, si, so) in enumerate(reversed(self._lstm_steps(T, st["reverse"]))):
-                    ops.lstm_cell_bwd(st["gates"][t], st["Cs"][si], st["Cs"][so], ctx.q_len, t, st["dh"], st["dc"],
+                    ops.lstm_cell_bwd(st["gates"][t], st["Cs"][si], st["Cs"][so], q_len, t, st["dh"], st["dc"],
                                       st["dgates"][t])
                     if n != T - 1:
                         ops.gemm(st["dgates"][t], st["w_hh"], st["dh"], B, H, 4 * H, transB=False, lda=4 * H, ldb=H,
                                  accumulate=True, tag=50)
+        return dirs
+
+    def _question_bwd(self, P, ctx, dcomb, Gr):
+        """BPTT over the masked steps, the LSTM weight gradients of every direction and the embedding gradient, on the
+        current stream."""
+        B, T = ctx.B, ctx.T
+        E, H, Dc, GC = self.E, self.H, self.Dc, self.GC
+        dev = dcomb.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        # ---- the recurrence: dgates [T][B][4H] of every direction
+        self._recurrence_bwd(P, ctx.lstm, ctx.q_len, dcomb[:, GC:], Dc, B, T)
         # ---- weight gradients and dx per direction.  The forward's decision (ctx.x16: bf16 path, T * B a multiple of 8):
         # one bf16 copy of dgates feeds the three products; dW_ih and dx come out Ek wide (the padded embedding width) and
         # their first E columns are copied to where the fp32 products write them

@@ -181,7 +181,17 @@ class Attribution(NamedTuple):
     logits: torch.Tensor
 
 
-TOPK_MAX = 64     # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
+class WordAttribution(NamedTuple):
+    """What VqaNet.explain_words returns: words fp32 [B, T] -- the gradient x input value of each token slot of each question
+    (signed, not normalised; 0 for t >= q_len[b]) -- and explain()'s maps fp32 [B, gh, gw], answers int64 [B] and logits fp32
+    [B, A] for the same arguments, bit for bit."""
+    words: torch.Tensor
+    maps: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+
+
+TOPK_MAX = 64    # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
 
 
 def _check_k(what: str, k, A: int) -> int:
@@ -1074,3 +1084,52 @@ class VqaNet(nn.Module):
         out = self._engine.explain_pairs(self._param_dict(), feats, qfeats, *index, answers=cols)
         return self._attribution(feats, out, B)
 
+
+    # ------------------------------------------------------------------ gradient x input per question token
+    @torch.no_grad()
+    def explain_words(self, feats: ImageFeatures, q, q_len, image_index, answers=None, *, _stages=None) -> WordAttribution:
+        """explain() carried on to the other input of the answer: WordAttribution(words fp32 [B, T], maps fp32 [B, gh, gw],
+        answers int64 [B], logits fp32 [B, A]).  For question b, token slot t and the answer column a_b = answers[b], with
+        e[b, t, :] = embedding.weight[q[b, t]] the embedding output before tanh,
+
+            words[b, t] = sum_e e[b, t, e] * d logits[b, a_b] / d e[b, t, e]
+
+        in eval mode WITH THE IMAGE FEATURES HELD FIXED: signed, not normalised.  The gradient follows the question along
+        both of its paths to the logit -- the question half of the classifier input, and q' = q_lin(qf) in the attention
+        scores -- back through the LSTM to the embedding stage.  For do_option '|' the second path is identically zero (the q'
+        half adds the same constant to every position's score, and softmax is shift-invariant), and nothing runs for it.
+        words[b, t] is 0 for t >= q_len[b], and 0 for a token id outside the vocabulary (counted as answer() counts it);
+        the padding row of the embedding is zero, so a token 0 inside a question gives 0 too.  Data gradients only: no
+        weight, bias or embedding gradient is formed (include/vqa_hip.h has the formulas).
+
+        maps, answers and logits are explain()'s for the same arguments, bit for bit, and so are the `answers` argument, the
+        argument rules and the refusals, all judged before any device work: eval mode only (RuntimeError in train mode),
+        fp32 / fp32x3 (NotImplementedError for "bf16"), features that hold v', the feature-ownership checks and image_index
+        rules; fp32 and float16 caches (a float16 cache gives, bit for bit, what feats.to(torch.float32) gives); B == 0
+        returns empty tensors.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad and the dropout seed
+        stream are left alone, and a later forward / backward is unchanged.
+
+        There is no explain_words_pairs: QuestionFeatures holds the encoder's results (qf, q'), not the recurrence state
+        (gates, hidden and cell states per step) that the gradient has to go back through, so cached questions cannot be
+        explained without encoding them again -- which is this call.
+
+        _stages (tests and tools): a dict that receives the engine's intermediate gradients (Engine.explain_words)."""
+        self._check_inference("explain_words")
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError("VqaNet.explain_words: feats must come from VqaNet.encode_images")
+        # what the host alone can judge comes first, in words _answer_args would use: a bank without v', the index count
+        self._need_vprime("explain_words", feats)
+        n_idx = torch.as_tensor(image_index).numel()
+        if n_idx != len(q):
+            raise ValueError(f"VqaNet.explain_words: {n_idx} image_index entries for {len(q)} questions")
+        cols = self._answer_columns("explain_words", answers, len(q))
+        q, q_len, index = self._answer_args("explain_words", feats, q, q_len, image_index)
+        B, T = q.shape
+        dev = feats.vn.device
+        if B == 0:
+            return WordAttribution(torch.empty(0, T, dtype=torch.float32, device=dev), *self._attribution(feats, None, 0))
+        index, cols = _upload_with_columns(dev, index, cols)
+        words, *out = self._engine.explain_words(self._param_dict(), feats, q, q_len, *index, answers=cols,
+                                                 bad_tokens=self._token_counter(q), stages=_stages)
+        self._after_forward_tokens(q)
+        return WordAttribution(words, *self._attribution(feats, out, B))

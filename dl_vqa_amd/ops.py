@@ -689,6 +689,44 @@ def att_attr_score_grouped(r1, dscore, vprime, qp, wx, order, offsets, N: int, B
     return out
 
 
+def att_attr_dq_grouped(dscore, vprime, qp, wx, order, offsets, N: int, B: int, P: int, mode: int, dq_part=None):
+    """d logit / d q' through the attention scores (include/vqa_hip.h), from the dscore [B, G, P] of att_attr_apply_gather:
+    att_score_grouped_bwd at p = 0 without dvprime and dwx_part, bit for bit.  Returns (dq_part [B*NT, mid], NT);
+    sum_parts(dq_part, out, B, NT, mid) finishes it.  vprime fp32 or float16; mode 0 '+' or 1 '*' (2, '|': the library
+    refuses -- that gradient is identically zero).  dq_part: written in place; the rows of questions that are not listed in
+    order / offsets are left as they are."""
+    G, xld, mid = _score_dims(wx, mode == 2)
+    _chk(order, torch.int32), _chk(offsets, torch.int32), _chk(dscore), _chk(qp)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and qp.shape == (B, mid)
+    assert dscore.shape == (B, G, P) and dscore.is_contiguous()
+    NT = _lib.load().vqa_att_score_grouped_tiles(P)
+    if dq_part is None:
+        dq_part = torch.empty(B * NT, mid, dtype=torch.float32, device=vprime.device)
+    assert dq_part.shape == (B * NT, mid) and dq_part.is_contiguous() and dq_part.dtype == torch.float32
+    call("vqa_att_attr_dq_grouped" + _cache_suffix(vprime), ptr(dscore), ptr(vprime), ptr(qp), ptr(wx), xld, ptr(order),
+         ptr(offsets), ptr(dq_part), N, B, P, mid, G, mode, stream())
+    return dq_part, NT
+
+
+def embed_attr(q, emb, x, dx0, dx1, q_len, out=None):
+    """Gradient x input per token slot (include/vqa_hip.h vqa_embed_attr): words [B, T] from q int64 [B, T], the embedding
+    table emb [V, E], x = tanh(emb[q]) [T, B, E] as embed_tanh_fwd wrote it, the gradient at x as dx0 (+ dx1, or None)
+    [T*B, E] and q_len int64 [B].  Every element is written, 0 for t >= q_len[b] and for a token id outside [0, V)."""
+    B, T = q.shape
+    V, E = emb.shape
+    _chk(q, torch.int64), _chk(q_len, torch.int64)
+    for t in (emb, x, dx0) + (() if dx1 is None else (dx1,)):
+        _chk(t)
+        assert t.is_contiguous()
+    assert q.is_contiguous() and q_len.numel() == B and x.numel() == T * B * E and dx0.numel() == T * B * E
+    assert dx1 is None or dx1.numel() == T * B * E
+    if out is None:
+        out = torch.empty(B, T, dtype=torch.float32, device=emb.device)
+    assert out.shape == (B, T) and out.is_contiguous() and out.dtype == torch.float32
+    call("vqa_embed_attr", ptr(q), ptr(emb), ptr(x), ptr(dx0), ptr(dx1), ptr(q_len), ptr(out), B, T, E, V, stream())
+    return out
+
+
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C], fp32 or
     float16."""

@@ -43,7 +43,9 @@ extern "C" {
  * cached image features (vqa_gather_rows_drop_norm, vqa_gather_rows_drop_norm_f16; declared with the entry points of training
  * on cached image features), and then the seven of gradient x input attribution (vqa_att_attr_apply_gather, vqa_att_attr_apply_gather_f16,
  * vqa_att_attr_score_grouped_path, vqa_att_attr_score_grouped, vqa_att_attr_score_grouped_pairs, vqa_att_attr_score_grouped_f16,
- * vqa_att_attr_score_grouped_pairs_f16; declared behind those of the cached-feature paths they extend). */
+ * vqa_att_attr_score_grouped_pairs_f16; declared behind those of the cached-feature paths they extend), and then the three of
+ * gradient x input per question token (vqa_att_attr_dq_grouped, vqa_att_attr_dq_grouped_f16, vqa_embed_attr; declared behind
+ * the attribution entry points). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -459,6 +461,43 @@ int vqa_att_attr_score_grouped_pairs_f16(const float* r1, const float* dscore, c
                                          const int32_t* qrow, const float* wx, int wx_ld, const int32_t* order,
                                          const int32_t* offsets, float* out, int N, int B, int M, int P, int mid, int G, int mode,
                                          vqa_stream_t stream);
+
+/* ---- gradient x input per question token (inference, VqaNet.explain_words; csrc/att_score.hip, csrc/elementwise.hip) ----
+ * For question b, token slot t and the chosen answer column a_b, with e[b][t][:] = emb[q[b][t]] the embedding output before
+ * tanh (eval mode, no dropout, the image features held fixed):
+ *   words[b][t] = sum_e e[b][t][e] * d logit[b][a_b] / d e[b][t][e]
+ * The question reaches the logit through the question half of the classifier input and through q' = q_lin(qf) in the
+ * attention scores.  These two entry points are the ends of that chain; between them run products the library already has
+ * (the q_lin data gradient, the LSTM backward through time, dgates . W_ih) and no parameter gradient.
+ *   vqa_att_attr_dq_grouped / _f16: d logit / d q' through the scores, from the dscore [B][G][P] of vqa_att_attr_apply_gather:
+ *       dxpre[b][p][m]  = [x > 0] * sum_g dscore[b][g][p] * wx[g*wx_ld + m]         x = v'[n*P+p][m] (+|*) q'[b][m], n the image of b
+ *       dq_part[b*NT+t][m] = sum over the positions p of tile t of   '+': dxpre      '*': dxpre * v'[n*P+p][m]
+ *     with NT = vqa_att_score_grouped_tiles(P); vqa_sum_parts(batch B, parts NT) finishes dq_att [B][mid].  This is
+ *     vqa_att_score_grouped_bwd at p = 0 without dvprime and dwx_part -- the same device code under a compile-time flag, the
+ *     same ownership (16 positions of one image per workgroup, one channel quad per thread, the image's questions walked in
+ *     `order`'s order), the same per-thread operation order -- so dq_part equals that entry point's bit for bit, and the half
+ *     form (v' IEEE half, 8-byte aligned, widened on load) equals the fp32 form on the widened v' bit for bit.  No atomics, no
+ *     LDS.  Rows of questions that are not listed in order / offsets are left alone.
+ *     mode 0 '+' and 1 '*' only.  mode 2 ('|') is VQA_ERR_INVALID: there the q' half adds the same constant to every position's
+ *     score and softmax is shift-invariant, so this gradient is identically zero -- a caller launches nothing for it.
+ *     Limits and checks as vqa_att_score_grouped_bwd: mid % 4 == 0, mid <= 4096, wx_ld % 4 == 0, wx_ld >= mid, G in 1..4,
+ *     N <= 65535; v' (fp32 form), qp, wx and dq_part 16-byte aligned.  B == 0 returns without a launch.
+ *   vqa_embed_attr: the other end, from dx = dx0 + dx1 (dx1 may be NULL: a unidirectional encoder), the gradient at the
+ *     embedding stage's output x = tanh(e) [T][B][E] that vqa_embed_tanh_fwd wrote (p = 0):
+ *       words[b][t] = sum_e emb[q[b][t]*E + e] * (1 - x[t][b][e]^2) * (dx0[(t*B+b)*E + e] + dx1[(t*B+b)*E + e])
+ *     q int64 [B][T], q_len int64 [B], words [B][T]: every element is written, +0.0 for t >= q_len[b] and for a token id
+ *     outside [0, V) (which vqa_embed_tanh_fwd counts and reads as a zero row).  One wave per slot; lane l adds the terms of
+ *     elements 4*(l + 64*i) + k in ascending i, then k, each term rounded before the add, then the wave butterfly: one order,
+ *     whatever the grid.  16-byte accesses when E % 4 == 0 and emb, x, dx0, dx1 are 16-byte aligned, scalar otherwise (same
+ *     bits).  B >= 0, T, E, V >= 1; B == 0 returns without a launch. */
+int vqa_att_attr_dq_grouped(const float* dscore, const float* vprime, const float* qp, const float* wx, int wx_ld,
+                            const int32_t* order, const int32_t* offsets, float* dq_part, int N, int B, int P, int mid, int G,
+                            int mode, vqa_stream_t stream);
+int vqa_att_attr_dq_grouped_f16(const float* dscore, const void* vprime_f16, const float* qp, const float* wx, int wx_ld,
+                                const int32_t* order, const int32_t* offsets, float* dq_part, int N, int B, int P, int mid, int G,
+                                int mode, vqa_stream_t stream);
+int vqa_embed_attr(const int64_t* q, const float* emb, const float* x, const float* dx0, const float* dx1,
+                   const int64_t* q_len, float* words, int B, int T, int E, int V, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
