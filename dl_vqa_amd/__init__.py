@@ -19,10 +19,12 @@ resize, centre crop, normalisation and fp16 cast (preprocessing/preprocess_image
 (``Attribution``): why an answer, at the normalised feature layer, from the same caches and without a convolution.
 ``VqaNet.explain_words`` carries the same gradient on to the question: one gradient x input value per token
 (``WordAttribution``), back through q_lin, the attention scores and the LSTM, with no parameter gradient formed.
+``VqaNet.explain_occlusion`` / ``explain_occlusion_pairs`` return what those maps estimate, exactly (``Occlusion``): how far
+the logit falls when a window of grid positions is taken out of the image, for every position, in closed form.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
            "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
-           "WordAttribution"]
+           "WordAttribution", "Occlusion"]

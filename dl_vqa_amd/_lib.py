@@ -167,6 +167,9 @@ PROTOTYPES = {
     "vqa_att_attr_dq_grouped": (i32, [f32p, f32p, f32p, f32p, i32, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_att_attr_dq_grouped_f16": (i32, [f32p, vp, f32p, f32p, i32, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp]),
     "vqa_embed_attr": (i32, [i64p, f32p, f32p, f32p, f32p, i64p, f32p, i32, i32, i32, i32, vp]),
+    # occlusion maps from cached features (bound with the attribution entry points, before the last two)
+    "vqa_occl_logit": (i32, [f32p, f32p, f32p, vp, i32, f32p, f32p, f32p, f32p, i64, f32p, vp, f32p, i64, f32p, i32, i32, i32, i32,
+                             i32, i32, i32, i32, vp]),
     # image dropout on a bank of cached image features
     "vqa_gather_rows_drop_norm": (i32, [f32p, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),
     "vqa_gather_rows_drop_norm_f16": (i32, [vp, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),

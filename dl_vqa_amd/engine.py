@@ -604,6 +604,75 @@ class Engine:
             tail.update(dh=dh, dscore=dscore)
         return maps, answers, logits
 
+    # ------------------------------------------------------------------ occlusion maps from cached features
+    # What explain estimates to first order, exactly: the fall of ONE logit per question when a window of grid positions is
+    # taken out of the image, for every position, in closed form (include/vqa_hip.h vqa_occl_logit).  answer's
+    # front and tail, the classifier's first layer applied to every feature row of the distinct asked images (one product per
+    # image, question-independent), and one streaming kernel.  No second forward, no parameter gradient, nothing kept.
+    U_BYTES = 256 << 20             # workspace cap of U [images, Pn, G, hid]: more asked images are walked in chunks
+
+    @_device_current("feats", _cache_device)
+    def explain_occlusion(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
+                          rows: Tensor, slot: Tensor, answers: Optional[Tensor] = None, window: int = 1,
+                          bad_tokens: Optional[Tensor] = None, u_bytes: Optional[int] = None):
+        """answer's arguments plus rows [n_u] / slot [B] (device int32, model.compact_image_index of the image index: the
+        distinct asked images and each question's place among them), answers (device int32 [B], None: each question's arg-max)
+        and window.  Returns (maps [B,Pn], answers int32 [B], logits [B,A])."""
+        assert not self.bf16, "explain_occlusion: fp32 / fp32x3 only"
+        score, qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        return self._occlusion_tail(P, feats, score, img, txt.combined, None, qp, None, rows, slot, answers, window, u_bytes)
+
+    @_device_current("feats", _cache_device)
+    def explain_occlusion_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor,
+                                qrow: Tensor, rows: Tensor, slot: Tensor, answers: Optional[Tensor] = None, window: int = 1,
+                                u_bytes: Optional[int] = None):
+        """answer_pairs' arguments plus rows, slot, answers and window, as explain_occlusion."""
+        assert not self.bf16, "explain_occlusion_pairs: fp32 / fp32x3 only"
+        score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
+        return self._occlusion_tail(P, feats, score, img, combined, (qfeats.qf, qrow), qfeats.qprime, qrow, rows, slot, answers,
+                                    window, u_bytes)
+
+    def _occlusion_tail(self, P, feats, score, img, combined, cached, qp, qrow, rows, slot, answers, window, u_bytes):
+        """What explain_occlusion and explain_occlusion_pairs end with: _answer_tail, the per-question operands of the closed
+        form (cnull, base, Z), then U = W1_g . vn for the distinct asked images in chunks that fit the workspace cap, each
+        followed by the kernel for the questions of its images.  qp: q' [B,mid], or the pairs' table read through qrow."""
+        logits, probs, score, _h1 = self._answer_tail(P, feats, score, img, combined, cached)
+        B, hid, G, C, GC, Dc, dev = img.numel(), self.hid, self.G, self.C, self.GC, self.Dc, feats.vn.device
+        Pn = feats.vn.shape[1]
+        gh, gw = feats.grid
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        if answers is None:                                # topk_answers' arg-max, on the device
+            answers = ops.softmax_topk(logits, 1)[0].view(B)
+        # cnull: the score kernel's own bits for a position whose v' is 0 -- one all-zero position, every question in one group
+        wx, bx = P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"]
+        zero_v = torch.zeros(1, self.mid, dtype=torch.float32, device=dev)
+        order1 = torch.arange(B, dtype=torch.int32, device=dev)
+        offsets1 = torch.arange(0, B + 1, B, dtype=torch.int32, device=dev)                     # [0, B]
+        if qrow is None:
+            cnull = ops.att_score_grouped_fwd(zero_v, qp, wx, bx, order1, offsets1, 1, B, 1, self.att_mode)
+        else:
+            cnull = ops.att_score_grouped_pairs_fwd(zero_v, qp, qrow, wx, bx, order1, offsets1, 1, B, 1, self.att_mode)
+        # base = b1 + W1[:, GC:] . qf and Z_g = W1_g . out_g: the two halves of lin1 apart, plain fp32 in every compute mode
+        w1 = P["classifier.lin1.weight"]
+        base = ops.gemm(combined[:, GC:], w1[:, GC:], new(B, hid), B, hid, self.Q, lda=Dc, ldb=Dc, bias1=P["classifier.lin1.bias"])
+        Z = new(B, G, hid)
+        for g in range(G):
+            ops.gemm(combined[:, g * C:], w1[:, g * C:], Z[:, g], B, hid, C, lda=Dc, ldb=Dc, ldc=G * hid)
+        # U [n, Pn, G, hid] for n images at a time, by the rule v' follows in encode_images; _bank_rows gathers the asked rows
+        # and widens a float16 cache
+        n_u = rows.numel()
+        per = max(1, int((self.U_BYTES if u_bytes is None else u_bytes) // (Pn * G * hid * 4)))
+        U = new(min(per, n_u), Pn, G, hid)
+        maps = new(B, Pn)
+        for r0 in range(0, n_u, per):
+            n = min(per, n_u - r0)
+            v_in = self._bank_rows(feats.vn, rows[r0:r0 + n], 0.0, 0.0, 0)[1]
+            for g in range(G):
+                _gemm(v_in, w1[:, g * C:], U[:n, :, g], n * Pn, hid, C, ldb=Dc, ldc=G * hid, x3=self._x3_gemm(n * Pn))
+            ops.occl_logit(base, Z, U[:n], slot, probs, score, cnull, P["classifier.lin2.weight"], P["classifier.lin2.bias"],
+                           answers, logits, gh, gw, window, slot0=r0, out=maps)
+        return maps, answers, logits
+
     # ------------------------------------------------------------------ gradient x input per question token
     # explain_words is explain carried on to the other input: the same logit's gradient at the question half of the classifier
     # input and, through the scores, at q' (one kernel, csrc/att_score.hip), back through q_lin and the recurrence to the

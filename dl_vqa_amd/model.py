@@ -191,7 +191,27 @@ class WordAttribution(NamedTuple):
     logits: torch.Tensor
 
 
-TOPK_MAX = 64    # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
+class Occlusion(NamedTuple):
+    """What VqaNet.explain_occlusion / explain_occlusion_pairs return: maps fp32 [B, gh, gw] -- how far the explained logit
+    falls when the window around each grid position is taken out of the image (signed, no upsampling, no normalisation) --,
+    answers int64 [B] -- the answer column each map explains, as Attribution.answers -- and logits fp32 [B, A] -- what answer()
+    / answer_pairs() return for the same arguments, bit for bit."""
+    maps: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+
+
+OCCLUSION_WINDOW_MAX = 7    # include/vqa_hip.h vqa_occl_logit
+
+
+def _check_window(what: str, window) -> int:
+    """The window argument of explain_occlusion / explain_occlusion_pairs: an odd int in 1..7 (a bool is not one)."""
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= OCCLUSION_WINDOW_MAX or window % 2 == 0:
+        raise ValueError(f"{what}: window must be an odd int in 1..{OCCLUSION_WINDOW_MAX}, got {window!r}")
+    return window
+
+
+TOPK_MAX = 64   # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
 
 
 def _check_k(what: str, k, A: int) -> int:
@@ -1083,6 +1103,76 @@ class VqaNet(nn.Module):
         index, cols = _upload_with_columns(feats.vn.device, index, cols)
         out = self._engine.explain_pairs(self._param_dict(), feats, qfeats, *index, answers=cols)
         return self._attribution(feats, out, B)
+
+    # ------------------------------------------------------------------ occlusion maps from cached features
+    @torch.no_grad()
+    def explain_occlusion(self, feats: ImageFeatures, q, q_len, image_index, answers=None, window: int = 1, *,
+                          _u_bytes=None) -> Occlusion:
+        """answer() with an occlusion map per question: Occlusion(maps fp32 [B, gh, gw], answers int64 [B], logits fp32
+        [B, A]).  For question b about image n = image_index[b] and the answer column a_b = answers[b],
+
+            maps[b, p] = logits[b, a_b] - logit_occluded[b, a_b; S(p)]
+
+        where S(p) is the window x window square of grid positions centred on p, clipped at the grid border, and "occluded"
+        means that the L2-normalised features vn[n, s, :] of every s in S(p) are zero (hence v'[n, s, :] too: v_conv has no
+        bias) -- exactly what answer() computes on a cache whose rows s are zeroed in vn and in v'.  This is the quantity that
+        explain()'s gradient x input map estimates to first order, computed exactly and in closed form for every position at
+        once: no second forward runs (include/vqa_hip.h vqa_occl_logit has the formulas; the classifier's first layer is
+        applied to every feature row of the distinct asked images, in chunks of images that fit a 256 MiB workspace, and one
+        streaming kernel does the rest).  Eval mode, the question held fixed; signed, not upsampled, not normalised.
+
+        window: an odd int in 1..7 (default 1: single positions); anything else, a bool included, is a ValueError raised
+        before any device work.
+
+        Conditioning.  The occluded attention is renormalised by alpha = 1 / (1 - mass + |S| * r) per glimpse, where mass is
+        the attention S(p) held and r the weight an occluded position keeps.  The closed form subtracts like-sized numbers and
+        multiplies the difference by alpha, so its fp32 rounding error grows in proportion to alpha: the maps agree with the
+        brute-force route to a few ulp of the logit while alpha <= 16, and stay defined and finite beyond that, with an error
+        that grows as the window swallows the whole attention mass (DESIGN.md 4.18 records it at mass 0.99).
+
+        answers, logits, the `answers` argument, the argument rules and the refusals are explain()'s, judged before any device
+        work: eval mode only (RuntimeError in train mode), fp32 / fp32x3 (NotImplementedError for "bf16"), features that hold
+        v', the feature-ownership checks and image_index rules; all three do_option values; fp32 and float16 caches (a float16
+        cache gives, bit for bit, what feats.to(torch.float32) gives); a CUDA `answers` entry outside [0, A) gives a map of
+        zeros; B == 0 returns empty tensors.  Rows come back in the caller's order and do not depend on how the batch is
+        ordered.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad and the dropout seed stream are left
+        alone.
+
+        _u_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
+        self._check_inference("explain_occlusion")
+        window = _check_window("VqaNet.explain_occlusion", window)
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError("VqaNet.explain_occlusion: feats must come from VqaNet.encode_images")
+        cols = self._answer_columns("explain_occlusion", answers, len(q))
+        q, q_len, index = self._answer_args("explain_occlusion", feats, q, q_len, image_index)
+        B = q.shape[0]
+        if B == 0:
+            return Occlusion(*self._attribution(feats, None, 0))
+        index, cols = _upload_with_columns(feats.vn.device, index + compact_image_index(index[-1], feats.N)[:2], cols)
+        out = self._engine.explain_occlusion(self._param_dict(), feats, q, q_len, *index, answers=cols, window=window,
+                                             bad_tokens=self._token_counter(q), u_bytes=_u_bytes)
+        self._after_forward_tokens(q)
+        return Occlusion(*self._attribution(feats, out, B))
+
+    @torch.no_grad()
+    def explain_occlusion_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
+                                answers=None, window: int = 1, *, _u_bytes=None) -> Occlusion:
+        """explain_occlusion() for B (image, question) pairs from the two caches, as answer_pairs() is to answer(): pair b
+        looks at image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  maps,
+        answers, window and the `answers` argument are explain_occlusion()'s; logits are answer_pairs()'s for the same
+        arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the window and
+        `answers` checks judged first."""
+        self._check_inference("explain_occlusion_pairs")
+        window = _check_window("VqaNet.explain_occlusion_pairs", window)
+        cols = self._answer_columns("explain_occlusion_pairs", answers, torch.as_tensor(image_index).numel())
+        index = self._pairs_args("explain_occlusion_pairs", feats, qfeats, image_index, question_index)
+        B = index[-1].numel()
+        if B == 0:
+            return Occlusion(*self._attribution(feats, None, 0))
+        index, cols = _upload_with_columns(feats.vn.device, index + compact_image_index(index[2], feats.N)[:2], cols)
+        out = self._engine.explain_occlusion_pairs(self._param_dict(), feats, qfeats, *index, answers=cols, window=window,
+                                                   u_bytes=_u_bytes)
+        return Occlusion(*self._attribution(feats, out, B))
 
 
     # ------------------------------------------------------------------ gradient x input per question token

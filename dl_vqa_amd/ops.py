@@ -727,6 +727,32 @@ def embed_attr(q, emb, x, dx0, dx1, q_len, out=None):
     return out
 
 
+def occl_logit(base, Z, U, slot, probs, score, cnull, W2, b2, answers, logits, gh: int, gw: int, window: int, slot0: int = 0,
+               out=None):
+    """Occlusion maps [B, P] (include/vqa_hip.h vqa_occl_logit): maps[b, p] = logits[b, a_b] - the same logit with the window x
+    window square of grid positions around p taken out of image slot[b].  base [B, hid], Z [B, G, hid], U [R, P, G, hid] (the
+    rows slot0 .. slot0 + R - 1; a question whose slot is outside them is left alone), slot and answers device int32 [B], probs
+    and score [B, G, P], cnull [B, G], W2 [A, hid] and logits [B, A] row-major views with unit column stride, b2 [A].  out:
+    written in place."""
+    B, G, P = probs.shape
+    R, hid, A = U.shape[0], base.shape[1], W2.shape[0]
+    for t in (base, Z, U, probs, score, cnull, b2):
+        _chk(t)
+        assert t.is_contiguous()
+    _chk(slot, torch.int32), _chk(answers, torch.int32), _chk(W2), _chk(logits)
+    assert P == gh * gw and score.shape == probs.shape and base.shape == (B, hid) and Z.shape == (B, G, hid)
+    assert U.shape == (R, P, G, hid) and cnull.numel() == B * G and slot.numel() == B and answers.numel() == B
+    assert W2.shape[1] == hid and b2.numel() == A and logits.shape == (B, A)
+    assert (hid == 1 or W2.stride(1) == 1) and (A == 1 or logits.stride(1) == 1)
+    if out is None:
+        out = torch.empty(B, P, dtype=torch.float32, device=probs.device)
+    assert out.shape == (B, P) and out.is_contiguous() and out.dtype == torch.float32
+    call("vqa_occl_logit", ptr(base), ptr(Z), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2),
+         W2.stride(0) if A > 1 else hid, ptr(b2), ptr(answers), ptr(logits), logits.stride(0) if B > 1 else A, ptr(out),
+         R, B, gh, gw, hid, G, A, window, stream())
+    return out
+
+
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C], fp32 or
     float16."""

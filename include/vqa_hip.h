@@ -45,7 +45,7 @@ extern "C" {
  * vqa_att_attr_score_grouped_path, vqa_att_attr_score_grouped, vqa_att_attr_score_grouped_pairs, vqa_att_attr_score_grouped_f16,
  * vqa_att_attr_score_grouped_pairs_f16; declared behind those of the cached-feature paths they extend), and then the three of
  * gradient x input per question token (vqa_att_attr_dq_grouped, vqa_att_attr_dq_grouped_f16, vqa_embed_attr; declared behind
- * the attribution entry points). */
+ * the attribution entry points), and then the one of occlusion maps (vqa_occl_logit; declared behind those). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -498,6 +498,37 @@ int vqa_att_attr_dq_grouped_f16(const float* dscore, const void* vprime_f16, con
                                 int mode, vqa_stream_t stream);
 int vqa_embed_attr(const int64_t* q, const float* emb, const float* x, const float* dx0, const float* dx1,
                    const int64_t* q_len, float* words, int B, int T, int E, int V, vqa_stream_t stream);
+
+/* ---- occlusion maps from cached features (inference, VqaNet.explain_occlusion; csrc/occlusion.hip) ----
+ * What the gradient x input maps estimate to first order, computed exactly: for question b about image n, answer column a_b and
+ * every grid position p, how far logit[b][a_b] falls when the features vn[n][s][:] (hence v'[n][s][:]: v_conv has no bias) of the
+ * positions s in S(p) are zero -- S(p) the window x window square centred on p, clipped at the grid border (eval mode, the
+ * question held fixed):
+ *   maps[b][p] = logit[b][a_b] - logit_occluded[b][a_b ; S(p)]
+ * An occluded position scores cnull[b][g] (the score of a position whose v' is 0), so per glimpse g, with hid = the
+ * classifier's hidden width and W1_g = columns [g*C, (g+1)*C) of lin1.weight,
+ *   r[b][g]      = exp(cnull[b][g] - m) / sum_p exp(score[b][g][p] - m),   m = max_p score[b][g][p]
+ *   mass[b][g][p] = sum_{s in S(p)} probs[b][g][s]
+ *   alpha        = 1 / (1 - mass + |S(p)| * r)                    (> 0: r > 0)
+ *   U[n][s][g][:] = W1_g . vn[n][s][:]       Z[b][g][:] = W1_g . out[b][g][:]       base[b][:] = b1 + W1[:, G*C:] . qf[b]
+ *   pre'[h]      = base[b][h] + sum_g alpha[b][g][p] * (Z[b][g][h] - sum_{s in S(p)} probs[b][g][s] * U[n][s][g][h])
+ *   logit_occluded = W2[a_b][:] . relu(pre') + b2[a_b]
+ * base [B][hid], Z [B][G][hid], probs and score [B][G][P] (P = gh * gw), cnull [B][G], answers int32 [B], maps [B][P].  U holds
+ * the rows of R images, [R][P][G][hid]; question b reads row slot[b] - slot0 of it, and a question whose row is outside [0, R)
+ * is LEFT ALONE -- a caller whose U does not fit one buffer walks it in chunks of images and every question is written by
+ * exactly one of the calls.  A column a_b outside [0, A) gives a row of zeros.
+ * One workgroup per (question, 16 consecutive positions): its head stages base, Z and W2[a_b] in LDS and forms r by a block
+ * reduction (the same order in every workgroup of the question); then one wave per position, lane l over the quads l, l + 64,
+ * ... of hid with 16-byte loads, the window's positions row by row, g ascending, and the wave butterfly.  One summation order
+ * per (b, p), no atomics, every element written once: permuting the questions permutes the rows of maps bit for bit.  r,
+ * mass and alpha are fp32.  Conditioning: Z - sum probs * U is a difference of like-sized numbers whose rounding error alpha
+ * multiplies; alpha grows as the window swallows the attention mass (DESIGN.md 4.18 has the measured error).
+ * Limits: hid % 4 == 0, w2_ld % 4 == 0, (G + 2) * hid * 4 + 80 <= 65536 bytes of LDS, G in 1..4, window odd in 1..7, base, Z,
+ * U and W2 16-byte aligned; anything else is VQA_ERR_INVALID before any HIP call.  B == 0 returns without a launch. */
+int vqa_occl_logit(const float* base, const float* Z, const float* U, const int32_t* slot, int slot0, const float* probs,
+                   const float* score, const float* cnull, const float* W2, int64_t w2_ld, const float* b2,
+                   const int32_t* answers, const float* logits, int64_t logits_ld, float* maps, int R, int B, int gh, int gw,
+                   int hid, int G, int A, int window, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch

@@ -1,0 +1,221 @@
+"""CPU: occlusion maps from cached features (VqaNet.explain_occlusion / explain_occlusion_pairs) -- the closed form behind
+vqa_occl_logit against a brute-force forward with the occluded features zeroed (float64), that the exact map is not a
+restatement of the gradient x input map, the new entry point in the header, the ctypes prototypes and the built library with
+its host-side argument validation, and the errors the public calls raise before any device work."""
+import re
+
+import pytest
+import torch
+
+from dl_vqa_amd import ImageFeatures, Occlusion, QuestionFeatures, VqaNet
+from tests import attribution_ref as R
+from tests import occlusion_ref as OR
+from tests.golden_util import Golden, full_cfg, tiny_cfg
+
+
+# ----------------------------------------------------------------------------- the identity, in float64
+def _columns(B, A):
+    return [(3 * b + 1) % A for b in range(B)]
+
+
+@pytest.mark.parametrize("window", [1, 3])
+@pytest.mark.parametrize("do_option", ["+", "*", "|"])
+def test_closed_form_equals_brute_force_on_the_fixtures(do_option, window):
+    f = R.fixture_case(do_option)
+    sd, A = f["golden"].sd, f["cfg"]["max_answers"]
+    assert f["vn"].shape[1] == 4                                  # a 2 x 2 grid: window 3 covers all of it from anywhere
+    top = R.forward64(sd, do_option, f["vn"], f["qf"], f["img"], f["grid"]).argmax(1).tolist()
+    for cols in (top, _columns(len(top), A)):
+        want = OR.fixture_brute(do_option, cols, window)
+        got, parts = OR.closed_form(sd, do_option, f["vn"], f["qf"], f["img"], cols, f["grid"], window)
+        err = float((got - want).abs().max())
+        print(f"[identity-occlusion] {R.FIXTURES[do_option]} window {window}: closed form vs brute force {err:.3e}, "
+              f"max|map| {float(want.abs().max()):.3e}, max alpha {float(parts['alpha'].max()):.3f}")
+        assert float(want.abs().max()) > 0 and err < 1e-12
+        if window == 3:                                           # the whole grid: one value per question
+            assert float((want - want[:, :1]).abs().max()) < 1e-12
+
+
+def _random_case(do_option, G, grid, seed):
+    """A random attention stage + classifier in float64 (state-dict names and shapes of the model) and random inputs, with
+    weights of a size that keeps the logits O(1)."""
+    g = torch.Generator().manual_seed(seed)
+    N, B, C, mid, Q, hid, A = 3, 5, 10, 12, 6, 9, 5
+    gh, gw = grid
+    xld = 2 * mid if do_option == "|" else mid
+    rn = lambda *s: 0.5 * torch.randn(*s, generator=g, dtype=torch.float64)
+    sd = {"attention.v_conv.weight": rn(mid, C, 1, 1), "attention.q_lin.weight": rn(mid, Q), "attention.q_lin.bias": rn(mid),
+          "attention.x_conv.weight": rn(G, xld, 1, 1), "attention.x_conv.bias": rn(G),
+          "classifier.lin1.weight": rn(hid, G * C + Q), "classifier.lin1.bias": rn(hid),
+          "classifier.lin2.weight": rn(A, hid), "classifier.lin2.bias": rn(A)}
+    vn = torch.randn(N, gh * gw, C, generator=g, dtype=torch.float64)
+    vn = vn / vn.norm(dim=-1, keepdim=True)
+    qf = torch.randn(B, Q, generator=g, dtype=torch.float64)
+    img = torch.randint(0, N, (B,), generator=g)
+    answers = torch.randint(0, A, (B,), generator=g)
+    return sd, vn, qf, img, answers
+
+
+@pytest.mark.parametrize("G", [1, 2])
+@pytest.mark.parametrize("do_option", ["+", "*", "|"])
+@pytest.mark.parametrize("grid", [(3, 4), (5, 7)])
+def test_closed_form_equals_brute_force_on_synthetic_grids(grid, do_option, G):
+    sd, vn, qf, img, answers = _random_case(do_option, G, grid, seed=100 * grid[0] + 10 * G + R.MODES[do_option])
+    for window in (1, 3, 5):
+        want = OR.brute(sd, do_option, vn, qf, img, answers, grid, window)
+        got, parts = OR.closed_form(sd, do_option, vn, qf, img, answers, grid, window)
+        err = float((got - want).abs().max())
+        print(f"[identity-occlusion] {grid} '{do_option}' G={G} window {window}: closed form vs brute force {err:.3e}, "
+              f"max|map| {float(want.abs().max()):.3e}, max alpha {float(parts['alpha'].max()):.3f}")
+        assert float(want.abs().max()) > 0 and err < 1e-12
+        assert float(parts["alpha"].min()) > 0
+    # a window clipped at the border holds fewer positions: the corner of a 3-wide window has 4, the centre 9
+    counts = OR.windows(*grid, 3).sum(-1)
+    assert counts[0] == 4 and counts.max() == 9
+
+
+@pytest.mark.parametrize("do_option", ["+", "*", "|"])
+def test_the_occlusion_map_is_not_the_gradient_x_input_map(do_option):
+    """The exact map and its first-order estimate differ by more than 5 % of the exact map's maximum on every fixture."""
+    f = R.fixture_case(do_option)
+    sd = f["golden"].sd
+    top = R.forward64(sd, do_option, f["vn"], f["qf"], f["img"], f["grid"]).argmax(1).tolist()
+    exact = OR.fixture_brute(do_option, top, 1)
+    first_order = R.autograd_reference(sd, do_option, f["vn"], f["qf"], f["img"], top, f["grid"])
+    gap = float((exact - first_order).abs().max()) / float(exact.abs().max())
+    print(f"[identity-occlusion] {R.FIXTURES[do_option]}: |occlusion - gradient x input| = {gap:.3f} of max|occlusion| = "
+          f"{float(exact.abs().max()):.3e}")
+    assert gap > 0.05
+
+
+# ----------------------------------------------------------------------------- the ABI
+def test_new_entry_point_in_header_prototypes_and_library():
+    from dl_vqa_amd import _lib, build
+    build.build_library(verbose=False)
+    with open(_lib.HEADER_PATH) as f:
+        header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    assert re.search(r"\bvqa_occl_logit\s*\(", header) and "vqa_occl_logit" in _lib.PROTOTYPES
+    lib = _lib.load()
+    assert lib.vqa_abi_version() == _lib.header_abi_version() == 9          # appended, not bumped
+    assert hasattr(lib, "vqa_occl_logit")
+    from dl_vqa_amd import ops
+    assert callable(ops.occl_logit)
+
+
+def test_occl_logit_argument_validation_without_gpu():
+    """base, Z, U, slot, slot0, probs, score, cnull, W2, w2_ld, b2, answers, logits, logits_ld, maps, R, B, gh, gw, hid, G, A,
+    window, stream (pointers are made-up aligned integers: every check runs on the host before any HIP call)."""
+    from dl_vqa_amd import _lib
+    lib = _lib.load()
+    err = lib.vqa_last_error
+    f = lib.vqa_occl_logit
+    ok = dict(base=16, Z=16, U=16, slot=16, slot0=0, probs=16, score=16, cnull=16, W2=16, w2_ld=20, b2=16, answers=16, logits=16,
+              logits_ld=12, maps=16, R=2, B=3, gh=2, gw=2, hid=20, G=2, A=12, window=1, stream=None)
+
+    def call(**kw):
+        return f(*{**ok, **kw}.values())
+
+    assert call(B=0) == 0                                             # nothing to do, nothing launched
+    assert call(hid=18, B=0) == 1 and b"multiple of 4" in err() and b"hid=18" in err()
+    assert call(w2_ld=16, B=0) == 1 and b"w2_ld" in err()             # w2_ld < hid
+    assert call(G=5, B=0) == 1 and b"glimpses" in err()
+    for window in (0, 2, 9, -1):
+        assert call(window=window, B=0) == 1 and b"window" in err()
+    for name in ("base", "Z", "U", "slot", "probs", "score", "cnull", "W2", "b2", "answers", "logits", "maps"):
+        assert call(**{name: None}, B=0) == 1 and b"null pointer" in err(), name
+    for name in ("base", "Z", "U", "W2"):
+        assert call(**{name: 20}, B=0) == 1 and b"aligned" in err(), name
+    assert call(R=0, B=0) == 1 and b"out of range" in err()
+    assert call(logits_ld=11, B=0) == 1 and b"out of range" in err()  # logits_ld < A
+    assert call(hid=4096, w2_ld=4096, G=4, B=0) == 1 and b"LDS" in err()
+
+
+# ----------------------------------------------------------------------------- errors before any device work
+def _tiny():
+    g = Golden("tiny_plus")
+    m = VqaNet(tiny_cfg(g.meta), g.meta["V"])
+    m.load_state_dict(g.sd)
+    return g, m
+
+
+def _host_caches(m, N=3, M=2):
+    """Holders as encode_images / encode_questions build them, around host tensors (tests/test_attribution_cpu.py)."""
+    eng = m._engine
+    m._flat_param = torch.zeros(4)
+    feats = ImageFeatures(torch.zeros(N, 4, eng.C), torch.zeros(N * 4, eng.mid), (2, 2), m)
+    qfeats = QuestionFeatures(torch.zeros(M, eng.Q), torch.zeros(M, eng.mid), m)
+    return feats, qfeats
+
+
+def test_bf16_then_train_mode_then_device():
+    assert Occlusion._fields == ("maps", "answers", "logits")
+    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
+    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
+    for call in (lambda: m.explain_occlusion(None, q, ql, [0]), lambda: m.explain_occlusion_pairs(None, None, [0], [0])):
+        with pytest.raises(NotImplementedError, match="compute_dtype"):
+            call()
+    g, m = _tiny()
+    m.train()
+    for call in (lambda: m.explain_occlusion(None, g.t["q"], g.t["q_len"], [0, 1, 2]),
+                 lambda: m.explain_occlusion_pairs(None, None, [0], [0])):
+        with pytest.raises(RuntimeError, match="training mode"):
+            call()
+    m.eval()                                                        # eval mode on the CPU: the device check speaks
+    feats, qfeats = _host_caches(m)
+    with pytest.raises(RuntimeError, match="cuda"):
+        m.explain_occlusion(feats, g.t["q"][:3], g.t["q_len"][:3], [0, 1, 2], window=3)
+    with pytest.raises(RuntimeError, match="cuda"):
+        m.explain_occlusion_pairs(feats, qfeats, [0, 1, 2], [0, 1, 1], answers=[0, 1, 2], window=7)
+    assert m._last_ctx is None
+
+
+def test_window_answers_and_features_are_judged_before_any_device_work():
+    g, m = _tiny()
+    m.eval()
+    A = m._engine.A
+    feats, qfeats = _host_caches(m, N=3, M=2)
+    q, ql = g.t["q"][:3], g.t["q_len"][:3]
+    single = lambda **kw: m.explain_occlusion(feats, q, ql, [0, 1, 2], **kw)
+    pairs = lambda **kw: m.explain_occlusion_pairs(feats, qfeats, [0, 1, 2], [0, 1, 1], **kw)
+    for call in (single, pairs):
+        for window in (0, 2, 4, 9, -1, True, 3.0, "3", None):
+            with pytest.raises(ValueError, match="window must be an odd int in 1..7"):
+                call(window=window)
+        with pytest.raises(ValueError, match="2 answers for 3"):
+            call(answers=[0, 1])
+        with pytest.raises(IndexError, match=rf"answers entry {A} out of range \[0, {A}\)"):
+            call(answers=[0, A, 1])
+        with pytest.raises(IndexError, match="answers entry -1"):
+            call(answers=torch.tensor([0, 1, -1], dtype=torch.int32))
+        with pytest.raises(TypeError, match="integer"):
+            call(answers=[0.0, 1.0, 2.0])
+        with pytest.raises(RuntimeError, match="cuda"):             # everything the host can judge is in order
+            call(answers=[0, A - 1, 1], window=5)
+    # what explain / explain_pairs raise for the same arguments, the call's own name in the message
+    with pytest.raises(TypeError, match="encode_images"):
+        m.explain_occlusion(torch.zeros(3), q, ql, [0, 1, 2])
+    with pytest.raises(TypeError, match="encode_images"):
+        m.explain_occlusion_pairs(torch.zeros(3), qfeats, [0], [0])
+    with pytest.raises(TypeError, match="encode_questions"):
+        m.explain_occlusion_pairs(feats, feats, [0], [0])
+    # an index out of range, features without v' and foreign features: whatever explain / explain_pairs raise for the same
+    # arguments on this host (the device checks of the GPU tests judge them where a device is present), word for word
+    bank = ImageFeatures(torch.zeros(3, 4, m._engine.C), None, (2, 2), m)
+    _, other = _tiny()
+    other.eval()
+    theirs, their_q = _host_caches(other)
+
+    def raised(call):
+        with pytest.raises(Exception) as e:
+            call()
+        return type(e.value), str(e.value).replace("explain_occlusion", "explain")
+
+    for images in (feats, bank, theirs):
+        for index in ([0, 1, 2], [0, 1, feats.N]):
+            assert raised(lambda: m.explain_occlusion(images, q, ql, index)) == raised(lambda: m.explain(images, q, ql, index))
+            for questions in (qfeats, their_q):
+                assert raised(lambda: m.explain_occlusion_pairs(images, questions, index, [0, 1, 1])) == \
+                    raised(lambda: m.explain_pairs(images, questions, index, [0, 1, 1]))
+    with pytest.raises(IndexError):
+        m.explain_occlusion_pairs(feats, qfeats, [0, 1, feats.N], [0, 1, 1])
+    assert m._last_ctx is None and all(p.grad is None for p in m.parameters())
