@@ -21,10 +21,12 @@ resize, centre crop, normalisation and fp16 cast (preprocessing/preprocess_image
 (``WordAttribution``), back through q_lin, the attention scores and the LSTM, with no parameter gradient formed.
 ``VqaNet.explain_occlusion`` / ``explain_occlusion_pairs`` return what those maps estimate, exactly (``Occlusion``): how far
 the logit falls when a window of grid positions is taken out of the image, for every position, in closed form.
+``VqaNet.explain_words_occlusion`` does the same for the question (``WordOcclusion``): how far the logit falls when one token's
+embedding output is zeroed, for every token, from the prefixes the variant recurrences share with the question itself.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
            "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
-           "WordAttribution", "Occlusion"]
+           "WordAttribution", "Occlusion", "WordOcclusion"]

@@ -719,6 +719,76 @@ class Engine:
                           dqf=dqf, dx=(ops.add(dx[0], dx[1], new(T * B, E)) if self.ndir > 1 else dx[0]).view(T, B, E))
         return words, maps, answers, logits
 
+    # ------------------------------------------------------------------ exact word occlusion from cached features
+    # What explain_words estimates to first order, exactly: the fall of ONE logit per question when the embedding output of one
+    # token slot is the zero vector, for every slot (include/vqa_hip.h vqa_lstm_occl_cell_fwd).  The recurrence has
+    # no closed form, but a variant (b, t) shares the forward direction's prefix before t and the reverse direction's after t
+    # with the base question, whose states answer's own encoder run has left in Hs / Cs: the variant chains start there.  Per
+    # step one recurrent product over the rows whose chain has started and one cell kernel; then q_lin, the grouped scores, the
+    # weighted sum and the classifier's first layer on the variant rows (the forward's own stages) and one tail kernel.
+    WORDS_BYTES = 256 << 20         # workspace cap of one chunk's variant buffers: more variants are walked in chunks of questions
+
+    def word_occlusion_rows(self, Pn: int) -> int:
+        """How many variant rows fit WORDS_BYTES: per row hg [4H], h and c [H] per direction, the classifier input [Dc], q' [mid],
+        score and probs [G, Pn] and the hidden layer [hid], fp32."""
+        per_row = 4 * (self.ndir * 6 * self.H + self.Dc + self.mid + 2 * self.G * Pn + self.hid)
+        return max(1, self.WORDS_BYTES // per_row)
+
+    @_device_current("feats", _cache_device)
+    def explain_words_occlusion(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor,
+                                img: Tensor, chunks, answers: Optional[Tensor] = None, bad_tokens: Optional[Tensor] = None):
+        """explain's arguments plus chunks: model.word_occlusion_table of every chunk of questions, its index tensors on the
+        device as int32 and with order / offsets / img, the chunk's variant rows (forward order) grouped by their question's image.
+        Returns (words [B,T], answers int32 [B], logits [B,A]); answers and logits are explain's."""
+        assert not self.bf16, "explain_words_occlusion: fp32 / fp32x3 only"
+        score, _qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
+        logits, _probs, _score, _h1 = self._answer_tail(P, feats, score, img, txt.combined)
+        B, T = txt.q.shape
+        N, Pn, _ = feats.vn.shape
+        E, H, GC, Dc, hid, dev = self.E, self.H, self.GC, self.Dc, self.hid, feats.vn.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        if answers is None:                                # topk_answers' arg-max, on the device
+            answers = ops.softmax_topk(logits, 1)[0].view(B)
+        # xg0 = b_ih + b_hh in the base product's own bits: the question encoder's xg product on one all-zero input row
+        zero_x = torch.zeros(1, E, dtype=torch.float32, device=dev)
+        xg0 = [_gemm(zero_x, P["text.lstm.weight_ih_l0" + _SFX[d]], new(1, 4 * H), 1, 4 * H, E,
+                     bias1=P["text.lstm.bias_ih_l0" + _SFX[d]], bias2=P["text.lstm.bias_hh_l0" + _SFX[d]], tag=10)
+               for d in range(self.ndir)]
+        wx, bx = P["attention.x_conv.weight"].view(self.G, -1), P["attention.x_conv.bias"]
+        words = new(B, T)
+        for tab in chunks:
+            V = tab.V
+            if V == 0:                                     # no variants: the tail writes the chunk's zeros
+                ops.occl_words(new(0, hid), P["classifier.lin2.weight"], P["classifier.lin2.bias"], answers, logits, tab.fwd_b,
+                               tab.fwd_t, txt.q_len, words, tab.b0, tab.b1 - tab.b0)
+                continue
+            combined = new(V, Dc)
+            hg = new(V, 4 * H)
+            for d, st in enumerate(txt.lstm):
+                rev = st["reverse"]
+                var_b, var_t, seed = (tab.rev_b, tab.rev_t, tab.rev_seed) if rev else (tab.fwd_b, tab.fwd_t, tab.fwd_seed)
+                counts = tab.n_rev if rev else tab.n_fwd
+                # the chains' first states: slot t (forward) / t + 1 (reverse) of the base run, one gather per tensor
+                h_var = ops.gather_rows(st["Hs"].view((T + 1) * B, H), seed, new(V, H))
+                c_var = ops.gather_rows(st["Cs"].view((T + 1) * B, H), seed, new(V, H))
+                c_final = combined[:, GC + d * H:]
+                for s in (range(tab.steps - 1, -1, -1) if rev else range(tab.steps)):
+                    n = counts[s]
+                    if n == 0:
+                        continue
+                    ops.gemm(h_var, st["w_hh"], hg, n, 4 * H, H, tag=11)
+                    ops.lstm_occl_cell_fwd(st["xg"].view(T, B, 4 * H), xg0[d], hg, h_var, c_var, txt.q_len, var_b, var_t, s, n,
+                                           c_final=c_final, cf_row=tab.rev_row if rev else None)
+            # the forward's own stages on V rows: q_lin, the grouped scores, the weighted sum, the classifier's first layer
+            qp = self._q_lin_fwd(P, combined[:, GC:], 0.0, 0)[0]
+            score_v = ops.att_score_grouped_fwd(feats.vprime, qp, wx, bx, tab.order, tab.offsets, N, V, Pn, self.att_mode)
+            ops.att_apply_gather_fwd(score_v, feats.vn, tab.img, combined, Dc)
+            h1 = _gemm(combined, P["classifier.lin1.weight"], new(V, hid), V, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True,
+                       tag=30)
+            ops.occl_words(h1, P["classifier.lin2.weight"], P["classifier.lin2.bias"], answers, logits, tab.fwd_b, tab.fwd_t,
+                           txt.q_len, words, tab.b0, tab.b1 - tab.b0)
+        return words, answers, logits
+
     # ------------------------------------------------------------------ cached question features (inference)
     # The mirror image of encode_images / answer: the question encoder and q_lin run once per DISTINCT question, and
     # (image, question) pairs are answered from the two caches -- no recurrence, no convolution in answer_pairs.

@@ -16,6 +16,7 @@ from __future__ import annotations
 import warnings
 import weakref
 from collections import OrderedDict
+from types import SimpleNamespace
 from typing import Dict, List, NamedTuple, Optional
 
 import torch
@@ -201,7 +202,78 @@ class Occlusion(NamedTuple):
     logits: torch.Tensor
 
 
+class WordOcclusion(NamedTuple):
+    """What VqaNet.explain_words_occlusion returns: words fp32 [B, T] -- how far the explained logit falls when the embedding
+    output of each token slot is replaced by the zero vector (signed, not normalised; +0.0 for t >= q_len[b]) --, answers int64
+    [B] -- the answer column each row explains, as Attribution.answers -- and logits fp32 [B, A] -- what answer() returns for the
+    same arguments, bit for bit."""
+    words: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+
+
 OCCLUSION_WINDOW_MAX = 7    # include/vqa_hip.h vqa_occl_logit
+
+
+def word_occlusion_chunks(lengths, T: int, max_rows: Optional[int] = None):
+    """The questions of a batch cut into chunks [(b0, b1), ...] of consecutive questions whose variants -- the pairs (b, t), t <
+    min(lengths[b], T), none for a length <= 0 -- number at most max_rows per chunk (None: one chunk).  Chunks cut between
+    questions, never inside one: a question with more variants than max_rows is a chunk of its own.  Every question is in
+    exactly one chunk, those without variants included.  lengths: host integers."""
+    counts = [min(max(int(n), 0), T) for n in lengths]
+    if max_rows is None:
+        return [(0, len(counts))] if counts else []
+    chunks, b0, rows = [], 0, 0
+    for b, n in enumerate(counts):
+        if b > b0 and rows + n > max_rows:
+            chunks.append((b0, b))
+            b0, rows = b, 0
+        rows += n
+    if counts:
+        chunks.append((b0, len(counts)))
+    return chunks
+
+
+def word_occlusion_table(lengths, T: int, b0: int = 0, b1: Optional[int] = None):
+    """The variant table of VqaNet.explain_words_occlusion for the questions [b0, b1) of a batch of B = len(lengths) questions
+    with T token slots, from host lengths.  A variant is a pair (b, t) with t < min(lengths[b], T); there are V of them, none
+    for a length <= 0.  Zeroing slot t leaves the forward direction's state before t and the reverse direction's state after t
+    unchanged, so a variant's chain starts at time t in both directions.  Per direction the table holds the variant rows in the
+    order their chains start and, for every time s, how many have started -- at time s a direction steps its first n[s] rows:
+
+      fwd_b, fwd_t   int32 [V]   ascending t (then b): the chain of row r runs s = t .. ; this is also the row order of the
+                                 classifier-input buffer and of the tail
+      rev_b, rev_t   int32 [V]   descending t (then ascending b): the chain of row r runs s = t, t - 1, .. 0
+      rev_row        int32 [V]   the row of (rev_b[r], rev_t[r]) in the forward order
+      fwd_seed       int32 [V]   t * B + b: the row of the base state the forward chain starts from (slot t of [(T+1)*B, H])
+      rev_seed       int32 [V]   (t + 1) * B + b: the same for the reverse chain (slot t + 1)
+      n_fwd, n_rev   lists [T]   n_fwd[s] = #{t <= s}, n_rev[s] = #{t >= s}
+      steps          the chunk's largest clamped length: the loops stop there (n_rev[s] = 0 for s >= steps)
+      row_steps      sum over both directions and s < steps of n[s]: the rows of the recurrent products, <= V * (steps + 1)
+                     <= V * (T + 1); running every variant in full takes 2 * T * V
+
+    Pure host code: nothing here touches a device."""
+    B = len(lengths)
+    b1 = B if b1 is None else b1
+    counts = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)[b0:b1].clamp(0, T)
+    live = (torch.arange(T)[:, None] < counts[None, :])                     # [T, questions of the chunk], time-major
+    fwd = live.nonzero()                                                    # rows (t, i): ascending t, then ascending i
+    rev = live.flip(0).nonzero()                                            # rows (T - 1 - t, i): descending t, then ascending i
+    fwd_t, fwd_b = fwd[:, 0], fwd[:, 1] + b0
+    rev_t, rev_b = T - 1 - rev[:, 0], rev[:, 1] + b0
+    V = fwd.shape[0]
+    row_of = torch.zeros(T, max(b1 - b0, 1), dtype=torch.int64)
+    row_of[fwd[:, 0], fwd[:, 1]] = torch.arange(V)
+    per_t = live.sum(1)                                                     # variants whose slot is t
+    n_fwd = torch.cumsum(per_t, 0).tolist()
+    n_rev = torch.cumsum(per_t.flip(0), 0).flip(0).tolist()
+    steps = int(counts.max()) if counts.numel() else 0
+    i32 = lambda x: x.to(torch.int32)
+    return SimpleNamespace(V=V, b0=b0, b1=b1, steps=steps, n_fwd=n_fwd, n_rev=n_rev,
+                           row_steps=sum(n_fwd[:steps]) + sum(n_rev[:steps]),
+                           fwd_b=i32(fwd_b), fwd_t=i32(fwd_t), fwd_seed=i32(fwd_t * B + fwd_b),
+                           rev_b=i32(rev_b), rev_t=i32(rev_t), rev_seed=i32((rev_t + 1) * B + rev_b),
+                           rev_row=i32(row_of[rev_t, rev_b - b0]))
 
 
 def _check_window(what: str, window) -> int:
@@ -1223,3 +1295,83 @@ class VqaNet(nn.Module):
                                                  bad_tokens=self._token_counter(q), stages=_stages)
         self._after_forward_tokens(q)
         return WordAttribution(words, *self._attribution(feats, out, B))
+
+    # ------------------------------------------------------------------ exact word occlusion from cached features
+    _WORD_TABLE_FIELDS = ("fwd_b", "fwd_t", "fwd_seed", "rev_b", "rev_t", "rev_seed", "rev_row", "order", "offsets", "img")
+
+    @torch.no_grad()
+    def explain_words_occlusion(self, feats: ImageFeatures, q, q_len, image_index, answers=None, *,
+                                _variant_rows=None) -> WordOcclusion:
+        """answer() with the exact occlusion value of every question token: WordOcclusion(words fp32 [B, T], answers int64 [B],
+        logits fp32 [B, A]).  For question b, token slot t < q_len[b] and the answer column a_b = answers[b], with e[b, t, :] =
+        embedding.weight[q[b, t]] the embedding output before tanh,
+
+            words[b, t] = logits[b, a_b] - logit_t[b, a_b]
+
+        where logit_t is the same forward with e[b, t, :] replaced by the zero vector, in eval mode WITH THE IMAGE FEATURES HELD
+        FIXED: the LSTM input of that step is tanh(0) = 0, so its gate pre-activation is b_ih + b_hh + h W_hh^T; the question's
+        length and every other token are unchanged.  This is the quantity whose first-order estimate is explain_words().words --
+        occluding a word means zeroing its input, as explain_occlusion() zeroes feature rows -- and through an LSTM that
+        estimate is a poor one (DESIGN.md 4.19 records how far apart they are).  It is defined on the embedding output, so it does
+        not depend on what row 0 of the table holds.  Signed, not normalised.
+
+        words[b, t] is +0.0 for t >= q_len[b], and a row is all zeros where answers[b] is outside [0, A) (a CUDA `answers`
+        entry, as explain()'s map).  A slot whose embedding row is zero already -- token 0, and an id outside the vocabulary,
+        which the forward reads as a zero row and counts -- is NOT forced to zero: its value is the difference of two evaluations
+        of the same function along two kernel routes (the base run's recurrence and the variant steps), a few ulp of the
+        logit, within the parity bound of the tests.
+
+        How it runs.  The recurrence has no closed form, but it has shared prefixes: zeroing slot t leaves the forward
+        direction's state before t and the reverse direction's state after t as answer()'s own encoder run left them.  A
+        variant (b, t) therefore takes q_len[b] - t forward and t + 1 reverse steps from those saved states instead of 2 *
+        q_len[b], and its tail needs one column of lin2, not A (include/vqa_hip.h vqa_lstm_occl_cell_fwd, vqa_occl_words).
+        The variant table is built on the host from the lengths: device-resident lengths are copied to the host ONCE, which
+        synchronises (as a CUDA image_index does).  The questions are walked in chunks whose variant buffers stay within a 256
+        MiB workspace; chunks cut between questions.
+
+        answers and logits are explain()'s for the same arguments, bit for bit, and so are the `answers` argument, the argument
+        rules and the refusals, all judged before any device work: eval mode only (RuntimeError in train mode), fp32 / fp32x3
+        (NotImplementedError for "bf16"), features that hold v', the feature-ownership checks and image_index rules; fp32 and
+        float16 caches (a float16 cache gives, bit for bit, what feats.to(torch.float32) gives); B == 0 returns empty tensors.
+        Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad and the dropout seed stream are left alone, and a
+        later forward / backward is unchanged.
+
+        There is no pairs form, for the reason explain_words() gives: QuestionFeatures holds the encoder's results, not the
+        per-step states the variant chains start from.
+
+        _variant_rows (tests and tools): caps the variants per chunk, to force several chunks at small sizes."""
+        what = "explain_words_occlusion"
+        self._check_inference(what)
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
+        # what the host alone can judge comes first, as in explain_words
+        self._need_vprime(what, feats)
+        n_idx = torch.as_tensor(image_index).numel()
+        if n_idx != len(q):
+            raise ValueError(f"VqaNet.{what}: {n_idx} image_index entries for {len(q)} questions")
+        cols = self._answer_columns(what, answers, len(q))
+        q, q_len, index = self._answer_args(what, feats, q, q_len, image_index)
+        B, T = q.shape
+        dev, eng = feats.vn.device, self._engine
+        if B == 0:
+            return WordOcclusion(torch.empty(0, T, dtype=torch.float32, device=dev), *self._attribution(feats, None, 0)[1:])
+        lengths = q_len.detach().to(device="cpu", dtype=torch.int64).reshape(-1)      # the one copy to the host: synchronises
+        cap = eng.word_occlusion_rows(feats.vn.shape[1])
+        if _variant_rows is not None:
+            cap = max(1, min(cap, int(_variant_rows)))
+        img = index[-1]
+        chunks, parts = [], []
+        for b0, b1 in word_occlusion_chunks(lengths.tolist(), T, cap):
+            tab = word_occlusion_table(lengths, T, b0, b1)
+            tab.img = img[tab.fwd_b.long()]
+            tab.order, tab.offsets = _group(tab.img, feats.N)
+            chunks.append(tab)
+            parts += [getattr(tab, k) for k in self._WORD_TABLE_FIELDS]
+        index, cols = _upload_with_columns(dev, tuple(index) + tuple(parts), cols)
+        for i, tab in enumerate(chunks):                                                # the tables on the device: the same copy
+            for j, k in enumerate(self._WORD_TABLE_FIELDS):
+                setattr(tab, k, index[3 + i * len(self._WORD_TABLE_FIELDS) + j])
+        words, picked, logits = eng.explain_words_occlusion(self._param_dict(), feats, q, q_len, *index[:3], chunks, answers=cols,
+                                                            bad_tokens=self._token_counter(q))
+        self._after_forward_tokens(q)
+        return WordOcclusion(words, picked.long(), logits)

@@ -753,6 +753,63 @@ def occl_logit(base, Z, U, slot, probs, score, cnull, W2, b2, answers, logits, g
     return out
 
 
+def lstm_occl_cell_fwd(xg_base, xg0, hg, h_var, c_var, q_len, var_b, var_t, s: int, n: Optional[int] = None, c_final=None,
+                       cf_row=None):
+    """One step, time s, of the variant recurrence of exact word occlusion (include/vqa_hip.h vqa_lstm_occl_cell_fwd), in place
+    on the first n rows (default: all) of h_var / c_var [V, H] (row-major views with unit column stride and the same row
+    stride): row r is the variant (var_b[r], var_t[r]) (device int32 [>= n]); held for s >= q_len[b], otherwise the cell on
+    (xg0 if s == t else xg_base[s, b]) + hg[r].  xg_base [T, B, 4H] and hg [>= n, 4H] contiguous, xg0 [4H] (the base product's
+    bits for a zero input row), q_len int64 [B].  c_final (a view [V, >= H] with unit column stride): the new cell state also
+    goes to its row cf_row[r] (device int32, None: row r) on every active step."""
+    T, B, H4 = xg_base.shape
+    H = H4 // 4
+    n = h_var.shape[0] if n is None else n
+    for t in (xg_base, xg0, hg):
+        _chk(t)
+        assert t.is_contiguous()
+    _chk(h_var), _chk(c_var), _chk(q_len, torch.int64), _chk(var_b, torch.int32), _chk(var_t, torch.int32)
+    assert H4 == 4 * H and xg0.numel() == H4 and hg.dim() == 2 and hg.shape[1] == H4 and hg.shape[0] >= n and q_len.numel() == B
+    assert h_var.dim() == 2 and h_var.shape == c_var.shape and h_var.shape[1] == H and 0 <= n <= h_var.shape[0]
+    assert (H == 1 or (h_var.stride(1) == 1 and c_var.stride(1) == 1)) and var_b.numel() >= n and var_t.numel() >= n
+    st_ld = h_var.stride(0) if h_var.shape[0] > 1 else H
+    assert c_var.shape[0] <= 1 or c_var.stride(0) == st_ld
+    cf_ld = 0
+    if c_final is not None:
+        _chk(c_final)
+        assert c_final.dim() == 2 and c_final.shape[1] >= H and (c_final.shape[1] == 1 or c_final.stride(1) == 1)
+        cf_ld = c_final.stride(0) if c_final.shape[0] > 1 else c_final.shape[1]
+        if cf_row is not None:
+            _chk(cf_row, torch.int32)
+            assert cf_row.numel() >= n
+        else:
+            assert c_final.shape[0] >= n
+    else:
+        assert cf_row is None
+    call("vqa_lstm_occl_cell_fwd", ptr(xg_base), ptr(xg0), ptr(hg), ptr(h_var), ptr(c_var), st_ld, ptr(q_len), ptr(var_b),
+         ptr(var_t), s, ptr(c_final), cf_ld, ptr(cf_row), n, B, T, H, stream())
+
+
+def occl_words(h1, W2, b2, answers, logits, var_b, var_t, q_len, out, b0: int = 0, nb: Optional[int] = None):
+    """The tail of exact word occlusion (include/vqa_hip.h vqa_occl_words): out[b, t] = logits[b, a_b] - (W2[a_b] . h1[r] + b2[a_b])
+    for the variant rows r = (var_b[r], var_t[r]) (device int32 [n]) and +0.0 for t >= q_len[b], for the questions b0 .. b0 + nb
+    - 1 (default: all B) of out [B, T]: every element of those rows is written, no other row is touched.  h1 [n, hid], W2
+    [A, hid] and logits [B, A] row-major views with unit column stride, b2 [A], answers device int32 [B] (a column outside
+    [0, A): a row of zeros), q_len int64 [B]."""
+    B, T = out.shape
+    n, hid = h1.shape
+    A = W2.shape[0]
+    nb = B - b0 if nb is None else nb
+    _chk(h1), _chk(W2), _chk(b2), _chk(logits), _chk(answers, torch.int32), _chk(q_len, torch.int64), _chk(out)
+    _chk(var_b, torch.int32), _chk(var_t, torch.int32)
+    assert out.is_contiguous() and W2.shape[1] == hid and b2.numel() == A and logits.shape == (B, A) and answers.numel() == B
+    assert q_len.numel() == B and var_b.numel() == n and var_t.numel() == n and 0 <= b0 and 0 <= nb and b0 + nb <= B
+    assert hid == 1 or (W2.stride(1) == 1 and h1.stride(1) == 1)
+    assert A == 1 or logits.stride(1) == 1
+    call("vqa_occl_words", ptr(h1), h1.stride(0) if n > 1 else hid, ptr(W2), W2.stride(0) if A > 1 else hid, ptr(b2), ptr(answers),
+         ptr(logits), logits.stride(0) if B > 1 else A, ptr(var_b), ptr(var_t), ptr(q_len), ptr(out), n, b0, nb, T, hid, A, stream())
+    return out
+
+
 def att_apply_gather_fwd(score, vn, img, out, out_ld):
     """att_apply_fwd where sample b weights the rows of image img[b] (device int32 [B]); vn [N, P, C], fp32 or
     float16."""

@@ -45,7 +45,8 @@ extern "C" {
  * vqa_att_attr_score_grouped_path, vqa_att_attr_score_grouped, vqa_att_attr_score_grouped_pairs, vqa_att_attr_score_grouped_f16,
  * vqa_att_attr_score_grouped_pairs_f16; declared behind those of the cached-feature paths they extend), and then the three of
  * gradient x input per question token (vqa_att_attr_dq_grouped, vqa_att_attr_dq_grouped_f16, vqa_embed_attr; declared behind
- * the attribution entry points), and then the one of occlusion maps (vqa_occl_logit; declared behind those). */
+ * the attribution entry points), and then the one of occlusion maps (vqa_occl_logit; declared behind those), and
+ * then the two of exact word occlusion (vqa_lstm_occl_cell_fwd, vqa_occl_words; declared behind vqa_occl_logit). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -529,6 +530,49 @@ int vqa_occl_logit(const float* base, const float* Z, const float* U, const int3
                    const float* score, const float* cnull, const float* W2, int64_t w2_ld, const float* b2,
                    const int32_t* answers, const float* logits, int64_t logits_ld, float* maps, int R, int B, int gh, int gw,
                    int hid, int G, int A, int window, vqa_stream_t stream);
+
+/* ---- exact word occlusion from cached features (inference, VqaNet.explain_words_occlusion; csrc/lstm_occl.hip, DESIGN.md
+ * 4.19) ----
+ * What the per-token gradient x input values estimate to first order, computed exactly: for question b, answer column a_b and
+ * every token slot t < q_len[b], how far logit[b][a_b] falls when the embedding output e[b][t][:] is the zero vector (eval
+ * mode, the image features held fixed, the length and every other token unchanged):
+ *   words[b][t] = logit[b][a_b] - logit_t[b][a_b]
+ * The LSTM input of that step is tanh(0) = 0, so its gate pre-activation is b_ih + b_hh + h W_hh^T.  A variant is a pair
+ * (b, t); zeroing slot t leaves the forward direction's state before t and the reverse direction's state after t as the base
+ * run left them, so a variant's chain starts from that saved state and runs the remaining steps only.
+ *   vqa_lstm_occl_cell_fwd: one step, time s, of n variant rows.  Row r is the variant (b, t) = (var_b[r], var_t[r]) (int32):
+ *       s >= q_len[b]:  h_var[r], c_var[r] are left as they are (vqa_lstm_cell_fwd's rule for a finished sample)
+ *       otherwise:      pre = (s == t ? xg0 : xg_base[s][b]) + hg[r]                  [4H], gate order i, f, g, o
+ *                       c = sigmoid(f) * c + sigmoid(i) * tanh(g);   h = sigmoid(o) * tanh(c)
+ *     with the device functions of vqa_lstm_cell_fwd's kernel, in place in h_var / c_var (row stride st_ld elements, the same
+ *     for both).  xg_base [T][B][4H] is the base run's x-projection with both biases (vqa_gemm with bias1 = b_ih, bias2 =
+ *     b_hh), hg [n][4H] = h_var . W_hh^T (vqa_gemm, before this call), q_len int64 [B].  xg0 [4H] is b_ih + b_hh in the
+ *     base product's own bits for a zero input row: the caller obtains it from THE SAME vqa_gemm call as xg_base (same
+ *     weight, biases and epilogue) on one all-zero input row -- the accumulator of a zero row is exactly +0 under every
+ *     plan, and the epilogue that adds the two biases is the one the base rows went through.
+ *     c_final (optional, leading dimension cf_ld): the new cell state is also written to row cf_row[r] of it (cf_row int32
+ *     [n], NULL: row r) on every active step, so after a chain's last step it holds the final cell state.
+ *     16-byte accesses when H % 4 == 0, st_ld % 4 == 0, cf_ld % 4 == 0 and xg_base, xg0, hg, h_var, c_var, c_final are
+ *     16-byte aligned; scalar otherwise, same bits.  No LDS, no atomics; a row's result depends on that row alone; a row
+ *     whose (b, t) is outside [0, B) x [0, T) is left alone.  n == 0 returns without a launch.  Null pointers, n < 0, B, T,
+ *     H < 1, s outside [0, T), st_ld < H, cf_ld < H with c_final, cf_row without c_final: VQA_ERR_INVALID before any HIP call.
+ *   vqa_occl_words: the tail.  h1 [n][hid] (leading dimension h1_ld) = relu(lin1(.)) of the n variant rows' classifier inputs:
+ *       words[b][t] = logits[b][a_b] - (W2[a_b][:] . h1[r][:] + b2[a_b])         for the variant rows r = (b, t)
+ *       words[b][t] = +0.0                                                       for t >= q_len[b]
+ *     for the questions b in [b0, b0 + nb); words [B][T].  EVERY element of those nb rows is written by this call, and no
+ *     other row is touched: a caller that walks the questions in chunks covers each row with exactly one call, and its
+ *     variant rows must list every (b, t), t < min(q_len[b], T), of the call's questions once.  A column a_b outside [0, A)
+ *     gives +0.0 for the whole row.  One wave per variant row; lane l adds the terms of the quads l + 64*i of hid in ascending
+ *     i and, inside a quad, k = 0..3, each term rounded before the add, then the wave butterfly (vqa_embed_attr's order): one
+ *     order whatever the grid.  16-byte loads when hid % 4 == 0, h1_ld % 4 == 0, w2_ld % 4 == 0 and h1, W2 are 16-byte
+ *     aligned, scalar otherwise (same bits).  No LDS, no atomics.  nb == 0 returns without a launch; n == 0 writes the zeros.
+ *     n > nb * T, a leading dimension below its row, T, hid, A < 1 or a null pointer: VQA_ERR_INVALID before any HIP call. */
+int vqa_lstm_occl_cell_fwd(const float* xg_base, const float* xg0, const float* hg, float* h_var, float* c_var, int64_t st_ld,
+                           const int64_t* q_len, const int32_t* var_b, const int32_t* var_t, int s, float* c_final, int64_t cf_ld,
+                           const int32_t* cf_row, int n, int B, int T, int H, vqa_stream_t stream);
+int vqa_occl_words(const float* h1, int64_t h1_ld, const float* W2, int64_t w2_ld, const float* b2, const int32_t* answers,
+                   const float* logits, int64_t logits_ld, const int32_t* var_b, const int32_t* var_t, const int64_t* q_len,
+                   float* words, int n, int b0, int nb, int T, int hid, int A, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
