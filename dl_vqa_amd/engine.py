@@ -532,64 +532,86 @@ class Engine:
         """B questions against the N encoded images of `feats` (vn, vprime): question b looks at image img[b]; order /
         offsets (device int32) group the questions by image.  Returns (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer: fp32 / fp32x3 only"
-        score, _qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        return self._answer_tail(P, feats, score, img, txt.combined)[:3]
+        run = self._answer_tail(P, feats, self._answer_front(P, feats, q, q_len, (order, offsets, img), bad_tokens))
+        return run.logits, run.probs, run.score
 
-    def _answer_front(self, P, feats, q, q_len, order, offsets, bad_tokens):
-        """What answer, explain and explain_words begin with.  Returns (score [B,G,Pn], q' [B,mid], _question_front's
-        namespace: txt.combined is the classifier-input buffer whose question half the encoder has written, and the
-        recurrence state, which explain_words goes back through, stays alive with it)."""
+    def _grouped_scores(self, P, feats, qp, order, offsets, B, qrow=None):
+        """Scores [B,G,Pn] straight from v' (one per image) and q' (one per question; a table read through qrow): x is never
+        written."""
         N, Pn, _ = feats.vn.shape
-        # ---- question encoder and q_lin, eval mode, on the current stream (there are no convolutions to hide them under)
+        return ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
+                                         P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode, qrow=qrow)
+
+    # The base run: what a front leaves and every tail reads, one record.  score [B,G,Pn]; combined, the classifier-input
+    # buffer [B,Dc]; qp, q' [B,mid] or the pairs' table [M,mid] read through qrow (None on the questions route); cached =
+    # (qf, qrow), the pairs' question half of the classifier input (None on the questions route, where the encoder has written
+    # it); order / offsets / img; txt, _question_front's namespace on the questions route (the recurrence state, which
+    # explain_words goes back through and explain_words_occlusion starts its chains from, stays alive with it).  _answer_tail
+    # adds logits, probs and h1.
+    def _answer_front(self, P, feats, q, q_len, index, bad_tokens):
+        """What answer and the explain calls about questions begin with: the question encoder and q_lin, eval mode, on the
+        current stream (there are no convolutions to hide them under), then the scores.  index = (order, offsets, img).
+        Returns the base run."""
+        order, offsets, img = index
         txt, _ = self._question_front(P, q, q_len, feats.vn.device, 0.0, 0, bad_tokens, side=False)
         qp = self._q_lin_fwd(P, txt.combined[:, self.GC:], 0.0, 0)[0]
-        # ---- attention: scores straight from v' (one per image) and q' (one per question); x is never written
-        score = ops.att_score_grouped_fwd(feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1),
-                                          P["attention.x_conv.bias"], order, offsets, N, q.shape[0], Pn, self.att_mode)
-        return score, qp, txt
+        score = self._grouped_scores(P, feats, qp, order, offsets, q.shape[0])
+        return SimpleNamespace(score=score, combined=txt.combined, qp=qp, qrow=None, cached=None, order=order, offsets=offsets,
+                               img=img, txt=txt)
 
-    def _answer_tail(self, P, feats, score, img, combined, cached=None):
-        """What answer, answer_pairs, explain and explain_pairs end with: softmax over positions + weighted sum of the image
-        img[b]'s features into combined[:, :GC], and the eval-mode classifier.  cached = (qf, qrow): answer_pairs' question
-        half of the classifier input (models/model.py:64), one cached row per pair; answer's encoder has written it.
-        Returns (logits, probs, score, h1): h1 = relu(lin1(combined)), which only the explain calls read."""
-        probs = ops.att_apply_gather_fwd(score, feats.vn, img, combined, self.Dc)
-        if cached is not None:
-            ops.gather_rows(*cached, combined[:, self.GC:], self.Q)
-        logits, _c_in, h1, _h1d = self._classifier_fwd(P, combined, 0.0, 0, None)
-        return logits, probs, score, h1
+    def _pairs_front(self, P, feats, qfeats, index):
+        """What answer_pairs and the explain calls about pairs begin with: the scores from the two caches.  index = (order,
+        offsets, img, qrow).  Returns the base run, with an empty classifier-input buffer."""
+        order, offsets, img, qrow = index
+        B = img.numel()
+        score = self._grouped_scores(P, feats, qfeats.qprime, order, offsets, B, qrow)
+        combined = torch.empty(B, self.Dc, dtype=torch.float32, device=feats.vn.device)
+        return SimpleNamespace(score=score, combined=combined, qp=qfeats.qprime, qrow=qrow, cached=(qfeats.qf, qrow), order=order,
+                               offsets=offsets, img=img, txt=None)
+
+    def _asked_front(self, P, feats, ask):
+        """The front of an explain call: _answer_front for an ask that holds questions (q, q_len), _pairs_front for one that
+        holds cached questions (qfeats).  ask: what VqaNet._ask_upload leaves -- the source, on_device = (order, offsets, img[,
+        qrow]) (device int32), answers (device int32 [B], None: each question's arg-max) and bad_tokens."""
+        if ask.qfeats is None:
+            return self._answer_front(P, feats, ask.q, ask.q_len, ask.on_device, ask.bad_tokens)
+        return self._pairs_front(P, feats, ask.qfeats, ask.on_device)
+
+    def _answer_tail(self, P, feats, run):
+        """What every base run ends with: softmax over positions + weighted sum of the image img[b]'s features into
+        combined[:, :GC], the pairs' cached question half (models/model.py:64) where there is one, and the eval-mode
+        classifier.  Adds logits, probs and h1 = relu(lin1(combined)), which only the explain calls read; returns run."""
+        run.probs = ops.att_apply_gather_fwd(run.score, feats.vn, run.img, run.combined, self.Dc)
+        if run.cached is not None:
+            ops.gather_rows(*run.cached, run.combined[:, self.GC:], self.Q)
+        run.logits, _c_in, run.h1, _h1d = self._classifier_fwd(P, run.combined, 0.0, 0, None)
+        return run
+
+    @staticmethod
+    def _picked(logits, answers):
+        """The answer column each question is explained at: `answers`, or (None) topk_answers' arg-max, on the device."""
+        return ops.softmax_topk(logits, 1)[0].view(-1) if answers is None else answers
 
     # ------------------------------------------------------------------ gradient x input maps from cached features
     # explain / explain_pairs are answer / answer_pairs with the tail kept: from (probs, h1, logits) the gradient of ONE logit
     # per question is carried back to the classifier input (two small products, no parameter gradient), and two kernels turn
     # it into R[b, p] = sum_c vn * d logit / d vn (include/vqa_hip.h) without forming the gradient tensor.
     @_device_current("feats", _cache_device)
-    def explain(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
-                answers: Optional[Tensor] = None, bad_tokens: Optional[Tensor] = None):
-        """answer's arguments plus answers (device int32 [B], None: each question's arg-max).  Returns (maps [B,Pn],
+    def explain(self, P: Dict[str, Tensor], feats, ask):
+        """answer's or answer_pairs' arguments plus answers, as the ask holds them (_asked_front).  Returns (maps [B,Pn],
         answers int32 [B], logits [B,A])."""
         assert not self.bf16, "explain: fp32 / fp32x3 only"
-        score, qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        return self._explain_tail(P, feats, score, img, txt.combined, None, qp, None, order, offsets, answers)
+        return self._explain_tail(P, feats, self._asked_front(P, feats, ask), ask.answers)
 
-    @_device_current("feats", _cache_device)
-    def explain_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor, qrow: Tensor,
-                      answers: Optional[Tensor] = None):
-        """answer_pairs' arguments plus answers, as explain."""
-        assert not self.bf16, "explain_pairs: fp32 / fp32x3 only"
-        score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
-        return self._explain_tail(P, feats, score, img, combined, (qfeats.qf, qrow), qfeats.qprime, qrow, order, offsets, answers)
-
-    def _explain_tail(self, P, feats, score, img, combined, cached, qp, qrow, order, offsets, answers, tail=None):
-        """What explain, explain_pairs and explain_words end the image side with: _answer_tail, then the gradient of
-        logit[b, answers[b]] back to the image half of the classifier input, and the two attribution kernels.  qp: q'
-        [B,mid], or explain_pairs' table read through qrow.  Returns (maps [B,Pn], answers int32 [B], logits [B,A]).
-        tail: a dict that receives dh = d logit / d h1 [B,hid] and dscore [B,G,Pn], which explain_words carries on from."""
-        logits, probs, score, h1 = self._answer_tail(P, feats, score, img, combined, cached)
+    def _explain_tail(self, P, feats, run, answers, tail=None):
+        """What explain and explain_words end the image side with: _answer_tail, then the gradient of logit[b, answers[b]]
+        back to the image half of the classifier input, and the two attribution kernels.  Returns (maps [B,Pn], answers
+        int32 [B], logits [B,A]).  tail: a dict that receives dh = d logit / d h1 [B,hid] and dscore [B,G,Pn], which
+        explain_words carries on from."""
+        logits, probs, h1, img = self._answer_tail(P, feats, run).logits, run.probs, run.h1, run.img
         B, hid, GC, dev = img.numel(), self.hid, self.GC, feats.vn.device
         N, Pn, _ = feats.vn.shape
-        if answers is None:                                # topk_answers' arg-max, on the device
-            answers = ops.softmax_topk(logits, 1)[0].view(B)
+        answers = self._picked(logits, answers)
         # d logit[b, a_b] / d h1 = W2[a_b, :] where h1 > 0 (a column outside [0, A): a zero row, hence a zero map)
         dh = torch.empty(B, hid, dtype=torch.float32, device=dev)
         ops.gather_rows(P["classifier.lin2.weight"], answers, dh)
@@ -598,8 +620,8 @@ class Engine:
         dcomb = torch.empty(B, GC, dtype=torch.float32, device=dev)
         ops.gemm(dh, P["classifier.lin1.weight"], dcomb, B, GC, hid, transB=False, lda=hid, ldb=self.Dc)
         dscore, r1 = ops.att_attr_apply_gather(dcomb, GC, probs, feats.vn, img)
-        maps = ops.att_attr_score_grouped(r1, dscore, feats.vprime, qp, P["attention.x_conv.weight"].view(self.G, -1), order,
-                                          offsets, N, B, Pn, self.att_mode, qrow=qrow)
+        maps = ops.att_attr_score_grouped(r1, dscore, feats.vprime, run.qp, P["attention.x_conv.weight"].view(self.G, -1),
+                                          run.order, run.offsets, N, B, Pn, self.att_mode, qrow=run.qrow)
         if tail is not None:
             tail.update(dh=dh, dscore=dscore)
         return maps, answers, logits
@@ -612,46 +634,27 @@ class Engine:
     U_BYTES = 256 << 20             # workspace cap of U [images, Pn, G, hid]: more asked images are walked in chunks
 
     @_device_current("feats", _cache_device)
-    def explain_occlusion(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
-                          rows: Tensor, slot: Tensor, answers: Optional[Tensor] = None, window: int = 1,
-                          bad_tokens: Optional[Tensor] = None, u_bytes: Optional[int] = None):
-        """answer's arguments plus rows [n_u] / slot [B] (device int32, model.compact_image_index of the image index: the
-        distinct asked images and each question's place among them), answers (device int32 [B], None: each question's arg-max)
-        and window.  Returns (maps [B,Pn], answers int32 [B], logits [B,A])."""
+    def explain_occlusion(self, P: Dict[str, Tensor], feats, ask, rows: Tensor, slot: Tensor, window: int = 1,
+                          u_bytes: Optional[int] = None):
+        """explain's arguments plus rows [n_u] / slot [B] (device int32, model.compact_image_index of the image index: the
+        distinct asked images and each question's place among them) and window.  Returns (maps [B,Pn], answers int32 [B],
+        logits [B,A]).  Behind the base run: the per-question operands of the closed form (cnull, base, Z), then U = W1_g . vn
+        for the distinct asked images in chunks that fit the workspace cap, each followed by the kernel for the questions of
+        its images."""
         assert not self.bf16, "explain_occlusion: fp32 / fp32x3 only"
-        score, qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        return self._occlusion_tail(P, feats, score, img, txt.combined, None, qp, None, rows, slot, answers, window, u_bytes)
-
-    @_device_current("feats", _cache_device)
-    def explain_occlusion_pairs(self, P: Dict[str, Tensor], feats, qfeats, order: Tensor, offsets: Tensor, img: Tensor,
-                                qrow: Tensor, rows: Tensor, slot: Tensor, answers: Optional[Tensor] = None, window: int = 1,
-                                u_bytes: Optional[int] = None):
-        """answer_pairs' arguments plus rows, slot, answers and window, as explain_occlusion."""
-        assert not self.bf16, "explain_occlusion_pairs: fp32 / fp32x3 only"
-        score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
-        return self._occlusion_tail(P, feats, score, img, combined, (qfeats.qf, qrow), qfeats.qprime, qrow, rows, slot, answers,
-                                    window, u_bytes)
-
-    def _occlusion_tail(self, P, feats, score, img, combined, cached, qp, qrow, rows, slot, answers, window, u_bytes):
-        """What explain_occlusion and explain_occlusion_pairs end with: _answer_tail, the per-question operands of the closed
-        form (cnull, base, Z), then U = W1_g . vn for the distinct asked images in chunks that fit the workspace cap, each
-        followed by the kernel for the questions of its images.  qp: q' [B,mid], or the pairs' table read through qrow."""
-        logits, probs, score, _h1 = self._answer_tail(P, feats, score, img, combined, cached)
-        B, hid, G, C, GC, Dc, dev = img.numel(), self.hid, self.G, self.C, self.GC, self.Dc, feats.vn.device
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        logits, probs, score, combined = run.logits, run.probs, run.score, run.combined
+        B, hid, G, C, GC, Dc, dev = run.img.numel(), self.hid, self.G, self.C, self.GC, self.Dc, feats.vn.device
         Pn = feats.vn.shape[1]
         gh, gw = feats.grid
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        if answers is None:                                # topk_answers' arg-max, on the device
-            answers = ops.softmax_topk(logits, 1)[0].view(B)
+        answers = self._picked(logits, ask.answers)
         # cnull: the score kernel's own bits for a position whose v' is 0 -- one all-zero position, every question in one group
         wx, bx = P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"]
         zero_v = torch.zeros(1, self.mid, dtype=torch.float32, device=dev)
         order1 = torch.arange(B, dtype=torch.int32, device=dev)
         offsets1 = torch.arange(0, B + 1, B, dtype=torch.int32, device=dev)                     # [0, B]
-        if qrow is None:
-            cnull = ops.att_score_grouped_fwd(zero_v, qp, wx, bx, order1, offsets1, 1, B, 1, self.att_mode)
-        else:
-            cnull = ops.att_score_grouped_pairs_fwd(zero_v, qp, qrow, wx, bx, order1, offsets1, 1, B, 1, self.att_mode)
+        cnull = ops.att_score_grouped_fwd(zero_v, run.qp, wx, bx, order1, offsets1, 1, B, 1, self.att_mode, qrow=run.qrow)
         # base = b1 + W1[:, GC:] . qf and Z_g = W1_g . out_g: the two halves of lin1 apart, plain fp32 in every compute mode
         w1 = P["classifier.lin1.weight"]
         base = ops.gemm(combined[:, GC:], w1[:, GC:], new(B, hid), B, hid, self.Q, lda=Dc, ldb=Dc, bias1=P["classifier.lin1.bias"])
@@ -679,17 +682,15 @@ class Engine:
     # embedding stage, where one kernel (csrc/elementwise.hip) turns it into words[b, t] = sum_e e * d logit / d e.  Data
     # gradients only: no dW_hh, dW_ih, bias or embedding gradient is formed, nothing is written to a gradient buffer.
     @_device_current("feats", _cache_device)
-    def explain_words(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor, img: Tensor,
-                      answers: Optional[Tensor] = None, bad_tokens: Optional[Tensor] = None, stages: Optional[dict] = None):
-        """explain's arguments.  Returns (words [B,T], maps [B,Pn], answers int32 [B], logits [B,A]); maps, answers and
-        logits are explain's.  stages (a dict) receives dq_att [B,mid] = d logit / d q' through the scores (zeros for '|'),
-        attention_path (the launches made for that path: none for '|'), dqf [B,Q] = d logit / d (question features) and dx
-        [T,B,E] = d logit / d tanh(e), summed over the directions."""
+    def explain_words(self, P: Dict[str, Tensor], feats, ask, stages: Optional[dict] = None):
+        """explain's arguments, for an ask that holds questions.  Returns (words [B,T], maps [B,Pn], answers int32 [B], logits
+        [B,A]); maps, answers and logits are explain's.  stages (a dict) receives dq_att [B,mid] = d logit / d q' through the
+        scores (zeros for '|'), attention_path (the launches made for that path: none for '|'), dqf [B,Q] = d logit / d
+        (question features) and dx [T,B,E] = d logit / d tanh(e), summed over the directions."""
         assert not self.bf16, "explain_words: fp32 / fp32x3 only"
-        score, qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        tail = {}
-        maps, answers, logits = self._explain_tail(P, feats, score, img, txt.combined, None, qp, None, order, offsets, answers,
-                                                   tail)
+        run, tail = self._asked_front(P, feats, ask), {}
+        maps, answers, logits = self._explain_tail(P, feats, run, ask.answers, tail)
+        txt, qp, order, offsets = run.txt, run.qp, run.order, run.offsets
         B, T = txt.q.shape
         N, Pn, _ = feats.vn.shape
         E, H, Q, GC, mid, hid, dev = self.E, self.H, self.Q, self.GC, self.mid, self.hid, feats.vn.device
@@ -735,26 +736,22 @@ class Engine:
         return max(1, self.WORDS_BYTES // per_row)
 
     @_device_current("feats", _cache_device)
-    def explain_words_occlusion(self, P: Dict[str, Tensor], feats, q: Tensor, q_len: Tensor, order: Tensor, offsets: Tensor,
-                                img: Tensor, chunks, answers: Optional[Tensor] = None, bad_tokens: Optional[Tensor] = None):
-        """explain's arguments plus chunks: model.word_occlusion_table of every chunk of questions, its index tensors on the
-        device as int32 and with order / offsets / img, the chunk's variant rows (forward order) grouped by their question's image.
-        Returns (words [B,T], answers int32 [B], logits [B,A]); answers and logits are explain's."""
+    def explain_words_occlusion(self, P: Dict[str, Tensor], feats, ask, chunks):
+        """explain's arguments, for an ask that holds questions, plus chunks: model.word_occlusion_table of every chunk of
+        questions, its index tensors on the device as int32 and with order / offsets / img, the chunk's variant rows (forward
+        order) grouped by their question's image.  Returns (words [B,T], answers int32 [B], logits [B,A]); answers and logits
+        are explain's."""
         assert not self.bf16, "explain_words_occlusion: fp32 / fp32x3 only"
-        score, _qp, txt = self._answer_front(P, feats, q, q_len, order, offsets, bad_tokens)
-        logits, _probs, _score, _h1 = self._answer_tail(P, feats, score, img, txt.combined)
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        txt, logits, answers = run.txt, run.logits, self._picked(run.logits, ask.answers)
         B, T = txt.q.shape
-        N, Pn, _ = feats.vn.shape
         E, H, GC, Dc, hid, dev = self.E, self.H, self.GC, self.Dc, self.hid, feats.vn.device
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        if answers is None:                                # topk_answers' arg-max, on the device
-            answers = ops.softmax_topk(logits, 1)[0].view(B)
         # xg0 = b_ih + b_hh in the base product's own bits: the question encoder's xg product on one all-zero input row
         zero_x = torch.zeros(1, E, dtype=torch.float32, device=dev)
         xg0 = [_gemm(zero_x, P["text.lstm.weight_ih_l0" + _SFX[d]], new(1, 4 * H), 1, 4 * H, E,
                      bias1=P["text.lstm.bias_ih_l0" + _SFX[d]], bias2=P["text.lstm.bias_hh_l0" + _SFX[d]], tag=10)
                for d in range(self.ndir)]
-        wx, bx = P["attention.x_conv.weight"].view(self.G, -1), P["attention.x_conv.bias"]
         words = new(B, T)
         for tab in chunks:
             V = tab.V
@@ -781,7 +778,7 @@ class Engine:
                                            c_final=c_final, cf_row=tab.rev_row if rev else None)
             # the forward's own stages on V rows: q_lin, the grouped scores, the weighted sum, the classifier's first layer
             qp = self._q_lin_fwd(P, combined[:, GC:], 0.0, 0)[0]
-            score_v = ops.att_score_grouped_fwd(feats.vprime, qp, wx, bx, tab.order, tab.offsets, N, V, Pn, self.att_mode)
+            score_v = self._grouped_scores(P, feats, qp, tab.order, tab.offsets, V)
             ops.att_apply_gather_fwd(score_v, feats.vn, tab.img, combined, Dc)
             h1 = _gemm(combined, P["classifier.lin1.weight"], new(V, hid), V, hid, Dc, bias1=P["classifier.lin1.bias"], relu=True,
                        tag=30)
@@ -807,17 +804,8 @@ class Engine:
         looks at image img[b] with question qrow[b]; order / offsets (device int32) group the pairs by image.  Returns
         (logits [B,A], probs [B,G,Pn], score [B,G,Pn])."""
         assert not self.bf16, "answer_pairs: fp32 / fp32x3 only"
-        score, combined = self._pairs_front(P, feats, qfeats, order, offsets, img, qrow)
-        return self._answer_tail(P, feats, score, img, combined, cached=(qfeats.qf, qrow))[:3]
-
-    def _pairs_front(self, P, feats, qfeats, order, offsets, img, qrow):
-        """What answer_pairs and explain_pairs begin with.  Returns (score [B,G,Pn], an empty classifier-input buffer)."""
-        B = img.numel()
-        N, Pn, _ = feats.vn.shape
-        # ---- attention: scores from v' (one per image) and q' (one per distinct question)
-        score = ops.att_score_grouped_pairs_fwd(feats.vprime, qfeats.qprime, qrow, P["attention.x_conv.weight"].view(self.G, -1),
-                                                P["attention.x_conv.bias"], order, offsets, N, B, Pn, self.att_mode)
-        return score, torch.empty(B, self.Dc, dtype=torch.float32, device=feats.vn.device)
+        run = self._answer_tail(P, feats, self._pairs_front(P, feats, qfeats, (order, offsets, img, qrow)))
+        return run.logits, run.probs, run.score
 
     # ------------------------------------------------------------------ training through grouped image features
     # fp32 / fp32x3.  Question b looks at image img[b]; order / offsets group the questions by image.  The question encoder,

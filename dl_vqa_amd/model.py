@@ -456,6 +456,12 @@ def _check_question_ranks(what: str, q, q_len, rows: str = "B", v=None):
         raise ValueError(f"{what}: {lead}q [{rows},T] and q_len [{rows}] expected, got {got}")
 
 
+def _check_index_count(what: str, n_index: int, n: int, of: str = "questions"):
+    """ValueError unless an index of n_index entries goes with n questions (or n entries of the other index)."""
+    if n_index != n:
+        raise ValueError(f"{what}: {n_index} image_index entries for {n} {of}")
+
+
 def _need_cuda(what: str, on_device: bool):
     if not on_device:
         raise RuntimeError(f"dl_vqa_amd.VqaNet.{what} needs CUDA (HIP) tensors; there is no CPU fallback")
@@ -813,8 +819,7 @@ class VqaNet(nn.Module):
         B, N = q.shape[0], v.shape[0]
         img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
         order, offsets = _group(img, N)
-        if order.numel() != B:
-            raise ValueError(f"VqaNet.forward_shared: {order.numel()} image_index entries for {B} questions")
+        _check_index_count("VqaNet.forward_shared", order.numel(), B)
         if N == 0 or B == 0:
             raise ValueError(f"VqaNet.forward_shared: an empty batch ({N} images, {B} questions)")
         self._ensure_flat()
@@ -888,8 +893,7 @@ class VqaNet(nn.Module):
         B, N = q.shape[0], feats.N
         img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
         rows, slot, order, offsets = compact_image_index(img, N)
-        if order.numel() != B:
-            raise ValueError(f"VqaNet.forward_features: {order.numel()} image_index entries for {B} questions")
+        _check_index_count("VqaNet.forward_features", order.numel(), B)
         if N == 0 or B == 0:
             raise ValueError(f"VqaNet.forward_features: an empty batch ({N} feature rows, {B} questions)")
         self._validate_tokens(q)
@@ -915,6 +919,11 @@ class VqaNet(nn.Module):
             raise RuntimeError(f"VqaNet.{what} is an inference call and the model is in training mode: the image, attention "
                                "and classifier dropout sites (models/model.py:84,185,186,194) draw a new mask per forward, so "
                                "image features cached across questions would be meaningless; call model.eval() first")
+
+    @staticmethod
+    def _need_image_features(what: str, feats):
+        if not isinstance(feats, ImageFeatures):
+            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
 
     @staticmethod
     def _need_vprime(what: str, feats):
@@ -978,8 +987,7 @@ class VqaNet(nn.Module):
         """What answer() and explain() check after _check_inference, in answer()'s order.  Returns (q, q_len as tensors, the
         host index tensors (order, offsets, img) of the questions grouped by image)."""
         self._ensure_flat()
-        if not isinstance(feats, ImageFeatures):
-            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
+        self._need_image_features(what, feats)
         self._check_owned(what, feats, "image", "encode_images")
         self._need_vprime(what, feats)
         q = torch.as_tensor(q)
@@ -990,8 +998,7 @@ class VqaNet(nn.Module):
         B, N = q.shape[0], feats.N
         img = _host_image_index(image_index, N)                      # the one copy to the host, reused below
         order, offsets = _group(img, N)
-        if order.numel() != B:
-            raise ValueError(f"VqaNet.{what}: {order.numel()} image_index entries for {B} questions")
+        _check_index_count(f"VqaNet.{what}", order.numel(), B)
         return q, q_len, (order, offsets, img)
 
     @torch.no_grad()
@@ -1061,14 +1068,12 @@ class VqaNet(nn.Module):
     def _pairs_args(self, what: str, feats, qfeats, image_index, question_index):
         """What answer_pairs() and explain_pairs() check after _check_inference, in answer_pairs()'s order.  Returns the host
         index tensors (order, offsets, img, qidx) of the pairs grouped by image."""
-        if not isinstance(feats, ImageFeatures):
-            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
+        self._need_image_features(what, feats)
         if not isinstance(qfeats, QuestionFeatures):
             raise TypeError(f"VqaNet.{what}: qfeats must come from VqaNet.encode_questions")
         N, M = feats.N, qfeats.M
         n_img, n_q = torch.as_tensor(image_index).numel(), torch.as_tensor(question_index).numel()
-        if n_img != n_q:
-            raise ValueError(f"VqaNet.{what}: {n_img} image_index entries for {n_q} question_index entries")
+        _check_index_count(f"VqaNet.{what}", n_img, n_q, "question_index entries")
         img = _host_image_index(image_index, N)                      # each index: one copy to the host, reused below
         order, offsets = _group(img, N)
         qidx = _host_image_index(question_index, M, "question_index", "questions")
@@ -1110,15 +1115,63 @@ class VqaNet(nn.Module):
             raise IndexError(f"VqaNet.{what}: answers entry {bad} out of range [0, {A})")
         return cols.to(torch.int32)
 
-    def _attribution(self, feats, out, B: int) -> Attribution:
-        """Attribution of the engine's (maps [B,P], answers int32 [B], logits), or the empty one for B == 0."""
-        eng, dev = self._engine, feats.vn.device
-        if out is None:
-            return Attribution(torch.empty(0, *feats.grid, dtype=torch.float32, device=dev),
-                               torch.empty(0, dtype=torch.int64, device=dev),
-                               torch.empty(0, eng.A, dtype=torch.float32, device=dev))
+    # The front door of the explain family.  Every call asks (_ask_questions / _ask_pairs: all the argument checks, on the
+    # host), returns _no_result for an empty batch, uploads (_ask_upload: the index, host answers and the call's own host
+    # tensors in ONE copy), runs its engine schedule (_ask_run) and wraps what comes back.
+    def _ask_questions(self, what: str, feats, q, q_len, image_index, answers, own=None, host_first: bool = False):
+        """What an explain call about (q, q_len, image_index) checks, in order: the inference check, the call's `own` check
+        (explain_occlusion's window), the type of feats, the `answers` columns, then _answer_args.  host_first (explain_words,
+        explain_words_occlusion): what the host alone can judge -- a bank without v', the index count -- comes before
+        `answers`, in _answer_args' words.  Returns the ask: B, q / q_len as tensors, the host index tensors, the columns."""
+        self._check_inference(what)
+        if own is not None:
+            own()
+        self._need_image_features(what, feats)
+        if host_first:
+            self._need_vprime(what, feats)
+            _check_index_count(f"VqaNet.{what}", torch.as_tensor(image_index).numel(), len(q))
+        cols = self._answer_columns(what, answers, len(q))
+        q, q_len, index = self._answer_args(what, feats, q, q_len, image_index)
+        return SimpleNamespace(B=q.shape[0], q=q, q_len=q_len, qfeats=None, index=index, cols=cols)
+
+    def _ask_pairs(self, what: str, feats, qfeats, image_index, question_index, answers, own=None):
+        """_ask_questions for (image, question) pairs from the two caches: the inference check, `own`, the `answers` columns,
+        then _pairs_args.  The ask holds qfeats in place of q / q_len, and the host index has the question rows behind img."""
+        self._check_inference(what)
+        if own is not None:
+            own()
+        cols = self._answer_columns(what, answers, torch.as_tensor(image_index).numel())
+        index = self._pairs_args(what, feats, qfeats, image_index, question_index)
+        return SimpleNamespace(B=index[-1].numel(), q=None, q_len=None, qfeats=qfeats, index=index, cols=cols)
+
+    def _ask_upload(self, feats, ask, extra=()):
+        """The ask on the device of feats, as the engine reads it: on_device, the index tensors, and answers as int32, and
+        bad_tokens.  `extra`: the call's own host index tensors, which travel in the same single copy; their device views are
+        returned in the same order."""
+        n = len(ask.index)
+        index, ask.answers = _upload_with_columns(feats.vn.device, tuple(ask.index) + tuple(extra), ask.cols)
+        ask.on_device = index[:n]
+        ask.bad_tokens = self._token_counter(ask.q) if ask.q is not None else None
+        return index[n:]
+
+    def _ask_run(self, schedule, feats, ask, *args):
+        """The engine schedule on an uploaded ask, and the token count read back where question tokens were embedded."""
+        out = schedule(self._param_dict(), feats, ask, *args)
+        if ask.q is not None:
+            self._after_forward_tokens(ask.q)
+        return out
+
+    def _no_result(self, kind, feats, T: int = 0):
+        """What an explain call returns for B == 0: the result type `kind` with every field empty."""
+        shape = dict(words=(0, T), maps=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A))
+        return kind(*(torch.empty(shape[f], dtype=torch.int64 if f == "answers" else torch.float32, device=feats.vn.device)
+                      for f in kind._fields))
+
+    @staticmethod
+    def _maps_result(kind, feats, out):
+        """Attribution / Occlusion of the engine's (maps [B,P], answers int32 [B], logits)."""
         maps, cols, logits = out
-        return Attribution(maps.view(B, *feats.grid), cols.long(), logits)
+        return kind(maps.view(-1, *feats.grid), cols.long(), logits)
 
     @torch.no_grad()
     def explain(self, feats: ImageFeatures, q, q_len, image_index, answers=None) -> Attribution:
@@ -1146,18 +1199,13 @@ class VqaNet(nn.Module):
         what feats.to(torch.float32) gives); B == 0 returns empty tensors.  Rows come back in the caller's order and do not
         depend on how the batch is ordered or split.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad
         and the dropout seed stream are left alone."""
-        self._check_inference("explain")
-        if not isinstance(feats, ImageFeatures):
-            raise TypeError("VqaNet.explain: feats must come from VqaNet.encode_images")
-        cols = self._answer_columns("explain", answers, len(q))
-        q, q_len, index = self._answer_args("explain", feats, q, q_len, image_index)
-        B = q.shape[0]
-        if B == 0:
-            return self._attribution(feats, None, 0)
-        index, cols = _upload_with_columns(feats.vn.device, index, cols)
-        out = self._engine.explain(self._param_dict(), feats, q, q_len, *index, answers=cols, bad_tokens=self._token_counter(q))
-        self._after_forward_tokens(q)
-        return self._attribution(feats, out, B)
+        return self._explain(feats, self._ask_questions("explain", feats, q, q_len, image_index, answers))
+
+    def _explain(self, feats, ask) -> Attribution:
+        if ask.B == 0:
+            return self._no_result(Attribution, feats)
+        self._ask_upload(feats, ask)
+        return self._maps_result(Attribution, feats, self._ask_run(self._engine.explain, feats, ask))
 
     @torch.no_grad()
     def explain_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
@@ -1166,15 +1214,7 @@ class VqaNet(nn.Module):
         image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  maps, answers
         and the `answers` argument are explain()'s; logits are answer_pairs()'s for the same arguments, bit for bit; the index
         rules, ownership checks and errors are answer_pairs()'s, with the `answers` checks of explain() judged first."""
-        self._check_inference("explain_pairs")
-        cols = self._answer_columns("explain_pairs", answers, torch.as_tensor(image_index).numel())
-        index = self._pairs_args("explain_pairs", feats, qfeats, image_index, question_index)
-        B = index[-1].numel()
-        if B == 0:
-            return self._attribution(feats, None, 0)
-        index, cols = _upload_with_columns(feats.vn.device, index, cols)
-        out = self._engine.explain_pairs(self._param_dict(), feats, qfeats, *index, answers=cols)
-        return self._attribution(feats, out, B)
+        return self._explain(feats, self._ask_pairs("explain_pairs", feats, qfeats, image_index, question_index, answers))
 
     # ------------------------------------------------------------------ occlusion maps from cached features
     @torch.no_grad()
@@ -1211,20 +1251,17 @@ class VqaNet(nn.Module):
         alone.
 
         _u_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
-        self._check_inference("explain_occlusion")
-        window = _check_window("VqaNet.explain_occlusion", window)
-        if not isinstance(feats, ImageFeatures):
-            raise TypeError("VqaNet.explain_occlusion: feats must come from VqaNet.encode_images")
-        cols = self._answer_columns("explain_occlusion", answers, len(q))
-        q, q_len, index = self._answer_args("explain_occlusion", feats, q, q_len, image_index)
-        B = q.shape[0]
-        if B == 0:
-            return Occlusion(*self._attribution(feats, None, 0))
-        index, cols = _upload_with_columns(feats.vn.device, index + compact_image_index(index[-1], feats.N)[:2], cols)
-        out = self._engine.explain_occlusion(self._param_dict(), feats, q, q_len, *index, answers=cols, window=window,
-                                             bad_tokens=self._token_counter(q), u_bytes=_u_bytes)
-        self._after_forward_tokens(q)
-        return Occlusion(*self._attribution(feats, out, B))
+        ask = self._ask_questions("explain_occlusion", feats, q, q_len, image_index, answers,
+                                  own=lambda: _check_window("VqaNet.explain_occlusion", window))
+        return self._explain_occlusion(feats, ask, window, _u_bytes)
+
+    def _explain_occlusion(self, feats, ask, window, u_bytes) -> Occlusion:
+        if ask.B == 0:
+            return self._no_result(Occlusion, feats)
+        # the distinct asked images and each question's place among them
+        rows, slot = self._ask_upload(feats, ask, compact_image_index(ask.index[2], feats.N)[:2])
+        out = self._ask_run(self._engine.explain_occlusion, feats, ask, rows, slot, window, u_bytes)
+        return self._maps_result(Occlusion, feats, out)
 
     @torch.no_grad()
     def explain_occlusion_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
@@ -1234,18 +1271,9 @@ class VqaNet(nn.Module):
         answers, window and the `answers` argument are explain_occlusion()'s; logits are answer_pairs()'s for the same
         arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the window and
         `answers` checks judged first."""
-        self._check_inference("explain_occlusion_pairs")
-        window = _check_window("VqaNet.explain_occlusion_pairs", window)
-        cols = self._answer_columns("explain_occlusion_pairs", answers, torch.as_tensor(image_index).numel())
-        index = self._pairs_args("explain_occlusion_pairs", feats, qfeats, image_index, question_index)
-        B = index[-1].numel()
-        if B == 0:
-            return Occlusion(*self._attribution(feats, None, 0))
-        index, cols = _upload_with_columns(feats.vn.device, index + compact_image_index(index[2], feats.N)[:2], cols)
-        out = self._engine.explain_occlusion_pairs(self._param_dict(), feats, qfeats, *index, answers=cols, window=window,
-                                                   u_bytes=_u_bytes)
-        return Occlusion(*self._attribution(feats, out, B))
-
+        ask = self._ask_pairs("explain_occlusion_pairs", feats, qfeats, image_index, question_index, answers,
+                              own=lambda: _check_window("VqaNet.explain_occlusion_pairs", window))
+        return self._explain_occlusion(feats, ask, window, _u_bytes)
 
     # ------------------------------------------------------------------ gradient x input per question token
     @torch.no_grad()
@@ -1276,25 +1304,12 @@ class VqaNet(nn.Module):
         explained without encoding them again -- which is this call.
 
         _stages (tests and tools): a dict that receives the engine's intermediate gradients (Engine.explain_words)."""
-        self._check_inference("explain_words")
-        if not isinstance(feats, ImageFeatures):
-            raise TypeError("VqaNet.explain_words: feats must come from VqaNet.encode_images")
-        # what the host alone can judge comes first, in words _answer_args would use: a bank without v', the index count
-        self._need_vprime("explain_words", feats)
-        n_idx = torch.as_tensor(image_index).numel()
-        if n_idx != len(q):
-            raise ValueError(f"VqaNet.explain_words: {n_idx} image_index entries for {len(q)} questions")
-        cols = self._answer_columns("explain_words", answers, len(q))
-        q, q_len, index = self._answer_args("explain_words", feats, q, q_len, image_index)
-        B, T = q.shape
-        dev = feats.vn.device
-        if B == 0:
-            return WordAttribution(torch.empty(0, T, dtype=torch.float32, device=dev), *self._attribution(feats, None, 0))
-        index, cols = _upload_with_columns(dev, index, cols)
-        words, *out = self._engine.explain_words(self._param_dict(), feats, q, q_len, *index, answers=cols,
-                                                 bad_tokens=self._token_counter(q), stages=_stages)
-        self._after_forward_tokens(q)
-        return WordAttribution(words, *self._attribution(feats, out, B))
+        ask = self._ask_questions("explain_words", feats, q, q_len, image_index, answers, host_first=True)
+        if ask.B == 0:
+            return self._no_result(WordAttribution, feats, ask.q.shape[1])
+        self._ask_upload(feats, ask)
+        words, maps, cols, logits = self._ask_run(self._engine.explain_words, feats, ask, _stages)
+        return WordAttribution(words, maps.view(-1, *feats.grid), cols.long(), logits)
 
     # ------------------------------------------------------------------ exact word occlusion from cached features
     _WORD_TABLE_FIELDS = ("fwd_b", "fwd_t", "fwd_seed", "rev_b", "rev_t", "rev_seed", "rev_row", "order", "offsets", "img")
@@ -1340,38 +1355,23 @@ class VqaNet(nn.Module):
         per-step states the variant chains start from.
 
         _variant_rows (tests and tools): caps the variants per chunk, to force several chunks at small sizes."""
-        what = "explain_words_occlusion"
-        self._check_inference(what)
-        if not isinstance(feats, ImageFeatures):
-            raise TypeError(f"VqaNet.{what}: feats must come from VqaNet.encode_images")
-        # what the host alone can judge comes first, as in explain_words
-        self._need_vprime(what, feats)
-        n_idx = torch.as_tensor(image_index).numel()
-        if n_idx != len(q):
-            raise ValueError(f"VqaNet.{what}: {n_idx} image_index entries for {len(q)} questions")
-        cols = self._answer_columns(what, answers, len(q))
-        q, q_len, index = self._answer_args(what, feats, q, q_len, image_index)
-        B, T = q.shape
-        dev, eng = feats.vn.device, self._engine
-        if B == 0:
-            return WordOcclusion(torch.empty(0, T, dtype=torch.float32, device=dev), *self._attribution(feats, None, 0)[1:])
-        lengths = q_len.detach().to(device="cpu", dtype=torch.int64).reshape(-1)      # the one copy to the host: synchronises
-        cap = eng.word_occlusion_rows(feats.vn.shape[1])
+        ask = self._ask_questions("explain_words_occlusion", feats, q, q_len, image_index, answers, host_first=True)
+        T = ask.q.shape[1]
+        if ask.B == 0:
+            return self._no_result(WordOcclusion, feats, T)
+        lengths = ask.q_len.detach().to(device="cpu", dtype=torch.int64).reshape(-1)  # the one copy to the host: synchronises
+        cap = self._engine.word_occlusion_rows(feats.vn.shape[1])
         if _variant_rows is not None:
             cap = max(1, min(cap, int(_variant_rows)))
-        img = index[-1]
-        chunks, parts = [], []
+        img, fields = ask.index[2], self._WORD_TABLE_FIELDS
+        chunks = []
         for b0, b1 in word_occlusion_chunks(lengths.tolist(), T, cap):
             tab = word_occlusion_table(lengths, T, b0, b1)
             tab.img = img[tab.fwd_b.long()]
             tab.order, tab.offsets = _group(tab.img, feats.N)
             chunks.append(tab)
-            parts += [getattr(tab, k) for k in self._WORD_TABLE_FIELDS]
-        index, cols = _upload_with_columns(dev, tuple(index) + tuple(parts), cols)
+        on_device = self._ask_upload(feats, ask, [getattr(tab, k) for tab in chunks for k in fields])
         for i, tab in enumerate(chunks):                                                # the tables on the device: the same copy
-            for j, k in enumerate(self._WORD_TABLE_FIELDS):
-                setattr(tab, k, index[3 + i * len(self._WORD_TABLE_FIELDS) + j])
-        words, picked, logits = eng.explain_words_occlusion(self._param_dict(), feats, q, q_len, *index[:3], chunks, answers=cols,
-                                                            bad_tokens=self._token_counter(q))
-        self._after_forward_tokens(q)
+            vars(tab).update(zip(fields, on_device[i * len(fields):]))
+        words, picked, logits = self._ask_run(self._engine.explain_words_occlusion, feats, ask, chunks)
         return WordOcclusion(words, picked.long(), logits)

@@ -550,27 +550,31 @@ def _grouped_score_head(vprime, qp, wx, order, offsets, N: int, B: int, P: int, 
     return G, xld, mid, torch.empty(B, G, P, dtype=torch.float32, device=vprime.device)
 
 
-def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
+def att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N: int, B: int, P: int, mode: int, qrow=None) -> torch.Tensor:
     """Scores [B, G, P] of B questions against N images from ONE v' [N*P, mid] per image: order / offsets (device int32,
     model.group_by_image) list the questions of image n as order[offsets[n]:offsets[n+1]].  mode 0 '+', 1 '*', 2 '|'
-    (wx [G, 2*mid]).  vprime is fp32 or float16 (a float16 cache: the same scores as from vprime.float(), bit for bit)."""
+    (wx [G, 2*mid]).  vprime is fp32 or float16 (a float16 cache: the same scores as from vprime.float(), bit for bit).
+    qrow (device int32 [B]): the pairs form over a table qp [M, mid] of distinct questions -- pair b reads the row
+    qp[qrow[b]] --, bit-identical to the plain form on qp[qrow]."""
     _chk(qp)
-    G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, B)
-    call("vqa_att_score_grouped_fwd" + _cache_suffix(vprime), ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
-         N, B, P, mid, G, mode, stream())
+    sfx = _cache_suffix(vprime)
+    if qrow is None:
+        G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, B)
+        call("vqa_att_score_grouped_fwd" + sfx, ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets), ptr(score),
+             N, B, P, mid, G, mode, stream())
+    else:
+        M = qp.shape[0]
+        _chk(qrow, torch.int32)
+        assert qrow.numel() == B
+        G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, M)
+        call("vqa_att_score_grouped_pairs_fwd" + sfx, ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(order),
+             ptr(offsets), ptr(score), N, B, M, P, mid, G, mode, stream())
     return score
 
 
 def att_score_grouped_pairs_fwd(vprime, qp, qrow, wx, bx, order, offsets, N: int, B: int, P: int, mode: int) -> torch.Tensor:
-    """att_score_grouped_fwd for B (image, question) pairs over a table qp [M, mid] of distinct questions: pair b reads the
-    row qp[qrow[b]] (qrow device int32 [B]).  Bit-identical to att_score_grouped_fwd(vprime, qp[qrow], ...)."""
-    M = qp.shape[0]
-    _chk(qrow, torch.int32), _chk(qp)
-    assert qrow.numel() == B
-    G, xld, mid, score = _grouped_score_head(vprime, qp, wx, order, offsets, N, B, P, mode, M)
-    call("vqa_att_score_grouped_pairs_fwd" + _cache_suffix(vprime), ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(order), ptr(offsets),
-         ptr(score), N, B, M, P, mid, G, mode, stream())
-    return score
+    """att_score_grouped_fwd with qrow: the name the pairs form had when it was a wrapper of its own."""
+    return att_score_grouped_fwd(vprime, qp, wx, bx, order, offsets, N, B, P, mode, qrow=qrow)
 
 
 def gather_rows(src, rows, dst, cols: Optional[int] = None):

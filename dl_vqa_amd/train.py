@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from ._lib import ADAM_MAX_SEGMENTS as MAX_ADAM_SEGMENTS     # what one launch carries in its arguments
-from .model import validate_question_lengths
+from .model import _check_index_count, validate_question_lengths
 
 
 # ------------------------------------------------------------------ loss head
@@ -104,8 +104,7 @@ def run_batch_shared(model, batch_data, max_answers, image_index, batch_divisor:
     run once per image, forward and backward (VqaNet.forward_shared, which also states the dropout semantics)."""
     v, q, a_indices, a_values, a_length, idx, q_len = batch_data
     n_index = len(image_index) if not torch.is_tensor(image_index) else image_index.numel()
-    if n_index != q.shape[0]:
-        raise ValueError(f"run_batch_shared: {n_index} image_index entries for {q.shape[0]} questions")
+    _check_index_count("run_batch_shared", n_index, q.shape[0])
     dev = next(model.parameters()).device
     v = v.to(dev, non_blocking=True)
     q = q.to(dev, non_blocking=True)
@@ -136,8 +135,7 @@ def run_batch_features(model, batch_data, max_answers, feats, image_index, batch
         raise ValueError(f"run_batch_features: image_dropout must be a bool, got {image_dropout!r}")
     _v, q, a_indices, a_values, a_length, idx, q_len = batch_data
     n_index = len(image_index) if not torch.is_tensor(image_index) else image_index.numel()
-    if n_index != q.shape[0]:
-        raise ValueError(f"run_batch_features: {n_index} image_index entries for {q.shape[0]} questions")
+    _check_index_count("run_batch_features", n_index, q.shape[0])
     dev = next(model.parameters()).device
     q = q.to(dev, non_blocking=True)
     a_indices = a_indices.to(dev, non_blocking=True)

@@ -1,16 +1,15 @@
 """CPU: gradient x input maps from cached features (VqaNet.explain / explain_pairs) -- the identity behind the closed form
 (float64, against autograd through the oracle's differentiable pieces), the condition under which the GPU tests on the golden
 fixtures are meaningful (no ReLU pre-activation within rounding of zero), the new entry points in the header, the ctypes
-prototypes and the built library with their host-side argument validation, and the errors the public calls raise before any
-device work."""
+prototypes and the built library with their host-side argument validation.  (The errors the public calls raise before any
+device work: tests/test_explain_refusals_cpu.py.)"""
 import re
 
 import pytest
 import torch
 
-from dl_vqa_amd import Attribution, ImageFeatures, QuestionFeatures, VqaNet
+from dl_vqa_amd import Attribution
 from tests import attribution_ref as R
-from tests.golden_util import Golden, full_cfg, tiny_cfg
 
 NEW_ENTRY_POINTS = ("vqa_att_attr_apply_gather", "vqa_att_attr_apply_gather_f16", "vqa_att_attr_score_grouped",
                     "vqa_att_attr_score_grouped_pairs", "vqa_att_attr_score_grouped_f16", "vqa_att_attr_score_grouped_pairs_f16",
@@ -146,66 +145,7 @@ def test_attr_score_grouped_argument_validation_without_gpu():
         [0, 0, 4, 4, 2, 2, 1]
 
 
-# ----------------------------------------------------------------------------- errors before any device work
-def _tiny():
-    g = Golden("tiny_plus")
-    m = VqaNet(tiny_cfg(g.meta), g.meta["V"])
-    m.load_state_dict(g.sd)
-    return g, m
-
-
-def _host_caches(m, N=3, M=2):
-    """Holders as encode_images / encode_questions build them, around host tensors (tests/test_question_cache_cpu.py)."""
-    eng = m._engine
-    m._flat_param = torch.zeros(4)
-    feats = ImageFeatures(torch.zeros(N, 4, eng.C), torch.zeros(N * 4, eng.mid), (2, 2), m)
-    qfeats = QuestionFeatures(torch.zeros(M, eng.Q), torch.zeros(M, eng.mid), m)
-    return feats, qfeats
-
-
-def test_bf16_then_train_mode_then_device():
+# ----------------------------------------------------------------------------- the result type
+# (what explain / explain_pairs refuse before any device work: tests/test_explain_refusals_cpu.py)
+def test_attribution_fields():
     assert Attribution._fields == ("maps", "answers", "logits")
-    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
-    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
-    for call in (lambda: m.explain(None, q, ql, [0]), lambda: m.explain_pairs(None, None, [0], [0])):
-        with pytest.raises(NotImplementedError, match="compute_dtype"):
-            call()
-    g, m = _tiny()
-    m.train()
-    for call in (lambda: m.explain(None, g.t["q"], g.t["q_len"], [0, 1, 2]), lambda: m.explain_pairs(None, None, [0], [0])):
-        with pytest.raises(RuntimeError, match="training mode"):
-            call()
-    m.eval()                                                        # eval mode on the CPU: the device check speaks
-    feats, qfeats = _host_caches(m)
-    with pytest.raises(RuntimeError, match="cuda"):
-        m.explain(feats, g.t["q"][:3], g.t["q_len"][:3], [0, 1, 2])
-    with pytest.raises(RuntimeError, match="cuda"):
-        m.explain_pairs(feats, qfeats, [0, 1, 2], [0, 1, 1], answers=[0, 1, 2])
-    assert m._last_ctx is None
-
-
-def test_answers_and_foreign_features_are_judged_before_any_device_work():
-    g, m = _tiny()
-    m.eval()
-    A = m._engine.A
-    feats, qfeats = _host_caches(m, N=3, M=2)
-    q, ql = g.t["q"][:3], g.t["q_len"][:3]
-    with pytest.raises(TypeError, match="encode_images"):
-        m.explain(torch.zeros(3), q, ql, [0, 1, 2])
-    with pytest.raises(TypeError, match="encode_images"):
-        m.explain_pairs(torch.zeros(3), qfeats, [0], [0])
-    with pytest.raises(TypeError, match="encode_questions"):
-        m.explain_pairs(feats, feats, [0], [0])
-    for call in (lambda a: m.explain(feats, q, ql, [0, 1, 2], answers=a),
-                 lambda a: m.explain_pairs(feats, qfeats, [0, 1, 2], [0, 1, 1], answers=a)):
-        with pytest.raises(ValueError, match="2 answers for 3"):
-            call([0, 1])
-        with pytest.raises(IndexError, match=rf"answers entry {A} out of range \[0, {A}\)"):
-            call([0, A, 1])
-        with pytest.raises(IndexError, match="answers entry -1"):
-            call(torch.tensor([0, 1, -1], dtype=torch.int32))
-        with pytest.raises(TypeError, match="integer"):
-            call([0.0, 1.0, 2.0])
-        with pytest.raises(RuntimeError, match="cuda"):             # everything the host can judge is in order
-            call([0, A - 1, 1])
-    assert m._last_ctx is None and all(p.grad is None for p in m.parameters())

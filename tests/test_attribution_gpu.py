@@ -6,6 +6,7 @@ import torch
 
 from dl_vqa_amd import Attribution, group_by_image, unique_questions
 from tests import attribution_ref as R
+from tests.explain_util import build, fixture_model as _fixture_model, grouping as _grouping, rel
 from tests.golden_util import Golden, full_cfg, tiny_cfg
 from tests.test_kernels_gpu import check
 
@@ -16,29 +17,6 @@ DEV = "cuda:0"
 def _ops():
     from dl_vqa_amd import ops
     return ops
-
-
-def rel(got, ref):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-30)
-
-
-def build(cfg, V, sd=None, compute_dtype="fp32"):
-    from dl_vqa_amd import VqaNet
-    m = VqaNet(cfg, V, compute_dtype=compute_dtype)
-    if sd is not None:
-        m.load_state_dict(sd)
-    return m.to(DEV)
-
-
-def _grouping(kind, N, B, g):
-    """tests/test_multi_question_gpu.py's groupings, restated."""
-    if kind == "empty":          # image N-1 (and, for N > 2, image 1) has no question; every other one has some
-        pool = [n for n in range(N) if n != N - 1 and (N <= 2 or n != 1)]
-        return torch.tensor(pool)[torch.randint(0, len(pool), (B,), generator=g)]
-    if kind == "single":         # one image holds every question
-        return torch.full((B,), N // 2, dtype=torch.int64)
-    return torch.randint(0, N, (B,), generator=g)      # shuffled
 
 
 # ----------------------------------------------------------------------------- kernel 1: dscore's bits, and r1
@@ -164,13 +142,6 @@ def test_attr_score_grouped_matches_float64(N, B, P, mid, G, mode, kind):
 
 
 # ----------------------------------------------------------------------------- the whole path on the golden fixtures
-def _fixture_model(do_option, compute_dtype="fp32"):
-    f = R.fixture_case(do_option)
-    g = f["golden"]
-    m = build(f["cfg"], g.meta["V"], g.sd, compute_dtype).eval()
-    return f, m, m.encode_images(f["v"].to(DEV))
-
-
 def _parity(tag, att, do_option, bound=2e-4):
     ref, r1, r2 = R.fixture_reference(do_option, att.answers.tolist())
     B = ref.shape[0]

@@ -1,23 +1,20 @@
 """CPU: occlusion maps from cached features (VqaNet.explain_occlusion / explain_occlusion_pairs) -- the closed form behind
 vqa_occl_logit against a brute-force forward with the occluded features zeroed (float64), that the exact map is not a
 restatement of the gradient x input map, the new entry point in the header, the ctypes prototypes and the built library with
-its host-side argument validation, and the errors the public calls raise before any device work."""
+its host-side argument validation, and the errors only these calls raise before any device work (the window; what explain /
+explain_pairs raise for the same arguments).  The refusals every explain call shares: tests/test_explain_refusals_cpu.py."""
 import re
 
 import pytest
 import torch
 
-from dl_vqa_amd import ImageFeatures, Occlusion, QuestionFeatures, VqaNet
+from dl_vqa_amd import ImageFeatures, Occlusion
 from tests import attribution_ref as R
 from tests import occlusion_ref as OR
-from tests.golden_util import Golden, full_cfg, tiny_cfg
+from tests.explain_util import columns as _columns, host_caches as _host_caches, tiny as _tiny
 
 
 # ----------------------------------------------------------------------------- the identity, in float64
-def _columns(B, A):
-    return [(3 * b + 1) % A for b in range(B)]
-
-
 @pytest.mark.parametrize("window", [1, 3])
 @pytest.mark.parametrize("do_option", ["+", "*", "|"])
 def test_closed_form_equals_brute_force_on_the_fixtures(do_option, window):
@@ -131,48 +128,11 @@ def test_occl_logit_argument_validation_without_gpu():
 
 
 # ----------------------------------------------------------------------------- errors before any device work
-def _tiny():
-    g = Golden("tiny_plus")
-    m = VqaNet(tiny_cfg(g.meta), g.meta["V"])
-    m.load_state_dict(g.sd)
-    return g, m
-
-
-def _host_caches(m, N=3, M=2):
-    """Holders as encode_images / encode_questions build them, around host tensors (tests/test_attribution_cpu.py)."""
-    eng = m._engine
-    m._flat_param = torch.zeros(4)
-    feats = ImageFeatures(torch.zeros(N, 4, eng.C), torch.zeros(N * 4, eng.mid), (2, 2), m)
-    qfeats = QuestionFeatures(torch.zeros(M, eng.Q), torch.zeros(M, eng.mid), m)
-    return feats, qfeats
-
-
-def test_bf16_then_train_mode_then_device():
-    assert Occlusion._fields == ("maps", "answers", "logits")
-    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
-    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
-    for call in (lambda: m.explain_occlusion(None, q, ql, [0]), lambda: m.explain_occlusion_pairs(None, None, [0], [0])):
-        with pytest.raises(NotImplementedError, match="compute_dtype"):
-            call()
-    g, m = _tiny()
-    m.train()
-    for call in (lambda: m.explain_occlusion(None, g.t["q"], g.t["q_len"], [0, 1, 2]),
-                 lambda: m.explain_occlusion_pairs(None, None, [0], [0])):
-        with pytest.raises(RuntimeError, match="training mode"):
-            call()
-    m.eval()                                                        # eval mode on the CPU: the device check speaks
-    feats, qfeats = _host_caches(m)
-    with pytest.raises(RuntimeError, match="cuda"):
-        m.explain_occlusion(feats, g.t["q"][:3], g.t["q_len"][:3], [0, 1, 2], window=3)
-    with pytest.raises(RuntimeError, match="cuda"):
-        m.explain_occlusion_pairs(feats, qfeats, [0, 1, 2], [0, 1, 1], answers=[0, 1, 2], window=7)
-    assert m._last_ctx is None
-
-
+# (what the six explain calls refuse alike: tests/test_explain_refusals_cpu.py)
 def test_window_answers_and_features_are_judged_before_any_device_work():
+    assert Occlusion._fields == ("maps", "answers", "logits")
     g, m = _tiny()
     m.eval()
-    A = m._engine.A
     feats, qfeats = _host_caches(m, N=3, M=2)
     q, ql = g.t["q"][:3], g.t["q_len"][:3]
     single = lambda **kw: m.explain_occlusion(feats, q, ql, [0, 1, 2], **kw)
@@ -181,23 +141,6 @@ def test_window_answers_and_features_are_judged_before_any_device_work():
         for window in (0, 2, 4, 9, -1, True, 3.0, "3", None):
             with pytest.raises(ValueError, match="window must be an odd int in 1..7"):
                 call(window=window)
-        with pytest.raises(ValueError, match="2 answers for 3"):
-            call(answers=[0, 1])
-        with pytest.raises(IndexError, match=rf"answers entry {A} out of range \[0, {A}\)"):
-            call(answers=[0, A, 1])
-        with pytest.raises(IndexError, match="answers entry -1"):
-            call(answers=torch.tensor([0, 1, -1], dtype=torch.int32))
-        with pytest.raises(TypeError, match="integer"):
-            call(answers=[0.0, 1.0, 2.0])
-        with pytest.raises(RuntimeError, match="cuda"):             # everything the host can judge is in order
-            call(answers=[0, A - 1, 1], window=5)
-    # what explain / explain_pairs raise for the same arguments, the call's own name in the message
-    with pytest.raises(TypeError, match="encode_images"):
-        m.explain_occlusion(torch.zeros(3), q, ql, [0, 1, 2])
-    with pytest.raises(TypeError, match="encode_images"):
-        m.explain_occlusion_pairs(torch.zeros(3), qfeats, [0], [0])
-    with pytest.raises(TypeError, match="encode_questions"):
-        m.explain_occlusion_pairs(feats, feats, [0], [0])
     # an index out of range, features without v' and foreign features: whatever explain / explain_pairs raise for the same
     # arguments on this host (the device checks of the GPU tests judge them where a device is present), word for word
     bank = ImageFeatures(torch.zeros(3, 4, m._engine.C), None, (2, 2), m)

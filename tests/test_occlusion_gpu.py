@@ -11,11 +11,12 @@ import torch
 from dl_vqa_amd import ImageFeatures, Occlusion, unique_questions
 from tests import attribution_ref as R
 from tests import occlusion_ref as OR
-from tests.test_attribution_gpu import _fixture_model, _grouping
+from tests.explain_util import columns as _columns, fixture_model as _fixture_model, grouping as _grouping, within
 from tests.test_kernels_gpu import check
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+_within = functools.partial(within, label="parity-occlusion")
 ALPHA_MAX = 16.0          # the numerical contract of vqa_occl_logit (include/vqa_hip.h)
 
 
@@ -137,10 +138,6 @@ def test_occl_logit_refuses_a_width_that_is_no_multiple_of_4():
 MODELS = [("+", "fp32"), ("*", "fp32"), ("|", "fp32"), ("+", "fp32x3"), ("*", "fp32x3"), ("|", "fp32x3")]
 
 
-def _columns(B, n_answers):
-    return [(3 * b + 1) % n_answers for b in range(B)]
-
-
 @functools.lru_cache(maxsize=None)
 def _fixture_run(do_option, compute_dtype):
     """One fixture in one compute mode: the model, its caches, answer() on the full caches and on the four caches with one
@@ -184,13 +181,6 @@ def _bound(compute_dtype):
     print(f"[parity-occlusion] {compute_dtype}: answer() on zeroed caches vs float64 brute force, max|diff| over the three "
           f"fixtures = {worst:.3e}; whole-path bound = max(4 x that, 1e-7) = {bound:.3e}")
     return bound
-
-
-def _within(tag, got, ref, bound):
-    e = float((got.double().cpu() - ref.double().cpu()).abs().max())
-    print(f"[parity-occlusion] {tag}: max|diff| = {e:.3e} (bound {bound:.3e}), max|ref| = {float(ref.abs().max()):.3e}")
-    assert e <= bound, f"{tag}: {e} > {bound}"
-    return e
 
 
 @pytest.mark.parametrize("do_option,compute_dtype", MODELS)

@@ -1,16 +1,16 @@
 """CPU: per-token gradient x input (VqaNet.explain_words) -- the closed forms of the two new kernels in float64 against autograd
 through the oracle's pieces (tests/word_attribution_ref.py), the '|' identity, the conditions under which the GPU tests on the
 fixtures and on the random fused-recurrence models are meaningful, the new entry points in the header, the ctypes prototypes
-and the built library with their host-side argument validation, and the errors the public call raises before any device work."""
+and the built library with their host-side argument validation.  (The errors the public call raises before any device work:
+tests/test_explain_refusals_cpu.py.)"""
 import re
 
 import pytest
 import torch
 
-from dl_vqa_amd import ImageFeatures, VqaNet, WordAttribution
+from dl_vqa_amd import VqaNet, WordAttribution
 from tests import attribution_ref as R
 from tests import word_attribution_ref as W
-from tests.golden_util import Golden, full_cfg, tiny_cfg
 
 NEW_ENTRY_POINTS = ("vqa_att_attr_dq_grouped", "vqa_att_attr_dq_grouped_f16", "vqa_embed_attr")
 
@@ -162,65 +162,11 @@ def test_embed_attr_argument_validation_without_gpu():
     assert f(16, 20, 16, 16, 16, 16, 16, 0, 4, 7, 10, None) == 0            # no alignment or width rule: the scalar form
 
 
-# ----------------------------------------------------------------------------- errors before any device work
-def _tiny():
-    g = Golden("tiny_plus")
-    m = VqaNet(tiny_cfg(g.meta), g.meta["V"])
-    m.load_state_dict(g.sd)
-    return g, m
-
-
-def _host_features(m, N=3, vprime=True):
-    """A holder as encode_images builds it, around host tensors (tests/test_attribution_cpu.py)."""
-    eng = m._engine
-    m._flat_param = torch.zeros(4)
-    return ImageFeatures(torch.zeros(N, 4, eng.C), torch.zeros(N * 4, eng.mid) if vprime else None, (2, 2), m)
-
-
+# ----------------------------------------------------------------------------- the result type and the missing pairs form
+# (what explain_words refuses before any device work: tests/test_explain_refusals_cpu.py)
 def test_word_attribution_is_exported():
     import dl_vqa_amd
     assert "WordAttribution" in dl_vqa_amd.__all__ and dl_vqa_amd.WordAttribution is WordAttribution
     assert WordAttribution._fields == ("words", "maps", "answers", "logits")
     assert not hasattr(VqaNet, "explain_words_pairs")                # QuestionFeatures holds no recurrence state
     assert "no explain_words_pairs" in VqaNet.explain_words.__doc__
-
-
-def test_bf16_then_train_mode_then_device():
-    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
-    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
-    with pytest.raises(NotImplementedError, match="compute_dtype"):
-        m.explain_words(None, q, ql, [0])
-    g, m = _tiny()
-    m.train()
-    with pytest.raises(RuntimeError, match="training mode"):
-        m.explain_words(None, g.t["q"], g.t["q_len"], [0, 1, 2])
-    m.eval()                                                        # eval mode on the CPU: the device check speaks
-    with pytest.raises(RuntimeError, match="cuda"):
-        m.explain_words(_host_features(m), g.t["q"][:3], g.t["q_len"][:3], [0, 1, 2])
-    assert m._last_ctx is None
-
-
-def test_features_index_and_answers_are_judged_before_any_device_work():
-    g, m = _tiny()
-    m.eval()
-    A = m._engine.A
-    feats = _host_features(m)
-    q, ql = g.t["q"][:3], g.t["q_len"][:3]
-    with pytest.raises(TypeError, match="encode_images"):
-        m.explain_words(torch.zeros(3), q, ql, [0, 1, 2])
-    with pytest.raises(RuntimeError, match="with_vprime=False"):    # a bank without v'
-        m.explain_words(_host_features(m, vprime=False), q, ql, [0, 1, 2])
-    with pytest.raises(ValueError, match="2 image_index entries for 3 questions"):
-        m.explain_words(feats, q, ql, [0, 1])
-    call =lambda a: m.explain_words(feats, q, ql, [0, 1, 2], answers=a)
-    with pytest.raises(ValueError, match="2 answers for 3"):
-        call([0, 1])
-    with pytest.raises(IndexError, match=rf"answers entry {A} out of range \[0, {A}\)"):
-        call([0, A, 1])
-    with pytest.raises(IndexError, match="answers entry -1"):
-        call(torch.tensor([0, 1, -1], dtype=torch.int32))
-    with pytest.raises(TypeError, match="integer"):
-        call([0.0, 1.0, 2.0])
-    with pytest.raises(RuntimeError, match="cuda"):                 # everything the host can judge is in order
-        call([0, A - 1, 1])
-    assert m._last_ctx is None and all(p.grad is None for p in m.parameters())

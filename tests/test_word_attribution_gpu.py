@@ -15,8 +15,8 @@ import torch
 from dl_vqa_amd import WordAttribution, group_by_image
 from tests import attribution_ref as R
 from tests import word_attribution_ref as W
+from tests.explain_util import build, grouping as _grouping, off_by_one_float as _off_by_one_float, rel
 from tests.golden_util import Golden, tiny_cfg
-from tests.test_attribution_gpu import _grouping, build, rel
 from tests.test_kernels_gpu import check
 
 pytestmark = pytest.mark.gpu
@@ -87,15 +87,6 @@ def test_attr_dq_grouped_matches_float64_and_the_training_kernel(N, B, P, mid, G
 
 
 # ----------------------------------------------------------------------------- kernel B: the embedding stage
-def _off_by_one_float(t):
-    """The same values at an address that is 4 (mod 16): forces the scalar form."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
-
-
 @pytest.mark.parametrize("two", [False, True])
 @pytest.mark.parametrize("B,T,E,V", [(3, 5, 12, 50), (2, 1, 300, 40), (5, 7, 20, 30), (4, 14, 302, 60)])
 def test_embed_attr_matches_float64(B, T, E, V, two):

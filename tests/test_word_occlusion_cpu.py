@@ -1,15 +1,16 @@
 """CPU: exact word occlusion from cached features (VqaNet.explain_words_occlusion) -- the host variant table, the prefix claim
 in float64 (chains that start from the base run's saved states give what a full forward per variant gives), the scale of the
 signal and its distance from the gradient x input words, the two new entry points' host-side argument validation, and the
-errors the public call raises before any device work."""
+errors the public call raises before any device work, which are explain_words' (those every explain call shares:
+tests/test_explain_refusals_cpu.py)."""
 import pytest
 import torch
 
-from dl_vqa_amd import ImageFeatures, VqaNet, WordOcclusion
+from dl_vqa_amd import WordOcclusion
 from dl_vqa_amd.model import word_occlusion_chunks, word_occlusion_table
 from tests import attribution_ref as R
 from tests import word_occlusion_ref as WO
-from tests.golden_util import Golden, full_cfg, tiny_cfg
+from tests.explain_util import host_caches, tiny as _tiny
 
 
 # ----------------------------------------------------------------------------- the host table
@@ -198,48 +199,18 @@ def test_occl_words_argument_validation_without_gpu():
 
 
 # ----------------------------------------------------------------------------- errors before any device work
-def _tiny():
-    g = Golden("tiny_plus")
-    m = VqaNet(tiny_cfg(g.meta), g.meta["V"])
-    m.load_state_dict(g.sd)
-    return g, m
-
-
 def _host_features(m, N=3, vprime=True):
-    eng = m._engine
-    m._flat_param = torch.zeros(4)
-    return ImageFeatures(torch.zeros(N, 4, eng.C), torch.zeros(N * 4, eng.mid) if vprime else None, (2, 2), m)
+    return host_caches(m, N, vprime=vprime)[0]
 
 
+# (what the six explain calls refuse alike: tests/test_explain_refusals_cpu.py)
 def test_refusals_that_need_no_device():
     assert WordOcclusion._fields == ("words", "answers", "logits")
-    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU: bf16 speaks first
-    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
-    with pytest.raises(NotImplementedError, match="compute_dtype"):
-        m.explain_words_occlusion(None, q, ql, [0])
     g, m = _tiny()
-    m.train()
-    with pytest.raises(RuntimeError, match="training mode"):
-        m.explain_words_occlusion(None, g.t["q"], g.t["q_len"], [0, 1, 2])
     m.eval()
     A = m._engine.A
     q, ql = g.t["q"][:3], g.t["q_len"][:3]
-    with pytest.raises(TypeError, match="encode_images"):
-        m.explain_words_occlusion(torch.zeros(3), q, ql, [0, 1, 2])
-    with pytest.raises(RuntimeError, match="with_vprime=False"):
-        m.explain_words_occlusion(_host_features(m, vprime=False), q, ql, [0, 1, 2])
     feats = _host_features(m)
-    call = lambda index=(0, 1, 2), **kw: m.explain_words_occlusion(feats, q, ql, list(index), **kw)
-    with pytest.raises(ValueError, match="2 image_index entries for 3 questions"):
-        call(index=(0, 1))
-    with pytest.raises(ValueError, match="2 answers for 3"):
-        call(answers=[0, 1])
-    with pytest.raises(IndexError, match=rf"answers entry {A} out of range \[0, {A}\)"):
-        call(answers=[0, A, 1])
-    with pytest.raises(IndexError, match="answers entry -1"):
-        call(answers=torch.tensor([0, 1, -1], dtype=torch.int32))
-    with pytest.raises(TypeError, match="integer"):
-        call(answers=[0.0, 1.0, 2.0])
     # what explain_words raises for the same arguments, the call's own name in the message
     _, other = _tiny()
     other.eval()
@@ -255,6 +226,4 @@ def test_refusals_that_need_no_device():
             for answers in (None, [0, 1], [0, A - 1, 1]):
                 assert raised(lambda: m.explain_words_occlusion(images, q, ql, index, answers=answers)) == \
                     raised(lambda: m.explain_words(images, q, ql, index, answers=answers))
-    with pytest.raises(RuntimeError, match="cuda"):                 # everything the host can judge is in order
-        call(answers=[0, A - 1, 1], _variant_rows=2)
     assert m._last_ctx is None and all(p.grad is None for p in m.parameters())

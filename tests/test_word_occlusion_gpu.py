@@ -20,13 +20,13 @@ from dl_vqa_amd.model import word_occlusion_chunks, word_occlusion_table
 from tests import attribution_ref as R
 from tests import word_attribution_ref as W
 from tests import word_occlusion_ref as WO
+from tests.explain_util import build, off_by_one_float as _off_by_one_float, within
 from tests.golden_util import Golden, tiny_cfg
-from tests.test_attribution_gpu import build
 from tests.test_kernels_gpu import check
-from tests.test_word_attribution_gpu import _off_by_one_float
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+_within = functools.partial(within, label="parity-word-occlusion")
 MODELS = [("+", "fp32"), ("*", "fp32"), ("|", "fp32"), ("+", "fp32x3")]
 
 
@@ -233,13 +233,6 @@ def _bound(compute_dtype):
     print(f"[parity-word-occlusion] {compute_dtype}: answer() on the substituted questions vs float64 brute force, max|diff| over "
           f"the three fixtures = {worst:.3e}; whole-path bound = max(4 x that, 1e-7) = {bound:.3e}")
     return bound
-
-
-def _within(tag, got, ref, bound):
-    e = float((got.double().cpu() - ref.double().cpu()).abs().max())
-    print(f"[parity-word-occlusion] {tag}: max|diff| = {e:.3e} (bound {bound:.3e}), max|ref| = {float(ref.abs().max()):.3e}")
-    assert e <= bound, f"{tag}: {e} > {bound}"
-    return e
 
 
 @pytest.mark.parametrize("do_option,compute_dtype", MODELS)

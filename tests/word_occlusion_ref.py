@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from tests import attribution_ref as R
 from tests import word_attribution_ref as W
+from tests.explain_util import columns        # noqa: F401 -- the given answer columns, under the name the tests ask for
 
 _SFX = W._SFX
 
@@ -161,6 +162,3 @@ def fixture_brute(do_option, answers):
     return _fixture_brute(do_option, tuple(int(a) for a in answers))
 
 
-def columns(B, A):
-    """The given answer columns of the tests (tests/test_occlusion_cpu.py asks the same)."""
-    return [(3 * b + 1) % A for b in range(B)]

@@ -18,52 +18,27 @@ tools/bench_explain.py; the figure is the median over --reps windows of --iters 
 The driver never touches the GPU: the measurement is a child process under its own `timeout`, and a failure ends the run.
 Output: one JSON object on stdout and in OUT_DIR/explain_occlusion_bench.json.
 """
-import argparse
 import json
-import os
 import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bench_explain_common import A, S, SHAPES, T, V, main, setup, window as _window
 
-S, T, A, V = 224, 14, 1000, 5000
-SHAPES = [(256, 1), (32, 8)]          # (images, questions per image)
 BRUTE_POSITIONS = 8
-
-
-def _window(fn, iters):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(iters):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / iters
 
 
 def step_time(reps, iters):
     import torch
-    from dl_vqa_amd import ImageFeatures, VqaNet, compact_image_index, ops
-    from oracle import vqa_oracle as O
-    from tests.golden_util import full_cfg
+    from dl_vqa_amd import ImageFeatures, compact_image_index, ops
     med = statistics.median
     res = {"shape": dict(S=S, T=T, A=A, V=V, dtype="fp32"),
            "method": f"HIP events, interleaved, median of {reps} windows of {iters} calls (kernels: {10 * iters}), 2 warm-up calls "
                      f"per path; brute_force: answer() on {BRUTE_POSITIONS} zeroed caches, SCALED by P / {BRUTE_POSITIONS}",
            "cases": []}
     for N, per in SHAPES:
-        torch.manual_seed(1)
-        m = VqaNet(full_cfg(A), V).cuda().eval()
-        B = N * per
-        v, q, _, _, _, _, ql = O.synthetic_batch(B, S, T, V, A, seed=2)
-        v, q, ql = v[:N].cuda(), q.cuda(), ql.cuda()
-        image_index = torch.arange(B) % N
-        feats = m.encode_images(v)
+        cs = setup(N, per)
+        m, B, q, ql, image_index, feats = cs.m, cs.B, cs.q, cs.ql, cs.image_index, cs.feats
         f16 = feats.to(torch.float16)
-        del v
+        del cs
         Pn = feats.vn.shape[1]
         zeroed = []
         for p in range(0, Pn, Pn // BRUTE_POSITIONS)[:BRUTE_POSITIONS]:
@@ -139,27 +114,5 @@ def step_time(reps, iters):
     print(json.dumps(res))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--step", choices=["time"], help="internal: run the GPU step in this process")
-    a = ap.parse_args()
-    if a.step == "time":
-        return step_time(a.reps, a.iters)
-    os.makedirs(a.out_dir, exist_ok=True)
-    cmd = ["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--iters", str(a.iters),
-           "--step", "time"]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-        raise SystemExit(f"the measurement ended with status {r.returncode}")
-    line = json.dumps(json.loads(r.stdout.strip().splitlines()[-1]))
-    with open(os.path.join(a.out_dir, "explain_occlusion_bench.json"), "w") as f:
-        f.write(line + "\n")
-    print(line)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, step_time, "explain_occlusion_bench.json", iters=3, limit=540)

@@ -22,29 +22,10 @@ which is reported next to the recurrence's.
 The driver never touches the GPU: the measurement is a child process under its own `timeout`, and a failure ends the run.
 Output: one JSON object on stdout and in OUT_DIR/explain_words_bench.json.
 """
-import argparse
 import json
-import os
 import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-S, T, A, V = 224, 14, 1000, 5000
-SHAPES = [(256, 1), (32, 8)]          # (images, questions per image)
-
-
-def _window(fn, iters):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(iters):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / iters
+from bench_explain_common import A, S, SHAPES, T, V, main, setup, window as _window
 
 
 def dq_bytes(N, B, P, mid, G, NT, elt):
@@ -57,21 +38,14 @@ def score_bwd_bytes(N, B, P, mid, G, NT):
 
 def step_time(reps, iters):
     import torch
-    from dl_vqa_amd import VqaNet, group_by_image, ops
-    from oracle import vqa_oracle as O
-    from tests.golden_util import full_cfg
+    from dl_vqa_amd import group_by_image, ops
     med = statistics.median
     res = {"shape": dict(S=S, T=T, A=A, V=V),
            "method": f"HIP events, interleaved, median of {reps} windows of {iters} calls (kernels and the recurrence: {10 * iters}), "
                      "2 warm-up calls per path", "cases": []}
     for N, per in SHAPES:
-        torch.manual_seed(1)
-        m = VqaNet(full_cfg(A), V).cuda().eval()
-        B = N * per
-        v, q, _, _, _, _, ql = O.synthetic_batch(B, S, T, V, A, seed=2)
-        v, q, ql = v[:N].cuda(), q.cuda(), ql.cuda()
-        image_index = torch.arange(B) % N
-        f32 = m.encode_images(v)
+        cs = setup(N, per)
+        m, B, q, ql, image_index, f32 = cs.m, cs.B, cs.q, cs.ql, cs.image_index, cs.feats
         f16 = f32.to(torch.float16)
         eng, P = m._engine, m._param_dict()
         Pn, mid, G, mode, Q, H = f32.vn.shape[1], eng.mid, eng.G, eng.att_mode, eng.Q, eng.H
@@ -140,32 +114,10 @@ def step_time(reps, iters):
                          dq_over_score_bwd=round(ms["dq"] / ms["score_bwd"], 3))
             case["caches"][name] = c
         res["cases"].append(case)
-        del m, v, f32, f16, txt
+        del cs, m, f32, f16, txt
         torch.cuda.empty_cache()
     print(json.dumps(res))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--step", choices=["time"], help="internal: run the GPU step in this process")
-    a = ap.parse_args()
-    if a.step == "time":
-        return step_time(a.reps, a.iters)
-    os.makedirs(a.out_dir, exist_ok=True)
-    cmd = ["timeout", "-k", "10", "420", sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--iters", str(a.iters),
-           "--step", "time"]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-        raise SystemExit(f"the measurement ended with status {r.returncode}")
-    line = json.dumps(json.loads(r.stdout.strip().splitlines()[-1]))
-    with open(os.path.join(a.out_dir, "explain_words_bench.json"), "w") as f:
-        f.write(line + "\n")
-    print(line)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, step_time, "explain_words_bench.json", iters=5, limit=420)

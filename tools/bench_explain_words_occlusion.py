@@ -20,54 +20,29 @@ It also reports V, the recurrent row-steps of both routes and the largest differ
 The driver never touches the GPU: the measurement is a child process under its own `timeout`, and a failure ends the run.
 Output: one JSON object on stdout and in OUT_DIR/explain_words_occlusion_bench.json.
 """
-import argparse
 import json
-import os
 import statistics
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bench_explain_common import A, S, SHAPES, T, V, main, setup, window as _window
 
-S, T, A, V = 224, 14, 1000, 5000
-SHAPES = [(256, 1), (32, 8)]          # (images, questions per image)
 LENGTHS = (3, 5, 7, 9, 11, 14, 4, 6, 8, 10, 2, 5, 7, 9, 6, 6)      # mean 7.0
-
-
-def _window(fn, iters):
-    import torch
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(iters):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / iters
 
 
 def step_time(reps, iters):
     import torch
-    from dl_vqa_amd import VqaNet
     from dl_vqa_amd.model import word_occlusion_table
-    from oracle import vqa_oracle as O
-    from tests.golden_util import full_cfg
     med = statistics.median
     res = {"shape": dict(S=S, T=T, A=A, V=V, dtype="fp32", lengths=list(LENGTHS), mean_length=sum(LENGTHS) / len(LENGTHS)),
            "method": f"HIP events, interleaved, median of {reps} windows of {iters} calls, 2 warm-up calls per path; brute_force: "
                      "answer + encode_questions on the substituted questions (built outside the windows) + answer_pairs",
            "cases": []}
     for N, per in SHAPES:
-        torch.manual_seed(1)
-        m = VqaNet(full_cfg(A), V).cuda().eval()
+        cs = setup(N, per, questions_on_device=False)
+        m, B, q, image_index, feats = cs.m, cs.B, cs.q, cs.image_index, cs.feats
+        del cs
         assert float(m.text.embedding.weight[0].detach().abs().max()) == 0.0      # the brute-force route needs a zero padding row
-        B = N * per
-        v, q, *_ = O.synthetic_batch(B, S, T, V, A, seed=2)
         ql = torch.tensor([LENGTHS[b % len(LENGTHS)] for b in range(B)])
         q = torch.where(torch.arange(T)[None, :] < ql[:, None], q.clamp(min=1), torch.zeros_like(q))
-        image_index = torch.arange(B) % N
-        feats = m.encode_images(v[:N].cuda())
-        del v
         tab = word_occlusion_table(ql, T)
         vb, vt = tab.fwd_b.long(), tab.fwd_t.long()
         q_sub = q[vb].clone()
@@ -122,27 +97,5 @@ def step_time(reps, iters):
     print(json.dumps(res))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--step", choices=["time"], help="internal: run the GPU step in this process")
-    a = ap.parse_args()
-    if a.step == "time":
-        return step_time(a.reps, a.iters)
-    os.makedirs(a.out_dir, exist_ok=True)
-    cmd = ["timeout", "-k", "10", "540", sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--iters", str(a.iters),
-           "--step", "time"]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-        raise SystemExit(f"the measurement ended with status {r.returncode}")
-    line = json.dumps(json.loads(r.stdout.strip().splitlines()[-1]))
-    with open(os.path.join(a.out_dir, "explain_words_occlusion_bench.json"), "w") as f:
-        f.write(line + "\n")
-    print(line)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, step_time, "explain_words_occlusion_bench.json", iters=3, limit=540)
