@@ -23,10 +23,12 @@ resize, centre crop, normalisation and fp16 cast (preprocessing/preprocess_image
 the logit falls when a window of grid positions is taken out of the image, for every position, in closed form.
 ``VqaNet.explain_words_occlusion`` does the same for the question (``WordOcclusion``): how far the logit falls when one token's
 embedding output is zeroed, for every token, from the prefixes the variant recurrences share with the question itself.
+``VqaNet.explain_faithfulness`` / ``explain_faithfulness_pairs`` say how well any such map ranks the grid positions
+(``Faithfulness``): the deletion and insertion curves of the explained logit along the map's ranking, and their areas.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
            "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
-           "WordAttribution", "Occlusion", "WordOcclusion"]
+           "WordAttribution", "Occlusion", "WordOcclusion", "Faithfulness"]

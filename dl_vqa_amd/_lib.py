@@ -173,6 +173,12 @@ PROTOTYPES = {
     # exact word occlusion from cached features (bound with the attribution entry points, before the last two)
     "vqa_lstm_occl_cell_fwd": (i32, [f32p, f32p, f32p, f32p, f32p, i64, i64p, vp, vp, i32, f32p, i64, vp, i32, i32, i32, i32, vp]),
     "vqa_occl_words": (i32, [f32p, i64, f32p, i64, f32p, vp, f32p, i64, vp, vp, i64p, f32p, i32, i32, i32, i32, i32, i32, vp]),
+    # deletion and insertion curves of an attribution map (bound with the attribution entry points, before the last two)
+    "vqa_rank_desc": (i32, [f32p, vp, i32, i32, vp]),
+    "vqa_occl_curves_chunk": (i32, []),
+    "vqa_occl_curves_workspace_bytes": (i64, [i32, i32, i32, i32]),
+    "vqa_occl_curves": (i32, [f32p, f32p, vp, i32, f32p, f32p, f32p, f32p, i64, f32p, vp, vp, f32p, i64, f32p, f32p, i32, i32, i32,
+                              i32, i32, i32, vp]),
     # image dropout on a bank of cached image features
     "vqa_gather_rows_drop_norm": (i32, [f32p, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),
     "vqa_gather_rows_drop_norm_f16": (i32, [vp, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),

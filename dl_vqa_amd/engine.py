@@ -644,37 +644,78 @@ class Engine:
         assert not self.bf16, "explain_occlusion: fp32 / fp32x3 only"
         run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
         logits, probs, score, combined = run.logits, run.probs, run.score, run.combined
-        B, hid, G, C, GC, Dc, dev = run.img.numel(), self.hid, self.G, self.C, self.GC, self.Dc, feats.vn.device
+        B, hid, G, C, Dc, dev = run.img.numel(), self.hid, self.G, self.C, self.Dc, feats.vn.device
         Pn = feats.vn.shape[1]
         gh, gw = feats.grid
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         answers = self._picked(logits, ask.answers)
+        cnull, base = self._occlusion_operands(P, run)
+        # Z_g = W1_g . out_g: the image half of lin1 per glimpse, plain fp32 in every compute mode
+        w1 = P["classifier.lin1.weight"]
+        Z = new(B, G, hid)
+        for g in range(G):
+            ops.gemm(combined[:, g * C:], w1[:, g * C:], Z[:, g], B, hid, C, lda=Dc, ldb=Dc, ldc=G * hid)
+        maps = new(B, Pn)
+        for r0, U in self._u_chunks(P, feats, rows, u_bytes):
+            ops.occl_logit(base, Z, U, slot, probs, score, cnull, P["classifier.lin2.weight"], P["classifier.lin2.bias"],
+                           answers, logits, gh, gw, window, slot0=r0, out=maps)
+        return maps, answers, logits
+
+    def _occlusion_operands(self, P, run):
+        """The per-question operands of the closed form that every set of absent positions shares, from a finished base run:
+        (cnull [B,G], base [B,hid])."""
+        B, G, GC, Dc, dev = run.img.numel(), self.G, self.GC, self.Dc, run.score.device
         # cnull: the score kernel's own bits for a position whose v' is 0 -- one all-zero position, every question in one group
         wx, bx = P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"]
         zero_v = torch.zeros(1, self.mid, dtype=torch.float32, device=dev)
         order1 = torch.arange(B, dtype=torch.int32, device=dev)
         offsets1 = torch.arange(0, B + 1, B, dtype=torch.int32, device=dev)                     # [0, B]
         cnull = ops.att_score_grouped_fwd(zero_v, run.qp, wx, bx, order1, offsets1, 1, B, 1, self.att_mode, qrow=run.qrow)
-        # base = b1 + W1[:, GC:] . qf and Z_g = W1_g . out_g: the two halves of lin1 apart, plain fp32 in every compute mode
+        # base = b1 + W1[:, GC:] . qf: the question half of lin1, plain fp32 in every compute mode
         w1 = P["classifier.lin1.weight"]
-        base = ops.gemm(combined[:, GC:], w1[:, GC:], new(B, hid), B, hid, self.Q, lda=Dc, ldb=Dc, bias1=P["classifier.lin1.bias"])
-        Z = new(B, G, hid)
-        for g in range(G):
-            ops.gemm(combined[:, g * C:], w1[:, g * C:], Z[:, g], B, hid, C, lda=Dc, ldb=Dc, ldc=G * hid)
-        # U [n, Pn, G, hid] for n images at a time, by the rule v' follows in encode_images; _bank_rows gathers the asked rows
-        # and widens a float16 cache
+        base = ops.gemm(run.combined[:, GC:], w1[:, GC:], torch.empty(B, self.hid, dtype=torch.float32, device=dev), B, self.hid,
+                        self.Q, lda=Dc, ldb=Dc, bias1=P["classifier.lin1.bias"])
+        return cnull, base
+
+    def _u_chunks(self, P, feats, rows, u_bytes=None):
+        """U = W1_g . vn [n, Pn, G, hid] for the distinct asked images `rows`, n images at a time under the workspace cap, by the
+        rule v' follows in encode_images; _bank_rows gathers the asked rows and widens a float16 cache.  Yields (r0, U of the
+        images rows[r0 : r0 + n]); the buffer is reused from one chunk to the next."""
+        hid, G, C, Dc = self.hid, self.G, self.C, self.Dc
+        Pn = feats.vn.shape[1]
+        w1 = P["classifier.lin1.weight"]
         n_u = rows.numel()
         per = max(1, int((self.U_BYTES if u_bytes is None else u_bytes) // (Pn * G * hid * 4)))
-        U = new(min(per, n_u), Pn, G, hid)
-        maps = new(B, Pn)
+        U = torch.empty(min(per, n_u), Pn, G, hid, dtype=torch.float32, device=feats.vn.device)
         for r0 in range(0, n_u, per):
             n = min(per, n_u - r0)
             v_in = self._bank_rows(feats.vn, rows[r0:r0 + n], 0.0, 0.0, 0)[1]
             for g in range(G):
                 _gemm(v_in, w1[:, g * C:], U[:n, :, g], n * Pn, hid, C, ldb=Dc, ldc=G * hid, x3=self._x3_gemm(n * Pn))
-            ops.occl_logit(base, Z, U[:n], slot, probs, score, cnull, P["classifier.lin2.weight"], P["classifier.lin2.bias"],
-                           answers, logits, gh, gw, window, slot0=r0, out=maps)
-        return maps, answers, logits
+            yield r0, U[:n]
+
+    # ------------------------------------------------------------------ deletion and insertion curves of an attribution map
+    # How well a map ranks the positions: the explained logit with the first k positions of the map's ranking absent (deletion)
+    # and alone present (insertion), k = 0 .. Pn, in the kept form of the closed form (include/vqa_hip.h vqa_occl_curves;
+    # DESIGN.md 4.20).  explain_occlusion's parts -- the base run, cnull, base, U per chunk of images -- plus the ranking kernel
+    # and the curve kernels.  Z is not formed.
+    @_device_current("feats", _cache_device)
+    def explain_faithfulness(self, P: Dict[str, Tensor], feats, ask, rows: Tensor, slot: Tensor, maps: Tensor,
+                             u_bytes: Optional[int] = None):
+        """explain_occlusion's arguments with maps fp32 [B,Pn] (on the device) in place of window.  Returns (deletion [B,Pn+1],
+        insertion [B,Pn+1], order int32 [B,Pn], answers int32 [B], logits [B,A])."""
+        assert not self.bf16, "explain_faithfulness: fp32 / fp32x3 only"
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        B, Pn, dev = run.img.numel(), feats.vn.shape[1], feats.vn.device
+        answers = self._picked(run.logits, ask.answers)
+        order = ops.rank_desc(maps)
+        cnull, base = self._occlusion_operands(P, run)
+        out = tuple(torch.empty(B, Pn + 1, dtype=torch.float32, device=dev) for _ in range(2))
+        ws = ops.occl_curves_workspace(B, Pn, self.G, self.hid, dev)
+        for r0, U in self._u_chunks(P, feats, rows, u_bytes):
+            ops.occl_curves(base, U, slot, run.probs, run.score, cnull, P["classifier.lin2.weight"], P["classifier.lin2.bias"],
+                            answers, order, slot0=r0, out=out, workspace=ws)
+        return out[0], out[1], order, answers, run.logits
 
     # ------------------------------------------------------------------ gradient x input per question token
     # explain_words is explain carried on to the other input: the same logit's gradient at the question half of the classifier

@@ -212,7 +212,35 @@ class WordOcclusion(NamedTuple):
     logits: torch.Tensor
 
 
+class Faithfulness(NamedTuple):
+    """What VqaNet.explain_faithfulness / explain_faithfulness_pairs return: deletion fp32 [B, P+1] -- the explained logit with
+    the k best-ranked positions of the map absent, k = 0 .. P --, insertion fp32 [B, P+1] -- the same logit with only those k
+    positions present --, order int64 [B, P] -- the positions by descending map value, equal values by the smaller position --,
+    answers int64 [B] -- the answer column each curve follows, as Attribution.answers -- and logits fp32 [B, A] -- what answer()
+    / answer_pairs() return for the same arguments, bit for bit.  A map that ranks well has a deletion curve that falls fast (a
+    small deletion_auc) and an insertion curve that rises fast (a large insertion_auc)."""
+    deletion: torch.Tensor
+    insertion: torch.Tensor
+    order: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+
+    @staticmethod
+    def _auc(curve):
+        c = curve.double()
+        return (c[:, :-1] + c[:, 1:]).sum(1) / (2 * (c.shape[1] - 1))
+
+    def deletion_auc(self):
+        """The trapezoid mean of each deletion curve, sum_k (c[k] + c[k+1]) / (2P): float64 [B], formed on the curve's device."""
+        return self._auc(self.deletion)
+
+    def insertion_auc(self):
+        """The trapezoid mean of each insertion curve, as deletion_auc()."""
+        return self._auc(self.insertion)
+
+
 OCCLUSION_WINDOW_MAX = 7    # include/vqa_hip.h vqa_occl_logit
+FAITHFULNESS_MAX_POSITIONS = 8192    # include/vqa_hip.h vqa_rank_desc
 
 
 def word_occlusion_chunks(lengths, T: int, max_rows: Optional[int] = None):
@@ -281,6 +309,25 @@ def _check_window(what: str, window) -> int:
     if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= OCCLUSION_WINDOW_MAX or window % 2 == 0:
         raise ValueError(f"{what}: window must be an odd int in 1..{OCCLUSION_WINDOW_MAX}, got {window!r}")
     return window
+
+
+def _check_maps(what: str, maps, B: int, grid):
+    """The maps argument of explain_faithfulness / explain_faithfulness_pairs, judged on the host: a floating tensor of B * P
+    elements shaped [B, gh, gw] or [B, P], P = gh * gw at most the rank kernel's cap.  grid None (feats is no ImageFeatures,
+    which the next check refuses): the dtype alone."""
+    if not isinstance(maps, torch.Tensor):
+        maps = torch.as_tensor(maps)
+    if not maps.is_floating_point():
+        raise TypeError(f"{what}: maps must be a floating tensor, got {maps.dtype}")
+    if grid is None:
+        return
+    gh, gw = grid
+    P = gh * gw
+    if maps.numel() != B * P or tuple(maps.shape) not in ((B, gh, gw), (B, P)):
+        raise ValueError(f"{what}: maps of shape {tuple(maps.shape)} for {B} questions on a {gh} x {gw} grid "
+                         f"(expected [{B}, {gh}, {gw}] or [{B}, {P}])")
+    if P > FAITHFULNESS_MAX_POSITIONS:
+        raise ValueError(f"{what}: {P} grid positions, the ranking takes at most {FAITHFULNESS_MAX_POSITIONS}")
 
 
 TOPK_MAX = 64   # include/vqa_hip.h vqa_softmax_topk: one wave keeps the k picks of a row, one per lane
@@ -1163,9 +1210,11 @@ class VqaNet(nn.Module):
 
     def _no_result(self, kind, feats, T: int = 0):
         """What an explain call returns for B == 0: the result type `kind` with every field empty."""
-        shape = dict(words=(0, T), maps=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A))
-        return kind(*(torch.empty(shape[f], dtype=torch.int64 if f == "answers" else torch.float32, device=feats.vn.device)
-                      for f in kind._fields))
+        P = feats.grid[0] * feats.grid[1]
+        shape = dict(words=(0, T), maps=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A), deletion=(0, P + 1),
+                     insertion=(0, P + 1), order=(0, P))
+        return kind(*(torch.empty(shape[f], dtype=torch.int64 if f in ("answers", "order") else torch.float32,
+                                  device=feats.vn.device) for f in kind._fields))
 
     @staticmethod
     def _maps_result(kind, feats, out):
@@ -1274,6 +1323,77 @@ class VqaNet(nn.Module):
         ask = self._ask_pairs("explain_occlusion_pairs", feats, qfeats, image_index, question_index, answers,
                               own=lambda: _check_window("VqaNet.explain_occlusion_pairs", window))
         return self._explain_occlusion(feats, ask, window, _u_bytes)
+
+    # ------------------------------------------------------------------ deletion and insertion curves of an attribution map
+    @torch.no_grad()
+    def explain_faithfulness(self, feats: ImageFeatures, q, q_len, image_index, maps, answers=None, *,
+                             _u_bytes=None) -> Faithfulness:
+        """answer() with the deletion and insertion curves of a caller-supplied map per question: Faithfulness(deletion fp32
+        [B, P+1], insertion fp32 [B, P+1], order int64 [B, P], answers int64 [B], logits fp32 [B, A]), P = gh * gw.  For
+        question b about image n = image_index[b] and the answer column a_b = answers[b],
+
+            order[b, :]     = the grid positions by descending maps[b, :], equal values by the smaller position
+            deletion[b, k]  = logits[b, a_b] with the positions order[b, :k] absent
+            insertion[b, k] = logits[b, a_b] with only the positions order[b, :k] present              k = 0 .. P
+
+        where "absent" is explain_occlusion()'s "occluded": the rows of vn (hence of v') are zero, exactly what answer()
+        computes on a cache with those rows zeroed.  deletion[:, 0] and insertion[:, P] are the full logit, deletion[:, P] and
+        insertion[:, 0] the logit of the empty image (bit-equal).  This is the standard measure of how well a map RANKS the
+        positions, so two maps of the same question can be compared: the better ranking has the smaller deletion_auc() and the
+        larger insertion_auc().  Both whole curves cost about as much as one explain_occlusion() call: the same U product
+        (the classifier's first layer on every feature row of the distinct asked images, in chunks of images under a 256 MiB
+        workspace), a ranking kernel and a streaming walk along the ranking (include/vqa_hip.h vqa_rank_desc, vqa_occl_curves).
+        Eval mode, the question held fixed; logit curves, not probability curves.
+
+        maps: a floating tensor of B * P elements shaped [B, gh, gw] or [B, P], on the host or on the cache's device, used as
+        fp32 -- what explain(), explain_pairs(), explain_occlusion() give as .maps, or one glimpse of answer(...,
+        return_attention=True); a random map is the baseline.  Neither upsampled nor normalised: only its order matters.  -0.0
+        and +0.0 are equal and NaN ranks last.  TypeError for a non-floating dtype, ValueError for a wrong element count or
+        shape or for P above 8192, all raised before any device work.
+
+        Conditioning.  Every sum runs over the positions that remain, so nothing is subtracted and the alpha <= 16 condition of
+        explain_occlusion() does not apply: the curves keep their relative accuracy when a kept set holds a hundredth of the
+        attention mass and alpha reaches the thousands (DESIGN.md 4.20 has the measured error).
+
+        answers, logits, the `answers` argument, the argument rules and the refusals are explain()'s, judged before any device
+        work: eval mode only (RuntimeError in train mode), fp32 / fp32x3 (NotImplementedError for "bf16"), features that hold
+        v', the feature-ownership checks and image_index rules; all three do_option values; fp32 and float16 caches (a float16
+        cache gives, bit for bit, what feats.to(torch.float32) gives); a CUDA `answers` entry outside [0, A) gives two rows of
+        +0.0; B == 0 returns empty tensors.  Rows come back in the caller's order and do not depend on how the batch is
+        ordered.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad and the dropout seed stream are left
+        alone.
+
+        Not offered: bf16 mode, train mode, data parallelism; probability curves (every column of lin2 per step); strided or
+        coarser curves; word-level and pixel-level curves; upsampling or normalising the maps.
+
+        _u_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
+        what = "explain_faithfulness"
+        ask = self._ask_questions(what, feats, q, q_len, image_index, answers,
+                                  own=lambda: _check_maps(f"VqaNet.{what}", maps, len(q), getattr(feats, "grid", None)))
+        return self._explain_faithfulness(feats, ask, maps, _u_bytes)
+
+    def _explain_faithfulness(self, feats, ask, maps, u_bytes) -> Faithfulness:
+        if ask.B == 0:
+            return self._no_result(Faithfulness, feats)
+        rows, slot = self._ask_upload(feats, ask, compact_image_index(ask.index[2], feats.N)[:2])
+        maps = torch.as_tensor(maps).detach().to(device=feats.vn.device, dtype=torch.float32).reshape(ask.B, -1).contiguous()
+        deletion, insertion, order, cols, logits = self._ask_run(self._engine.explain_faithfulness, feats, ask, rows, slot, maps,
+                                                                 u_bytes)
+        return Faithfulness(deletion, insertion, order.long(), cols.long(), logits)
+
+    @torch.no_grad()
+    def explain_faithfulness_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, maps,
+                                   answers=None, *, _u_bytes=None) -> Faithfulness:
+        """explain_faithfulness() for B (image, question) pairs from the two caches, as answer_pairs() is to answer(): pair b
+        looks at image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  The
+        curves, order, answers, maps and the `answers` argument are explain_faithfulness()'s; logits are answer_pairs()'s for the
+        same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the maps and
+        `answers` checks judged first."""
+        what = "explain_faithfulness_pairs"
+        ask = self._ask_pairs(what, feats, qfeats, image_index, question_index, answers,
+                              own=lambda: _check_maps(f"VqaNet.{what}", maps, torch.as_tensor(image_index).numel(),
+                                                      getattr(feats, "grid", None)))
+        return self._explain_faithfulness(feats, ask, maps, _u_bytes)
 
     # ------------------------------------------------------------------ gradient x input per question token
     @torch.no_grad()

@@ -757,6 +757,62 @@ def occl_logit(base, Z, U, slot, probs, score, cnull, W2, b2, answers, logits, g
     return out
 
 
+RANK_MAX_P = 8192   # include/vqa_hip.h vqa_rank_desc: the row's keys live in LDS
+
+
+def rank_desc(maps, out=None):
+    """The positions of every row of maps fp32 [B, P] by descending value (include/vqa_hip.h vqa_rank_desc): int32 [B, P], equal
+    values by the smaller position, -0.0 equal to +0.0, NaN last; a permutation of 0 .. P-1 for any input.  P <= 8192."""
+    _chk(maps)
+    assert maps.dim() == 2 and maps.is_contiguous()
+    B, P = maps.shape
+    if out is None:
+        out = torch.empty(B, P, dtype=torch.int32, device=maps.device)
+    assert out.shape == (B, P) and out.is_contiguous() and out.dtype == torch.int32
+    call("vqa_rank_desc", ptr(maps), ptr(out), B, P, stream())
+    return out
+
+
+def occl_curves_chunk() -> int:
+    """L: the steps per chunk of the ranking that vqa_occl_curves was built with."""
+    return _lib.load().vqa_occl_curves_chunk()
+
+
+def occl_curves_workspace(B: int, P: int, G: int, hid: int, device):
+    """A buffer of vqa_occl_curves_workspace_bytes(B, P, G, hid): the chunk sums of one call, freed with the call."""
+    need = _lib.load().vqa_occl_curves_workspace_bytes(B, P, G, hid)
+    return torch.empty(max(need // 4, 4), dtype=torch.float32, device=device)
+
+
+def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot0: int = 0, out=None, workspace=None):
+    """Deletion and insertion curves (include/vqa_hip.h vqa_occl_curves): (deletion, insertion) fp32 [B, P+1], the logit of
+    column answers[b] with the positions order[b, :k] absent / alone present, k = 0 .. P, in the kept form.  The operands are
+    occl_logit's without Z, window and logits, plus order int32 [B, P].  out: (deletion, insertion), written in place for the
+    questions whose slot is in [slot0, slot0 + R); workspace: a float32 buffer of at least vqa_occl_curves_workspace_bytes."""
+    B, G, P = probs.shape
+    R, hid, A = U.shape[0], base.shape[1], W2.shape[0]
+    for t in (base, U, probs, score, cnull, b2):
+        _chk(t)
+        assert t.is_contiguous()
+    _chk(slot, torch.int32), _chk(answers, torch.int32), _chk(order, torch.int32), _chk(W2)
+    assert score.shape == probs.shape and base.shape == (B, hid) and U.shape == (R, P, G, hid)
+    assert cnull.numel() == B * G and slot.numel() == B and answers.numel() == B and order.shape == (B, P) and order.is_contiguous()
+    assert W2.shape[1] == hid and b2.numel() == A and (hid == 1 or W2.stride(1) == 1)
+    if out is None:
+        out = tuple(torch.empty(B, P + 1, dtype=torch.float32, device=probs.device) for _ in range(2))
+    deletion, insertion = out
+    for t in out:
+        assert t.shape == (B, P + 1) and t.is_contiguous() and t.dtype == torch.float32
+    if workspace is None:
+        workspace = occl_curves_workspace(B, P, G, hid, probs.device)
+    _chk(workspace)
+    assert workspace.is_contiguous()
+    call("vqa_occl_curves", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2),
+         W2.stride(0) if A > 1 else hid, ptr(b2), ptr(answers), ptr(order), ptr(workspace), workspace.numel() * 4, ptr(deletion),
+         ptr(insertion), R, B, P, hid, G, A, stream())
+    return deletion, insertion
+
+
 def lstm_occl_cell_fwd(xg_base, xg0, hg, h_var, c_var, q_len, var_b, var_t, s: int, n: Optional[int] = None, c_final=None,
                        cf_row=None):
     """One step, time s, of the variant recurrence of exact word occlusion (include/vqa_hip.h vqa_lstm_occl_cell_fwd), in place

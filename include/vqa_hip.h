@@ -46,7 +46,9 @@ extern "C" {
  * vqa_att_attr_score_grouped_pairs_f16; declared behind those of the cached-feature paths they extend), and then the three of
  * gradient x input per question token (vqa_att_attr_dq_grouped, vqa_att_attr_dq_grouped_f16, vqa_embed_attr; declared behind
  * the attribution entry points), and then the one of occlusion maps (vqa_occl_logit; declared behind those), and
- * then the two of exact word occlusion (vqa_lstm_occl_cell_fwd, vqa_occl_words; declared behind vqa_occl_logit). */
+ * then the two of exact word occlusion (vqa_lstm_occl_cell_fwd, vqa_occl_words; declared behind vqa_occl_logit), and then the
+ * four of deletion and insertion curves (vqa_rank_desc, vqa_occl_curves_chunk, vqa_occl_curves_workspace_bytes, vqa_occl_curves;
+ * declared behind those). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -573,6 +575,52 @@ int vqa_lstm_occl_cell_fwd(const float* xg_base, const float* xg0, const float* 
 int vqa_occl_words(const float* h1, int64_t h1_ld, const float* W2, int64_t w2_ld, const float* b2, const int32_t* answers,
                    const float* logits, int64_t logits_ld, const int32_t* var_b, const int32_t* var_t, const int64_t* q_len,
                    float* words, int n, int b0, int nb, int T, int hid, int A, vqa_stream_t stream);
+
+/* ---- deletion and insertion curves of an attribution map (inference, VqaNet.explain_faithfulness; csrc/faithfulness.hip,
+ * DESIGN.md 4.20) ----
+ * How well a map over the P grid positions ranks them: for question b about image n and answer column a_b, with order[b][:] the
+ * positions by descending map value,
+ *   insertion[b][k] = logit[b][a_b] with only the positions order[b][0 .. k) present
+ *   deletion[b][k]  = logit[b][a_b] with the positions order[b][0 .. k) absent                      k = 0 .. P
+ * "absent" in the sense of vqa_occl_logit: the rows of vn and v' are zero, so the position keeps the score cnull[b][g].  Both
+ * are computed in the KEPT FORM, for the kept set K (order[b][0 .. k) for insertion, order[b][k .. P) for deletion), with r,
+ * cnull, base and U as vqa_occl_logit defines them:
+ *   m[b][g]      = sum_{s in K} probs[b][g][s]
+ *   acc[b][g][:] = sum_{s in K} probs[b][g][s] * U[n][s][g][:]
+ *   alpha[b][g]  = 1 / (m + (P - |K|) * r[b][g])
+ *   logit_K      = W2[a_b][:] . relu(base[b] + sum_g alpha * acc[b][g]) + b2[a_b]
+ * Sums over what remains: nothing is subtracted, so neither the Z - sum nor the 1 - mass cancellation of vqa_occl_logit occurs
+ * and Z is not an operand.  deletion[b][0] and insertion[b][P] are the full logit by this route, deletion[b][P] and
+ * insertion[b][0] the logit of the empty image, bit-equal to each other.
+ *   vqa_rank_desc: order int32 [B][P] from maps fp32 [B][P] under ONE total order -- larger value first, equal values by the
+ *     smaller position (vqa_softmax_topk's rule); -0.0 and +0.0 are equal; every NaN ranks below -inf, several NaNs by position.
+ *     Each float becomes a monotone 32-bit key and rank[p] = #{s : key[s] > key[p] or (key[s] == key[p] and s < p)}, order[rank[p]]
+ *     = p: a permutation of 0 .. P-1 for any input.  One workgroup per row, the row's keys in LDS; 1 <= P <= 8192, anything else
+ *     is VQA_ERR_INVALID before any HIP call.  B == 0 returns without a launch.
+ *   vqa_occl_curves_chunk: L, the compile-time number of steps per chunk of the ranking (16).
+ *   vqa_occl_curves: the operands of vqa_occl_logit without Z, window, logits and maps, plus order int32 [B][P] (any int32
+ *     values: an entry outside [0, P) adds nothing to m and acc and is never used as an address; it still counts as a step, so
+ *     |K| is the number of steps), a workspace of vqa_occl_curves_workspace_bytes(B, P, G, hid) bytes, and deletion / insertion
+ *     [B][P + 1].  Three launches.  (1) one wave per (b, chunk of L steps): the chunk's sum of probs * U rows, its steps in
+ *     ascending order from 0, and of the weights.  (2) per element, over the chunks: the sums of the chunks before each chunk,
+ *     ascending, and of the chunks after it, descending.  (3) one wave per (b, chunk), four chunks per workgroup, whose head
+ *     stages base and W2[a_b] in LDS and forms r by vqa_occl_logit's two block reductions: the insertion sums start from the
+ *     chunk's prefix and add its rows forward, the deletion sums start from its suffix and add its rows backward, the masses
+ *     likewise; lane l over the quads l, l + 64, ... of hid with 16-byte loads, g ascending, and the wave butterfly per step.
+ *     One summation order per (b, k), fixed by order[b] and L alone: it does not depend on the grid, on the batch or on how the
+ *     images are chunked; no atomics; every element written once.  Permuting the questions permutes the rows bit for bit.
+ *     A question whose row slot[b] - slot0 is outside [0, R) is LEFT ALONE (both outputs), as by vqa_occl_logit; a column a_b
+ *     outside [0, A) gives two rows of +0.0.
+ *     Limits: hid % 4 == 0, w2_ld % 4 == 0, 2 * hid * 4 + 80 <= 65536 bytes of LDS, G in 1..4, P <= 2^20, base, U, W2 and the
+ *     workspace 16-byte aligned, the workspace large enough; anything else is VQA_ERR_INVALID before any HIP call.  B == 0
+ *     returns without a launch and needs no workspace. */
+int vqa_rank_desc(const float* maps, int32_t* order, int B, int P, vqa_stream_t stream);
+int vqa_occl_curves_chunk(void);
+int64_t vqa_occl_curves_workspace_bytes(int B, int P, int G, int hid);
+int vqa_occl_curves(const float* base, const float* U, const int32_t* slot, int slot0, const float* probs, const float* score,
+                    const float* cnull, const float* W2, int64_t w2_ld, const float* b2, const int32_t* answers,
+                    const int32_t* order, float* workspace, int64_t workspace_bytes, float* deletion, float* insertion, int R,
+                    int B, int P, int hid, int G, int A, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
