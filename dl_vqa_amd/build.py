@@ -16,7 +16,7 @@ SOURCES = ([("gemm.hip", f"_p{k}", [f"-DVQA_GEMM_PART={k}"]) for k in (2, 3, 4, 
            + ["bf16.hip", ("gemm.hip", "_p1", ["-DVQA_GEMM_PART=1"]), "conv.hip", "conv_x3.hip", "conv_bf16.hip", "conv_patch_bf16.hip", "conv_patch_f32.hip", "gemm_tall_bf16.hip", "gemm.hip",
               "gemm_x3.hip", "runtime.hip", "conv0.hip", "conv0_dgrad.hip", "lstm.hip", "elementwise.hip", "conv_generic.hip", "att_score.hip", "att_apply.hip", "occlusion.hip", "faithfulness.hip", "lstm_occl.hip", "topk.hip", "preprocess.hip",
               "gather.hip", "adam.hip"])
-HEADERS = ["common.hpp", "cache_load.hpp", "gemm_core.hpp", "gemm_epilogue.hpp", "gemm_host.hpp", "bf16_core.hpp", "x3_core.hpp", "conv_device.inc", "conv_host.inc", "conv_bf16.inc", os.path.join("..", "..", "include", "vqa_hip.h")]
+HEADERS = ["common.hpp", "cache_load.hpp", "occl_core.hpp", "gemm_core.hpp", "gemm_epilogue.hpp", "gemm_host.hpp", "bf16_core.hpp", "x3_core.hpp", "conv_device.inc", "conv_host.inc", "conv_bf16.inc", os.path.join("..", "..", "include", "vqa_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 
 

@@ -116,8 +116,7 @@ int vqa_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
 int vqa_adam_segments(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                       const vqa_adam_segment* segs, int n_segs, float grad_scale, vqa_stream_t stream) {
   VQA_REQUIRE(param && grad && exp_avg && exp_avg_sq && segs, "vqa_adam_segments: null pointer");
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-                reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
+  VQA_REQUIRE((ptr_bits(param, grad, exp_avg, exp_avg_sq) & 15) == 0,
               "vqa_adam_segments: param, grad, exp_avg and exp_avg_sq must be 16-byte aligned");
   VQA_REQUIRE(n >= 1 && n_segs >= 1 && n_segs <= VQA_ADAM_MAX_SEGMENTS, "vqa_adam_segments: n=%lld, n_segs=%d out of range (1..%d segments)",
               (long long)n, n_segs, VQA_ADAM_MAX_SEGMENTS);

@@ -276,12 +276,8 @@ using namespace vqa;
 // dynamic LDS of both forward kernels (the scalar one uses less of it): probs [G][P], 16 reduction slots, part [16][G][64]
 static size_t att_apply_fwd_lds(int G, int P) { return ((size_t)G * P + 16 + 16 * G * 64) * 4; }
 
-static uintptr_t quad_bits(const void* a, const void* b, const void* c) {
-  return reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
-}
-
 // What the entry points check, before any HIP call (`who` names the caller in the messages).  backward: the kernels
-// read dout / vn and write dvn as float4, so C and the leading dimension are multiples of 4 and `quads` (quad_bits of those
+// read dout / vn and write dvn as float4, so C and the leading dimension are multiples of 4 and `quads` (ptr_bits of those
 // pointers, a null one counts as aligned) is 16-byte aligned.  pointers / indices: the form's data pointers and its
 // img / order / offsets are all there (true for a form without indices).  N: 1 for a form without an image count.
 static int att_apply_check(const char* who, bool backward, bool pointers, bool indices, int N, int B, int P, int C, int G,
@@ -312,7 +308,7 @@ static int att_apply_fwd_launch(const float* score, const VT* vn, const int32_t*
   if (B == 0) return VQA_OK;
   const dim3 grid(B, (C + 63) / 64);
   const size_t lds = att_apply_fwd_lds(G, P);
-  const bool quads = C % 4 == 0 && (reinterpret_cast<uintptr_t>(vn) & (kQuadAlign<VT> - 1)) == 0;
+  const bool quads = C % 4 == 0 && (ptr_bits(vn) & (kQuadAlign<VT> - 1)) == 0;
   return with_int14(G, [&](auto g) {
     return with_gather<VT>(img != nullptr, [&](auto gather) {
       return with_flag(quads, [&](auto v4) {
@@ -388,7 +384,7 @@ int vqa_att_apply_bwd(const float* dout, int64_t dout_ld, const float* probs, co
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   const int rc = att_apply_check("vqa_att_apply_bwd", true, dout && probs && vn && dscore, true, 1, B, P, C, G, dout_ld,
-                                 quad_bits(dout, vn, dvn));
+                                 ptr_bits(dout, vn, dvn));
   return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, nullptr, nullptr, nullptr, dscore, dvn, dscore_rowsum, 0, B, P,
                                         C, G, STREAM);
 }
@@ -399,7 +395,7 @@ int vqa_att_apply_gather_bwd(const float* dout, int64_t dout_ld, const float* pr
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   const int rc = att_apply_check("vqa_att_apply_gather_bwd", true, dout && probs && vn && dscore && dvn, img && order && offsets,
-                                 N, B, P, C, G, dout_ld, quad_bits(dout, vn, dvn));
+                                 N, B, P, C, G, dout_ld, ptr_bits(dout, vn, dvn));
   return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, order, offsets, dscore, dvn, dscore_rowsum, N, B, P, C, G,
                                         STREAM);
 }
@@ -409,7 +405,7 @@ int vqa_att_apply_gather_dscore(const float* dout, int64_t dout_ld, const float*
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   const int rc = att_apply_check("vqa_att_apply_gather_dscore", true, dout && probs && vn && dscore, img, N, B, P, C, G, dout_ld,
-                                 quad_bits(dout, vn, nullptr));
+                                 ptr_bits(dout, vn));
   return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, nullptr, nullptr, dscore, nullptr, dscore_rowsum, N, B, P,
                                         C, G, STREAM);
 }
@@ -421,7 +417,7 @@ int vqa_att_attr_apply_gather(const float* dout, int64_t dout_ld, const float* p
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   const int rc = att_apply_check("vqa_att_attr_apply_gather", true, dout && probs && vn && dscore && r1, img, N, B, P, C, G,
-                                 dout_ld, quad_bits(dout, vn, nullptr));
+                                 dout_ld, ptr_bits(dout, vn));
   return rc ? rc : att_apply_bwd_launch(dout, dout_ld, probs, vn, img, nullptr, nullptr, dscore, nullptr, dscore_rowsum, N, B, P,
                                         C, G, STREAM, r1);
 }
@@ -432,9 +428,9 @@ int vqa_att_attr_apply_gather_f16(const float* dout, int64_t dout_ld, const floa
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   const int rc = att_apply_check("vqa_att_attr_apply_gather_f16", true, dout && probs && vn_f16 && dscore && r1, img, N, B, P, C,
-                                 G, dout_ld, quad_bits(dout, nullptr, nullptr));
+                                 G, dout_ld, ptr_bits(dout));
   if (rc) return rc;
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & (kQuadAlign<__half> - 1)) == 0,
+  VQA_REQUIRE((ptr_bits(vn_f16) & (kQuadAlign<__half> - 1)) == 0,
               "vqa_att_attr_apply_gather_f16: vn must be 8-byte aligned");
   return att_apply_bwd_launch(dout, dout_ld, probs, static_cast<const __half*>(vn_f16), img, nullptr, nullptr, dscore, nullptr,
                               dscore_rowsum, N, B, P, C, G, STREAM, r1);
@@ -449,7 +445,7 @@ int vqa_att_apply_gather_fwd_f16(const float* score, const void* vn_f16, const i
   const int rc = att_apply_check("vqa_att_apply_gather_fwd_f16", false, score && vn_f16 && probs && out, img, N, B, P, C, G, out_ld,
                                  0);
   if (rc) return rc;
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & 1) == 0, "vqa_att_apply_gather_fwd_f16: vn must be 2-byte aligned");
+  VQA_REQUIRE((ptr_bits(vn_f16) & 1) == 0, "vqa_att_apply_gather_fwd_f16: vn must be 2-byte aligned");
   return att_apply_fwd_launch(score, static_cast<const __half*>(vn_f16), img, probs, out, out_ld, N, B, P, C, G, STREAM);
 }
 
@@ -459,10 +455,10 @@ int vqa_att_apply_gather_dscore_f16(const float* dout, int64_t dout_ld, const fl
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_APPLY_BWD, (hipStream_t)stream);
   const int rc = att_apply_check("vqa_att_apply_gather_dscore_f16", true, dout && probs && vn_f16 && dscore, img, N, B, P, C, G,
-                                 dout_ld, quad_bits(dout, nullptr, nullptr));
+                                 dout_ld, ptr_bits(dout));
   if (rc) return rc;
   // the rows kernel reads a quad of halves as 8 bytes where the fp32 form reads 16
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(vn_f16) & (kQuadAlign<__half> - 1)) == 0,
+  VQA_REQUIRE((ptr_bits(vn_f16) & (kQuadAlign<__half> - 1)) == 0,
               "vqa_att_apply_gather_dscore_f16: vn must be 8-byte aligned");
   return att_apply_bwd_launch(dout, dout_ld, probs, static_cast<const __half*>(vn_f16), img, nullptr, nullptr, dscore, nullptr,
                               dscore_rowsum, N, B, P, C, G, STREAM);

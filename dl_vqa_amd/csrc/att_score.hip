@@ -917,16 +917,11 @@ __global__ __launch_bounds__(256) void att_attr_dq_grouped_general_kernel(const 
 using namespace vqa;
 
 // ---------------------------------------------------------------- host side
-static uintptr_t bits(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-         reinterpret_cast<uintptr_t>(d);
-}
-
 // What the six score entry points check, before any HIP call (`who` names the caller in the messages).
 // grouped: the form has an LDS tile of v' that bounds mid.  pointers: the form's data pointers are all there, those its mode
 // needs included.  indices: its order / offsets (true for a plain form).  N: 1 for a form without an image count.
 // mode: 0 '+', 1 '*', 2 '|' -- x has 2 * mid channels for '|' (the plain forward passes 2 where it has a qcat, else 0).
-// p: the x_conv dropout (0 for a form without).  quads: bits() of what the kernels read or write as float4 whatever the
+// p: the x_conv dropout (0 for a form without).  quads: ptr_bits() of what the kernels read or write as float4 whatever the
 // path -- wx, the q' / v' operands, the backward's outputs; a null pointer counts as aligned.  The plain forms' xs is not
 // among them: its alignment selects the forward's register kernels and is no error.
 static int att_score_check(const char* who, bool grouped, bool pointers, bool indices, int N, int B, int P, int mid, int wx_ld,
@@ -947,7 +942,7 @@ static int att_score_check(const char* who, bool grouped, bool pointers, bool in
 // the kernel of vqa_att_score_fwd: the register kernels need an xs they can read 16 bytes at a time and no concatenated half
 enum ScoreFwdPath { SCORE_FWD_BF16_ROWS, SCORE_FWD_ROWS, SCORE_FWD_GENERAL };
 static ScoreFwdPath att_score_fwd_path(const void* xs, bool bf16, bool qcat, int mid, int G) {
-  if (qcat || mid > 1024 || (bits(xs) & 15) != 0) return SCORE_FWD_GENERAL;
+  if (qcat || mid > 1024 || (ptr_bits(xs) & 15) != 0) return SCORE_FWD_GENERAL;
   if (bf16) return mid % 8 == 0 ? SCORE_FWD_BF16_ROWS : SCORE_FWD_GENERAL;
   return G <= 2 && mid % 256 == 0 ? SCORE_FWD_ROWS : SCORE_FWD_GENERAL;      // the rows kernel exists for one and two glimpses only
 }
@@ -975,9 +970,9 @@ static int grouped_fwd(const char* who, const VT* vprime, const float* qp, const
                        int mid, int G, int mode, float p, uint64_t seed, hipStream_t s) {
   constexpr bool f32 = std::is_same<VT, float>::value;
   const int rc = att_score_check(who, true, vprime && qp && wx && bx && score, order && offsets, N, B, P, mid, wx_ld, G, mode, p,
-                                 f32 ? bits(vprime, qp, wx) : bits(qp, wx));
+                                 f32 ? ptr_bits(vprime, qp, wx) : ptr_bits(qp, wx));
   if (rc) return rc;
-  VQA_REQUIRE((bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  VQA_REQUIRE((ptr_bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
   if (B == 0) return VQA_OK;
   const float ik = keep_scale(p);
   const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
@@ -1014,9 +1009,9 @@ static int grouped_attr(const char* who, const float* r1, const float* dscore, c
                         float* out, int N, int B, int P, int mid, int G, int mode, hipStream_t s) {
   constexpr bool f32 = std::is_same<VT, float>::value;
   const int rc = att_score_check(who, true, r1 && dscore && vprime && wx && out && (mode == 2 || qp), order && offsets, N, B, P,
-                                 mid, wx_ld, G, mode, 0.f, f32 ? bits(vprime, qp, wx) : bits(qp, wx));
+                                 mid, wx_ld, G, mode, 0.f, f32 ? ptr_bits(vprime, qp, wx) : ptr_bits(qp, wx));
   if (rc) return rc;
-  VQA_REQUIRE((bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  VQA_REQUIRE((ptr_bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
   if (B == 0) return VQA_OK;
   const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
   const dim3 grid((P + TP - 1) / TP, N);
@@ -1059,9 +1054,9 @@ static int grouped_attr_dq(const char* who, const float* dscore, const VT* vprim
               "softmax is shift-invariant, so d logit / d q' through the scores is identically zero (modes 0 '+' and 1 '*' only)",
               who);
   const int rc = att_score_check(who, true, dscore && vprime && qp && wx && dq_part, order && offsets, N, B, P, mid, wx_ld, G,
-                                 mode, 0.f, (f32 ? bits(vprime, qp, wx) : bits(qp, wx)) | bits(dq_part));
+                                 mode, 0.f, (f32 ? ptr_bits(vprime, qp, wx) : ptr_bits(qp, wx)) | ptr_bits(dq_part));
   if (rc) return rc;
-  VQA_REQUIRE((bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  VQA_REQUIRE((ptr_bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
   if (B == 0) return VQA_OK;
   const dim3 grid((P + BTP - 1) / BTP, N);                 // vqa_att_score_grouped_tiles(P)
   with_int14(G, [&](auto g) {
@@ -1096,7 +1091,7 @@ int vqa_att_score_fwd(const void* xs, int xs_is_bf16, const float* wx, int wx_ld
   set_launch_tag(-1);
   ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
   const int rc = att_score_check("vqa_att_score_fwd", false, xs && wx && bx && score, true, 1, B, P, mid, wx_ld, G, qcat ? 2 : 0, p,
-                                 bits(wx, qcat));
+                                 ptr_bits(wx, qcat));
   if (rc) return rc;
   if (B == 0) return VQA_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -1138,7 +1133,7 @@ int vqa_att_score_bwd(const float* dscore, const float* wx, int wx_ld, void* xs_
   ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
   const bool operands = (mode != 1 || (vprime && qp)) && (mode != 2 || qp);      // '+' reads neither
   const int rc = att_score_check("vqa_att_score_bwd", false, dscore && wx && xs_inout && dwx_part && dq_part && operands, true, 1,
-                                 B, P, mid, wx_ld, G, mode, p, bits(wx, dwx_part, dq_part, mode ? qp : nullptr) | bits(mode == 1 ? vprime : nullptr));
+                                 B, P, mid, wx_ld, G, mode, p, ptr_bits(wx, dwx_part, dq_part, mode ? qp : nullptr, mode == 1 ? vprime : nullptr));
   if (rc) return rc;
   if (B == 0) return VQA_OK;
   const int RS = vqa_att_row_splits(P);
@@ -1190,7 +1185,7 @@ int vqa_att_score_grouped_bwd(const float* dscore, const float* vprime, const fl
   ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
   const int rc = att_score_check("vqa_att_score_grouped_bwd", true, dscore && vprime && qp && wx && dvprime && dq_part && dwx_part,
                                  order && offsets, N, B, P, mid, wx_ld, G, mode, p,
-                                 bits(vprime, qp, wx) | bits(dvprime, dq_part, dwx_part));
+                                 ptr_bits(vprime, qp, wx, dvprime, dq_part, dwx_part));
   if (rc) return rc;
   if (B == 0) return VQA_OK;
   hipStream_t s = (hipStream_t)stream;

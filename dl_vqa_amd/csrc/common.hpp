@@ -72,6 +72,11 @@ static int with_int14(int v, F&& f) {
   }
 }
 
+// The addresses of the arguments ORed together (host only): (ptr_bits(a, b, c) & 15) == 0 says that all of them are 16-byte
+// aligned.  A null pointer contributes nothing, so an operand that is not there counts as aligned.
+template <class... P>
+static inline uintptr_t ptr_bits(const P*... p) { return (uintptr_t{0} | ... | reinterpret_cast<uintptr_t>(p)); }
+
 // what a kept element is multiplied by under dropout p: 1 / (1 - p), 1 at p = 0
 static inline float keep_scale(float p) { return p > 0.f ? 1.0f / (1.0f - p) : 1.0f; }
 

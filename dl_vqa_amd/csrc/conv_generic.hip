@@ -159,7 +159,6 @@ static int convk_geom(const char* fn, int B, int H, int W, int C, int ks, int st
   *Wo = (W - ks) / stride + 1;
   return VQA_OK;
 }
-#define ALIGNED16(p) (((uintptr_t)(p) % 16) == 0)
 
 }  // namespace vqa
 
@@ -187,7 +186,7 @@ int vqa_convk_unpack_wgrad(const float* dwk, float* dw, int Co, int Ci, int CiP,
 int vqa_convk_im2col(const float* x, float* cols, int B, int H, int W, int CiP, int ks, int stride, vqa_stream_t stream) {
   int Ho, Wo;
   if (int rc = convk_geom("vqa_convk_im2col", B, H, W, CiP, ks, stride, &Ho, &Wo)) return rc;
-  VQA_REQUIRE(x && cols && ALIGNED16(x) && ALIGNED16(cols), "vqa_convk_im2col: null or unaligned pointer");
+  VQA_REQUIRE(x && cols && (ptr_bits(x, cols) & 15) == 0, "vqa_convk_im2col: null or unaligned pointer");
   const int64_t total4 = (int64_t)B * Ho * Wo * ks * ks * (CiP / 4);
   hipLaunchKernelGGL(convk_im2col_kernel, dim3(convk_grid(total4)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(x),
                      reinterpret_cast<float4*>(cols), total4, H, W, CiP / 4, ks, stride, Ho, Wo);
@@ -195,7 +194,7 @@ int vqa_convk_im2col(const float* x, float* cols, int B, int H, int W, int CiP, 
 }
 
 int vqa_convk_relu_pool(const float* y, float* pooled, uint8_t* amax, int B, int Ho, int Wo, int Co, vqa_stream_t stream) {
-  VQA_REQUIRE(y && pooled && amax && ALIGNED16(y) && ALIGNED16(pooled) && ((uintptr_t)amax % 4) == 0,
+  VQA_REQUIRE(y && pooled && amax && (ptr_bits(y, pooled) & 15) == 0 && (ptr_bits(amax) & 3) == 0,
               "vqa_convk_relu_pool: null or unaligned pointer");
   VQA_REQUIRE(B > 0 && Ho >= 2 && Wo >= 2 && Co > 0 && Co % 4 == 0, "vqa_convk_relu_pool: bad shape B=%d Ho=%d Wo=%d Co=%d", B, Ho,
               Wo, Co);
@@ -207,7 +206,7 @@ int vqa_convk_relu_pool(const float* y, float* pooled, uint8_t* amax, int B, int
 }
 
 int vqa_convk_route(const float* dpooled, const uint8_t* amax, float* dy, int B, int Ho, int Wo, int Co, vqa_stream_t stream) {
-  VQA_REQUIRE(dpooled && amax && dy && ALIGNED16(dpooled) && ALIGNED16(dy) && ((uintptr_t)amax % 4) == 0,
+  VQA_REQUIRE(dpooled && amax && dy && (ptr_bits(dpooled, dy) & 15) == 0 && (ptr_bits(amax) & 3) == 0,
               "vqa_convk_route: null or unaligned pointer");
   VQA_REQUIRE(B > 0 && Ho >= 2 && Wo >= 2 && Co > 0 && Co % 4 == 0, "vqa_convk_route: bad shape B=%d Ho=%d Wo=%d Co=%d", B, Ho, Wo, Co);
   const int64_t total4 = (int64_t)B * Ho * Wo * (Co / 4);
@@ -219,7 +218,7 @@ int vqa_convk_route(const float* dpooled, const uint8_t* amax, float* dy, int B,
 int vqa_convk_col2im(const float* dcols, float* dx, int B, int H, int W, int CiP, int ks, int stride, vqa_stream_t stream) {
   int Ho, Wo;
   if (int rc = convk_geom("vqa_convk_col2im", B, H, W, CiP, ks, stride, &Ho, &Wo)) return rc;
-  VQA_REQUIRE(dcols && dx && ALIGNED16(dcols) && ALIGNED16(dx), "vqa_convk_col2im: null or unaligned pointer");
+  VQA_REQUIRE(dcols && dx && (ptr_bits(dcols, dx) & 15) == 0, "vqa_convk_col2im: null or unaligned pointer");
   const int64_t total4 = (int64_t)B * H * W * (CiP / 4);
   hipLaunchKernelGGL(convk_col2im_kernel, dim3(convk_grid(total4)), dim3(256), 0, STREAM, reinterpret_cast<const float4*>(dcols),
                      reinterpret_cast<float4*>(dx), total4, H, W, CiP / 4, ks, stride, Ho, Wo);

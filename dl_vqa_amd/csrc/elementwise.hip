@@ -755,7 +755,7 @@ int vqa_dropout_add(const float* x, float* y, int64_t n, float p, uint64_t seed,
   set_launch_tag(n >= (1 << 22) ? 1 : 0);
   ProfScope prof(VQA_K_DROPOUT, (hipStream_t)stream);
   VQA_REQUIRE(x && y && n > 0 && p >= 0.f && p < 1.f, "vqa_dropout_add: bad args");
-  VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0, "vqa_dropout_add: pointers must be 16-byte aligned");
+  VQA_REQUIRE((ptr_bits(x, y) & 15) == 0, "vqa_dropout_add: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(dropout_add_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, STREAM, x, y, n, p, keep_scale(p), seed);
   return check_hip(hipGetLastError(), "dropout_add launch");
 }
@@ -848,10 +848,8 @@ int vqa_embed_attr(const int64_t* q, const float* emb, const float* x, const flo
   VQA_REQUIRE(q && emb && x && dx0 && q_len && words, "vqa_embed_attr: null pointer");
   VQA_REQUIRE(B >= 0 && T >= 1 && E >= 1 && V >= 1, "vqa_embed_attr: B=%d, T=%d, E=%d, V=%d out of range", B, T, E, V);
   if (B == 0) return VQA_OK;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(emb) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx0) |
-                      reinterpret_cast<uintptr_t>(dx1);
   const dim3 grid(grid_for((int64_t)B * T, 4));             // four waves, four slots per workgroup
-  with_flag(E % 4 == 0 && (a & 15) == 0, [&](auto vec) {
+  with_flag(E % 4 == 0 && (ptr_bits(emb, x, dx0, dx1) & 15) == 0, [&](auto vec) {
     hipLaunchKernelGGL((embed_attr_kernel<decltype(vec)::value>), grid, dim3(256), 0, STREAM, q, emb, x, dx0, dx1, q_len, words,
                        B, T, E, V);
     return 0;

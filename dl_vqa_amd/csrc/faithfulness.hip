@@ -4,7 +4,7 @@
 // nothing is ever subtracted.  The ranking is cut into chunks of CURVE_L steps: one pass sums each chunk's probs * U rows, a
 // small pass turns the chunk sums into exclusive prefixes (insertion) and suffixes (deletion), and the walk gives one wave per
 // (question, chunk), which steps through its rows from its prefix forward and from its suffix backward.
-#include "common.hpp"
+#include "occl_core.hpp"
 
 namespace vqa {
 
@@ -73,8 +73,8 @@ curve_chunk_sum_kernel(const float* U, const int* slot, int slot0, int R, const 
   const int64_t task = (int64_t)blockIdx.x * CURVE_WAVES + (threadIdx.x >> 6);
   if (task >= (int64_t)B * nch) return;                               // wave-uniform; no barrier in this kernel
   const int b = (int)(task / nch), c = (int)(task - (int64_t)b * nch);
-  const int row = slot[b] - slot0;
-  if ((unsigned)row >= (unsigned)R) return;
+  const int row = occl_row(slot, b, slot0, R);
+  if (row < 0) return;
   const int k0 = c * CURVE_L, n = min(CURVE_L, P - k0), nq = hid >> 2;
   int pos;
   float w[G];
@@ -115,7 +115,7 @@ curve_scan_kernel(float* sum, float* pre, float* mass, float* mass_pre, const in
   const int64_t t = (int64_t)blockIdx.x * CURVE_THREADS + threadIdx.x;
   if (t >= (int64_t)B * per) return;
   const int b = (int)(t / per), e = (int)(t - (int64_t)b * per);
-  if ((unsigned)(slot[b] - slot0) >= (unsigned)R) return;
+  if (occl_row(slot, b, slot0, R) < 0) return;
   if (e < G * nq) {
     float4* s4 = reinterpret_cast<float4*>(sum) + (int64_t)b * nch * G * nq + e;
     float4* p4 = reinterpret_cast<float4*>(pre) + (int64_t)b * nch * G * nq + e;
@@ -164,13 +164,10 @@ __device__ __forceinline__ float kept_dot(const float4 (&acc)[G], const float (&
   return fmaf(w2.w, fmaxf(pre.w, 0.f), fmaf(w2.z, fmaxf(pre.z, 0.f), fmaf(w2.y, fmaxf(pre.y, 0.f), w2.x * fmaxf(pre.x, 0.f))));
 }
 
-// dynamic LDS of the walk: base [hid], W2[a] [hid], then 16 reduction slots and r [G] (4 floats kept for it)
-static size_t curve_lds(int hid) { return ((size_t)2 * hid + 16 + 4) * 4; }
-
-// The walk.  Workgroup = (question b, CURVE_WAVES consecutive chunks); its head is occl_logit_kernel's: base and W2[a] into
-// LDS and r[g] by the two block reductions.  Then wave w takes chunk c: state j of the chunk, j = 0 .. n, has the chunk's
-// first j steps on the insertion side (kept set order[: k0 + j]) and its steps j .. n-1 on the deletion side (kept set
-// order[k0 + j :]).  Lane j holds step j's position and weights and both alphas of state j; the masses are walked by every
+// The walk.  Workgroup = (question b, CURVE_WAVES consecutive chunks); it starts with occl_head (occl_core.hpp): base and
+// W2[a] into LDS and r[g]; dynamic LDS occl_lds(2, hid).  Then wave w takes chunk c: state j of the chunk, j = 0 .. n, has
+// the chunk's first j steps on the insertion side (kept set order[: k0 + j]) and its steps j .. n-1 on the deletion side (kept
+// set order[k0 + j :]).  Lane j holds step j's position and weights and both alphas of state j; the masses are walked by every
 // lane alike.  Per quad the insertion sums start from the prefix and add the rows j = 0 .. n-1, the deletion sums start from
 // the suffix and add the rows j = n-1 .. 0; each state's dot product is finished by the wave butterfly.  insertion[k0 + j] is
 // written for j = 1 .. n (j = 0 by chunk 0 alone), deletion[k0 + j] for j = 0 .. n-1 (j = n by the last chunk alone): every
@@ -184,8 +181,8 @@ curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0,
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int b = blockIdx.x / ngroup;
   const int cg = blockIdx.x - b * ngroup;
-  const int row = slot[b] - slot0;
-  if ((unsigned)row >= (unsigned)R) return;                           // block-uniform
+  const int row = occl_row(slot, b, slot0, R);
+  if (row < 0) return;                                                // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int a = answers[b];
   float* del = deletion + (int64_t)b * (P + 1);
@@ -201,22 +198,7 @@ curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0,
   float* red = sm + 2 * (size_t)hid;  // [16]
   float* s_r = red + 16;              // [G]
   const int nq = hid >> 2;
-  for (int q = tid; q < nq; q += CURVE_THREADS) {
-    reinterpret_cast<float4*>(s_base)[q] = reinterpret_cast<const float4*>(base + (int64_t)b * hid)[q];
-    reinterpret_cast<float4*>(s_w2)[q] = reinterpret_cast<const float4*>(W2 + (int64_t)a * w2_ld)[q];
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const float* s = score + ((int64_t)b * G + g) * P;
-    float mx = -INFINITY;
-    for (int i = tid; i < P; i += CURVE_THREADS) mx = fmaxf(mx, s[i]);
-    mx = block_reduce(mx, red, true);
-    float sum = 0.f;
-    for (int i = tid; i < P; i += CURVE_THREADS) sum += expf(s[i] - mx);
-    sum = block_reduce(sum, red, false);
-    if (tid == 0) s_r[g] = expf(cnull[b * G + g] - mx) / sum;
-  }
-  __syncthreads();
+  occl_head<G, CURVE_THREADS>(base, score, cnull, W2, w2_ld, b, a, P, hid, s_base, s_w2, red, s_r);
   const int c = cg * CURVE_WAVES + wave;
   if (c >= nch) return;                                               // wave-uniform; no barrier below
   const int k0 = c * CURVE_L, n = min(CURVE_L, P - k0);
@@ -334,19 +316,16 @@ int vqa_occl_curves(const float* base, const float* U, const int32_t* slot, int 
                     int B, int P, int hid, int G, int A, vqa_stream_t stream) {
   set_launch_tag(-1);
   const char* who = "vqa_occl_curves";
-  VQA_REQUIRE(G >= 1 && G <= 4, "%s: glimpses=%d unsupported (1..4)", who, G);
-  VQA_REQUIRE(base && U && slot && probs && score && cnull && W2 && b2 && answers && order && deletion && insertion,
-              "%s: null pointer", who);
-  VQA_REQUIRE(hid >= 4 && hid % 4 == 0 && w2_ld % 4 == 0 && w2_ld >= hid, "%s: hid=%d (a multiple of 4), w2_ld=%lld out of range",
-              who, hid, (long long)w2_ld);
-  VQA_REQUIRE(R >= 1 && B >= 0 && P >= 1 && P <= (1 << 20) && A >= 1, "%s: R=%d, B=%d, P=%d, A=%d out of range", who, R, B, P, A);
-  VQA_REQUIRE(curve_lds(hid) <= 64 * 1024, "%s: 2*hid=%d too large for LDS", who, 2 * hid);
+  const bool pointers = base && U && slot && probs && score && cnull && W2 && b2 && answers && order && deletion && insertion;
+  // without questions nothing is read, so no alignment is asked for (and no workspace, below)
+  if (const int rc = occl_check(who, G, pointers, hid, w2_ld, 2, "2", B ? ptr_bits(base, U, W2, workspace) : 0,
+                                "base, U, W2 and the workspace", R >= 1 && B >= 0 && P >= 1 && P <= (1 << 20) && A >= 1,
+                                "%s: R=%d, B=%d, P=%d, A=%d out of range", R, B, P, A))
+    return rc;
   if (B == 0) return VQA_OK;
   const int64_t need = vqa_occl_curves_workspace_bytes(B, P, G, hid);
   VQA_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes,
               (long long)need);
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(W2) |
-                reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "%s: base, U, W2 and the workspace must be 16-byte aligned", who);
   const int nch = curve_chunks(P), nq = hid >> 2;
   const int ngroup = (nch + CURVE_WAVES - 1) / CURVE_WAVES;
   const int64_t tasks = (int64_t)B * nch, scan = (int64_t)B * (G * nq + G);
@@ -371,7 +350,7 @@ int vqa_occl_curves(const float* base, const float* U, const int32_t* slot, int 
     // the attribute is set once per kernel, so for the largest LDS size the check above admits
     rc = set_smem(curve_walk_kernel<GG>, 64 * 1024, "attr(occl_curves)");
     if (rc) return rc;
-    hipLaunchKernelGGL(curve_walk_kernel<GG>, dim3(B * ngroup), dim3(CURVE_THREADS), curve_lds(hid), s, base, U, slot, slot0, R,
+    hipLaunchKernelGGL(curve_walk_kernel<GG>, dim3(B * ngroup), dim3(CURVE_THREADS), occl_lds(2, hid), s, base, U, slot, slot0, R,
                        probs, score, cnull, W2, w2_ld, b2, answers, order, sum, pre, mass, mass_pre, deletion, insertion, ngroup,
                        nch, P, hid, A);
     return check_hip(hipGetLastError(), "occl_curves walk launch");

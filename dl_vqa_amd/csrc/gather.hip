@@ -226,7 +226,7 @@ using namespace vqa;
 template <class VT>
 static int gather_rows_drop(const char* who, const VT* src, const int32_t* rows, float* dst, int n, int M, int64_t row_len, float p,
                             uint64_t seed, hipStream_t s) {
-  const uintptr_t sb = reinterpret_cast<uintptr_t>(src), db = reinterpret_cast<uintptr_t>(dst);
+  const uintptr_t sb = ptr_bits(src), db = ptr_bits(dst);
   VQA_REQUIRE(src && rows && dst, "%s: null pointer", who);
   VQA_REQUIRE(n >= 0 && M >= 1 && row_len >= 1, "%s: n=%d, M=%d, row_len=%lld out of range", who, n, M, (long long)row_len);
   VQA_REQUIRE(p >= 0.f && p < 1.f, "%s: p=%g outside [0, 1)", who, (double)p);
@@ -249,15 +249,13 @@ static int gather_rows_drop(const char* who, const VT* src, const int32_t* rows,
 template <class VT>
 static int gather_rows_drop_norm(const char* who, const VT* src, const int32_t* rows, float* vn_out, float* vdrop_out, int n, int M,
                                  int P, int C, float p, uint64_t seed, float p2, uint64_t seed2, hipStream_t s) {
-  const uintptr_t sb = reinterpret_cast<uintptr_t>(src), ob = reinterpret_cast<uintptr_t>(vn_out),
-                  db = reinterpret_cast<uintptr_t>(vdrop_out);
   VQA_REQUIRE(src && rows && vn_out, "%s: null pointer", who);
   VQA_REQUIRE(n >= 0 && M >= 1 && P >= 1, "%s: n=%d, M=%d, P=%d out of range", who, n, M, P);
   VQA_REQUIRE(C >= 4 && C % 4 == 0, "%s: C=%d must be a positive multiple of 4", who, C);
   VQA_REQUIRE(p >= 0.f && p < 1.f, "%s: p=%g outside [0, 1)", who, (double)p);
   VQA_REQUIRE(!vdrop_out || (p2 >= 0.f && p2 < 1.f), "%s: p2=%g outside [0, 1)", who, (double)p2);
-  VQA_REQUIRE((sb & (kQuadAlign<VT> - 1)) == 0, "%s: src must be %d-byte aligned", who, (int)kQuadAlign<VT>);
-  VQA_REQUIRE((ob & 15) == 0 && (db & 15) == 0, "%s: vn_out and vdrop_out must be 16-byte aligned", who);
+  VQA_REQUIRE((ptr_bits(src) & (kQuadAlign<VT> - 1)) == 0, "%s: src must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  VQA_REQUIRE((ptr_bits(vn_out, vdrop_out) & 15) == 0, "%s: vn_out and vdrop_out must be 16-byte aligned", who);
   if (n == 0) return VQA_OK;
   if (!vdrop_out) { p2 = 0.f; seed2 = 0; }
   const bool reg = C <= 256;
@@ -278,8 +276,7 @@ int vqa_gather_rows(const float* src, int64_t src_ld, const int32_t* rows, float
   VQA_REQUIRE(src_ld >= cols && dst_ld >= cols, "vqa_gather_rows: src_ld=%lld and dst_ld=%lld must be >= cols=%d",
               (long long)src_ld, (long long)dst_ld, cols);
   if (B == 0) return VQA_OK;
-  const bool vec = cols % 4 == 0 && src_ld % 4 == 0 && dst_ld % 4 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  const bool vec = cols % 4 == 0 && src_ld % 4 == 0 && dst_ld % 4 == 0 && (ptr_bits(src, dst) & 15) == 0;
   if (vec)
     hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(grid_for((int64_t)B * (cols / 4), 256)), dim3(256), 0, STREAM, src, src_ld,
                        rows, dst, dst_ld, B, M, cols);
@@ -296,7 +293,7 @@ int vqa_gather_rows_drop(const float* src, const int32_t* rows, float* dst, int 
 
 int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t stream) {
   VQA_REQUIRE(x_f16 && y && n > 0, "vqa_half_to_float: bad args");
-  VQA_REQUIRE(((uintptr_t)x_f16 % 16) == 0 && ((uintptr_t)y % 16) == 0, "vqa_half_to_float: pointers must be 16-byte aligned");
+  VQA_REQUIRE((ptr_bits(x_f16, y) & 15) == 0, "vqa_half_to_float: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(half_to_float_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, STREAM,
                      static_cast<const __half*>(x_f16), y, n);
   return check_hip(hipGetLastError(), "half_to_float launch");
@@ -305,7 +302,7 @@ int vqa_half_to_float(const void* x_f16, float* y, int64_t n, vqa_stream_t strea
 // ---- float16 image-feature caches: the converter and the cache readers of this file on a half operand
 int vqa_float_to_half(const float* x, void* y_f16, int64_t n, vqa_stream_t stream) {
   VQA_REQUIRE(x && y_f16 && n >= 0, "vqa_float_to_half: bad args");
-  VQA_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y_f16 % 16) == 0, "vqa_float_to_half: pointers must be 16-byte aligned");
+  VQA_REQUIRE((ptr_bits(x, y_f16) & 15) == 0, "vqa_float_to_half: pointers must be 16-byte aligned");
   if (n == 0) return VQA_OK;
   hipLaunchKernelGGL(float_to_half_kernel, dim3(grid_for(n / 8 + 1, 256)), dim3(256), 0, STREAM, x, static_cast<__half*>(y_f16), n);
   return check_hip(hipGetLastError(), "float_to_half launch");

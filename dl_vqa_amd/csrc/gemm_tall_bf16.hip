@@ -291,10 +291,9 @@ int vqa_gemm_tall_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, v
   VQA_REQUIRE(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && lda < (1 << 20) && ldw < (1 << 20),
               "vqa_gemm_tall_bf16: leading dimensions must be multiples of 8 (lda=%lld ldw=%lld ldc=%lld)", (long long)lda,
               (long long)ldw, (long long)ldc);
-  VQA_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(C) & 15) == 0, "vqa_gemm_tall_bf16: operands must be 16-byte aligned");
+  VQA_REQUIRE((ptr_bits(A, W, C) & 15) == 0, "vqa_gemm_tall_bf16: operands must be 16-byte aligned");
   // the row-group table is read 16 bytes (four columns) at a time
-  VQA_REQUIRE(!rowgroup || (rg_ld >= N && rg_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(rowgroup) & 15) == 0),
+  VQA_REQUIRE(!rowgroup || (rg_ld >= N && rg_ld % 4 == 0 && (ptr_bits(rowgroup) & 15) == 0),
               "vqa_gemm_tall_bf16: rowgroup must be 16-byte aligned with rg_ld >= N, a multiple of 4 (rg_ld=%lld)", (long long)rg_ld);
   TgParams P{};
   P.A = static_cast<const char*>(A); P.A_end = P.A + (int64_t)M * lda * 2; P.lda = lda;

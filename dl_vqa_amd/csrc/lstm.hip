@@ -573,10 +573,10 @@ static int make_args(const char* fn, const vqa_lstm_dir_t* dirs, int ndir, const
   for (int d = 0; d < ndir; ++d) {
     const vqa_lstm_dir_t& s = dirs[d];
     VQA_REQUIRE(s.w_hh && s.gates && s.Hs && s.Cs, "%s: direction %d has a null w_hh / gates / Hs / Cs", fn, d);
-    VQA_REQUIRE(((uintptr_t)s.w_hh % 16) == 0 && ((uintptr_t)s.Hs % 16) == 0, "%s: w_hh / Hs must be 16-byte aligned", fn);
+    VQA_REQUIRE((ptr_bits(s.w_hh, s.Hs) & 15) == 0, "%s: w_hh / Hs must be 16-byte aligned", fn);
     if (backward) {
       VQA_REQUIRE(s.dgates && s.dh && s.dc, "%s: direction %d has a null dgates / dh / dc", fn, d);
-      VQA_REQUIRE(((uintptr_t)s.dgates % 16) == 0, "%s: dgates must be 16-byte aligned", fn);
+      VQA_REQUIRE((ptr_bits(s.dgates) & 15) == 0, "%s: dgates must be 16-byte aligned", fn);
     } else {
       VQA_REQUIRE(s.xg, "%s: direction %d has a null xg", fn, d);
     }

@@ -6,8 +6,6 @@
 //   vqa_lstm_occl_cell_fwd   one recurrence step of a set of variant rows (the recurrent product h_var . W_hh^T is vqa_gemm's);
 //   vqa_occl_words           the tail: one column of lin2 per variant row, and the zeros of the slots past a question's end.
 // Neither needs LDS or atomics; every row's result depends on that row alone.
-#include <initializer_list>
-
 #include "common.hpp"
 
 namespace vqa {
@@ -131,12 +129,6 @@ __global__ __launch_bounds__(OW_THREADS) void occl_words_kernel(const float* h1,
   if (lane == 0) words[(int64_t)b * T + t] = out;
 }
 
-static bool aligned16(std::initializer_list<const void*> ps) {
-  uintptr_t a = 0;
-  for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
-  return (a & 15) == 0;
-}
-
 }  // namespace vqa
 
 using namespace vqa;
@@ -155,7 +147,7 @@ int vqa_lstm_occl_cell_fwd(const float* xg_base, const float* xg0, const float* 
   VQA_REQUIRE(c_final || !cf_row, "%s: cf_row without c_final", who);
   if (n == 0) return VQA_OK;
   const bool vec = H % 4 == 0 && st_ld % 4 == 0 && (!c_final || cf_ld % 4 == 0) &&
-                   aligned16({xg_base, xg0, hg, h_var, c_var, c_final});
+                   (ptr_bits(xg_base, xg0, hg, h_var, c_var, c_final) & 15) == 0;
   const int64_t items = (int64_t)n * (vec ? H / 4 : H);
   with_flag(vec, [&](auto v) {
     hipLaunchKernelGGL((lstm_occl_cell_kernel<decltype(v)::value>), dim3(grid_for(items, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -177,7 +169,7 @@ int vqa_occl_words(const float* h1, int64_t h1_ld, const float* W2, int64_t w2_l
   VQA_REQUIRE(h1_ld >= hid && w2_ld >= hid && logits_ld >= A, "%s: h1_ld=%lld, w2_ld=%lld (hid=%d), logits_ld=%lld (A=%d) out of range",
               who, (long long)h1_ld, (long long)w2_ld, hid, (long long)logits_ld, A);
   if (nb == 0) return VQA_OK;
-  const bool vec = hid % 4 == 0 && h1_ld % 4 == 0 && w2_ld % 4 == 0 && aligned16({h1, W2});
+  const bool vec = hid % 4 == 0 && h1_ld % 4 == 0 && w2_ld % 4 == 0 && (ptr_bits(h1, W2) & 15) == 0;
   const int row_blocks = (n + OW_THREADS / 64 - 1) / (OW_THREADS / 64);
   const int fill_blocks = grid_for((int64_t)nb * T, OW_THREADS, 1024);
   with_flag(vec, [&](auto v) {

@@ -2,21 +2,17 @@
 // positions taken out of the image, for every position, from the attention weights answer() already has and U = W1_g . vn --
 // the classifier's first layer applied to every feature row once per image.  One streaming kernel: U is read once per
 // question (window x window times for a larger window, from the cache), everything else is small and lives in LDS.
-#include "common.hpp"
+#include "occl_core.hpp"
 
 namespace vqa {
 
 constexpr int OCCL_THREADS = 256;     // 4 waves
 constexpr int OCCL_PPB = 16;          // positions per workgroup: 4 per wave, walked in order
 
-// dynamic LDS: base [hid], Z [G][hid], W2[a] [hid], then 16 reduction slots and r [G] (4 floats kept for it)
-static size_t occl_lds(int G, int hid) { return ((size_t)(G + 2) * hid + 16 + 4) * 4; }
-
-// Workgroup = (question b, 16 consecutive positions).  Head: the question's base, Z and W2 row into LDS, and
-//   r[g] = exp(cnull[b][g] - m) / sum_p exp(score[b][g][p] - m),  m = max_p score[b][g][p]
-// by the block reduction every workgroup of b runs in the same order.  Then one wave per position p: lane l owns the quads
-// l, l + 64, ... of hid, adds its terms in that order, and the wave butterfly finishes the dot product with W2[a] -- one
-// summation order per (b, p), whatever the grid.  A question whose row of U is not in [slot0, slot0 + R) is left alone (the
+// Workgroup = (question b, 16 consecutive positions).  The question's Z into LDS, then occl_head (occl_core.hpp): base, the
+// W2 row and r[g]; dynamic LDS occl_lds(G + 2, hid).  Then one wave per position p: lane l owns the quads l, l + 64, ... of
+// hid, adds its terms in that order, and the wave butterfly finishes the dot product with W2[a] -- one summation order per
+// (b, p), whatever the grid.  A question whose row of U is not in [slot0, slot0 + R) is left alone (the
 // caller walks U in chunks of images); an answer column outside [0, A) gives a row of zeros.
 template <int G>
 __global__ void __launch_bounds__(OCCL_THREADS)
@@ -27,8 +23,8 @@ occl_logit_kernel(const float* base, const float* Z, const float* U, const int* 
   const int P = gh * gw;
   const int b = blockIdx.x / nchunk;
   const int p0 = (blockIdx.x - b * nchunk) * OCCL_PPB;
-  const int row = slot[b] - slot0;
-  if ((unsigned)row >= (unsigned)R) return;                         // block-uniform
+  const int row = occl_row(slot, b, slot0, R);
+  if (row < 0) return;                                              // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int a = answers[b];
   if ((unsigned)a >= (unsigned)A) {
@@ -41,24 +37,9 @@ occl_logit_kernel(const float* base, const float* Z, const float* U, const int* 
   float* red = sm + (size_t)(G + 2) * hid;  // [16]
   float* s_r = red + 16;                    // [G]
   const int nq = hid >> 2;
-  for (int c = tid; c < nq; c += OCCL_THREADS) {
-    reinterpret_cast<float4*>(s_base)[c] = reinterpret_cast<const float4*>(base + (int64_t)b * hid)[c];
-    reinterpret_cast<float4*>(s_w2)[c] = reinterpret_cast<const float4*>(W2 + (int64_t)a * w2_ld)[c];
-  }
   for (int c = tid; c < G * nq; c += OCCL_THREADS)
     reinterpret_cast<float4*>(s_z)[c] = reinterpret_cast<const float4*>(Z + (int64_t)b * G * hid)[c];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const float* s = score + ((int64_t)b * G + g) * P;
-    float mx = -INFINITY;
-    for (int i = tid; i < P; i += OCCL_THREADS) mx = fmaxf(mx, s[i]);
-    mx = block_reduce(mx, red, true);
-    float sum = 0.f;
-    for (int i = tid; i < P; i += OCCL_THREADS) sum += expf(s[i] - mx);
-    sum = block_reduce(sum, red, false);
-    if (tid == 0) s_r[g] = expf(cnull[b * G + g] - mx) / sum;
-  }
-  __syncthreads();
+  occl_head<G, OCCL_THREADS>(base, score, cnull, W2, w2_ld, b, a, P, hid, s_base, s_w2, red, s_r);
   const float logit = logits[(int64_t)b * logits_ld + a];
   const float bias = b2[a];
   const float* Ub = U + (int64_t)row * P * G * hid;
@@ -122,16 +103,13 @@ int vqa_occl_logit(const float* base, const float* Z, const float* U, const int3
                    int hid, int G, int A, int window, vqa_stream_t stream) {
   set_launch_tag(-1);
   const char* who = "vqa_occl_logit";
-  VQA_REQUIRE(G >= 1 && G <= 4, "%s: glimpses=%d unsupported (1..4)", who, G);
-  VQA_REQUIRE(base && Z && U && slot && probs && score && cnull && W2 && b2 && answers && logits && maps, "%s: null pointer", who);
   VQA_REQUIRE(window >= 1 && window <= 7 && (window & 1), "%s: window=%d unsupported (odd, 1..7)", who, window);
-  VQA_REQUIRE(hid >= 4 && hid % 4 == 0 && w2_ld % 4 == 0 && w2_ld >= hid, "%s: hid=%d (a multiple of 4), w2_ld=%lld out of range",
-              who, hid, (long long)w2_ld);
-  VQA_REQUIRE(R >= 1 && B >= 0 && gh >= 1 && gw >= 1 && (int64_t)gh * gw <= (1 << 20) && A >= 1 && logits_ld >= A,
-              "%s: R=%d, B=%d, grid %d x %d, A=%d, logits_ld=%lld out of range", who, R, B, gh, gw, A, (long long)logits_ld);
-  VQA_REQUIRE(occl_lds(G, hid) <= 64 * 1024, "%s: (G+2)*hid=%d too large for LDS", who, (G + 2) * hid);
-  VQA_REQUIRE(((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(Z) | reinterpret_cast<uintptr_t>(U) |
-                reinterpret_cast<uintptr_t>(W2)) & 15) == 0, "%s: base, Z, U and W2 must be 16-byte aligned", who);
+  const bool pointers = base && Z && U && slot && probs && score && cnull && W2 && b2 && answers && logits && maps;
+  if (const int rc = occl_check(who, G, pointers, hid, w2_ld, G + 2, "(G+2)", ptr_bits(base, Z, U, W2), "base, Z, U and W2",
+                                R >= 1 && B >= 0 && gh >= 1 && gw >= 1 && (int64_t)gh * gw <= (1 << 20) && A >= 1 && logits_ld >= A,
+                                "%s: R=%d, B=%d, grid %d x %d, A=%d, logits_ld=%lld out of range", R, B, gh, gw, A,
+                                (long long)logits_ld))
+    return rc;
   if (B == 0) return VQA_OK;
   const int P = gh * gw;
   const int nchunk = (P + OCCL_PPB - 1) / OCCL_PPB;
@@ -140,7 +118,7 @@ int vqa_occl_logit(const float* base, const float* Z, const float* U, const int3
     // the attribute is set once per kernel, so for the largest LDS size the check above admits
     const int rc = set_smem(occl_logit_kernel<decltype(g)::value>, 64 * 1024, "attr(occl_logit)");
     if (rc) return rc;
-    hipLaunchKernelGGL(occl_logit_kernel<decltype(g)::value>, dim3(B * nchunk), dim3(OCCL_THREADS), occl_lds(G, hid),
+    hipLaunchKernelGGL(occl_logit_kernel<decltype(g)::value>, dim3(B * nchunk), dim3(OCCL_THREADS), occl_lds(G + 2, hid),
                        (hipStream_t)stream, base, Z, U, slot, slot0, R, probs, score, cnull, W2, w2_ld, b2, answers, logits,
                        logits_ld, maps, nchunk, gh, gw, hid, A, window / 2);
     return check_hip(hipGetLastError(), "occl_logit launch");

@@ -35,6 +35,11 @@ def _chk(t: torch.Tensor, dtype=torch.float32):
     assert t.is_cuda and t.dtype == dtype, (t.device, t.dtype)
 
 
+def _ld(t: torch.Tensor) -> int:
+    """The leading dimension of a row-major 2-D view with unit column stride: its row stride, or its width for a single row."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
 def _cache_suffix(t: torch.Tensor) -> str:
     """The entry-point suffix for an image-feature cache operand (vn, v', a bank): fp32, or float16 read natively by the
     *_f16 entry points.  Every other operand of those calls stays fp32."""
@@ -587,9 +592,7 @@ def gather_rows(src, rows, dst, cols: Optional[int] = None):
     _chk(rows, torch.int32)
     assert rows.numel() == B and src.shape[1] >= cols and dst.shape[1] >= cols
     assert (cols == 1 or (src.stride(1) == 1 and dst.stride(1) == 1))
-    src_ld = src.stride(0) if M > 1 else max(src.shape[1], cols)
-    dst_ld = dst.stride(0) if B > 1 else max(dst.shape[1], cols)
-    call("vqa_gather_rows", ptr(src), src_ld, ptr(rows), ptr(dst), dst_ld, B, M, cols, stream())
+    call("vqa_gather_rows", ptr(src), _ld(src), ptr(rows), ptr(dst), _ld(dst), B, M, cols, stream())
     return dst
 
 
@@ -731,6 +734,19 @@ def embed_attr(q, emb, x, dx0, dx1, q_len, out=None):
     return out
 
 
+def _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers):
+    """What occl_logit and occl_curves ask of the operands they share: (B, G, P, R, hid, A, w2_ld)."""
+    (B, G, P), R, hid, A = probs.shape, U.shape[0], base.shape[1], W2.shape[0]
+    for t in (base, U, probs, score, cnull, b2):
+        _chk(t)
+        assert t.is_contiguous()
+    _chk(slot, torch.int32), _chk(answers, torch.int32), _chk(W2)
+    assert score.shape == probs.shape and base.shape == (B, hid) and U.shape == (R, P, G, hid)
+    assert cnull.numel() == B * G and slot.numel() == B and answers.numel() == B
+    assert W2.shape[1] == hid and b2.numel() == A and (hid == 1 or W2.stride(1) == 1)
+    return B, G, P, R, hid, A, _ld(W2)
+
+
 def occl_logit(base, Z, U, slot, probs, score, cnull, W2, b2, answers, logits, gh: int, gw: int, window: int, slot0: int = 0,
                out=None):
     """Occlusion maps [B, P] (include/vqa_hip.h vqa_occl_logit): maps[b, p] = logits[b, a_b] - the same logit with the window x
@@ -738,22 +754,15 @@ def occl_logit(base, Z, U, slot, probs, score, cnull, W2, b2, answers, logits, g
     rows slot0 .. slot0 + R - 1; a question whose slot is outside them is left alone), slot and answers device int32 [B], probs
     and score [B, G, P], cnull [B, G], W2 [A, hid] and logits [B, A] row-major views with unit column stride, b2 [A].  out:
     written in place."""
-    B, G, P = probs.shape
-    R, hid, A = U.shape[0], base.shape[1], W2.shape[0]
-    for t in (base, Z, U, probs, score, cnull, b2):
-        _chk(t)
-        assert t.is_contiguous()
-    _chk(slot, torch.int32), _chk(answers, torch.int32), _chk(W2), _chk(logits)
-    assert P == gh * gw and score.shape == probs.shape and base.shape == (B, hid) and Z.shape == (B, G, hid)
-    assert U.shape == (R, P, G, hid) and cnull.numel() == B * G and slot.numel() == B and answers.numel() == B
-    assert W2.shape[1] == hid and b2.numel() == A and logits.shape == (B, A)
-    assert (hid == 1 or W2.stride(1) == 1) and (A == 1 or logits.stride(1) == 1)
+    B, G, P, R, hid, A, w2_ld = _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers)
+    _chk(Z), _chk(logits)
+    assert P == gh * gw and Z.shape == (B, G, hid) and Z.is_contiguous()
+    assert logits.shape == (B, A) and (A == 1 or logits.stride(1) == 1)
     if out is None:
         out = torch.empty(B, P, dtype=torch.float32, device=probs.device)
     assert out.shape == (B, P) and out.is_contiguous() and out.dtype == torch.float32
-    call("vqa_occl_logit", ptr(base), ptr(Z), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2),
-         W2.stride(0) if A > 1 else hid, ptr(b2), ptr(answers), ptr(logits), logits.stride(0) if B > 1 else A, ptr(out),
-         R, B, gh, gw, hid, G, A, window, stream())
+    call("vqa_occl_logit", ptr(base), ptr(Z), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2), w2_ld,
+         ptr(b2), ptr(answers), ptr(logits), _ld(logits), ptr(out), R, B, gh, gw, hid, G, A, window, stream())
     return out
 
 
@@ -789,15 +798,9 @@ def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot
     column answers[b] with the positions order[b, :k] absent / alone present, k = 0 .. P, in the kept form.  The operands are
     occl_logit's without Z, window and logits, plus order int32 [B, P].  out: (deletion, insertion), written in place for the
     questions whose slot is in [slot0, slot0 + R); workspace: a float32 buffer of at least vqa_occl_curves_workspace_bytes."""
-    B, G, P = probs.shape
-    R, hid, A = U.shape[0], base.shape[1], W2.shape[0]
-    for t in (base, U, probs, score, cnull, b2):
-        _chk(t)
-        assert t.is_contiguous()
-    _chk(slot, torch.int32), _chk(answers, torch.int32), _chk(order, torch.int32), _chk(W2)
-    assert score.shape == probs.shape and base.shape == (B, hid) and U.shape == (R, P, G, hid)
-    assert cnull.numel() == B * G and slot.numel() == B and answers.numel() == B and order.shape == (B, P) and order.is_contiguous()
-    assert W2.shape[1] == hid and b2.numel() == A and (hid == 1 or W2.stride(1) == 1)
+    B, G, P, R, hid, A, w2_ld = _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers)
+    _chk(order, torch.int32)
+    assert order.shape == (B, P) and order.is_contiguous()
     if out is None:
         out = tuple(torch.empty(B, P + 1, dtype=torch.float32, device=probs.device) for _ in range(2))
     deletion, insertion = out
@@ -807,9 +810,9 @@ def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot
         workspace = occl_curves_workspace(B, P, G, hid, probs.device)
     _chk(workspace)
     assert workspace.is_contiguous()
-    call("vqa_occl_curves", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2),
-         W2.stride(0) if A > 1 else hid, ptr(b2), ptr(answers), ptr(order), ptr(workspace), workspace.numel() * 4, ptr(deletion),
-         ptr(insertion), R, B, P, hid, G, A, stream())
+    call("vqa_occl_curves", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2), w2_ld, ptr(b2),
+         ptr(answers), ptr(order), ptr(workspace), workspace.numel() * 4, ptr(deletion), ptr(insertion), R, B, P, hid, G, A,
+         stream())
     return deletion, insertion
 
 
@@ -831,13 +834,12 @@ def lstm_occl_cell_fwd(xg_base, xg0, hg, h_var, c_var, q_len, var_b, var_t, s: i
     assert H4 == 4 * H and xg0.numel() == H4 and hg.dim() == 2 and hg.shape[1] == H4 and hg.shape[0] >= n and q_len.numel() == B
     assert h_var.dim() == 2 and h_var.shape == c_var.shape and h_var.shape[1] == H and 0 <= n <= h_var.shape[0]
     assert (H == 1 or (h_var.stride(1) == 1 and c_var.stride(1) == 1)) and var_b.numel() >= n and var_t.numel() >= n
-    st_ld = h_var.stride(0) if h_var.shape[0] > 1 else H
-    assert c_var.shape[0] <= 1 or c_var.stride(0) == st_ld
+    assert _ld(c_var) == _ld(h_var)
     cf_ld = 0
     if c_final is not None:
         _chk(c_final)
         assert c_final.dim() == 2 and c_final.shape[1] >= H and (c_final.shape[1] == 1 or c_final.stride(1) == 1)
-        cf_ld = c_final.stride(0) if c_final.shape[0] > 1 else c_final.shape[1]
+        cf_ld = _ld(c_final)
         if cf_row is not None:
             _chk(cf_row, torch.int32)
             assert cf_row.numel() >= n
@@ -845,7 +847,7 @@ def lstm_occl_cell_fwd(xg_base, xg0, hg, h_var, c_var, q_len, var_b, var_t, s: i
             assert c_final.shape[0] >= n
     else:
         assert cf_row is None
-    call("vqa_lstm_occl_cell_fwd", ptr(xg_base), ptr(xg0), ptr(hg), ptr(h_var), ptr(c_var), st_ld, ptr(q_len), ptr(var_b),
+    call("vqa_lstm_occl_cell_fwd", ptr(xg_base), ptr(xg0), ptr(hg), ptr(h_var), ptr(c_var), _ld(h_var), ptr(q_len), ptr(var_b),
          ptr(var_t), s, ptr(c_final), cf_ld, ptr(cf_row), n, B, T, H, stream())
 
 
@@ -865,8 +867,8 @@ def occl_words(h1, W2, b2, answers, logits, var_b, var_t, q_len, out, b0: int = 
     assert q_len.numel() == B and var_b.numel() == n and var_t.numel() == n and 0 <= b0 and 0 <= nb and b0 + nb <= B
     assert hid == 1 or (W2.stride(1) == 1 and h1.stride(1) == 1)
     assert A == 1 or logits.stride(1) == 1
-    call("vqa_occl_words", ptr(h1), h1.stride(0) if n > 1 else hid, ptr(W2), W2.stride(0) if A > 1 else hid, ptr(b2), ptr(answers),
-         ptr(logits), logits.stride(0) if B > 1 else A, ptr(var_b), ptr(var_t), ptr(q_len), ptr(out), n, b0, nb, T, hid, A, stream())
+    call("vqa_occl_words", ptr(h1), _ld(h1), ptr(W2), _ld(W2), ptr(b2), ptr(answers), ptr(logits), _ld(logits), ptr(var_b),
+         ptr(var_t), ptr(q_len), ptr(out), n, b0, nb, T, hid, A, stream())
     return out
 
 
@@ -950,11 +952,10 @@ def softmax_topk(logits: torch.Tensor, k: int, want_lse: bool = False):
     _chk(logits)
     assert logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1), (tuple(logits.shape), logits.stride())
     B, A = logits.shape
-    ld = logits.stride(0) if B > 1 else A
     idx = torch.empty(B, k, dtype=torch.int32, device=logits.device)
     prob = torch.empty(B, k, dtype=torch.float32, device=logits.device)
     lse = torch.empty(B, dtype=torch.float32, device=logits.device) if want_lse else None
-    call("vqa_softmax_topk", ptr(logits), ld, B, A, k, ptr(idx), ptr(prob), ptr(lse), stream())
+    call("vqa_softmax_topk", ptr(logits), _ld(logits), B, A, k, ptr(idx), ptr(prob), ptr(lse), stream())
     return (idx, prob, lse) if want_lse else (idx, prob)
 
 
