@@ -25,10 +25,13 @@ the logit falls when a window of grid positions is taken out of the image, for e
 embedding output is zeroed, for every token, from the prefixes the variant recurrences share with the question itself.
 ``VqaNet.explain_faithfulness`` / ``explain_faithfulness_pairs`` say how well any such map ranks the grid positions
 (``Faithfulness``): the deletion and insertion curves of the explained logit along the map's ranking, and their areas.
+``VqaNet.explain_integrated`` / ``explain_integrated_pairs`` repair the first-order map (``IntegratedGradients``): the same
+gradient averaged along the path from a cache of zeros to the real one, which sums to the logit's rise over that baseline;
+v' is read twice whatever the number of steps.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness, IntegratedGradients  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
            "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
-           "WordAttribution", "Occlusion", "WordOcclusion", "Faithfulness"]
+           "WordAttribution", "Occlusion", "WordOcclusion", "Faithfulness", "IntegratedGradients"]

@@ -179,6 +179,22 @@ PROTOTYPES = {
     "vqa_occl_curves_workspace_bytes": (i64, [i32, i32, i32, i32]),
     "vqa_occl_curves": (i32, [f32p, f32p, vp, i32, f32p, f32p, f32p, f32p, i64, f32p, vp, vp, f32p, i64, f32p, f32p, i32, i32, i32,
                               i32, i32, i32, vp]),
+    # integrated gradients from cached features (bound with the attribution entry points, before the last two)
+    "vqa_att_path_scale_rows": (i32, [f32p, i64, f32p, i32, i64, i32, vp]),
+    "vqa_att_path_score_grouped": (i32, [f32p, f32p, f32p, i32, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_path_score_grouped_pairs": (i32, [f32p, f32p, vp, f32p, i32, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32,
+                                               i32, i32, vp]),
+    "vqa_att_path_score_grouped_f16": (i32, [vp, f32p, f32p, i32, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "vqa_att_path_score_grouped_pairs_f16": (i32, [vp, f32p, vp, f32p, i32, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32,
+                                                   i32, i32, vp]),
+    "vqa_att_path_attr_grouped": (i32, [f32p, f32p, f32p, f32p, f32p, i32, f32p, f32, vp, vp, f32p, i32, i32, i32, i32, i32, i32,
+                                        i32, vp]),
+    "vqa_att_path_attr_grouped_pairs": (i32, [f32p, f32p, f32p, f32p, vp, f32p, i32, f32p, f32, vp, vp, f32p, i32, i32, i32, i32,
+                                              i32, i32, i32, i32, vp]),
+    "vqa_att_path_attr_grouped_f16": (i32, [f32p, f32p, vp, f32p, f32p, i32, f32p, f32, vp, vp, f32p, i32, i32, i32, i32, i32, i32,
+                                            i32, vp]),
+    "vqa_att_path_attr_grouped_pairs_f16": (i32, [f32p, f32p, vp, f32p, vp, f32p, i32, f32p, f32, vp, vp, f32p, i32, i32, i32, i32,
+                                                  i32, i32, i32, i32, vp]),
     # image dropout on a bank of cached image features
     "vqa_gather_rows_drop_norm": (i32, [f32p, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),
     "vqa_gather_rows_drop_norm_f16": (i32, [vp, vp, f32p, f32p, i32, i32, i32, i32, f32, u64, f32, u64, vp]),

@@ -745,6 +745,334 @@ __global__ __launch_bounds__(256) void att_attr_score_grouped_general_kernel(con
   }
 }
 
+// ------------------------------------------------------------------ integrated gradients: the path alpha * v' (inference)
+// VqaNet.explain_integrated (include/vqa_hip.h): the grouped forward and the grouped attribution evaluated at
+// S points x = alpha_s * v' of the straight path from the zero cache to the real one.  v_conv has no bias, so scaling vn by
+// alpha scales v' by alpha: the path costs a multiply on the staged quad, and ONE staged tile serves every question of the
+// image and every step of every question -- v' leaves HBM once per walk, as in the kernels above, whatever S is.
+//   path scores   score[b][s][g][p] = bx[g] + sum_m wx[g][m] * relu((alpha_s v'[n*P+p][m]) (+|*) q'[b][m])   ('|': as the forward)
+//   path attr     out[b][p] = scale * sum_s (r1[b][s][p] + sum_m c_s[m] * s_s[m] * (alpha_s v'[n*P+p][m]))
+// with c_s = sum_g dscore[b][s][g][p] * wx[g][m] and s_s the indicator of att_attr_quad AT alpha_s v'.  The step-rows (b, s)
+// are laid out as a batch of B*S questions, [B][S][G][P] and [B][S][P], so the apply-gather kernels between the two walks take
+// them as they are.  Evaluation order: x = alpha_s * v' is rounded FIRST (att_path_quad: never contracted into the add that
+// follows), then the element math of the kernels above runs on x -- both walks see the same pre-activation bits, and with
+// dyadic inputs the fp32 indicator is the exact one.  Per (b, s, p) the summation order is the forward's / the attribution's;
+// the path sum runs over s ascending, each step's r1 + r2 formed first, then scale: one order for every (b, p), no atomics,
+// every asked (b, p) written exactly once.  The s loop sits inside the question walk: a register loop, nothing per step is
+// kept but alpha_s.
+__device__ __forceinline__ float4 att_path_quad(const float4 v, const float a) {
+#pragma clang fp contract(off)
+  return make_float4(a * v.x, a * v.y, a * v.z, a * v.w);
+}
+
+// Between the two walks the classifier sees the image half of its input at the step's path position: x[r][c] *= alphas[r % S]
+// for the step-row r = b*S + s, over the first `cols` columns of a [rows][ld] buffer (the weighted sum of vn is linear in vn).
+__global__ void att_path_scale_rows_kernel(float* x, int64_t ld, const float* alphas, int S, int64_t rows, int cols) {
+  const int64_t n = rows * cols;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cols;
+    x[r * ld + (i - r * cols)] *= alphas[r % S];
+  }
+}
+
+// '+' / '*', mid = 256 * IT <= 1024: att_score_grouped_kernel (DROP = false) with the step loop around its reduction.
+// grid (ceil(P/16), N), 256 threads, 16 * mid floats of dynamic LDS.
+template <int G, int IT, bool MUL, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_path_score_grouped_kernel(const VT* vprime, const float* qp, const int* qrow, int M,
+                                                                     const float* wx, int wx_ld, const float* bx,
+                                                                     const float* alphas, const int* order, const int* offsets,
+                                                                     float* score, int B, int S, int P) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  constexpr int mid = 256 * IT, PW = 4, TP = 16;
+  const int n = blockIdx.y, p0 = blockIdx.x * TP;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  if (k0 >= k1) return;                                   // nobody asks about this image
+  const int rows = min(TP, P - p0);
+  att_tile_to_lds(vprime, tile, (int64_t)n * P + p0, rows, mid);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float4 w[IT][G];
+  float bias[G];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int g = 0; g < G; ++g) w[i][g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[lane + 64 * i];
+#pragma unroll
+  for (int g = 0; g < G; ++g) bias[g] = bx[g];
+  __syncthreads();
+  const int pl = wave * PW;                               // first local position of this wave
+  if (pl >= rows) return;
+  float4 q[IT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  int b = order[k0];
+  const int r0 = att_q_row<PAIRS>(qrow, b, B, M);
+  bool ok = r0 >= 0;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) q[i] = reinterpret_cast<const float4*>(qp + (int64_t)r0 * mid)[lane + 64 * i];
+  }
+  for (int k = k0; k < k1; ++k) {
+    // the next question's q' row is in flight while this one's steps are reduced
+    float4 qn[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) qn[i] = q[i];
+    int bn = -1;
+    bool okn = false;
+    if (k + 1 < k1) {
+      bn = order[k + 1];
+      const int rn = att_q_row<PAIRS>(qrow, bn, B, M);
+      okn = rn >= 0;
+      if (okn) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) qn[i] = reinterpret_cast<const float4*>(qp + (int64_t)rn * mid)[lane + 64 * i];
+      }
+    }
+    if (ok) {
+      for (int s = 0; s < S; ++s) {
+        const float a = alphas[s];
+        float acc[PW][G];
+#pragma unroll
+        for (int j = 0; j < PW; ++j)
+#pragma unroll
+          for (int g = 0; g < G; ++g) acc[j][g] = 0.f;
+#pragma unroll
+        for (int i = 0; i < IT; ++i) {
+#pragma unroll
+          for (int j = 0; j < PW; ++j) {
+            if (pl + j < rows) {                          // wave-uniform
+              const float4 v = reinterpret_cast<const float4*>(tile + (pl + j) * mid)[lane + 64 * i];
+              const float4 x = att_combine<MUL>(att_path_quad(v, a), q[i]);
+#pragma unroll
+              for (int g = 0; g < G; ++g) acc[j][g] += dot4(x, w[i][g]);
+            }
+          }
+        }
+        const int64_t row = ((int64_t)b * S + s) * G;
+#pragma unroll
+        for (int j = 0; j < PW; ++j) {
+          if (pl + j < rows) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+              const float t = wave_sum(acc[j][g]);
+              if (lane == 0) score[(row + g) * P + p0 + pl + j] = t + bias[g];
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < IT; ++i) q[i] = qn[i];
+    b = bn;
+    ok = okn;
+  }
+}
+
+// Any mid % 4 == 0 and every mode: att_score_grouped_general_kernel (DROP = false) with the step loop inside the question
+// walk.  '|': the q' half does not depend on the step and is reduced once per (position, question); the v' half, relu(alpha_s
+// v'), is the step's own.
+template <int G, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_path_score_grouped_general_kernel(const VT* vprime, const float* qp, const int* qrow,
+                                                                             int M, const float* wx, int wx_ld, const float* bx,
+                                                                             const float* alphas, const int* order,
+                                                                             const int* offsets, float* score, int B, int S, int P,
+                                                                             int mid, int pw, int mode) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  const int TP = 4 * pw;
+  const int n = blockIdx.y, p0 = blockIdx.x * TP;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  if (k0 >= k1) return;
+  const int rows = min(TP, P - p0);
+  att_tile_to_lds(vprime, tile, (int64_t)n * P + p0, rows, mid);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nq = mid >> 2;
+  for (int j = 0; j < pw; ++j) {
+    const int pl = wave * pw + j;
+    if (pl >= rows) break;
+    const float4* vrow = reinterpret_cast<const float4*>(tile + pl * mid);
+    for (int k = k0; k < k1; ++k) {
+      const int b = order[k];
+      const int r = att_q_row<PAIRS>(qrow, b, B, M);
+      if (r < 0) continue;
+      const float4* qv = reinterpret_cast<const float4*>(qp + (int64_t)r * mid);
+      float qpart[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) qpart[g] = 0.f;
+      if (mode == 2) {
+        float acc[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = 0.f;
+        for (int c = lane; c < nq; c += 64) {
+          const float4 x = relu4(qv[c]);
+#pragma unroll
+          for (int g = 0; g < G; ++g) acc[g] += dot4(x, reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld + mid)[c]);
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) qpart[g] = wave_sum(acc[g]);
+      }
+      for (int s = 0; s < S; ++s) {
+        const float a = alphas[s];
+        float acc[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = 0.f;
+        for (int c = lane; c < nq; c += 64) {
+          const float4 xv = att_path_quad(vrow[c], a);
+          const float4 x = mode == 2 ? relu4(xv) : (mode == 1 ? att_combine<true>(xv, qv[c]) : att_combine<false>(xv, qv[c]));
+#pragma unroll
+          for (int g = 0; g < G; ++g) acc[g] += dot4(x, reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[c]);
+        }
+        const int64_t row = ((int64_t)b * S + s) * G;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const float t = wave_sum(acc[g]) + bx[g];       // '|': the bias goes with the v' half, as in the forward
+          if (lane == 0) score[(row + g) * P + p0 + pl] = mode == 2 ? t + qpart[g] : t;
+        }
+      }
+    }
+  }
+}
+
+// '+' / '*', mid = 256 * IT <= 1024: att_attr_score_grouped_kernel with the step loop around its reduction and the path sum
+// in a register per position.  The four positions of a wave advance through a step together, so that the step's dscore and
+// r1 values (4 * (G + 1) broadcast loads) are in flight at once.
+template <int G, int IT, bool MUL, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_path_attr_grouped_kernel(const float* r1, const float* dscore, const VT* vprime,
+                                                                    const float* qp, const int* qrow, int M, const float* wx,
+                                                                    int wx_ld, const float* alphas, float scale, const int* order,
+                                                                    const int* offsets, float* out, int B, int S, int P) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  constexpr int mid = 256 * IT, PW = 4, TP = 16;
+  const int n = blockIdx.y, p0 = blockIdx.x * TP;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  if (k0 >= k1) return;                                   // nobody asks about this image
+  const int rows = min(TP, P - p0);
+  att_tile_to_lds(vprime, tile, (int64_t)n * P + p0, rows, mid);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float4 w[IT][G];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int g = 0; g < G; ++g) w[i][g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[lane + 64 * i];
+  __syncthreads();
+  const int pl = wave * PW;                               // first local position of this wave
+  if (pl >= rows) return;
+  float4 q[IT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  int b = order[k0];
+  const int r0 = att_q_row<PAIRS>(qrow, b, B, M);
+  bool ok = r0 >= 0;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < IT; ++i) q[i] = reinterpret_cast<const float4*>(qp + (int64_t)r0 * mid)[lane + 64 * i];
+  }
+  for (int k = k0; k < k1; ++k) {
+    float4 qn[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) qn[i] = q[i];
+    int bn = -1;
+    bool okn = false;
+    if (k + 1 < k1) {
+      bn = order[k + 1];
+      const int rn = att_q_row<PAIRS>(qrow, bn, B, M);
+      okn = rn >= 0;
+      if (okn) {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) qn[i] = reinterpret_cast<const float4*>(qp + (int64_t)rn * mid)[lane + 64 * i];
+      }
+    }
+    if (ok) {
+      float total[PW];
+#pragma unroll
+      for (int j = 0; j < PW; ++j) total[j] = 0.f;
+      for (int s = 0; s < S; ++s) {
+        const float a = alphas[s];
+        const int64_t row = (int64_t)b * S + s;
+        float ds[PW][G], r[PW];
+#pragma unroll
+        for (int j = 0; j < PW; ++j) {
+          const bool in = pl + j < rows;                  // wave-uniform
+          const int64_t pos = p0 + pl + j;
+          r[j] = in ? r1[row * P + pos] : 0.f;
+#pragma unroll
+          for (int g = 0; g < G; ++g) ds[j][g] = in ? dscore[(row * G + g) * P + pos] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < PW; ++j) {
+          if (pl + j < rows) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+              acc += att_attr_quad<G, MUL ? 1 : 0>(
+                  ds[j], w[i], att_path_quad(reinterpret_cast<const float4*>(tile + (pl + j) * mid)[lane + 64 * i], a), q[i]);
+            total[j] += r[j] + wave_sum(acc);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < PW; ++j)
+        if (pl + j < rows && lane == 0) out[(int64_t)b * P + p0 + pl + j] = scale * total[j];
+    }
+#pragma unroll
+    for (int i = 0; i < IT; ++i) q[i] = qn[i];
+    b = bn;
+    ok = okn;
+  }
+}
+
+// Any mid % 4 == 0 and every mode: att_attr_score_grouped_general_kernel with the step loop inside the question walk.
+template <int G, int MODE, bool PAIRS, class VT = float>
+__global__ __launch_bounds__(256) void att_path_attr_grouped_general_kernel(const float* r1, const float* dscore, const VT* vprime,
+                                                                            const float* qp, const int* qrow, int M,
+                                                                            const float* wx, int wx_ld, const float* alphas,
+                                                                            float scale, const int* order, const int* offsets,
+                                                                            float* out, int B, int S, int P, int mid, int pw) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  const int TP = 4 * pw;
+  const int n = blockIdx.y, p0 = blockIdx.x * TP;
+  int k0, k1;
+  att_group_range(offsets, n, B, k0, k1);
+  if (k0 >= k1) return;
+  const int rows = min(TP, P - p0);
+  att_tile_to_lds(vprime, tile, (int64_t)n * P + p0, rows, mid);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nq = mid >> 2;
+  for (int j = 0; j < pw; ++j) {
+    const int pl = wave * pw + j;
+    if (pl >= rows) break;
+    const int64_t pos = p0 + pl;
+    const float4* vrow = reinterpret_cast<const float4*>(tile + pl * mid);
+    for (int k = k0; k < k1; ++k) {
+      const int b = order[k];
+      const int r = att_q_row<PAIRS>(qrow, b, B, M);
+      if (r < 0) continue;
+      const float4* qv = MODE == 2 ? nullptr : reinterpret_cast<const float4*>(qp + (int64_t)r * mid);     // '|' reads no q'
+      float total = 0.f;
+      for (int s = 0; s < S; ++s) {
+        const float a = alphas[s];
+        const int64_t row = (int64_t)b * S + s;
+        float ds[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) ds[g] = dscore[(row * G + g) * P + pos];
+        float acc = 0.f;
+        for (int c = lane; c < nq; c += 64) {
+          float4 w[G];
+#pragma unroll
+          for (int g = 0; g < G; ++g) w[g] = reinterpret_cast<const float4*>(wx + (int64_t)g * wx_ld)[c];
+          const float4 q = MODE == 2 ? make_float4(0.f, 0.f, 0.f, 0.f) : qv[c];
+          acc += att_attr_quad<G, MODE>(ds, w, att_path_quad(vrow[c], a), q);
+        }
+        total += r1[row * P + pos] + wave_sum(acc);
+      }
+      if (lane == 0) out[(int64_t)b * P + pos] = scale * total;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ grouped backward (training through shared image features)
 // d loss / d v' (one row per IMAGE position, summed over the image's questions), d loss / d q' and the x_conv weight
 // gradient from dscore; x = relu(v' (+|*) q') is recomputed, never read.  With
@@ -1042,6 +1370,92 @@ static int grouped_attr(const char* who, const float* r1, const float* dscore, c
   return check_hip(hipGetLastError(), "att_attr_score_grouped launch");
 }
 
+// what the eight path entry points add to the grouped checks: the step positions
+static int att_path_check(const char* who, const float* alphas, int S) {
+  VQA_REQUIRE(alphas, "%s: null alphas", who);
+  VQA_REQUIRE(S >= 1 && S <= VQA_ATT_PATH_MAX_STEPS, "%s: S=%d steps out of range (1..%d)", who, S, VQA_ATT_PATH_MAX_STEPS);
+  return VQA_OK;
+}
+
+// the four path-score entry points: grouped_fwd's checks, grid, LDS size and path choice at p = 0, over S step positions
+template <class VT>
+static int grouped_path_fwd(const char* who, const VT* vprime, const float* qp, const int32_t* qrow, int M, const float* wx,
+                            int wx_ld, const float* bx, const float* alphas, const int32_t* order, const int32_t* offsets,
+                            float* score, int N, int B, int S, int P, int mid, int G, int mode, hipStream_t s) {
+  constexpr bool f32 = std::is_same<VT, float>::value;
+  int rc = att_score_check(who, true, vprime && qp && wx && bx && score, order && offsets, N, B, P, mid, wx_ld, G, mode, 0.f,
+                           f32 ? ptr_bits(vprime, qp, wx) : ptr_bits(qp, wx));
+  if (rc) return rc;
+  if ((rc = att_path_check(who, alphas, S))) return rc;
+  VQA_REQUIRE((ptr_bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  if (B == 0) return VQA_OK;
+  const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
+  const dim3 grid((P + TP - 1) / TP, N);
+  const size_t lds = (size_t)TP * mid * 4;
+  with_int14(G, [&](auto g) {
+    return with_flag(qrow != nullptr, [&](auto pairs) {
+      constexpr int kG = decltype(g)::value;
+      constexpr bool kPairs = decltype(pairs)::value;
+      if (pw)
+        hipLaunchKernelGGL((att_path_score_grouped_general_kernel<kG, kPairs, VT>), grid, dim3(256), lds, s, vprime, qp, qrow, M, wx,
+                           wx_ld, bx, alphas, order, offsets, score, B, S, P, mid, pw, mode);
+      else
+        with_int14(mid / 256, [&](auto it) {
+          return with_flag(mode == 1, [&](auto mul) {
+            hipLaunchKernelGGL((att_path_score_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, kPairs, VT>), grid,
+                               dim3(256), lds, s, vprime, qp, qrow, M, wx, wx_ld, bx, alphas, order, offsets, score, B, S, P);
+            return 0;
+          });
+        });
+      return 0;
+    });
+  });
+  return check_hip(hipGetLastError(), "att_path_score_grouped launch");
+}
+
+// the four path-attribution entry points: grouped_attr's checks, grid, LDS size and path choice, over S step positions
+template <class VT>
+static int grouped_path_attr(const char* who, const float* r1, const float* dscore, const VT* vprime, const float* qp,
+                             const int32_t* qrow, int M, const float* wx, int wx_ld, const float* alphas, float scale,
+                             const int32_t* order, const int32_t* offsets, float* out, int N, int B, int S, int P, int mid, int G,
+                             int mode, hipStream_t s) {
+  constexpr bool f32 = std::is_same<VT, float>::value;
+  int rc = att_score_check(who, true, r1 && dscore && vprime && wx && out && (mode == 2 || qp), order && offsets, N, B, P, mid,
+                           wx_ld, G, mode, 0.f, f32 ? ptr_bits(vprime, qp, wx) : ptr_bits(qp, wx));
+  if (rc) return rc;
+  if ((rc = att_path_check(who, alphas, S))) return rc;
+  VQA_REQUIRE((ptr_bits(vprime) & (kQuadAlign<VT> - 1)) == 0, "%s: vprime must be %d-byte aligned", who, (int)kQuadAlign<VT>);
+  if (B == 0) return VQA_OK;
+  const int pw = att_score_grouped_pw(mode, mid), TP = pw ? 4 * pw : 16;
+  const dim3 grid((P + TP - 1) / TP, N);
+  const size_t lds = (size_t)TP * mid * 4;
+  // MODE is a template argument of the general kernel: a macro passes the constant
+#define GROUPED_PATH_ATTR_GENERAL(kMODE)                                                                                          \
+  hipLaunchKernelGGL((att_path_attr_grouped_general_kernel<kG, kMODE, kPairs, VT>), grid, dim3(256), lds, s, r1, dscore, vprime,  \
+                     qp, qrow, M, wx, wx_ld, alphas, scale, order, offsets, out, B, S, P, mid, pw)
+  with_int14(G, [&](auto g) {
+    return with_flag(qrow != nullptr, [&](auto pairs) {
+      constexpr int kG = decltype(g)::value;
+      constexpr bool kPairs = decltype(pairs)::value;
+      if (pw == 0)
+        with_int14(mid / 256, [&](auto it) {
+          return with_flag(mode == 1, [&](auto mul) {
+            hipLaunchKernelGGL((att_path_attr_grouped_kernel<kG, decltype(it)::value, decltype(mul)::value, kPairs, VT>), grid,
+                               dim3(256), lds, s, r1, dscore, vprime, qp, qrow, M, wx, wx_ld, alphas, scale, order, offsets, out, B,
+                               S, P);
+            return 0;
+          });
+        });
+      else if (mode == 0) GROUPED_PATH_ATTR_GENERAL(0);
+      else if (mode == 1) GROUPED_PATH_ATTR_GENERAL(1);
+      else GROUPED_PATH_ATTR_GENERAL(2);
+      return 0;
+    });
+  });
+#undef GROUPED_PATH_ATTR_GENERAL
+  return check_hip(hipGetLastError(), "att_path_attr_grouped launch");
+}
+
 // the two entry points of d logit / d q' through the scores: the checks and limits of att_score_check, the grid and the
 // path choice of vqa_att_score_grouped_bwd.  '|' is refused: that gradient is identically zero (see att_score_bwd_quad)
 template <class VT>
@@ -1299,6 +1713,104 @@ int vqa_att_attr_dq_grouped_f16(const float* dscore, const void* vprime_f16, con
   ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
   return grouped_attr_dq("vqa_att_attr_dq_grouped_f16", dscore, static_cast<const __half*>(vprime_f16), qp, wx, wx_ld, order,
                          offsets, dq_part, N, B, P, mid, G, mode, (hipStream_t)stream);
+}
+
+// ---- integrated gradients along the path alpha * v' 
+int vqa_att_path_scale_rows(float* x, int64_t ld, const float* alphas, int S, int64_t rows, int cols, vqa_stream_t stream) {
+  const char* who = "vqa_att_path_scale_rows";
+  VQA_REQUIRE(x, "%s: null pointer", who);
+  const int rc = att_path_check(who, alphas, S);
+  if (rc) return rc;
+  VQA_REQUIRE(rows >= 0 && cols >= 1 && ld >= cols, "%s: rows=%lld, cols=%d, ld=%lld out of range (ld >= cols >= 1)", who,
+              (long long)rows, cols, (long long)ld);
+  if (rows == 0) return VQA_OK;
+  hipLaunchKernelGGL(att_path_scale_rows_kernel, dim3(grid_for(rows * cols, 256)), dim3(256), 0, (hipStream_t)stream, x, ld, alphas,
+                     S, rows, cols);
+  return check_hip(hipGetLastError(), "att_path_scale_rows launch");
+}
+
+int vqa_att_path_score_grouped(const float* vprime, const float* qp, const float* wx, int wx_ld, const float* bx,
+                               const float* alphas, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                               int S, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  return grouped_path_fwd("vqa_att_path_score_grouped", vprime, qp, nullptr, 0, wx, wx_ld, bx, alphas, order, offsets, score, N, B,
+                          S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_score_grouped_pairs(const float* vprime, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                     const float* bx, const float* alphas, const int32_t* order, const int32_t* offsets,
+                                     float* score, int N, int B, int M, int S, int P, int mid, int G, int mode,
+                                     vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_path_score_grouped_pairs: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_path_score_grouped_pairs: M=%d question rows (>= 1)", M);
+  return grouped_path_fwd("vqa_att_path_score_grouped_pairs", vprime, qp, qrow, M, wx, wx_ld, bx, alphas, order, offsets, score, N,
+                          B, S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_score_grouped_f16(const void* vprime_f16, const float* qp, const float* wx, int wx_ld, const float* bx,
+                                   const float* alphas, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                                   int S, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  return grouped_path_fwd("vqa_att_path_score_grouped_f16", static_cast<const __half*>(vprime_f16), qp, nullptr, 0, wx, wx_ld, bx,
+                          alphas, order, offsets, score, N, B, S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_score_grouped_pairs_f16(const void* vprime_f16, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                         const float* bx, const float* alphas, const int32_t* order, const int32_t* offsets,
+                                         float* score, int N, int B, int M, int S, int P, int mid, int G, int mode,
+                                         vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_FWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_path_score_grouped_pairs_f16: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_path_score_grouped_pairs_f16: M=%d question rows (>= 1)", M);
+  return grouped_path_fwd("vqa_att_path_score_grouped_pairs_f16", static_cast<const __half*>(vprime_f16), qp, qrow, M, wx, wx_ld,
+                          bx, alphas, order, offsets, score, N, B, S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_attr_grouped(const float* r1, const float* dscore, const float* vprime, const float* qp, const float* wx,
+                              int wx_ld, const float* alphas, float scale, const int32_t* order, const int32_t* offsets,
+                              float* out, int N, int B, int S, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  return grouped_path_attr("vqa_att_path_attr_grouped", r1, dscore, vprime, qp, nullptr, 0, wx, wx_ld, alphas, scale, order,
+                           offsets, out, N, B, S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_attr_grouped_pairs(const float* r1, const float* dscore, const float* vprime, const float* qp,
+                                    const int32_t* qrow, const float* wx, int wx_ld, const float* alphas, float scale,
+                                    const int32_t* order, const int32_t* offsets, float* out, int N, int B, int M, int S, int P,
+                                    int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_path_attr_grouped_pairs: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_path_attr_grouped_pairs: M=%d question rows (>= 1)", M);
+  return grouped_path_attr("vqa_att_path_attr_grouped_pairs", r1, dscore, vprime, qp, qrow, M, wx, wx_ld, alphas, scale, order,
+                           offsets, out, N, B, S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_attr_grouped_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp, const float* wx,
+                                  int wx_ld, const float* alphas, float scale, const int32_t* order, const int32_t* offsets,
+                                  float* out, int N, int B, int S, int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  return grouped_path_attr("vqa_att_path_attr_grouped_f16", r1, dscore, static_cast<const __half*>(vprime_f16), qp, nullptr, 0, wx,
+                           wx_ld, alphas, scale, order, offsets, out, N, B, S, P, mid, G, mode, (hipStream_t)stream);
+}
+
+int vqa_att_path_attr_grouped_pairs_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp,
+                                        const int32_t* qrow, const float* wx, int wx_ld, const float* alphas, float scale,
+                                        const int32_t* order, const int32_t* offsets, float* out, int N, int B, int M, int S,
+                                        int P, int mid, int G, int mode, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  ProfScope prof(VQA_K_ATT_SCORE_BWD, (hipStream_t)stream);
+  VQA_REQUIRE(qrow, "vqa_att_path_attr_grouped_pairs_f16: null qrow");
+  VQA_REQUIRE(M >= 1, "vqa_att_path_attr_grouped_pairs_f16: M=%d question rows (>= 1)", M);
+  return grouped_path_attr("vqa_att_path_attr_grouped_pairs_f16", r1, dscore, static_cast<const __half*>(vprime_f16), qp, qrow, M,
+                           wx, wx_ld, alphas, scale, order, offsets, out, N, B, S, P, mid, G, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -626,6 +626,62 @@ class Engine:
             tail.update(dh=dh, dscore=dscore)
         return maps, answers, logits
 
+    # ------------------------------------------------------------------ integrated gradients from cached features
+    # explain's map averaged over S points alpha_s * (vn, v') of the straight path from the zero cache to the real one
+    # (include/vqa_hip.h).  The base run gives logits and the column; then, per chunk of questions, explain's
+    # tail on the rows x S step-rows: two walks of v' (path scores, path attribution) that read it once each whatever S is,
+    # the apply-gather kernels and the classifier's first layer between them.  No parameter gradient, nothing kept.
+    IG_BYTES = 256 << 20            # workspace cap of score, probs, dscore and r1 over rows x S: more questions walk in chunks
+
+    def integrated_rows(self, Pn: int, steps: int, ig_bytes: Optional[int] = None) -> int:
+        """Questions per chunk of explain_integrated: score, probs and dscore [rows, S, G, Pn] and r1 [rows, S, Pn] fit the cap."""
+        return max(1, int((self.IG_BYTES if ig_bytes is None else ig_bytes) // (steps * Pn * (3 * self.G + 1) * 4)))
+
+    @_device_current("feats", _cache_device)
+    def explain_integrated(self, P: Dict[str, Tensor], feats, ask, alphas: Tensor, chunks):
+        """explain's arguments plus alphas (device fp32 [S], the step positions) and chunks: (b0, b1, order, offsets) per range
+        of questions, order / offsets (device int32) grouping the questions b0 .. b1-1, numbered from 0, by image.  Returns
+        (maps [B,Pn], answers int32 [B], logits [B,A], baseline_logits [B])."""
+        assert not self.bf16, "explain_integrated: fp32 / fp32x3 only"
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        logits, img = run.logits, run.img
+        B, S, hid, G, GC, Dc, Q, A, dev = img.numel(), alphas.numel(), self.hid, self.G, self.GC, self.Dc, self.Q, self.A, feats.vn.device
+        N, Pn, _ = feats.vn.shape
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        answers = self._picked(logits, ask.answers)
+        wx, bx = P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"]
+        w1, w2, lin1_bias = P["classifier.lin1.weight"], P["classifier.lin2.weight"], P["classifier.lin1.bias"]
+        # the step-rows r = b*S + s of every question: its image, its column, and where its question half lies
+        rep = lambda t: t.repeat_interleave(S)
+        img_r, ans_r, b_r = rep(img), rep(answers), rep(torch.arange(B, dtype=torch.int32, device=dev))
+        maps = new(B, Pn)
+        rows = max(b1 - b0 for b0, b1, _, _ in chunks)
+        score, comb, h1, dh, dcomb = new(rows, S, G, Pn), new(rows * S, Dc), new(rows * S, hid), new(rows * S, hid), new(rows * S, GC)
+        for b0, b1, order, offsets in chunks:
+            n, R = b1 - b0, (b1 - b0) * S
+            qp, qrow = (run.qp[b0:b1], None) if run.qrow is None else (run.qp, run.qrow[b0:b1])
+            ops.att_path_score_grouped(feats.vprime, qp, wx, bx, alphas, order, offsets, N, n, Pn, self.att_mode, qrow=qrow,
+                                       out=score[:n])
+            # combined of the step-rows: alpha_s * sum_p probs_s vn | the question's own half
+            probs = ops.att_apply_gather_fwd(score[:n].view(R, G, Pn), feats.vn, img_r[b0 * S:b1 * S], comb[:R], Dc)
+            ops.att_path_scale_rows(comb[:R], alphas, GC)
+            ops.gather_rows(run.combined[:, GC:], b_r[b0 * S:b1 * S], comb[:R, GC:], Q)
+            _gemm(comb[:R], w1, h1[:R], R, hid, Dc, bias1=lin1_bias, relu=True, tag=30)
+            # explain's tail on the step-rows: dh = W2[a_b] where h1_s > 0, dcomb = dh . W1[:, :GC] in plain fp32
+            ops.gather_rows(w2, ans_r[b0 * S:b1 * S], dh[:R])
+            ops.relu_drop_bwd(h1[:R], dh[:R], dh[:R], 0.0, 0)
+            ops.gemm(dh[:R], w1, dcomb[:R], R, GC, hid, transB=False, lda=hid, ldb=Dc)
+            dscore, r1 = ops.att_attr_apply_gather(dcomb[:R], GC, probs, feats.vn, img_r[b0 * S:b1 * S])
+            ops.att_path_attr_grouped(r1.view(n, S, Pn), dscore.view(n, S, G, Pn), feats.vprime, qp, wx, alphas, 1.0 / S, order,
+                                      offsets, N, n, Pn, self.att_mode, qrow=qrow, out=maps[b0:b1])
+        # the baseline: the eval-mode classifier on [0, qf_b] at column a_b (a column outside [0, A): +0.0)
+        comb0 = torch.zeros(B, Dc, dtype=torch.float32, device=dev)
+        ops.add2d(run.combined[:, GC:], Dc, None, 0, comb0[:, GC:], Dc, B, Q)
+        logits0 = self._classifier_fwd(P, comb0, 0.0, 0, None)[0]
+        flat = torch.where((answers >= 0) & (answers < A), torch.arange(B, dtype=torch.int32, device=dev) * A + answers, -1)
+        baseline = ops.gather_rows(logits0.view(B * A, 1), flat.to(torch.int32), new(B, 1), 1).view(B)
+        return maps, answers, logits, baseline
+
     # ------------------------------------------------------------------ occlusion maps from cached features
     # What explain estimates to first order, exactly: the fall of ONE logit per question when a window of grid positions is
     # taken out of the image, for every position, in closed form (include/vqa_hip.h vqa_occl_logit; DESIGN.md 4.18).  answer's

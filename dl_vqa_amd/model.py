@@ -239,7 +239,28 @@ class Faithfulness(NamedTuple):
         return self._auc(self.insertion)
 
 
+class IntegratedGradients(NamedTuple):
+    """What VqaNet.explain_integrated / explain_integrated_pairs return: maps fp32 [B, gh, gw] -- the integrated-gradients map
+    of each question on the feature grid, zero baseline, midpoint rule (signed, no upsampling, no normalisation) --, answers
+    int64 [B] -- the answer column each map explains, as Attribution.answers --, logits fp32 [B, A] -- what answer() /
+    answer_pairs() return for the same arguments, bit for bit -- and baseline_logits fp32 [B] -- the explained logit of each
+    question on an image cache of zeros.  The maps sum to logits[b, a_b] - baseline_logits[b] up to the quadrature error:
+    completeness_gap() says how far off they are."""
+    maps: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+    baseline_logits: torch.Tensor
+
+    def completeness_gap(self):
+        """maps.sum over positions - (logits[b, a_b] - baseline_logits[b]): float64 [B], formed on the maps' device.  A column
+        outside [0, A) (a zero map, a zero baseline) is read as the nearest column."""
+        cols = self.answers.clamp(0, self.logits.shape[1] - 1)[:, None]
+        picked = self.logits.gather(1, cols)[:, 0].double()
+        return self.maps.double().sum((1, 2)) - (picked - self.baseline_logits.double())
+
+
 OCCLUSION_WINDOW_MAX = 7    # include/vqa_hip.h vqa_occl_logit
+INTEGRATED_MAX_STEPS = 64   # include/vqa_hip.h VQA_ATT_PATH_MAX_STEPS
 FAITHFULNESS_MAX_POSITIONS = 8192    # include/vqa_hip.h vqa_rank_desc
 
 
@@ -309,6 +330,19 @@ def _check_window(what: str, window) -> int:
     if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= OCCLUSION_WINDOW_MAX or window % 2 == 0:
         raise ValueError(f"{what}: window must be an odd int in 1..{OCCLUSION_WINDOW_MAX}, got {window!r}")
     return window
+
+
+def _check_steps(what: str, steps) -> int:
+    """The steps argument of explain_integrated / explain_integrated_pairs: an int in 1..64 (a bool is not one)."""
+    if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= INTEGRATED_MAX_STEPS:
+        raise ValueError(f"{what}: steps must be an int in 1..{INTEGRATED_MAX_STEPS}, got {steps!r}")
+    return steps
+
+
+def integrated_alphas(steps: int) -> torch.Tensor:
+    """The step positions of explain_integrated on the host: the midpoint rule alpha_s = float32((2s + 1) / (2 * steps)), s = 0 ..
+    steps-1, each rounded once from the double."""
+    return torch.tensor([(2 * s + 1) / (2 * steps) for s in range(steps)], dtype=torch.float64).to(torch.float32)
 
 
 def _check_maps(what: str, maps, B: int, grid):
@@ -1212,7 +1246,7 @@ class VqaNet(nn.Module):
         """What an explain call returns for B == 0: the result type `kind` with every field empty."""
         P = feats.grid[0] * feats.grid[1]
         shape = dict(words=(0, T), maps=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A), deletion=(0, P + 1),
-                     insertion=(0, P + 1), order=(0, P))
+                     insertion=(0, P + 1), order=(0, P), baseline_logits=(0,))
         return kind(*(torch.empty(shape[f], dtype=torch.int64 if f in ("answers", "order") else torch.float32,
                                   device=feats.vn.device) for f in kind._fields))
 
@@ -1264,6 +1298,74 @@ class VqaNet(nn.Module):
         and the `answers` argument are explain()'s; logits are answer_pairs()'s for the same arguments, bit for bit; the index
         rules, ownership checks and errors are answer_pairs()'s, with the `answers` checks of explain() judged first."""
         return self._explain(feats, self._ask_pairs("explain_pairs", feats, qfeats, image_index, question_index, answers))
+
+    # ------------------------------------------------------------------ integrated gradients from cached features
+    @torch.no_grad()
+    def explain_integrated(self, feats: ImageFeatures, q, q_len, image_index, answers=None, steps: int = 16, *,
+                           _ig_bytes=None) -> IntegratedGradients:
+        """answer() with an integrated-gradients map per question: IntegratedGradients(maps fp32 [B, gh, gw], answers int64
+        [B], logits fp32 [B, A], baseline_logits fp32 [B]).  For question b about image n = image_index[b] and the answer column
+        a_b = answers[b], with explain()'s map R evaluated on a scaled cache,
+
+            G_s[b, p]  = sum_c vn[n, p, c] * d logits[b, a_b] / d x[p, c]     at x = alpha_s * vn[n]
+            maps[b, p] = (1 / steps) * sum_s G_s[b, p]                        alpha_s = float32((2s + 1) / (2 * steps))
+
+        the midpoint-rule Riemann sum of the gradient along the straight path from an image cache of ZEROS to the real one, eval
+        mode, the question held fixed (v_conv has no bias, so scaling vn scales v').  explain()'s gradient x input map is the
+        one-point rule at alpha = 1 and misses logits[b, a_b] - baseline_logits[b] by tens of per cent of it (DESIGN.md 4.21);
+        these maps sum to that difference up to the quadrature error, which completeness_gap() returns and which falls as steps
+        grows (first order only: the ReLUs put kinks on the path).  The midpoint rule never evaluates alpha = 0, where '*' and
+        '|' have every pre-activation exactly zero.  baseline_logits[b] is the eval-mode classifier on [0, question features].
+
+        steps: an int in 1..64 (default 16); anything else, a bool included, is a ValueError raised before any device work.
+
+        How it runs.  Composing it from explain() reads v' from memory 2 * steps times and runs the question encoder steps
+        times.  Here the question encoder, q_lin and answer()'s tail run once; two kernels walk v' once each whatever steps is
+        (include/vqa_hip.h vqa_att_path_score_grouped, vqa_att_path_attr_grouped: a tile of v' staged once serves every question
+        of the image and every step), and the softmax, the weighted sum and the classifier's first layer run on the B * steps
+        step-rows between them, in chunks of questions whose buffers stay within a 256 MiB workspace.  No parameter gradient is
+        formed and nothing is kept.
+
+        answers, logits, the `answers` argument, the argument rules and the refusals are explain()'s, judged before any device
+        work: eval mode only (RuntimeError in train mode), fp32 / fp32x3 (NotImplementedError for "bf16"), features that hold
+        v', the feature-ownership checks and image_index rules; all three do_option values; fp32 and float16 caches (a float16
+        cache gives, bit for bit, what feats.to(torch.float32) gives); a CUDA `answers` entry outside [0, A) gives a map of
+        zeros and a zero baseline; B == 0 returns empty tensors.  Rows come back in the caller's order and do not depend on how
+        the batch is ordered, split or chunked, bit for bit.
+
+        Not offered: other baselines (mean or blurred features), other quadratures, integrated gradients for the words or the
+        pixels, SmoothGrad, bf16 mode, train mode, data parallelism.
+
+        _ig_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
+        ask = self._ask_questions("explain_integrated", feats, q, q_len, image_index, answers,
+                                  own=lambda: _check_steps("VqaNet.explain_integrated", steps))
+        return self._explain_integrated(feats, ask, steps, _ig_bytes)
+
+    def _explain_integrated(self, feats, ask, steps, ig_bytes) -> IntegratedGradients:
+        if ask.B == 0:
+            return self._no_result(IntegratedGradients, feats)
+        # chunks cut between questions, in the caller's order; a single chunk walks the ask's own grouping
+        rows = self._engine.integrated_rows(feats.vn.shape[1], steps, ig_bytes)
+        cuts = [(b0, min(b0 + rows, ask.B)) for b0 in range(0, ask.B, rows)]
+        img = ask.index[2]
+        groups = [t for b0, b1 in cuts for t in _group(img[b0:b1], feats.N)] if len(cuts) > 1 else []
+        on_device = self._ask_upload(feats, ask, groups) or ask.on_device[:2]
+        chunks = [(b0, b1, on_device[2 * i], on_device[2 * i + 1]) for i, (b0, b1) in enumerate(cuts)]
+        alphas = integrated_alphas(steps).to(feats.vn.device)
+        maps, cols, logits, base = self._ask_run(self._engine.explain_integrated, feats, ask, alphas, chunks)
+        return IntegratedGradients(maps.view(-1, *feats.grid), cols.long(), logits, base)
+
+    @torch.no_grad()
+    def explain_integrated_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
+                                 answers=None, steps: int = 16, *, _ig_bytes=None) -> IntegratedGradients:
+        """explain_integrated() for B (image, question) pairs from the two caches, as answer_pairs() is to answer(): pair b
+        looks at image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  maps,
+        answers, baseline_logits, steps and the `answers` argument are explain_integrated()'s; logits are answer_pairs()'s for
+        the same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the steps and
+        `answers` checks judged first."""
+        ask = self._ask_pairs("explain_integrated_pairs", feats, qfeats, image_index, question_index, answers,
+                              own=lambda: _check_steps("VqaNet.explain_integrated_pairs", steps))
+        return self._explain_integrated(feats, ask, steps, _ig_bytes)
 
     # ------------------------------------------------------------------ occlusion maps from cached features
     @torch.no_grad()

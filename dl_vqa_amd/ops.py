@@ -696,6 +696,71 @@ def att_attr_score_grouped(r1, dscore, vprime, qp, wx, order, offsets, N: int, B
     return out
 
 
+ATT_PATH_MAX_STEPS = 64     # VQA_ATT_PATH_MAX_STEPS
+
+
+def att_path_score_grouped(vprime, qp, wx, bx, alphas, order, offsets, N: int, B: int, P: int, mode: int, qrow=None,
+                           out=None) -> torch.Tensor:
+    """att_score_grouped_fwd at every step of the path alpha * v' (include/vqa_hip.h): score [B, S, G, P] from ONE v' [N*P, mid]
+    per image (fp32 or float16), read once whatever S is; alphas device fp32 [S], 1 <= S <= 64.  qrow: the pairs form, as
+    att_score_grouped_fwd's.  out: written in place (a [>= B, S, G, P] workspace's first B rows)."""
+    _chk(qp), _chk(alphas)
+    S = alphas.numel()
+    G, xld, mid = _score_dims(wx, mode == 2)
+    _chk(order, torch.int32), _chk(offsets, torch.int32)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid)
+    assert qp.shape == (B if qrow is None else qp.shape[0], mid) and alphas.is_contiguous()
+    if out is None:
+        out = torch.empty(B, S, G, P, dtype=torch.float32, device=vprime.device)
+    assert out.shape == (B, S, G, P) and out.is_contiguous() and out.dtype == torch.float32
+    sfx = _cache_suffix(vprime)
+    if qrow is None:
+        call("vqa_att_path_score_grouped" + sfx, ptr(vprime), ptr(qp), ptr(wx), xld, ptr(bx), ptr(alphas), ptr(order), ptr(offsets),
+             ptr(out), N, B, S, P, mid, G, mode, stream())
+    else:
+        _chk(qrow, torch.int32)
+        assert qrow.numel() == B
+        call("vqa_att_path_score_grouped_pairs" + sfx, ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld, ptr(bx), ptr(alphas),
+             ptr(order), ptr(offsets), ptr(out), N, B, qp.shape[0], S, P, mid, G, mode, stream())
+    return out
+
+
+def att_path_scale_rows(x, alphas, cols: int):
+    """x[r, :cols] *= alphas[r % S] in place, for the step-rows r = b*S + s of a 2-D fp32 view x with unit column stride (the
+    image half of the classifier input at each step's path position); alphas device fp32 [S]."""
+    _chk(x), _chk(alphas)
+    assert x.dim() == 2 and x.shape[1] >= cols and (x.shape[1] == 1 or x.stride(1) == 1) and alphas.is_contiguous()
+    call("vqa_att_path_scale_rows", ptr(x), _ld(x), ptr(alphas), alphas.numel(), x.shape[0], cols, stream())
+    return x
+
+
+def att_path_attr_grouped(r1, dscore, vprime, qp, wx, alphas, scale: float, order, offsets, N: int, B: int, P: int, mode: int,
+                          qrow=None, out=None):
+    """The path sum of att_attr_score_grouped (include/vqa_hip.h): out [B, P] = scale * sum_s (r1[:, s] + r2_s) from r1
+    [B, S, P] and dscore [B, S, G, P] (att_attr_apply_gather on the B*S step-rows), ONE v' [N*P, mid] per image (fp32 or
+    float16), read once whatever S is; alphas device fp32 [S].  qrow, mode 2 without q' and out: att_attr_score_grouped's."""
+    G, xld, mid = _score_dims(wx, mode == 2)
+    _chk(order, torch.int32), _chk(offsets, torch.int32), _chk(r1), _chk(dscore), _chk(alphas)
+    S = alphas.numel()
+    M = qp.shape[0] if qp is not None else (B if qrow is None else 1)
+    assert order.numel() == B and offsets.numel() == N + 1 and vprime.shape == (N * P, mid) and alphas.is_contiguous()
+    assert r1.shape == (B, S, P) and dscore.shape == (B, S, G, P) and r1.is_contiguous() and dscore.is_contiguous()
+    assert qp is None or (qp.dtype == torch.float32 and qp.shape == (M if qrow is not None else B, mid))
+    if out is None:
+        out = torch.empty(B, P, dtype=torch.float32, device=vprime.device)
+    assert out.shape == (B, P) and out.is_contiguous() and out.dtype == torch.float32
+    sfx = _cache_suffix(vprime)
+    if qrow is None:
+        call("vqa_att_path_attr_grouped" + sfx, ptr(r1), ptr(dscore), ptr(vprime), ptr(qp), ptr(wx), xld, ptr(alphas), scale,
+             ptr(order), ptr(offsets), ptr(out), N, B, S, P, mid, G, mode, stream())
+    else:
+        _chk(qrow, torch.int32)
+        assert qrow.numel() == B
+        call("vqa_att_path_attr_grouped_pairs" + sfx, ptr(r1), ptr(dscore), ptr(vprime), ptr(qp), ptr(qrow), ptr(wx), xld,
+             ptr(alphas), scale, ptr(order), ptr(offsets), ptr(out), N, B, M, S, P, mid, G, mode, stream())
+    return out
+
+
 def att_attr_dq_grouped(dscore, vprime, qp, wx, order, offsets, N: int, B: int, P: int, mode: int, dq_part=None):
     """d logit / d q' through the attention scores (include/vqa_hip.h), from the dscore [B, G, P] of att_attr_apply_gather:
     att_score_grouped_bwd at p = 0 without dvprime and dwx_part, bit for bit.  Returns (dq_part [B*NT, mid], NT);

@@ -48,7 +48,8 @@ extern "C" {
  * the attribution entry points), and then the one of occlusion maps (vqa_occl_logit; declared behind those), and
  * then the two of exact word occlusion (vqa_lstm_occl_cell_fwd, vqa_occl_words; declared behind vqa_occl_logit), and then the
  * four of deletion and insertion curves (vqa_rank_desc, vqa_occl_curves_chunk, vqa_occl_curves_workspace_bytes, vqa_occl_curves;
- * declared behind those). */
+ * declared behind those), and then those of integrated gradients (vqa_att_path_score_grouped, vqa_att_path_attr_grouped and
+ * their _pairs, _f16 and _pairs_f16 forms, with vqa_att_path_scale_rows; declared behind those). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -621,6 +622,71 @@ int vqa_occl_curves(const float* base, const float* U, const int32_t* slot, int 
                     const float* cnull, const float* W2, int64_t w2_ld, const float* b2, const int32_t* answers,
                     const int32_t* order, float* workspace, int64_t workspace_bytes, float* deletion, float* insertion, int R,
                     int B, int P, int hid, int G, int A, vqa_stream_t stream);
+
+/* ---- integrated gradients from cached image features (inference, VqaNet.explain_integrated; csrc/att_score.hip) ----
+ * The gradient x input map above, averaged along the straight path from the zero cache to the real one (eval mode, the
+ * question held fixed, zero baseline).  For question b about image n, column a_b and S step positions alpha_s in (0, 1]:
+ *   G_s[b][p] = sum_c vn[n][p][c] * d logit[b][a_b] / d x[p][c]   at x = alpha_s * vn[n]
+ *   IG[b][p]  = scale * sum_s G_s[b][p]                            scale = 1 / S
+ * v_conv has no bias, so x = alpha_s * vn[n] means v' = alpha_s * v'[n].  With the symbols of the attribution section at
+ * step s (probs_s the softmax of score_s; dwv_s from h1_s = relu(lin1([alpha_s * sum_p probs_s vn, qf])); t_s = vn . dwv_s):
+ *   r1_s[b][p]        = sum_g probs_s[b][g][p] * t_s[b][g][p]
+ *   dscore_s[b][g][p] = probs_s * (t_s - sum_p' probs_s * t_s)      (vqa_att_attr_apply_gather on vn, without the factor alpha_s)
+ *   c_s[b][p][m]      = sum_g dscore_s[b][g][p] * wx[g][m]
+ *   r2_s[b][p]        = sum_m c_s[b][p][m] * s_s[b][p][m] * (alpha_s * v'[n][p][m])
+ *                       '+': s_s = [alpha_s v' + q' > 0]   '*': s_s = [(alpha_s v') q' > 0] * q'   '|': s_s = [alpha_s v' > 0]
+ *   G_s = r1_s + r2_s
+ * The step-rows (b, s) are laid out as a batch of B*S questions -- score and dscore [B][S][G][P], r1 [B][S][P] -- so the
+ * apply-gather entry points run between the two walks with the image index repeated S times.
+ *   vqa_att_path_score_grouped / _pairs / _f16 / _pairs_f16: the grouped forward at every step,
+ *       score[b][s][g][p] = bx[g] + sum_m wx[g][m] * relu((alpha_s * v'[n*P+p][m]) (+|*) q'[b][m])
+ *       '|': score[b][s][g][p] = (bx[g] + sum_m wx[g][m] * relu(alpha_s * v'[n*P+p][m])) + sum_m wx[g][mid+m] * relu(q'[b][m])
+ *   vqa_att_path_attr_grouped / _pairs / _f16 / _pairs_f16: the path sum of the grouped attribution,
+ *       out[b][p] = scale * sum_s (r1[b][s][p] + r2_s[b][p])       from r1 [B][S][P] and dscore [B][S][G][P]
+ * alphas: device float [S], 1 <= S <= VQA_ATT_PATH_MAX_STEPS.  Evaluation order: x = alpha_s * v' is rounded to fp32 first, then
+ * the element math of vqa_att_score_grouped_fwd / vqa_att_attr_score_grouped runs on x, so both walks see the same
+ * pre-activation bits; per (b, s, p) the summation order is theirs (a lane's channel quads lane*4 + 256*i in ascending i, x,
+ * y, z, w inside a quad, then the wave butterfly); the path sum adds r1 + r2_s in ascending s and multiplies by scale last.
+ * Ownership, argument checks, limits and path choice are vqa_att_score_grouped_fwd's / vqa_att_attr_score_grouped's
+ * (vqa_att_attr_score_grouped_path): a workgroup stages a tile of positions of ONE image in LDS once and walks that image's
+ * questions, and per question its S steps -- v' is read from memory once per walk whatever S is.  No atomics; every (b, s, p)
+ * / (b, p) of a listed question is written exactly once, so permuting or splitting the batch permutes the rows bit for bit;
+ * rows of questions that are not listed are left alone.  The pairs forms equal the plain forms on qp[qrow], the half forms the
+ * fp32 forms on the widened v', bit for bit.  '|' reads no q' in the attribution forms (qp may be NULL there).  A null
+ * alphas or an S outside the range is VQA_ERR_INVALID before any HIP call; B == 0 returns without a launch.
+ *   vqa_att_path_scale_rows: x[r*ld + c] *= alphas[r % S] for r < rows, c < cols (ld >= cols >= 1): the image half of the
+ *     classifier input of the step-rows r = b*S + s, between the two walks (the weighted sum of alpha_s * vn is alpha_s times
+ *     the weighted sum of vn, rounded once).  rows == 0 returns without a launch. */
+#define VQA_ATT_PATH_MAX_STEPS 64
+int vqa_att_path_scale_rows(float* x, int64_t ld, const float* alphas, int S, int64_t rows, int cols, vqa_stream_t stream);
+int vqa_att_path_score_grouped(const float* vprime, const float* qp, const float* wx, int wx_ld, const float* bx,
+                               const float* alphas, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                               int S, int P, int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_path_score_grouped_pairs(const float* vprime, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                     const float* bx, const float* alphas, const int32_t* order, const int32_t* offsets,
+                                     float* score, int N, int B, int M, int S, int P, int mid, int G, int mode,
+                                     vqa_stream_t stream);
+int vqa_att_path_score_grouped_f16(const void* vprime_f16, const float* qp, const float* wx, int wx_ld, const float* bx,
+                                   const float* alphas, const int32_t* order, const int32_t* offsets, float* score, int N, int B,
+                                   int S, int P, int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_path_score_grouped_pairs_f16(const void* vprime_f16, const float* qp, const int32_t* qrow, const float* wx, int wx_ld,
+                                         const float* bx, const float* alphas, const int32_t* order, const int32_t* offsets,
+                                         float* score, int N, int B, int M, int S, int P, int mid, int G, int mode,
+                                         vqa_stream_t stream);
+int vqa_att_path_attr_grouped(const float* r1, const float* dscore, const float* vprime, const float* qp, const float* wx,
+                              int wx_ld, const float* alphas, float scale, const int32_t* order, const int32_t* offsets,
+                              float* out, int N, int B, int S, int P, int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_path_attr_grouped_pairs(const float* r1, const float* dscore, const float* vprime, const float* qp,
+                                    const int32_t* qrow, const float* wx, int wx_ld, const float* alphas, float scale,
+                                    const int32_t* order, const int32_t* offsets, float* out, int N, int B, int M, int S, int P,
+                                    int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_path_attr_grouped_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp, const float* wx,
+                                  int wx_ld, const float* alphas, float scale, const int32_t* order, const int32_t* offsets,
+                                  float* out, int N, int B, int S, int P, int mid, int G, int mode, vqa_stream_t stream);
+int vqa_att_path_attr_grouped_pairs_f16(const float* r1, const float* dscore, const void* vprime_f16, const float* qp,
+                                        const int32_t* qrow, const float* wx, int wx_ld, const float* alphas, float scale,
+                                        const int32_t* order, const int32_t* offsets, float* out, int N, int B, int M, int S,
+                                        int P, int mid, int G, int mode, vqa_stream_t stream);
 
 /* ---- loss head (train.py:190-207, utils/train_utils.py:12-25) -------------------------------
  * loss_rows[b] = sum_k -log_softmax(logits[b])[a_idx[b][k]-1] * a_val[b][k]/10 * inv_batch
