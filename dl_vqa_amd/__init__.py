@@ -28,10 +28,13 @@ embedding output is zeroed, for every token, from the prefixes the variant recur
 ``VqaNet.explain_integrated`` / ``explain_integrated_pairs`` repair the first-order map (``IntegratedGradients``): the same
 gradient averaged along the path from a cache of zeros to the real one, which sums to the logit's rise over that baseline;
 v' is read twice whatever the number of steps.
+``VqaNet.explain_shapley`` / ``explain_shapley_pairs`` give the sampled Shapley value of every grid position (``Shapley``) for
+the set function those curves walk, with a standard error per entry, from orders drawn by ``shapley_orders``.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness, IntegratedGradients  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness, IntegratedGradients, Shapley, shapley_orders  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
            "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
-           "WordAttribution", "Occlusion", "WordOcclusion", "Faithfulness", "IntegratedGradients"]
+           "WordAttribution", "Occlusion", "WordOcclusion", "Faithfulness", "IntegratedGradients", "Shapley",
+           "shapley_orders"]

@@ -773,6 +773,42 @@ class Engine:
                             answers, order, slot0=r0, out=out, workspace=ws)
         return out[0], out[1], order, answers, run.logits
 
+    # ------------------------------------------------------------------ sampled Shapley maps from cached features
+    # The Shapley value of every grid position for the set function explain_faithfulness walks -- the explained logit with an
+    # arbitrary set of positions present -- from M orders that every question shares, and their reverses (include/vqa_hip.h
+    # vqa_occl_curves_orders, vqa_shapley_accumulate).  explain_faithfulness's parts once -- the base run, cnull,
+    # base, U per chunk of images -- no ranking, and per chunk the orders in groups: the curve kernels over the (question, order)
+    # pairs of a group, then the kernel that folds the group's curves into the running mean and M2 of every (question, position).
+    SHAPLEY_WS_BYTES = 256 << 20    # cap of the curve workspace of one launch: more orders walk in groups
+
+    @_device_current("feats", _cache_device)
+    def explain_shapley(self, P: Dict[str, Tensor], feats, ask, rows: Tensor, slot: Tensor, orders: Tensor, rank: Tensor,
+                        u_bytes: Optional[int] = None, ws_bytes: Optional[int] = None):
+        """explain_occlusion's arguments with orders / rank (device int32 [M,Pn]: the shared table of permutations and the
+        inverse of each row) in place of window, and ws_bytes, the cap of the curve workspace.  Returns (maps [B,Pn], stderr
+        [B,Pn], answers int32 [B], logits [B,A], baseline_logits [B])."""
+        assert not self.bf16, "explain_shapley: fp32 / fp32x3 only"
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        B, Pn, dev = run.img.numel(), feats.vn.shape[1], feats.vn.device
+        M = orders.shape[0]
+        answers = self._picked(run.logits, ask.answers)
+        cnull, base = self._occlusion_operands(P, run)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        one = max(1, ops._lib.load().vqa_occl_curves_orders_workspace_bytes(B, 1, Pn, self.G, self.hid))
+        per = min(M, max(1, int((self.SHAPLEY_WS_BYTES if ws_bytes is None else ws_bytes) // one)))
+        ws = ops.occl_curves_orders_workspace(B, per, Pn, self.G, self.hid, dev)
+        curves = (new(B * per * (Pn + 1)), new(B * per * (Pn + 1)))
+        state, out, baseline = (new(B, Pn), new(B, Pn)), (new(B, Pn), new(B, Pn)), new(B)
+        for r0, U in self._u_chunks(P, feats, rows, u_bytes):
+            for m0 in range(0, M, per):
+                n = min(per, M - m0)
+                group = tuple(c[:B * n * (Pn + 1)].view(B, n, Pn + 1) for c in curves)
+                ops.occl_curves_orders(base, U, slot, run.probs, run.score, cnull, P["classifier.lin2.weight"],
+                                       P["classifier.lin2.bias"], answers, orders[m0:m0 + n], slot0=r0, out=group, workspace=ws)
+                ops.shapley_accumulate(*group, rank[m0:m0 + n], slot, answers, state, self.A, U.shape[0], slot0=r0, m0=m0,
+                                       total=M if m0 + n == M else 0, out=out, empty=baseline)
+        return out[0], out[1], answers, run.logits, baseline
+
     # ------------------------------------------------------------------ gradient x input per question token
     # explain_words is explain carried on to the other input: the same logit's gradient at the question half of the classifier
     # input and, through the scores, at q' (one kernel, csrc/att_score.hip), back through q_lin and the recurrence to the

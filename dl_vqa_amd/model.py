@@ -259,6 +259,72 @@ class IntegratedGradients(NamedTuple):
         return self.maps.double().sum((1, 2)) - (picked - self.baseline_logits.double())
 
 
+class Shapley(NamedTuple):
+    """What VqaNet.explain_shapley / explain_shapley_pairs return: maps fp32 [B, gh, gw] -- the sampled Shapley value of each
+    grid position for the explained logit as a function of the set of positions present (signed, no upsampling, no
+    normalisation) --, stderr fp32 [B, gh, gw] -- the standard error of each entry over the drawn orders, NaN when one order
+    was drawn --, answers int64 [B] -- the answer column each map explains, as Attribution.answers --, logits fp32 [B, A] --
+    what answer() / answer_pairs() return for the same arguments, bit for bit -- and baseline_logits fp32 [B] -- the explained
+    logit of the empty image, explain_faithfulness()'s insertion[:, 0].  The maps sum to logits[b, a_b] - baseline_logits[b] up
+    to fp32 rounding, whatever the orders: completeness_gap() says how far off they are."""
+    maps: torch.Tensor
+    stderr: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+    baseline_logits: torch.Tensor
+
+    def completeness_gap(self):
+        """maps.sum over positions - (logits[b, a_b] - baseline_logits[b]): float64 [B], formed on the maps' device, as
+        IntegratedGradients.completeness_gap().  Zero up to fp32 rounding: every order's estimates telescope."""
+        return IntegratedGradients.completeness_gap(self)
+
+
+def shapley_orders(permutations: int, P: int, seed: int = 0) -> torch.Tensor:
+    """The table of orders VqaNet.explain_shapley draws for `permutations` permutations (counted with the reverses) of P grid
+    positions: int64 [permutations // 2, P] on the host, row m = torch.randperm(P) under ONE CPU torch.Generator seeded with
+    `seed`, drawn in ascending m.  The global seed stream is not touched."""
+    gen = torch.Generator(device="cpu").manual_seed(int(seed))
+    return torch.stack([torch.randperm(P, generator=gen) for _ in range(permutations // 2)]).reshape(permutations // 2, P)
+
+
+SHAPLEY_MAX_PERMUTATIONS = 256      # explain_shapley: permutations, counted with the reverses; a table holds half as many orders
+
+
+def _check_permutations(what: str, permutations) -> int:
+    """The permutations argument of explain_shapley / explain_shapley_pairs: an even int in 2..256 (a bool is not one)."""
+    if isinstance(permutations, bool) or not isinstance(permutations, int):
+        raise TypeError(f"{what}: permutations must be an int, got {type(permutations).__name__}")
+    if not 2 <= permutations <= SHAPLEY_MAX_PERMUTATIONS or permutations % 2:
+        raise ValueError(f"{what}: permutations must be an even int in 2..{SHAPLEY_MAX_PERMUTATIONS} (each drawn order is walked "
+                         f"with its reverse), got {permutations}")
+    return permutations
+
+
+def _check_orders(what: str, orders, grid):
+    """The orders argument of explain_shapley / explain_shapley_pairs, judged on the host: an integer tensor [M, P], 1 <= M <=
+    128, every row a permutation of 0 .. P-1, P = gh * gw.  Returns it on the host as int64; grid None (feats is no
+    ImageFeatures, which the next check refuses): the dtype and rank alone."""
+    orders = torch.as_tensor(orders).detach()
+    if orders.is_floating_point() or orders.is_complex() or orders.dtype == torch.bool:
+        raise TypeError(f"{what}: orders must be an integer tensor, got {orders.dtype}")
+    if orders.dim() != 2 or not 1 <= orders.shape[0] <= SHAPLEY_MAX_PERMUTATIONS // 2:
+        raise ValueError(f"{what}: orders of shape {tuple(orders.shape)} (expected [M, P] with 1 <= M <= "
+                         f"{SHAPLEY_MAX_PERMUTATIONS // 2})")
+    orders = orders.cpu().long()
+    if grid is None:
+        return orders
+    P = grid[0] * grid[1]
+    if orders.shape[1] != P:
+        raise ValueError(f"{what}: orders of shape {tuple(orders.shape)} on a {grid[0]} x {grid[1]} grid (expected "
+                         f"[M, {P}])")
+    if P > (1 << 20):
+        raise ValueError(f"{what}: {P} grid positions, the curves take at most {1 << 20}")
+    bad = (orders.sort(dim=1).values != torch.arange(P)).any(dim=1).nonzero()
+    if bad.numel():
+        raise ValueError(f"{what}: orders row {int(bad[0])} is no permutation of 0..{P - 1}")
+    return orders
+
+
 OCCLUSION_WINDOW_MAX = 7    # include/vqa_hip.h vqa_occl_logit
 INTEGRATED_MAX_STEPS = 64   # include/vqa_hip.h VQA_ATT_PATH_MAX_STEPS
 FAITHFULNESS_MAX_POSITIONS = 8192    # include/vqa_hip.h vqa_rank_desc
@@ -1245,8 +1311,8 @@ class VqaNet(nn.Module):
     def _no_result(self, kind, feats, T: int = 0):
         """What an explain call returns for B == 0: the result type `kind` with every field empty."""
         P = feats.grid[0] * feats.grid[1]
-        shape = dict(words=(0, T), maps=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A), deletion=(0, P + 1),
-                     insertion=(0, P + 1), order=(0, P), baseline_logits=(0,))
+        shape = dict(words=(0, T), maps=(0, *feats.grid), stderr=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A),
+                     deletion=(0, P + 1), insertion=(0, P + 1), order=(0, P), baseline_logits=(0,))
         return kind(*(torch.empty(shape[f], dtype=torch.int64 if f in ("answers", "order") else torch.float32,
                                   device=feats.vn.device) for f in kind._fields))
 
@@ -1496,6 +1562,100 @@ class VqaNet(nn.Module):
                               own=lambda: _check_maps(f"VqaNet.{what}", maps, torch.as_tensor(image_index).numel(),
                                                       getattr(feats, "grid", None)))
         return self._explain_faithfulness(feats, ask, maps, _u_bytes)
+
+    # ------------------------------------------------------------------ sampled Shapley maps from cached features
+    @torch.no_grad()
+    def explain_shapley(self, feats: ImageFeatures, q, q_len, image_index, answers=None, permutations: int = 16, *, seed: int = 0,
+                        orders=None, _u_bytes=None, _ws_bytes=None) -> Shapley:
+        """answer() with a sampled Shapley map per question: Shapley(maps fp32 [B, gh, gw], stderr fp32 [B, gh, gw], answers
+        int64 [B], logits fp32 [B, A], baseline_logits fp32 [B]).  For question b about image n = image_index[b] and the answer
+        column a_b = answers[b], let f_b(S) be logits[b, a_b] with only the grid positions S present -- "absent" is
+        explain_occlusion()'s "occluded": the rows of vn (hence of v') are zero; eval mode, the question held fixed.  The Shapley
+        value of position p is its marginal contribution f_b(S + p) - f_b(S) averaged over the sets S that precede p in a
+        uniformly random order of the positions.  explain_occlusion() asks that question for one context only (everything else
+        present) and misses redundancy: two positions that each suffice both get about 0.  Here, for M drawn orders,
+
+            e_m[b, orders[m, k]] = ((ins_m[k+1] - ins_m[k]) + (del_m[k] - del_m[k+1])) / 2              k = 0 .. P-1
+            maps[b, p]           = mean over m of e_m[b, p]
+            stderr[b, p]         = sqrt(sum_m (e_m[b, p] - maps[b, p])^2 / (M (M - 1))),  NaN for M = 1
+
+        with ins_m, del_m explain_faithfulness()'s insertion and deletion curves of question b along orders[m]: the insertion
+        step is the marginal of orders[m, k] under orders[m], the deletion step its marginal under the REVERSED order (the
+        deletion curve read backwards is the reversed order's insertion curve), so one walk serves a permutation and its
+        antithetic partner.  Every e_m telescopes, so the maps sum to logits[b, a_b] - baseline_logits[b] up to fp32 rounding
+        whatever M is (completeness_gap()); baseline_logits is the logit of the empty image, explain_faithfulness()'s
+        insertion[:, 0] for the same ask, bit for bit.
+
+        permutations: an even int in 2..256 (default 16), counted WITH the reverses: permutations // 2 orders are drawn, by
+        shapley_orders(permutations, P, seed) on the host (torch.randperm under a CPU generator of its own; the global seed
+        stream is not touched).  A bool or another type is a TypeError, an odd or out-of-range value a ValueError.  orders: an
+        integer tensor [M, P], 1 <= M <= 128, every row a permutation of 0 .. P-1, in place of permutations / seed (the
+        permutations are then the 2M rows and reverses); TypeError for a non-integer dtype, ValueError for another shape or a
+        row that is no permutation.  All of it is judged on the host before any device work.
+
+        ONE table of orders is shared by every question of the call.  Each question's estimate stays unbiased; only the errors
+        of different questions become correlated (do not average stderr over questions as if they were independent).  Sharing
+        is what makes a row depend on its question and the table alone: rows come back in the caller's order and do not depend
+        on how the batch is ordered, split or chunked, bit for bit.
+
+        How it runs.  Composing it from explain_faithfulness() repeats the base run and the U product per order.  Here they run
+        once; the curve kernels walk the (question, order) pairs from the shared table (include/vqa_hip.h
+        vqa_occl_curves_orders), the orders in groups whose curve workspace stays within 256 MiB, and one kernel folds each
+        group's curves into the running mean and M2 of every entry in ascending m (vqa_shapley_accumulate): the bits do not
+        depend on the grouping.  No ranking runs, nothing is kept.
+
+        answers, logits, the `answers` argument, the argument rules and the refusals are explain()'s, judged before any device
+        work: eval mode only (RuntimeError in train mode), fp32 / fp32x3 (NotImplementedError for "bf16"), features that hold
+        v', the feature-ownership checks and image_index rules; all three do_option values; fp32 and float16 caches (a float16
+        cache gives, bit for bit, what feats.to(torch.float32) gives); a CUDA `answers` entry outside [0, A) gives a map, an
+        error and a baseline of +0.0; B == 0 returns empty tensors.  Nothing is kept for a backward: _last_ctx, the gradient
+        buffer, p.grad and the dropout seed stream are left alone.
+
+        Not offered: per-question orders; other value functions (probabilities); KernelSHAP regression; Shapley values of the
+        words or the pixels; bf16 mode, train mode, data parallelism.
+
+        _u_bytes, _ws_bytes (tests and tools): the caps of U and of the curve workspace in bytes, to force several chunks and
+        several groups of orders at small sizes."""
+        what, table = "explain_shapley", []
+        ask = self._ask_questions(what, feats, q, q_len, image_index, answers,
+                                  own=lambda: table.append(self._shapley_table(what, feats, permutations, seed, orders)))
+        return self._explain_shapley(feats, ask, table[0], _u_bytes, _ws_bytes)
+
+    @staticmethod
+    def _shapley_table(what: str, feats, permutations, seed, orders):
+        """The host checks of permutations / seed / orders; returns the given table, or None where it is still to be drawn."""
+        if orders is not None:
+            return _check_orders(f"VqaNet.{what}", orders, getattr(feats, "grid", None))
+        _check_permutations(f"VqaNet.{what}", permutations)
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError(f"VqaNet.{what}: seed must be an int, got {type(seed).__name__}")
+        return lambda P: shapley_orders(permutations, P, seed)
+
+    def _explain_shapley(self, feats, ask, table, u_bytes, ws_bytes) -> Shapley:
+        if ask.B == 0:
+            return self._no_result(Shapley, feats)
+        P = feats.grid[0] * feats.grid[1]
+        orders = table(P) if callable(table) else table
+        rank = torch.empty_like(orders)
+        rank.scatter_(1, orders, torch.arange(P).expand_as(orders))          # the inverse of every row
+        rows, slot, orders, rank = self._ask_upload(feats, ask, compact_image_index(ask.index[2], feats.N)[:2]
+                                                    + (orders.reshape(-1), rank.reshape(-1)))
+        maps, err, cols, logits, base = self._ask_run(self._engine.explain_shapley, feats, ask, rows, slot, orders.view(-1, P),
+                                                      rank.view(-1, P), u_bytes, ws_bytes)
+        return Shapley(maps.view(-1, *feats.grid), err.view(-1, *feats.grid), cols.long(), logits, base)
+
+    @torch.no_grad()
+    def explain_shapley_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, answers=None,
+                              permutations: int = 16, *, seed: int = 0, orders=None, _u_bytes=None, _ws_bytes=None) -> Shapley:
+        """explain_shapley() for B (image, question) pairs from the two caches, as answer_pairs() is to answer(): pair b looks
+        at image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  maps, stderr,
+        answers, baseline_logits, permutations, seed, orders and the `answers` argument are explain_shapley()'s; logits are
+        answer_pairs()'s for the same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s,
+        with the permutations / orders and `answers` checks judged first."""
+        what, table = "explain_shapley_pairs", []
+        ask = self._ask_pairs(what, feats, qfeats, image_index, question_index, answers,
+                              own=lambda: table.append(self._shapley_table(what, feats, permutations, seed, orders)))
+        return self._explain_shapley(feats, ask, table[0], _u_bytes, _ws_bytes)
 
     # ------------------------------------------------------------------ gradient x input per question token
     @torch.no_grad()

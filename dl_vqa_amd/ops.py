@@ -881,6 +881,68 @@ def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot
     return deletion, insertion
 
 
+def occl_curves_orders_workspace(B: int, M: int, P: int, G: int, hid: int, device):
+    """A buffer of vqa_occl_curves_orders_workspace_bytes(B, M, P, G, hid): the chunk sums of one launch over M orders."""
+    need = _lib.load().vqa_occl_curves_orders_workspace_bytes(B, M, P, G, hid)
+    return torch.empty(max(need // 4, 4), dtype=torch.float32, device=device)
+
+
+def occl_curves_orders(base, U, slot, probs, score, cnull, W2, b2, answers, orders, slot0: int = 0, out=None, workspace=None):
+    """occl_curves over (question, order) pairs (include/vqa_hip.h vqa_occl_curves_orders): (deletion, insertion) fp32
+    [B, M, P+1], row (b, m) what occl_curves gives question b with orders[m] as its order, bit for bit.  The operands are
+    occl_curves' with orders int32 [M, P], one table for every question, in place of order [B, P].  out and workspace (at least
+    vqa_occl_curves_orders_workspace_bytes): as occl_curves'."""
+    B, G, P, R, hid, A, w2_ld = _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers)
+    _chk(orders, torch.int32)
+    assert orders.dim() == 2 and orders.shape[1] == P and orders.shape[0] >= 1 and orders.is_contiguous()
+    M = orders.shape[0]
+    if out is None:
+        out = tuple(torch.empty(B, M, P + 1, dtype=torch.float32, device=probs.device) for _ in range(2))
+    deletion, insertion = out
+    for t in out:
+        assert t.shape == (B, M, P + 1) and t.is_contiguous() and t.dtype == torch.float32
+    if workspace is None:
+        workspace = occl_curves_orders_workspace(B, M, P, G, hid, probs.device)
+    _chk(workspace)
+    assert workspace.is_contiguous()
+    call("vqa_occl_curves_orders", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2), w2_ld,
+         ptr(b2), ptr(answers), ptr(orders), ptr(workspace), workspace.numel() * 4, ptr(deletion), ptr(insertion), R, B, M, P, hid,
+         G, A, stream())
+    return deletion, insertion
+
+
+def shapley_accumulate(deletion, insertion, rank, slot, answers, state, A: int, R: int, slot0: int = 0, m0: int = 0, total: int = 0,
+                       out=None, empty=None):
+    """The curves of a group of orders folded into the running Shapley state (include/vqa_hip.h vqa_shapley_accumulate).
+    deletion, insertion [B, Mg, P+1] from occl_curves_orders, rank int32 [Mg, P] the inverse of the group's orders, slot and
+    answers device int32 [B]; state = (mean, M2) fp32 [B, P], updated in place (m0 == 0: started from zero); m0 the orders
+    folded before.  total == m0 + Mg on the last group: out = (maps, stderr) fp32 [B, P] are written (made when None) and
+    returned; otherwise total == 0 and None is returned.  empty (fp32 [B]) with m0 == 0: receives the logit of the empty image,
+    insertion[:, 0, 0].  Questions whose slot is outside [slot0, slot0 + R) are left alone."""
+    _chk(deletion), _chk(insertion), _chk(rank, torch.int32), _chk(slot, torch.int32), _chk(answers, torch.int32)
+    B, Mg, P1 = deletion.shape
+    P = P1 - 1
+    assert insertion.shape == deletion.shape and deletion.is_contiguous() and insertion.is_contiguous()
+    assert rank.shape == (Mg, P) and rank.is_contiguous() and slot.numel() == B and answers.numel() == B
+    mean, m2 = state
+    for t in state:
+        _chk(t)
+        assert t.shape == (B, P) and t.is_contiguous()
+    assert total in (0, m0 + Mg)
+    if empty is not None:
+        _chk(empty)
+        assert empty.numel() == B and empty.is_contiguous()
+    if total and out is None:
+        out = tuple(torch.empty(B, P, dtype=torch.float32, device=deletion.device) for _ in range(2))
+    maps, err = out if total else (None, None)
+    for t in (out if total else ()):
+        _chk(t)
+        assert t.shape == (B, P) and t.is_contiguous()
+    call("vqa_shapley_accumulate", ptr(deletion), ptr(insertion), ptr(rank), ptr(slot), slot0, ptr(answers), ptr(mean), ptr(m2),
+         ptr(maps), ptr(err), ptr(empty), R, B, P, Mg, m0, total, A, stream())
+    return out if total else None
+
+
 def lstm_occl_cell_fwd(xg_base, xg0, hg, h_var, c_var, q_len, var_b, var_t, s: int, n: Optional[int] = None, c_final=None,
                        cf_row=None):
     """One step, time s, of the variant recurrence of exact word occlusion (include/vqa_hip.h vqa_lstm_occl_cell_fwd), in place

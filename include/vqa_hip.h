@@ -49,7 +49,9 @@ extern "C" {
  * then the two of exact word occlusion (vqa_lstm_occl_cell_fwd, vqa_occl_words; declared behind vqa_occl_logit), and then the
  * four of deletion and insertion curves (vqa_rank_desc, vqa_occl_curves_chunk, vqa_occl_curves_workspace_bytes, vqa_occl_curves;
  * declared behind those), and then those of integrated gradients (vqa_att_path_score_grouped, vqa_att_path_attr_grouped and
- * their _pairs, _f16 and _pairs_f16 forms, with vqa_att_path_scale_rows; declared behind those). */
+ * their _pairs, _f16 and _pairs_f16 forms, with vqa_att_path_scale_rows; declared behind those), and then the three of sampled
+ * Shapley maps (vqa_occl_curves_orders_workspace_bytes, vqa_occl_curves_orders, vqa_shapley_accumulate; declared beside the
+ * curve entry points). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -622,6 +624,48 @@ int vqa_occl_curves(const float* base, const float* U, const int32_t* slot, int 
                     const float* cnull, const float* W2, int64_t w2_ld, const float* b2, const int32_t* answers,
                     const int32_t* order, float* workspace, int64_t workspace_bytes, float* deletion, float* insertion, int R,
                     int B, int P, int hid, int G, int A, vqa_stream_t stream);
+
+/* ---- sampled Shapley maps (inference, VqaNet.explain_shapley; csrc/faithfulness.hip) ----
+ * The Shapley value of grid position p for the set function f_b(S) = logit[b][a_b] with only the positions S present ("absent"
+ * as above: the rows of vn and v' zero; eval mode, the question held fixed), estimated from M orders of the positions and their
+ * reverses.  orders int32 [M][P], every row a permutation of 0 .. P-1, is ONE table shared by every question of the call: each
+ * question's estimate is unbiased, only the errors of different questions become correlated, and a row of the result depends
+ * on its question and the table alone -- not on the batch, its order or its split.  With ins_m, del_m the insertion and
+ * deletion curves of question b along orders[m] (vqa_occl_curves' definition),
+ *   e_m[b][orders[m][k]] = 0.5 * ((ins_m[k+1] - ins_m[k]) + (del_m[k] - del_m[k+1]))                 k = 0 .. P-1
+ * the mean of the marginal contribution of that position under orders[m] (the insertion step) and under its reverse (the
+ * deletion curve read backwards is the insertion curve of the reversed order: insertion_rev[k] = deletion[P-k]).  Then
+ *   maps[b][p]   = mean over m of e_m[b][p]
+ *   stderr[b][p] = sqrt(sum_m (e_m - maps)^2 / (M (M - 1))),  NaN for M == 1
+ * Every e_m telescopes: sum_p e_m[b][p] = ins_m[P] - ins_m[0] up to rounding, so the maps sum to the logit minus the logit of
+ * the empty image, ins_m[b][0] (bit-equal for every m).
+ *   vqa_occl_curves_orders: vqa_occl_curves over the (question, order) pairs.  The operands of vqa_occl_curves with orders int32
+ *     [M][P] in place of order [B][P], a workspace of vqa_occl_curves_orders_workspace_bytes(B, M, P, G, hid) bytes (M times
+ *     vqa_occl_curves'), and deletion / insertion [B][M][P + 1].  The same three kernels, whose tasks are the pairs t = b * M + m
+ *     (one place maps a task to its question row, its order row and its output row); row (b, m) holds, bit for bit, what
+ *     vqa_occl_curves gives question b with orders[m] as its order.  Slot window, columns outside [0, A) (+0.0 rows), entries
+ *     outside [0, P), limits and refusals are vqa_occl_curves'; in addition M >= 1 and B * M < 2^31 and the grids of B * M
+ *     tasks must fit, else VQA_ERR_INVALID before any HIP call.  No atomics; LDS as vqa_occl_curves.
+ *   vqa_shapley_accumulate: the curves of one group of Mg orders (deletion, insertion [B][Mg][P + 1]) into the running state.
+ *     rank int32 [Mg][P] is the inverse of each order of the group (rank[m][orders[m][k]] = k; an entry outside [0, P) is no
+ *     address and gives e = 0).  One thread owns (b, p) and folds the group in ascending m by Welford's update in fp32,
+ *       d = e - mean;  mean += d / (m0 + m + 1);  M2 = fma(d, e - mean, M2)
+ *     on mean, M2 [B][P]; m0 is the number of orders folded before this group (m0 == 0 starts from zero and reads no state).
+ *     One sequence of roundings per (b, p): the bits do not depend on how the orders are grouped into launches.  total == 0:
+ *     the state alone is written.  total == m0 + Mg (the last group): also maps = mean and err = stderr as above.  empty
+ *     (optional, [B]) with m0 == 0: empty[b] = ins_0[b][0] of the group's first order, the logit of the empty image.  A question
+ *     whose slot is outside [slot0, slot0 + R) is left alone; a column a_b outside [0, A) gives state, maps, err and empty of +0.0.
+ *     Null pointers (maps, err may be NULL when total == 0), Mg < 1, m0 < 0, another total, P outside 1..2^20, R, A < 1 or a
+ *     grid that does not fit: VQA_ERR_INVALID before any HIP call.  B == 0 returns without a launch.  No LDS, no atomics. */
+int64_t vqa_occl_curves_orders_workspace_bytes(int B, int M, int P, int G, int hid);
+int vqa_occl_curves_orders(const float* base, const float* U, const int32_t* slot, int slot0, const float* probs,
+                           const float* score, const float* cnull, const float* W2, int64_t w2_ld, const float* b2,
+                           const int32_t* answers, const int32_t* orders, float* workspace, int64_t workspace_bytes,
+                           float* deletion, float* insertion, int R, int B, int M, int P, int hid, int G, int A,
+                           vqa_stream_t stream);
+int vqa_shapley_accumulate(const float* deletion, const float* insertion, const int32_t* rank, const int32_t* slot, int slot0,
+                           const int32_t* answers, float* mean, float* m2, float* maps, float* err, float* empty, int R, int B,
+                           int P, int Mg, int m0, int total, int A, vqa_stream_t stream);
 
 /* ---- integrated gradients from cached image features (inference, VqaNet.explain_integrated; csrc/att_score.hip) ----
  * The gradient x input map above, averaged along the straight path from the zero cache to the real one (eval mode, the

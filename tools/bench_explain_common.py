@@ -1,4 +1,4 @@
-"""What the five explain benchmarks (tools/bench_explain*.py) share: the shapes, the timed window, the set-up of a case and the
+"""What the seven explain benchmarks (tools/bench_explain*.py) share: the shapes, the timed window, the set-up of a case and the
 driver, which never touches the GPU -- the measurement is a child process under its own `timeout`, a failure ends the run, and
 the last line the child prints is the result."""
 import argparse
