@@ -30,11 +30,14 @@ gradient averaged along the path from a cache of zeros to the real one, which su
 v' is read twice whatever the number of steps.
 ``VqaNet.explain_shapley`` / ``explain_shapley_pairs`` give the sampled Shapley value of every grid position (``Shapley``) for
 the set function those curves walk, with a standard error per entry, from orders drawn by ``shapley_orders``.
+``VqaNet.explain_faithfulness_probs`` / ``explain_faithfulness_probs_pairs`` walk the same curves on probabilities
+(``ProbabilityCurves``): the softmax probability of the explained column and the arg-max column at every step, the published
+deletion / insertion areas, and the steps at which the answer flips.
 """
-from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness, IntegratedGradients, Shapley, shapley_orders  # noqa: F401
+from .model import VqaNet, questionNet, ImageNet2, Attention, Classifier, ImageFeatures, group_by_image, TopAnswers, topk_answers, QuestionFeatures, unique_questions, compact_image_index, Attribution, WordAttribution, Occlusion, WordOcclusion, Faithfulness, IntegratedGradients, Shapley, shapley_orders, ProbabilityCurves  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 
 __all__ = ["VqaNet", "questionNet", "ImageNet2", "Attention", "Classifier", "ImageFeatures", "group_by_image", "TopAnswers",
            "topk_answers", "QuestionFeatures", "unique_questions", "preprocess_images", "compact_image_index", "Attribution",
            "WordAttribution", "Occlusion", "WordOcclusion", "Faithfulness", "IntegratedGradients", "Shapley",
-           "shapley_orders"]
+           "shapley_orders", "ProbabilityCurves"]

@@ -184,6 +184,10 @@ PROTOTYPES = {
     "vqa_occl_curves_orders": (i32, [f32p, f32p, vp, i32, f32p, f32p, f32p, f32p, i64, f32p, vp, vp, f32p, i64, f32p, f32p, i32,
                                      i32, i32, i32, i32, i32, i32, vp]),
     "vqa_shapley_accumulate": (i32, [f32p, f32p, vp, vp, i32, vp, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),
+    # probability curves: the walk that keeps its hidden rows, and the probability of a given column beside top-1 (bound with
+    # the curve entry points)
+    "vqa_occl_curves_hidden": (i32, [f32p, f32p, vp, i32, f32p, f32p, f32p, vp, f32p, i64, f32p, i32, i32, i32, i32, i32, vp]),
+    "vqa_softmax_pick": (i32, [f32p, i64, i32, i32, vp, i32, vp, f32p, f32p, vp]),
     # integrated gradients from cached features (bound with the attribution entry points, before the last two)
     "vqa_att_path_scale_rows": (i32, [f32p, i64, f32p, i32, i64, i32, vp]),
     "vqa_att_path_score_grouped": (i32, [f32p, f32p, f32p, i32, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp]),

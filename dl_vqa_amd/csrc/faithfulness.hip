@@ -7,6 +7,8 @@
 // Sampled Shapley maps (vqa_occl_curves_orders, vqa_shapley_accumulate) walk the same three kernels over
 // (question, order) pairs from one table of orders that every question shares -- curve_task is the one place that says which
 // question and which order row a task reads -- and one more kernel folds the curves' steps into maps and error bars.
+// Probability curves (vqa_occl_curves_hidden) run the same three kernels with the walk under a compile-time
+// flag: it keeps every state's hidden row, from which one GEMM with W2 gives every answer column.
 #include "occl_core.hpp"
 
 namespace vqa {
@@ -169,15 +171,29 @@ curve_scan_kernel(float* sum, float* pre, float* mass, float* mass_pre, const in
 // alpha of a kept set with mass m that leaves `absent` positions out: each of those keeps the weight r
 __device__ __forceinline__ float kept_alpha(float m, int absent, float r) { return 1.f / fmaf((float)absent, r, m); }
 
-// this lane's part of W2[a] . relu(base + sum_g alpha[g] * acc[g]) for one quad
+// one quad of base + sum_g alpha[g] * acc[g], g ascending: the hidden row of a kept set before its relu
 template <int G>
-__device__ __forceinline__ float kept_dot(const float4 (&acc)[G], const float (&alpha)[G], float4 pre, const float4 w2) {
+__device__ __forceinline__ float4 kept_pre(const float4 (&acc)[G], const float (&alpha)[G], float4 pre) {
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     pre.x = fmaf(alpha[g], acc[g].x, pre.x); pre.y = fmaf(alpha[g], acc[g].y, pre.y);
     pre.z = fmaf(alpha[g], acc[g].z, pre.z); pre.w = fmaf(alpha[g], acc[g].w, pre.w);
   }
+  return pre;
+}
+
+// this lane's part of W2[a] . relu(base + sum_g alpha[g] * acc[g]) for one quad
+template <int G>
+__device__ __forceinline__ float kept_dot(const float4 (&acc)[G], const float (&alpha)[G], float4 base, const float4 w2) {
+  const float4 pre = kept_pre<G>(acc, alpha, base);
   return fmaf(w2.w, fmaxf(pre.w, 0.f), fmaf(w2.z, fmaxf(pre.z, 0.f), fmaf(w2.y, fmaxf(pre.y, 0.f), w2.x * fmaxf(pre.x, 0.f))));
+}
+
+// the same quad as the hidden row itself: relu(base + sum_g alpha[g] * acc[g])
+template <int G>
+__device__ __forceinline__ float4 kept_hidden(const float4 (&acc)[G], const float (&alpha)[G], float4 base) {
+  const float4 pre = kept_pre<G>(acc, alpha, base);
+  return make_float4(fmaxf(pre.x, 0.f), fmaxf(pre.y, 0.f), fmaxf(pre.z, 0.f), fmaxf(pre.w, 0.f));
 }
 
 // The walk.  Workgroup = (task t, CURVE_WAVES consecutive chunks); it starts with occl_head (occl_core.hpp) for the task's
@@ -188,12 +204,17 @@ __device__ __forceinline__ float kept_dot(const float4 (&acc)[G], const float (&
 // the suffix and add the rows j = n-1 .. 0; each state's dot product is finished by the wave butterfly.  insertion[k0 + j] is
 // written for j = 1 .. n (j = 0 by chunk 0 alone), deletion[k0 + j] for j = 0 .. n-1 (j = n by the last chunk alone): every
 // element once.
-template <int G>
+// HIDDEN (vqa_occl_curves_hidden): the same walk -- the same chunk_steps, alphas, accumulation order and CURVE_L -- that keeps
+// each state's hidden row relu(base + sum_g alpha_g * acc_g) instead of collapsing it onto one W2 row.  No column is explained:
+// W2, b2, answers and A are not looked at, the head loads no W2 (dynamic LDS occl_lds(1, hid)) and there is no butterfly.  Lane l
+// stores its quad of state j as one float4, 64 lanes 1 KiB contiguous, into hidden [T][2][P + 1][hid]: [t][1][k0 + j] for the
+// insertion states, [t][0][k0 + j] for the deletion states, under the same once-only rule (deletion / insertion unused).
+template <int G, bool HIDDEN = false>
 __global__ void __launch_bounds__(CURVE_THREADS)
 curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0, int R, const float* probs, const float* score,
                   const float* cnull, const float* W2, int64_t w2_ld, const float* b2, const int* answers, const int* order,
                   const float* suf, const float* pre, const float* mass_suf, const float* mass_pre, float* deletion,
-                  float* insertion, int M, int ngroup, int nch, int P, int hid, int A) {
+                  float* insertion, int M, int ngroup, int nch, int P, int hid, int A, float* hidden) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int t = blockIdx.x / ngroup;
   const int cg = blockIdx.x - t * ngroup;
@@ -202,21 +223,25 @@ curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0,
   const int row = occl_row(slot, b, slot0, R);
   if (row < 0) return;                                                // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int a = answers[b];
-  float* del = deletion + (int64_t)t * (P + 1);
-  float* ins = insertion + (int64_t)t * (P + 1);
-  if ((unsigned)a >= (unsigned)A) {
-    const int k = cg * CURVE_WAVES * CURVE_L + tid;
-    if (tid < CURVE_WAVES * CURVE_L && k < P) del[k] = ins[k] = 0.f;
-    if (cg == ngroup - 1 && tid == 0) del[P] = ins[P] = 0.f;
-    return;
+  int a = 0;
+  float *del = nullptr, *ins = nullptr;
+  if constexpr (!HIDDEN) {
+    a = answers[b];
+    del = deletion + (int64_t)t * (P + 1);
+    ins = insertion + (int64_t)t * (P + 1);
+    if ((unsigned)a >= (unsigned)A) {
+      const int k = cg * CURVE_WAVES * CURVE_L + tid;
+      if (tid < CURVE_WAVES * CURVE_L && k < P) del[k] = ins[k] = 0.f;
+      if (cg == ngroup - 1 && tid == 0) del[P] = ins[P] = 0.f;
+      return;
+    }
   }
-  float* s_base = sm;                 // [hid]
-  float* s_w2 = sm + hid;             // [hid]
-  float* red = sm + 2 * (size_t)hid;  // [16]
-  float* s_r = red + 16;              // [G]
+  float* s_base = sm;                                   // [hid]
+  float* s_w2 = sm + hid;                               // [hid]; HIDDEN: not there
+  float* red = sm + (HIDDEN ? 1 : 2) * (size_t)hid;     // [16]
+  float* s_r = red + 16;                                // [G]
   const int nq = hid >> 2;
-  occl_head<G, CURVE_THREADS>(base, score, cnull, W2, w2_ld, b, a, P, hid, s_base, s_w2, red, s_r);
+  occl_head<G, CURVE_THREADS, !HIDDEN>(base, score, cnull, W2, w2_ld, b, a, P, hid, s_base, s_w2, red, s_r);
   const int c = cg * CURVE_WAVES + wave;
   if (c >= nch) return;                                               // wave-uniform; no barrier below
   const int k0 = c * CURVE_L, n = min(CURVE_L, P - k0);
@@ -245,12 +270,18 @@ curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0,
   const float4* Ub = reinterpret_cast<const float4*>(U + (int64_t)row * P * G * hid);
   const float4* pre4 = reinterpret_cast<const float4*>(pre) + ((int64_t)t * nch + c) * G * nq;
   const float4* suf4 = reinterpret_cast<const float4*>(suf) + ((int64_t)t * nch + c) * G * nq;
-  float d_ins[CURVE_L + 1], d_del[CURVE_L + 1];
+  // HIDDEN: the rows [t][0][k0] (deletion) and [t][1][k0] (insertion) of the output, as quads
+  float4* h_del = HIDDEN ? reinterpret_cast<float4*>(hidden) + (((int64_t)t * 2) * (P + 1) + k0) * nq : nullptr;
+  float4* h_ins = HIDDEN ? h_del + (int64_t)(P + 1) * nq : nullptr;
+  float d_ins[HIDDEN ? 1 : CURVE_L + 1], d_del[HIDDEN ? 1 : CURVE_L + 1];
+  if constexpr (!HIDDEN) {
 #pragma unroll
-  for (int j = 0; j <= CURVE_L; ++j) d_ins[j] = d_del[j] = 0.f;
+    for (int j = 0; j <= CURVE_L; ++j) d_ins[j] = d_del[j] = 0.f;
+  }
   for (int q = lane; q < nq; q += 64) {
     const float4 bq = reinterpret_cast<const float4*>(s_base)[q];
-    const float4 w2 = reinterpret_cast<const float4*>(s_w2)[q];
+    float4 w2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (!HIDDEN) w2 = reinterpret_cast<const float4*>(s_w2)[q];
     float4 acc[G];
     float al[G];
     // insertion: from the prefix, forward
@@ -261,7 +292,11 @@ curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0,
       if (j <= n) {
 #pragma unroll
         for (int g = 0; g < G; ++g) al[g] = lane_float(a_ins[g], j);
-        d_ins[j] += kept_dot<G>(acc, al, bq, w2);
+        if constexpr (HIDDEN) {
+          if (j > 0 || c == 0) h_ins[(int64_t)j * nq + q] = kept_hidden<G>(acc, al, bq);
+        } else {
+          d_ins[j] += kept_dot<G>(acc, al, bq, w2);
+        }
       }
       if (j < CURVE_L) {
         const int s = lane_int(pos, j);
@@ -286,18 +321,24 @@ curve_walk_kernel(const float* base, const float* U, const int* slot, int slot0,
       if (j <= n) {
 #pragma unroll
         for (int g = 0; g < G; ++g) al[g] = lane_float(a_del[g], j);
-        d_del[j] += kept_dot<G>(acc, al, bq, w2);
+        if constexpr (HIDDEN) {
+          if (j < n || c == nch - 1) h_del[(int64_t)j * nq + q] = kept_hidden<G>(acc, al, bq);
+        } else {
+          d_del[j] += kept_dot<G>(acc, al, bq, w2);
+        }
       }
     }
   }
-  const float bias = b2[a];
+  if constexpr (!HIDDEN) {
+    const float bias = b2[a];
 #pragma unroll
-  for (int j = 0; j <= CURVE_L; ++j) {
-    if (j <= n) {                                                     // wave-uniform
-      const float vi = wave_sum(d_ins[j]) + bias, vd = wave_sum(d_del[j]) + bias;
-      if (lane == 0) {
-        if (j > 0 || c == 0) ins[k0 + j] = vi;
-        if (j < n || c == nch - 1) del[k0 + j] = vd;
+    for (int j = 0; j <= CURVE_L; ++j) {
+      if (j <= n) {                                                   // wave-uniform
+        const float vi = wave_sum(d_ins[j]) + bias, vd = wave_sum(d_del[j]) + bias;
+        if (lane == 0) {
+          if (j > 0 || c == 0) ins[k0 + j] = vi;
+          if (j < n || c == nch - 1) del[k0 + j] = vd;
+        }
       }
     }
   }
@@ -358,16 +399,21 @@ static int64_t curve_workspace_bytes(int64_t T, int P, int G, int hid) {
 }
 
 // What vqa_occl_curves (M == 0: B tasks, order [B][P]) and vqa_occl_curves_orders (M >= 1: B * M tasks, order [M][P]) do
-// alike: the checks, the workspace layout and the three launches over the tasks (curve_task).
+// alike: the checks, the workspace layout and the three launches over the tasks (curve_task).  vqa_occl_curves_hidden (M == 0)
+// too: `hidden` [B][2][P + 1][hid] in place of W2, b2, answers, deletion and insertion (all null, w2_ld = hid, A = 1), the
+// third launch being the walk that keeps its hidden rows.
 static int curves_launch(const char* who, const float* base, const float* U, const int32_t* slot, int slot0, const float* probs,
                          const float* score, const float* cnull, const float* W2, int64_t w2_ld, const float* b2,
                          const int32_t* answers, const int32_t* order, float* workspace, int64_t workspace_bytes, float* deletion,
-                         float* insertion, int R, int B, int M, int P, int hid, int G, int A, hipStream_t s) {
-  const bool pointers = base && U && slot && probs && score && cnull && W2 && b2 && answers && order && deletion && insertion;
+                         float* insertion, float* hidden, int R, int B, int M, int P, int hid, int G, int A, hipStream_t s) {
+  const bool pointers = base && U && slot && probs && score && cnull && order &&
+                        (hidden ? true : W2 && b2 && answers && deletion && insertion);
   // without questions nothing is read, so no alignment is asked for (and no workspace, below)
-  if (const int rc = occl_check(who, G, pointers, hid, w2_ld, 2, "2", B ? ptr_bits(base, U, W2, workspace) : 0,
-                                "base, U, W2 and the workspace", R >= 1 && B >= 0 && P >= 1 && P <= (1 << 20) && A >= 1,
-                                "%s: R=%d, B=%d, P=%d, A=%d out of range", R, B, P, A))
+  if (const int rc = occl_check(who, G, pointers, hid, w2_ld, hidden ? 1 : 2, hidden ? "1" : "2",
+                                B ? ptr_bits(base, U, W2, workspace, hidden) : 0,
+                                hidden ? "base, U, the workspace and the hidden rows" : "base, U, W2 and the workspace",
+                                R >= 1 && B >= 0 && P >= 1 && P <= (1 << 20) && A >= 1, "%s: R=%d, B=%d, P=%d, A=%d out of range", R,
+                                B, P, A))
     return rc;
   if (B == 0) return VQA_OK;
   const int64_t T = (int64_t)B * (M ? M : 1);
@@ -395,12 +441,13 @@ static int curves_launch(const char* who, const float* base, const float* U, con
     rc = check_hip(hipGetLastError(), "occl_curves scan launch");
     if (rc) return rc;
     // the attribute is set once per kernel, so for the largest LDS size the check above admits
-    rc = set_smem(curve_walk_kernel<GG>, 64 * 1024, "attr(occl_curves)");
+    auto walk = hidden ? curve_walk_kernel<GG, true> : curve_walk_kernel<GG, false>;
+    rc = set_smem(walk, 64 * 1024, hidden ? "attr(occl_curves_hidden)" : "attr(occl_curves)");
     if (rc) return rc;
-    hipLaunchKernelGGL(curve_walk_kernel<GG>, dim3((unsigned)(T * ngroup)), dim3(CURVE_THREADS), occl_lds(2, hid), s, base, U, slot,
+    hipLaunchKernelGGL(walk, dim3((unsigned)(T * ngroup)), dim3(CURVE_THREADS), occl_lds(hidden ? 1 : 2, hid), s, base, U, slot,
                        slot0, R, probs, score, cnull, W2, w2_ld, b2, answers, order, sum, pre, mass, mass_pre, deletion, insertion,
-                       M, ngroup, nch, P, hid, A);
-    return check_hip(hipGetLastError(), "occl_curves walk launch");
+                       M, ngroup, nch, P, hid, A, hidden);
+    return check_hip(hipGetLastError(), hidden ? "occl_curves_hidden walk launch" : "occl_curves walk launch");
   });
 }
 
@@ -433,7 +480,17 @@ int vqa_occl_curves(const float* base, const float* U, const int32_t* slot, int 
                     int B, int P, int hid, int G, int A, vqa_stream_t stream) {
   set_launch_tag(-1);
   return curves_launch("vqa_occl_curves", base, U, slot, slot0, probs, score, cnull, W2, w2_ld, b2, answers, order, workspace,
-                       workspace_bytes, deletion, insertion, R, B, 0, P, hid, G, A, (hipStream_t)stream);
+                       workspace_bytes, deletion, insertion, nullptr, R, B, 0, P, hid, G, A, (hipStream_t)stream);
+}
+
+int vqa_occl_curves_hidden(const float* base, const float* U, const int32_t* slot, int slot0, const float* probs,
+                           const float* score, const float* cnull, const int32_t* order, float* workspace, int64_t workspace_bytes,
+                           float* hidden, int R, int B, int P, int hid, int G, vqa_stream_t stream) {
+  set_launch_tag(-1);
+  const char* who = "vqa_occl_curves_hidden";
+  // a null `hidden` reads as the column form without its operands: curves_launch's own "null pointer"
+  return curves_launch(who, base, U, slot, slot0, probs, score, cnull, nullptr, hid, nullptr, nullptr, order, workspace,
+                       workspace_bytes, nullptr, nullptr, hidden, R, B, 0, P, hid, G, 1, (hipStream_t)stream);
 }
 
 int64_t vqa_occl_curves_orders_workspace_bytes(int B, int M, int P, int G, int hid) {
@@ -450,7 +507,7 @@ int vqa_occl_curves_orders(const float* base, const float* U, const int32_t* slo
   const char* who = "vqa_occl_curves_orders";
   VQA_REQUIRE(M >= 1 && (int64_t)(B > 0 ? B : 0) * M < (1LL << 31), "%s: M=%d orders for B=%d questions out of range", who, M, B);
   return curves_launch(who, base, U, slot, slot0, probs, score, cnull, W2, w2_ld, b2, answers, orders, workspace, workspace_bytes,
-                       deletion, insertion, R, B, M, P, hid, G, A, (hipStream_t)stream);
+                       deletion, insertion, nullptr, R, B, M, P, hid, G, A, (hipStream_t)stream);
 }
 
 int vqa_shapley_accumulate(const float* deletion, const float* insertion, const int32_t* rank, const int32_t* slot, int slot0,

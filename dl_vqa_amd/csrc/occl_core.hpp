@@ -19,13 +19,14 @@ static size_t occl_lds(int rows, int hid) { return ((size_t)rows * hid + 16 + 4)
 //   s_r[g] = exp(cnull[b][g] - m) / sum_p exp(score[b][g][p] - m),  m = max_p score[b][g][p]
 // by the block reduction (red [16]) that every workgroup of b runs in the same order -- maps and curves agree on r because
 // both get it here.  Ends with the barrier after which these, and what the caller staged into LDS before, are readable.
-template <int G, int THREADS>
+// WITH_W2 == false (the hidden-row walk of faithfulness.hip, which explains no column): W2, a and s_w2 are not looked at.
+template <int G, int THREADS, bool WITH_W2 = true>
 __device__ __forceinline__ void occl_head(const float* base, const float* score, const float* cnull, const float* W2, int64_t w2_ld,
                                           int b, int a, int P, int hid, float* s_base, float* s_w2, float* red, float* s_r) {
   const int tid = threadIdx.x;
   for (int c = tid; c < (hid >> 2); c += THREADS) {
     reinterpret_cast<float4*>(s_base)[c] = reinterpret_cast<const float4*>(base + (int64_t)b * hid)[c];
-    reinterpret_cast<float4*>(s_w2)[c] = reinterpret_cast<const float4*>(W2 + (int64_t)a * w2_ld)[c];
+    if constexpr (WITH_W2) reinterpret_cast<float4*>(s_w2)[c] = reinterpret_cast<const float4*>(W2 + (int64_t)a * w2_ld)[c];
   }
 #pragma unroll
   for (int g = 0; g < G; ++g) {

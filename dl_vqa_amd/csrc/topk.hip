@@ -12,6 +12,9 @@
 // 64 hold the same bits): one fixed order, no atomics.
 // NJ > 0: the row (up to 64*NJ columns) lives in NJ key registers per lane, every loop fully unrolled (static indices:
 // nothing lands in scratch); NJ == 0: any A, the row is read again through the cache in every round.
+// vqa_softmax_pick (probability curves) is the same row code with k = 1 and a tail that also gives the
+// probability of one GIVEN column per row from the row's own maximum and sum: softmax_topk_row is written once, each kernel
+// hands it what to do with (row, x, max, sum) at the end.
 #include "common.hpp"
 
 namespace vqa {
@@ -26,9 +29,10 @@ __device__ __forceinline__ float topk_value(uint32_t key) {   // the inverse (Na
   return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }
 
-template <int NJ>
-__global__ __launch_bounds__(256) void softmax_topk_kernel(const float* logits, int64_t ld, int B, int A, int k, int32_t* idx,
-                                                           float* prob, float* lse) {
+// One wave's row.  tail(row, x, mx, sum, lane): what the kernel adds once max and sum are known (every lane holds both).
+template <int NJ, class Tail>
+__device__ __forceinline__ void softmax_topk_row(const float* logits, int64_t ld, int B, int A, int k, int32_t* idx, float* prob,
+                                                 float* lse, Tail tail) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;                                // wave-uniform; the kernel has no workgroup barrier
@@ -96,6 +100,37 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* logits, 
     prob[o] = expf(topk_value((uint32_t)(mine >> 32)) - mx) / sum;
   }
   if (lse && lane == 0) lse[row] = mx + logf(sum);
+  tail(row, x, mx, sum, lane);
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void softmax_topk_kernel(const float* logits, int64_t ld, int B, int A, int k, int32_t* idx,
+                                                           float* prob, float* lse) {
+  softmax_topk_row<NJ>(logits, ld, B, A, k, idx, prob, lse, [](int64_t, const float*, float, float, int) {});
+}
+
+// vqa_softmax_pick: k = 1 into top / top_prob, and prob_at[row] = exp(x[a] - max) / sum for the column a = answers[row / rpq]
+// -- top_prob's own expression, so a row whose given column is its arg-max holds the same bits twice -- or +0.0 for a column
+// outside [0, A).  x[a] is one more 4-byte load of a row the wave has just read.
+template <int NJ>
+__global__ __launch_bounds__(256) void softmax_pick_kernel(const float* logits, int64_t ld, int B, int A, const int32_t* answers,
+                                                           int rpq, int32_t* top, float* top_prob, float* prob_at) {
+  softmax_topk_row<NJ>(logits, ld, B, A, 1, top, top_prob, nullptr,
+                       [=](int64_t row, const float* x, float mx, float sum, int lane) {
+                         if (lane != 0) return;
+                         const int a = answers[row / rpq];
+                         prob_at[row] = (unsigned)a < (unsigned)A ? expf(x[a] - mx) / sum : 0.f;
+                       });
+}
+
+// NJ of a row of A columns, as a compile-time constant handed to f: the ladder both entry points launch by
+template <class F>
+static void with_topk_nj(int A, F&& f) {
+  if (A <= 64) f(std::integral_constant<int, 1>{});
+  else if (A <= 256) f(std::integral_constant<int, 4>{});
+  else if (A <= 1024) f(std::integral_constant<int, 16>{});
+  else if (A <= 3072) f(std::integral_constant<int, 48>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace vqa
@@ -113,14 +148,27 @@ int vqa_softmax_topk(const float* logits, int64_t ld, int B, int A, int k, int32
   VQA_REQUIRE(logits && idx && prob, "vqa_softmax_topk: null pointer (logits, idx and prob are required; lse is optional)");
   const dim3 grid((unsigned)(((int64_t)B + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
-#define VQA_TOPK_LAUNCH(NJ) hipLaunchKernelGGL(softmax_topk_kernel<NJ>, grid, dim3(256), 0, s, logits, ld, B, A, k, idx, prob, lse)
-  if (A <= 64) VQA_TOPK_LAUNCH(1);
-  else if (A <= 256) VQA_TOPK_LAUNCH(4);
-  else if (A <= 1024) VQA_TOPK_LAUNCH(16);
-  else if (A <= 3072) VQA_TOPK_LAUNCH(48);
-  else VQA_TOPK_LAUNCH(0);
-#undef VQA_TOPK_LAUNCH
+  with_topk_nj(A, [&](auto nj) {
+    hipLaunchKernelGGL(softmax_topk_kernel<decltype(nj)::value>, grid, dim3(256), 0, s, logits, ld, B, A, k, idx, prob, lse);
+  });
   return check_hip(hipGetLastError(), "softmax_topk launch");
+}
+
+int vqa_softmax_pick(const float* logits, int64_t ld, int rows, int A, const int32_t* answers, int rows_per_question, int32_t* top,
+                     float* top_prob, float* prob_at, vqa_stream_t stream) {
+  VQA_REQUIRE(rows >= 0 && A >= 1 && ld >= (int64_t)A, "vqa_softmax_pick: rows=%d, A=%d, ld=%lld out of range (rows >= 0, A >= 1, ld >= A)",
+              rows, A, (long long)ld);
+  VQA_REQUIRE(rows_per_question >= 1 && rows % rows_per_question == 0,
+              "vqa_softmax_pick: rows_per_question=%d must be >= 1 and divide rows=%d", rows_per_question, rows);
+  if (rows == 0) return VQA_OK;
+  VQA_REQUIRE(logits && answers && top && top_prob && prob_at, "vqa_softmax_pick: null pointer");
+  const dim3 grid((unsigned)(((int64_t)rows + 3) / 4));
+  hipStream_t s = (hipStream_t)stream;
+  with_topk_nj(A, [&](auto nj) {
+    hipLaunchKernelGGL(softmax_pick_kernel<decltype(nj)::value>, grid, dim3(256), 0, s, logits, ld, rows, A, answers,
+                       rows_per_question, top, top_prob, prob_at);
+  });
+  return check_hip(hipGetLastError(), "softmax_pick launch");
 }
 
 }  // extern "C"

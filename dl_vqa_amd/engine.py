@@ -773,6 +773,61 @@ class Engine:
                             answers, order, slot0=r0, out=out, workspace=ws)
         return out[0], out[1], order, answers, run.logits
 
+    # ------------------------------------------------------------------ probability curves and flip points
+    # explain_faithfulness's curves for EVERY answer column at once: the walk keeps each kept set's hidden row instead of
+    # collapsing it onto one row of lin2 (include/vqa_hip.h vqa_occl_curves_hidden), one product with lin2 turns
+    # the rows into logits, and one kernel reads each logits row once for the probability of the explained column and the best
+    # column with its probability (vqa_softmax_pick).  explain_faithfulness's parts as they are -- the base run, the ranking,
+    # cnull, base, U per chunk of images -- and per chunk the questions of its images in sub-chunks of whole questions, so that
+    # the curve workspace, the hidden rows and the logits of a sub-chunk stay under a cap.
+    PROB_WS_BYTES = 256 << 20       # cap of one sub-chunk's curve workspace, hidden rows and logits: more questions walk in sub-chunks
+
+    def prob_curve_questions(self, Pn: int, ws_bytes: Optional[int] = None) -> int:
+        """Questions per sub-chunk of explain_faithfulness_probs: per question the curve workspace, the hidden rows [2, Pn+1,
+        hid] and their logits [2, Pn+1, A] fit the cap; at least one."""
+        one = ops._lib.load().vqa_occl_curves_workspace_bytes(1, Pn, self.G, self.hid) + 2 * (Pn + 1) * (self.hid + self.A) * 4
+        return max(1, int((self.PROB_WS_BYTES if ws_bytes is None else ws_bytes) // one))
+
+    @_device_current("feats", _cache_device)
+    def explain_faithfulness_probs(self, P: Dict[str, Tensor], feats, ask, rows: Tensor, slot: Tensor, by_slot: Tensor, offsets,
+                                   maps: Tensor, u_bytes: Optional[int] = None, ws_bytes: Optional[int] = None):
+        """explain_faithfulness's arguments plus by_slot (device int32 [B]) and offsets (a HOST list [n_u+1]), the questions
+        grouped by their place among the distinct asked images (model.compact_image_index), and ws_bytes, the cap of a
+        sub-chunk.  Returns (prob [B,2,Pn+1], top int32 [B,2,Pn+1], top_prob [B,2,Pn+1] -- deletion at [:, 0], insertion at
+        [:, 1] --, order int32 [B,Pn], answers int32 [B], logits [B,A])."""
+        assert not self.bf16, "explain_faithfulness_probs: fp32 / fp32x3 only"
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        B, Pn, hid, A, dev = run.img.numel(), feats.vn.shape[1], self.hid, self.A, feats.vn.device
+        answers = self._picked(run.logits, ask.answers)
+        order = ops.rank_desc(maps)
+        cnull, base = self._occlusion_operands(P, run)
+        # the questions in the order of their images: a chunk of U then owns a contiguous range of them, cut into sub-chunks
+        sel = by_slot.long()
+        base, probs, score, cnull, ranked, slot_s, cols = (t.index_select(0, sel) for t in
+                                                           (base, run.probs, run.score, cnull.view(B, -1), order, slot, answers))
+        K = 2 * (Pn + 1)
+        per = min(B, self.prob_curve_questions(Pn, ws_bytes))
+        assert per * K < (1 << 31)
+        ws = ops.occl_curves_workspace(per, Pn, self.G, hid, dev)
+        H = torch.empty(per, 2, Pn + 1, hid, dtype=torch.float32, device=dev)
+        Y = torch.empty(per * K, A, dtype=torch.float32, device=dev)
+        top = torch.empty(B, 2, Pn + 1, dtype=torch.int32, device=dev)
+        top_prob, prob = (torch.empty(B, 2, Pn + 1, dtype=torch.float32, device=dev) for _ in range(2))
+        for r0, U in self._u_chunks(P, feats, rows, u_bytes):
+            q0, q1 = offsets[r0], offsets[r0 + U.shape[0]]
+            for b0 in range(q0, q1, per):
+                b1 = min(b0 + per, q1)
+                n = b1 - b0
+                ops.occl_curves_hidden(base[b0:b1], U, slot_s[b0:b1], probs[b0:b1], score[b0:b1], cnull[b0:b1], ranked[b0:b1],
+                                       slot0=r0, out=H[:n], workspace=ws)
+                # every column's logit of every step: plain fp32 in every compute mode, as base and Z are
+                ops.gemm(H[:n].view(n * K, hid), P["classifier.lin2.weight"], Y[:n * K], n * K, A, hid,
+                         bias1=P["classifier.lin2.bias"])
+                ops.softmax_pick(Y[:n * K], cols[b0:b1], K, out=(top[b0:b1], top_prob[b0:b1], prob[b0:b1]))
+        # back to the caller's order
+        prob, top, top_prob = (torch.empty_like(t).index_copy_(0, sel, t) for t in (prob, top, top_prob))
+        return prob, top, top_prob, order, answers, run.logits
+
     # ------------------------------------------------------------------ sampled Shapley maps from cached features
     # The Shapley value of every grid position for the set function explain_faithfulness walks -- the explained logit with an
     # arbitrary set of positions present -- from M orders that every question shares, and their reverses (include/vqa_hip.h

@@ -239,6 +239,49 @@ class Faithfulness(NamedTuple):
         return self._auc(self.insertion)
 
 
+class ProbabilityCurves(NamedTuple):
+    """What VqaNet.explain_faithfulness_probs / explain_faithfulness_probs_pairs return.  With the k best-ranked positions of the
+    map absent (deletion) or alone present (insertion), k = 0 .. P: deletion, insertion fp32 [B, P+1] -- the softmax
+    probability of the explained column a_b --, deletion_top, insertion_top int32 [B, P+1] -- the arg-max column at that step,
+    in topk_answers' order (ties by the smaller column) --, deletion_top_prob, insertion_top_prob fp32 [B, P+1] -- its
+    probability --, and Faithfulness' order int64 [B, P], answers int64 [B] and logits fp32 [B, A].  The AUCs are the published
+    deletion / insertion metric (on probabilities: adding a constant to every logit does not move them); the flip points say
+    how many of the map's best positions must go before the answer changes, and how few suffice to get it back."""
+    deletion: torch.Tensor
+    insertion: torch.Tensor
+    deletion_top: torch.Tensor
+    insertion_top: torch.Tensor
+    deletion_top_prob: torch.Tensor
+    insertion_top_prob: torch.Tensor
+    order: torch.Tensor
+    answers: torch.Tensor
+    logits: torch.Tensor
+
+    def deletion_auc(self):
+        """The trapezoid mean of each deletion curve, as Faithfulness.deletion_auc(): float64 [B] on the curve's device."""
+        return Faithfulness._auc(self.deletion)
+
+    def insertion_auc(self):
+        """The trapezoid mean of each insertion curve, as deletion_auc()."""
+        return Faithfulness._auc(self.insertion)
+
+    @staticmethod
+    def _first(hit):
+        """The smallest k with hit[b, k], P + 1 where there is none: int64 [B] on the device of hit [B, P+1]."""
+        steps = torch.arange(hit.shape[1], device=hit.device).expand_as(hit)
+        return torch.where(hit, steps, torch.full_like(steps, hit.shape[1])).min(dim=1).values.reshape(hit.shape[0])
+
+    def deletion_flip(self):
+        """The smallest k at which the arg-max is no longer the explained column, deletion_top[b, k] != answers[b]: how many
+        of the map's best positions must go before the answer changes.  int64 [B] on the device; P + 1 when it never does."""
+        return self._first(self.deletion_top != self.answers[:, None])
+
+    def insertion_flip(self):
+        """The smallest k at which the arg-max is the explained column, insertion_top[b, k] == answers[b]: how few of the
+        map's best positions suffice to get the answer back.  int64 [B] on the device; P + 1 when none does."""
+        return self._first(self.insertion_top == self.answers[:, None])
+
+
 class IntegratedGradients(NamedTuple):
     """What VqaNet.explain_integrated / explain_integrated_pairs return: maps fp32 [B, gh, gw] -- the integrated-gradients map
     of each question on the feature grid, zero baseline, midpoint rule (signed, no upsampling, no normalisation) --, answers
@@ -1313,8 +1356,9 @@ class VqaNet(nn.Module):
         P = feats.grid[0] * feats.grid[1]
         shape = dict(words=(0, T), maps=(0, *feats.grid), stderr=(0, *feats.grid), answers=(0,), logits=(0, self._engine.A),
                      deletion=(0, P + 1), insertion=(0, P + 1), order=(0, P), baseline_logits=(0,))
-        return kind(*(torch.empty(shape[f], dtype=torch.int64 if f in ("answers", "order") else torch.float32,
-                                  device=feats.vn.device) for f in kind._fields))
+        shape.update({f: (0, P + 1) for f in ("deletion_top", "insertion_top", "deletion_top_prob", "insertion_top_prob")})
+        dtype = lambda f: torch.int64 if f in ("answers", "order") else torch.int32 if f.endswith("_top") else torch.float32
+        return kind(*(torch.empty(shape[f], dtype=dtype(f), device=feats.vn.device) for f in kind._fields))
 
     @staticmethod
     def _maps_result(kind, feats, out):
@@ -1531,8 +1575,8 @@ class VqaNet(nn.Module):
         ordered.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad and the dropout seed stream are left
         alone.
 
-        Not offered: bf16 mode, train mode, data parallelism; probability curves (every column of lin2 per step); strided or
-        coarser curves; word-level and pixel-level curves; upsampling or normalising the maps.
+        Not offered: bf16 mode, train mode, data parallelism; strided or coarser curves; word-level and pixel-level curves;
+        upsampling or normalising the maps.  Probability curves and the arg-max at every step: explain_faithfulness_probs().
 
         _u_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
         what = "explain_faithfulness"
@@ -1562,6 +1606,73 @@ class VqaNet(nn.Module):
                               own=lambda: _check_maps(f"VqaNet.{what}", maps, torch.as_tensor(image_index).numel(),
                                                       getattr(feats, "grid", None)))
         return self._explain_faithfulness(feats, ask, maps, _u_bytes)
+
+    # ------------------------------------------------------------------ probability curves and flip points
+    @torch.no_grad()
+    def explain_faithfulness_probs(self, feats: ImageFeatures, q, q_len, image_index, maps, answers=None, *, _u_bytes=None,
+                                   _ws_bytes=None) -> ProbabilityCurves:
+        """explain_faithfulness() on probabilities, with the arg-max at every step: ProbabilityCurves(deletion, insertion fp32
+        [B, P+1], deletion_top, insertion_top int32 [B, P+1], deletion_top_prob, insertion_top_prob fp32 [B, P+1], order int64
+        [B, P], answers int64 [B], logits fp32 [B, A]), P = gh * gw.  With order and "absent" as explain_faithfulness() has
+        them, and logits_K the logits answer() computes on a cache that holds only the rows of the kept set K,
+
+            deletion[b, k]      = softmax(logits_K)[a_b]               K = order[b, k:]
+            insertion[b, k]     = the same                             K = order[b, :k]                  k = 0 .. P
+            deletion_top[b, k]  = the arg-max column of logits_K, ties by the smaller column (topk_answers' order)
+            deletion_top_prob   = its probability; insertion_top and insertion_top_prob likewise
+
+        deletion[:, 0] and insertion[:, P] are softmax(logits)[b, a_b]; deletion[:, P] and insertion[:, 0] belong to the empty
+        image (bit-equal).  deletion_auc() and insertion_auc() are the deletion / insertion metric as it is published, on the
+        class probability: unlike explain_faithfulness()'s logit curves they do not move when a constant is added to every
+        logit.  deletion_flip() is the number of the map's best positions that must go before the answer changes,
+        insertion_flip() how few of them get it back (P + 1: never).
+
+        How it runs.  The brute-force route is answer() on 2 (P + 1) edited banks per question, then torch.softmax.  Here
+        explain_faithfulness()'s parts run as they are (the base run, the ranking, the U product per chunk of images), the walk
+        along the ranking keeps each kept set's hidden row instead of one column's dot product (include/vqa_hip.h
+        vqa_occl_curves_hidden), one product with lin2 -- plain fp32 in every compute mode -- gives every column of every step,
+        and one kernel reads each logits row once (vqa_softmax_pick).  The questions of a chunk of images go through in
+        sub-chunks of whole questions whose curve workspace, hidden rows and logits stay within 256 MiB.
+
+        maps, answers, logits, order, the `answers` argument, the argument rules and the refusals are explain_faithfulness()'s,
+        judged before any device work; logits are answer()'s and order is explain_faithfulness()'s, bit for bit.  A CUDA
+        `answers` entry outside [0, A) gives two probability rows of +0.0; the tops do not depend on the column.  A float16
+        cache gives, bit for bit, what feats.to(torch.float32) gives; B == 0 returns empty tensors.  Rows come back in the
+        caller's order; how the batch is ordered and chunked may move the lin2 product's tiles, hence the last bits.
+
+        Not offered: probability-valued Shapley or occlusion maps, strided curves, word- and pixel-level curves, bf16 mode,
+        train mode, data parallelism.
+
+        _u_bytes, _ws_bytes (tests and tools): the two workspace caps in bytes, to force several chunks at small sizes."""
+        what = "explain_faithfulness_probs"
+        ask = self._ask_questions(what, feats, q, q_len, image_index, answers,
+                                  own=lambda: _check_maps(f"VqaNet.{what}", maps, len(q), getattr(feats, "grid", None)))
+        return self._explain_faithfulness_probs(feats, ask, maps, _u_bytes, _ws_bytes)
+
+    def _explain_faithfulness_probs(self, feats, ask, maps, u_bytes, ws_bytes) -> ProbabilityCurves:
+        if ask.B == 0:
+            return self._no_result(ProbabilityCurves, feats)
+        *index, offsets = compact_image_index(ask.index[2], feats.N)
+        rows, slot, by_slot = self._ask_upload(feats, ask, index)
+        maps = torch.as_tensor(maps).detach().to(device=feats.vn.device, dtype=torch.float32).reshape(ask.B, -1).contiguous()
+        prob, top, top_prob, order, cols, logits = self._ask_run(self._engine.explain_faithfulness_probs, feats, ask, rows, slot,
+                                                                 by_slot, offsets.tolist(), maps, u_bytes, ws_bytes)
+        return ProbabilityCurves(prob[:, 0], prob[:, 1], top[:, 0], top[:, 1], top_prob[:, 0], top_prob[:, 1], order.long(),
+                                 cols.long(), logits)
+
+    @torch.no_grad()
+    def explain_faithfulness_probs_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, maps,
+                                         answers=None, *, _u_bytes=None, _ws_bytes=None) -> ProbabilityCurves:
+        """explain_faithfulness_probs() for B (image, question) pairs from the two caches, as answer_pairs() is to answer():
+        pair b looks at image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.
+        The curves, tops, order, answers, maps and the `answers` argument are explain_faithfulness_probs()'s; logits are
+        answer_pairs()'s for the same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s,
+        with the maps and `answers` checks judged first."""
+        what = "explain_faithfulness_probs_pairs"
+        ask = self._ask_pairs(what, feats, qfeats, image_index, question_index, answers,
+                              own=lambda: _check_maps(f"VqaNet.{what}", maps, torch.as_tensor(image_index).numel(),
+                                                      getattr(feats, "grid", None)))
+        return self._explain_faithfulness_probs(feats, ask, maps, u_bytes=_u_bytes, ws_bytes=_ws_bytes)
 
     # ------------------------------------------------------------------ sampled Shapley maps from cached features
     @torch.no_grad()

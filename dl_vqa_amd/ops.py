@@ -799,15 +799,21 @@ def embed_attr(q, emb, x, dx0, dx1, q_len, out=None):
     return out
 
 
-def _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers):
-    """What occl_logit and occl_curves ask of the operands they share: (B, G, P, R, hid, A, w2_ld)."""
-    (B, G, P), R, hid, A = probs.shape, U.shape[0], base.shape[1], W2.shape[0]
-    for t in (base, U, probs, score, cnull, b2):
+def _occl_operands(base, U, slot, probs, score, cnull, W2=None, b2=None, answers=None):
+    """What occl_logit and occl_curves ask of the operands they share: (B, G, P, R, hid, A, w2_ld).  Without the column
+    operands W2, b2 and answers (occl_curves_hidden, which explains no column): (B, G, P, R, hid)."""
+    (B, G, P), R, hid = probs.shape, U.shape[0], base.shape[1]
+    for t in (base, U, probs, score, cnull):
         _chk(t)
         assert t.is_contiguous()
-    _chk(slot, torch.int32), _chk(answers, torch.int32), _chk(W2)
+    _chk(slot, torch.int32)
     assert score.shape == probs.shape and base.shape == (B, hid) and U.shape == (R, P, G, hid)
-    assert cnull.numel() == B * G and slot.numel() == B and answers.numel() == B
+    assert cnull.numel() == B * G and slot.numel() == B
+    if W2 is None:
+        return B, G, P, R, hid
+    A = W2.shape[0]
+    _chk(b2), _chk(answers, torch.int32), _chk(W2)
+    assert b2.is_contiguous() and answers.numel() == B
     assert W2.shape[1] == hid and b2.numel() == A and (hid == 1 or W2.stride(1) == 1)
     return B, G, P, R, hid, A, _ld(W2)
 
@@ -879,6 +885,26 @@ def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot
          ptr(answers), ptr(order), ptr(workspace), workspace.numel() * 4, ptr(deletion), ptr(insertion), R, B, P, hid, G, A,
          stream())
     return deletion, insertion
+
+
+def occl_curves_hidden(base, U, slot, probs, score, cnull, order, slot0: int = 0, out=None, workspace=None):
+    """The hidden rows of both curves (include/vqa_hip.h vqa_occl_curves_hidden): H fp32 [B, 2, P+1, hid], H[b, 0, k] = relu(base[b]
+    + sum_g alpha * acc) of the kept set order[b, k:] (deletion), H[b, 1, k] of order[b, :k] (insertion), k = 0 .. P -- what
+    occl_curves multiplies by one row of W2, for every column at once.  The operands are occl_curves' without W2, b2 and
+    answers.  out: H, written in place for the questions whose slot is in [slot0, slot0 + R); workspace: as occl_curves'."""
+    B, G, P, R, hid = _occl_operands(base, U, slot, probs, score, cnull)
+    _chk(order, torch.int32)
+    assert order.shape == (B, P) and order.is_contiguous()
+    if out is None:
+        out = torch.empty(B, 2, P + 1, hid, dtype=torch.float32, device=probs.device)
+    assert out.shape == (B, 2, P + 1, hid) and out.is_contiguous() and out.dtype == torch.float32
+    if workspace is None:
+        workspace = occl_curves_workspace(B, P, G, hid, probs.device)
+    _chk(workspace)
+    assert workspace.is_contiguous()
+    call("vqa_occl_curves_hidden", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(order),
+         ptr(workspace), workspace.numel() * 4, ptr(out), R, B, P, hid, G, stream())
+    return out
 
 
 def occl_curves_orders_workspace(B: int, M: int, P: int, G: int, hid: int, device):
@@ -1084,6 +1110,27 @@ def softmax_topk(logits: torch.Tensor, k: int, want_lse: bool = False):
     lse = torch.empty(B, dtype=torch.float32, device=logits.device) if want_lse else None
     call("vqa_softmax_topk", ptr(logits), _ld(logits), B, A, k, ptr(idx), ptr(prob), ptr(lse), stream())
     return (idx, prob, lse) if want_lse else (idx, prob)
+
+
+def softmax_pick(logits: torch.Tensor, answers: torch.Tensor, rows_per_question: int, out=None):
+    """(top int32 [R], top_prob fp32 [R], prob_at fp32 [R]) of the logits rows [R, A] (include/vqa_hip.h vqa_softmax_pick): top
+    and top_prob are softmax_topk(logits, 1)'s, bit for bit; prob_at[r] = softmax(logits[r])[answers[r // rows_per_question]],
+    +0.0 for a column outside [0, A).  answers: device int32 [R // rows_per_question].  logits: as softmax_topk's, a row view
+    into a padded buffer included.  out: (top, top_prob, prob_at), contiguous with R elements each, written in place."""
+    _chk(logits), _chk(answers, torch.int32)
+    assert logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1), (tuple(logits.shape), logits.stride())
+    R, A = logits.shape
+    assert rows_per_question >= 1 and R % rows_per_question == 0 and answers.numel() == R // rows_per_question
+    assert answers.is_contiguous()
+    if out is None:
+        out = (torch.empty(R, dtype=torch.int32, device=logits.device), torch.empty(R, dtype=torch.float32, device=logits.device),
+               torch.empty(R, dtype=torch.float32, device=logits.device))
+    top, top_prob, prob_at = out
+    _chk(top, torch.int32), _chk(top_prob), _chk(prob_at)
+    assert all(t.numel() == R and t.is_contiguous() for t in out)
+    call("vqa_softmax_pick", ptr(logits), _ld(logits), R, A, ptr(answers), rows_per_question, ptr(top), ptr(top_prob), ptr(prob_at),
+         stream())
+    return top, top_prob, prob_at
 
 
 def colsum(x: torch.Tensor, rows: int, cols: int, out: torch.Tensor, *, ld=None, mask=None, accumulate=False):

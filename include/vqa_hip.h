@@ -51,7 +51,8 @@ extern "C" {
  * declared behind those), and then those of integrated gradients (vqa_att_path_score_grouped, vqa_att_path_attr_grouped and
  * their _pairs, _f16 and _pairs_f16 forms, with vqa_att_path_scale_rows; declared behind those), and then the three of sampled
  * Shapley maps (vqa_occl_curves_orders_workspace_bytes, vqa_occl_curves_orders, vqa_shapley_accumulate; declared beside the
- * curve entry points). */
+ * curve entry points), and then the two of probability curves (vqa_occl_curves_hidden, declared behind those, and
+ * vqa_softmax_pick, declared behind vqa_softmax_topk). */
 #define VQA_ABI_VERSION 9
 
 #define VQA_OK 0
@@ -667,6 +668,33 @@ int vqa_shapley_accumulate(const float* deletion, const float* insertion, const 
                            const int32_t* answers, float* mean, float* m2, float* maps, float* err, float* empty, int R, int B,
                            int P, int Mg, int m0, int total, int A, vqa_stream_t stream);
 
+/* ---- probability curves: the curve walk that keeps its hidden rows (inference, VqaNet.explain_faithfulness_probs;
+ * csrc/faithfulness.hip) ----
+ * vqa_occl_curves collapses every kept set's hidden row onto ONE row of W2, so it can follow one logit.  A probability, or the
+ * arg-max, of a kept set needs every column: this entry point stops one step earlier and writes the hidden rows themselves,
+ *   H[b][0][k][:] = relu(base[b] + sum_g alpha[b][g] * acc[b][g])   of the kept set order[b][k .. P)   (deletion)
+ *   H[b][1][k][:] = the same                                         of the kept set order[b][0 .. k)   (insertion)   k = 0 .. P
+ * with m, acc and alpha as vqa_occl_curves defines them, so that H . W2^T + b2 (one GEMM over the 2 (P + 1) rows of every
+ * question) holds every column's logit of every step.  The hidden rows do not depend on the explained column.
+ *   vqa_occl_curves_hidden: the operands of vqa_occl_curves without W2, w2_ld, b2, answers and A, a workspace of
+ *     vqa_occl_curves_workspace_bytes(B, P, G, hid) bytes (the same layout), and hidden fp32 [B][2][P + 1][hid] in place of
+ *     deletion / insertion.  The same three launches: (1) and (2) are vqa_occl_curves' kernels as they are; (3) is its walk
+ *     under a compile-time flag -- the same chunks of L steps, alphas, forward / backward accumulation and fmaf chain, but
+ *     the head loads no W2, there is no dot product and no wave butterfly: after the chain lane l stores max(pre, 0) as one
+ *     float4 per state per quad (64 lanes write 1 KiB contiguous).  Every element of a listed question is written once:
+ *     insertion state 0 by chunk 0 alone, deletion state P by the last chunk alone.  One summation order per (b, k), that of
+ *     vqa_occl_curves: W2[a] . H[b][0][k] + b2[a] differs from its deletion[b][k] by the rounding of the dot product alone.
+ *     H[b][0][P] and H[b][1][0] (the empty image) are bit-equal.  Permuting the questions permutes the rows bit for bit; it
+ *     does not depend on the grid, the batch or the chunking of the images.  No atomics, no scratch.
+ *     An order entry outside [0, P) adds nothing and is never an address; a question whose row slot[b] - slot0 is outside
+ *     [0, R) is LEFT ALONE.
+ *     Limits: hid % 4 == 0, hid * 4 + 80 <= 65536 bytes of LDS, G in 1..4, P <= 2^20, base, U, the workspace and hidden 16-byte
+ *     aligned, the workspace large enough, no null pointer; anything else is VQA_ERR_INVALID before any HIP call.  B == 0
+ *     returns without a launch and needs no workspace. */
+int vqa_occl_curves_hidden(const float* base, const float* U, const int32_t* slot, int slot0, const float* probs,
+                           const float* score, const float* cnull, const int32_t* order, float* workspace, int64_t workspace_bytes,
+                           float* hidden, int R, int B, int P, int hid, int G, vqa_stream_t stream);
+
 /* ---- integrated gradients from cached image features (inference, VqaNet.explain_integrated; csrc/att_score.hip) ----
  * The gradient x input map above, averaged along the straight path from the zero cache to the real one (eval mode, the
  * question held fixed, zero baseline).  For question b about image n, column a_b and S step positions alpha_s in (0, 1]:
@@ -757,6 +785,21 @@ int vqa_softce_fwd_bwd(const float* logits, int64_t ld, const int64_t* a_idx, co
  * Nothing outside idx[B][k], prob[B][k] and lse[B] is written. */
 int vqa_softmax_topk(const float* logits, int64_t ld, int B, int A, int k, int32_t* idx /* [B][k] */, float* prob /* [B][k] */,
                      float* lse /* [B], optional */, vqa_stream_t stream);
+
+/* ---- the probability of a GIVEN column beside the best one (csrc/topk.hip; VqaNet.explain_faithfulness_probs)
+ * One launch over `rows` logits rows, one wave per row, the row read once into the wave's registers (A <= 3072; beyond that
+ * through the cache, as vqa_softmax_topk).  Row r belongs to question b = r / rows_per_question, whose column is answers[b]:
+ *   top[r], top_prob[r]  = idx[r][0], prob[r][0] of vqa_softmax_topk(k = 1) on the same rows, bit for bit: the same device code
+ *                          (csrc/topk.hip softmax_topk_row), hence the same total order -- larger value first, equal values by the
+ *                          smaller column, -0.0 equal to +0.0, NaN above +inf -- and the same fixed-order sum
+ *   prob_at[r]           = exp(x[r][answers[b]] - max_r) / sum_r   top_prob's own expression with the row's own max and sum, so a
+ *                          row whose given column is its arg-max holds the same bits in both; +0.0 for a column outside [0, A)
+ *                          (never an address); NaN for a row that holds a NaN, as vqa_softmax_topk
+ * rows >= 0, A >= 1, ld >= A (elements), rows_per_question >= 1 and a divisor of rows (answers holds rows / rows_per_question
+ * int32 entries); anything else, or a null pointer with rows > 0, is VQA_ERR_INVALID before any HIP call.  rows == 0 returns
+ * without a launch.  No alignment demand, no LDS, no atomics; nothing outside top[rows], top_prob[rows], prob_at[rows] is written. */
+int vqa_softmax_pick(const float* logits, int64_t ld, int rows, int A, const int32_t* answers, int rows_per_question,
+                     int32_t* top /* [rows] */, float* top_prob /* [rows] */, float* prob_at /* [rows] */, vqa_stream_t stream);
 
 /* ---- reductions / pointwise helpers -------------------------------------------------------- */
 /* out[n] (+)= sum_m x[m*ld + n]; if mask != NULL rows of x where mask[m*cols+n] == 4 are skipped
