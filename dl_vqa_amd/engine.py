@@ -592,6 +592,19 @@ class Engine:
         """The answer column each question is explained at: `answers`, or (None) topk_answers' arg-max, on the device."""
         return ops.softmax_topk(logits, 1)[0].view(-1) if answers is None else answers
 
+    def _explained(self, what: str, P, feats, ask):
+        """What every explain schedule but explain's own tail opens with: the fp32 check in the name of `what`, the finished base
+        run of the ask, and the answer column of each question.  Returns (run, answers int32 [B])."""
+        assert not self.bf16, f"{what}: fp32 / fp32x3 only"
+        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        return run, self._picked(run.logits, ask.answers)
+
+    @staticmethod
+    def _fits(cap: int, given: Optional[int], one: int) -> int:
+        """How many items of `one` bytes a workspace holds, at least one: under the schedule's *_BYTES constant `cap`, or under
+        `given` where a test or a tool passed bytes of its own."""
+        return max(1, int((cap if given is None else given) // one))
+
     # ------------------------------------------------------------------ gradient x input maps from cached features
     # explain / explain_pairs are answer / answer_pairs with the tail kept: from (probs, h1, logits) the gradient of ONE logit
     # per question is carried back to the classifier input (two small products, no parameter gradient), and two kernels turn
@@ -635,20 +648,18 @@ class Engine:
 
     def integrated_rows(self, Pn: int, steps: int, ig_bytes: Optional[int] = None) -> int:
         """Questions per chunk of explain_integrated: score, probs and dscore [rows, S, G, Pn] and r1 [rows, S, Pn] fit the cap."""
-        return max(1, int((self.IG_BYTES if ig_bytes is None else ig_bytes) // (steps * Pn * (3 * self.G + 1) * 4)))
+        return self._fits(self.IG_BYTES, ig_bytes, steps * Pn * (3 * self.G + 1) * 4)
 
     @_device_current("feats", _cache_device)
     def explain_integrated(self, P: Dict[str, Tensor], feats, ask, alphas: Tensor, chunks):
         """explain's arguments plus alphas (device fp32 [S], the step positions) and chunks: (b0, b1, order, offsets) per range
         of questions, order / offsets (device int32) grouping the questions b0 .. b1-1, numbered from 0, by image.  Returns
         (maps [B,Pn], answers int32 [B], logits [B,A], baseline_logits [B])."""
-        assert not self.bf16, "explain_integrated: fp32 / fp32x3 only"
-        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        run, answers = self._explained("explain_integrated", P, feats, ask)
         logits, img = run.logits, run.img
         B, S, hid, G, GC, Dc, Q, A, dev = img.numel(), alphas.numel(), self.hid, self.G, self.GC, self.Dc, self.Q, self.A, feats.vn.device
         N, Pn, _ = feats.vn.shape
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        answers = self._picked(logits, ask.answers)
         wx, bx = P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"]
         w1, w2, lin1_bias = P["classifier.lin1.weight"], P["classifier.lin2.weight"], P["classifier.lin1.bias"]
         # the step-rows r = b*S + s of every question: its image, its column, and where its question half lies
@@ -697,15 +708,13 @@ class Engine:
         logits [B,A]).  Behind the base run: the per-question operands of the closed form (cnull, base, Z), then U = W1_g . vn
         for the distinct asked images in chunks that fit the workspace cap, each followed by the kernel for the questions of
         its images."""
-        assert not self.bf16, "explain_occlusion: fp32 / fp32x3 only"
-        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
-        logits, probs, score, combined = run.logits, run.probs, run.score, run.combined
+        run, answers = self._explained("explain_occlusion", P, feats, ask)
+        cnull, base, column = self._occlusion_operands(P, run, answers)
+        combined = run.combined
         B, hid, G, C, Dc, dev = run.img.numel(), self.hid, self.G, self.C, self.Dc, feats.vn.device
         Pn = feats.vn.shape[1]
         gh, gw = feats.grid
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        answers = self._picked(logits, ask.answers)
-        cnull, base = self._occlusion_operands(P, run)
         # Z_g = W1_g . out_g: the image half of lin1 per glimpse, plain fp32 in every compute mode
         w1 = P["classifier.lin1.weight"]
         Z = new(B, G, hid)
@@ -713,13 +722,12 @@ class Engine:
             ops.gemm(combined[:, g * C:], w1[:, g * C:], Z[:, g], B, hid, C, lda=Dc, ldb=Dc, ldc=G * hid)
         maps = new(B, Pn)
         for r0, U in self._u_chunks(P, feats, rows, u_bytes):
-            ops.occl_logit(base, Z, U, slot, probs, score, cnull, P["classifier.lin2.weight"], P["classifier.lin2.bias"],
-                           answers, logits, gh, gw, window, slot0=r0, out=maps)
-        return maps, answers, logits
+            ops.occl_logit(base, Z, U, slot, run.probs, run.score, cnull, *column, run.logits, gh, gw, window, slot0=r0, out=maps)
+        return maps, answers, run.logits
 
-    def _occlusion_operands(self, P, run):
+    def _occlusion_operands(self, P, run, answers):
         """The per-question operands of the closed form that every set of absent positions shares, from a finished base run:
-        (cnull [B,G], base [B,hid])."""
+        (cnull [B,G], base [B,hid], column), column = (W2, b2, answers) as the kernels that explain one column take them."""
         B, G, GC, Dc, dev = run.img.numel(), self.G, self.GC, self.Dc, run.score.device
         # cnull: the score kernel's own bits for a position whose v' is 0 -- one all-zero position, every question in one group
         wx, bx = P["attention.x_conv.weight"].view(G, -1), P["attention.x_conv.bias"]
@@ -731,7 +739,7 @@ class Engine:
         w1 = P["classifier.lin1.weight"]
         base = ops.gemm(run.combined[:, GC:], w1[:, GC:], torch.empty(B, self.hid, dtype=torch.float32, device=dev), B, self.hid,
                         self.Q, lda=Dc, ldb=Dc, bias1=P["classifier.lin1.bias"])
-        return cnull, base
+        return cnull, base, (P["classifier.lin2.weight"], P["classifier.lin2.bias"], answers)
 
     def _u_chunks(self, P, feats, rows, u_bytes=None):
         """U = W1_g . vn [n, Pn, G, hid] for the distinct asked images `rows`, n images at a time under the workspace cap, by the
@@ -741,7 +749,7 @@ class Engine:
         Pn = feats.vn.shape[1]
         w1 = P["classifier.lin1.weight"]
         n_u = rows.numel()
-        per = max(1, int((self.U_BYTES if u_bytes is None else u_bytes) // (Pn * G * hid * 4)))
+        per = self._fits(self.U_BYTES, u_bytes, Pn * G * hid * 4)
         U = torch.empty(min(per, n_u), Pn, G, hid, dtype=torch.float32, device=feats.vn.device)
         for r0 in range(0, n_u, per):
             n = min(per, n_u - r0)
@@ -760,17 +768,14 @@ class Engine:
                              u_bytes: Optional[int] = None):
         """explain_occlusion's arguments with maps fp32 [B,Pn] (on the device) in place of window.  Returns (deletion [B,Pn+1],
         insertion [B,Pn+1], order int32 [B,Pn], answers int32 [B], logits [B,A])."""
-        assert not self.bf16, "explain_faithfulness: fp32 / fp32x3 only"
-        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        run, answers = self._explained("explain_faithfulness", P, feats, ask)
         B, Pn, dev = run.img.numel(), feats.vn.shape[1], feats.vn.device
-        answers = self._picked(run.logits, ask.answers)
         order = ops.rank_desc(maps)
-        cnull, base = self._occlusion_operands(P, run)
+        cnull, base, column = self._occlusion_operands(P, run, answers)
         out = tuple(torch.empty(B, Pn + 1, dtype=torch.float32, device=dev) for _ in range(2))
         ws = ops.occl_curves_workspace(B, Pn, self.G, self.hid, dev)
         for r0, U in self._u_chunks(P, feats, rows, u_bytes):
-            ops.occl_curves(base, U, slot, run.probs, run.score, cnull, P["classifier.lin2.weight"], P["classifier.lin2.bias"],
-                            answers, order, slot0=r0, out=out, workspace=ws)
+            ops.occl_curves(base, U, slot, run.probs, run.score, cnull, *column, order, slot0=r0, out=out, workspace=ws)
         return out[0], out[1], order, answers, run.logits
 
     # ------------------------------------------------------------------ probability curves and flip points
@@ -785,8 +790,8 @@ class Engine:
     def prob_curve_questions(self, Pn: int, ws_bytes: Optional[int] = None) -> int:
         """Questions per sub-chunk of explain_faithfulness_probs: per question the curve workspace, the hidden rows [2, Pn+1,
         hid] and their logits [2, Pn+1, A] fit the cap; at least one."""
-        one = ops._lib.load().vqa_occl_curves_workspace_bytes(1, Pn, self.G, self.hid) + 2 * (Pn + 1) * (self.hid + self.A) * 4
-        return max(1, int((self.PROB_WS_BYTES if ws_bytes is None else ws_bytes) // one))
+        one = ops.occl_curves_workspace_bytes(1, Pn, self.G, self.hid) + 2 * (Pn + 1) * (self.hid + self.A) * 4
+        return self._fits(self.PROB_WS_BYTES, ws_bytes, one)
 
     @_device_current("feats", _cache_device)
     def explain_faithfulness_probs(self, P: Dict[str, Tensor], feats, ask, rows: Tensor, slot: Tensor, by_slot: Tensor, offsets,
@@ -795,12 +800,10 @@ class Engine:
         grouped by their place among the distinct asked images (model.compact_image_index), and ws_bytes, the cap of a
         sub-chunk.  Returns (prob [B,2,Pn+1], top int32 [B,2,Pn+1], top_prob [B,2,Pn+1] -- deletion at [:, 0], insertion at
         [:, 1] --, order int32 [B,Pn], answers int32 [B], logits [B,A])."""
-        assert not self.bf16, "explain_faithfulness_probs: fp32 / fp32x3 only"
-        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        run, answers = self._explained("explain_faithfulness_probs", P, feats, ask)
         B, Pn, hid, A, dev = run.img.numel(), feats.vn.shape[1], self.hid, self.A, feats.vn.device
-        answers = self._picked(run.logits, ask.answers)
         order = ops.rank_desc(maps)
-        cnull, base = self._occlusion_operands(P, run)
+        cnull, base, (w2, b2, _) = self._occlusion_operands(P, run, answers)
         # the questions in the order of their images: a chunk of U then owns a contiguous range of them, cut into sub-chunks
         sel = by_slot.long()
         base, probs, score, cnull, ranked, slot_s, cols = (t.index_select(0, sel) for t in
@@ -821,8 +824,7 @@ class Engine:
                 ops.occl_curves_hidden(base[b0:b1], U, slot_s[b0:b1], probs[b0:b1], score[b0:b1], cnull[b0:b1], ranked[b0:b1],
                                        slot0=r0, out=H[:n], workspace=ws)
                 # every column's logit of every step: plain fp32 in every compute mode, as base and Z are
-                ops.gemm(H[:n].view(n * K, hid), P["classifier.lin2.weight"], Y[:n * K], n * K, A, hid,
-                         bias1=P["classifier.lin2.bias"])
+                ops.gemm(H[:n].view(n * K, hid), w2, Y[:n * K], n * K, A, hid, bias1=b2)
                 ops.softmax_pick(Y[:n * K], cols[b0:b1], K, out=(top[b0:b1], top_prob[b0:b1], prob[b0:b1]))
         # back to the caller's order
         prob, top, top_prob = (torch.empty_like(t).index_copy_(0, sel, t) for t in (prob, top, top_prob))
@@ -842,15 +844,13 @@ class Engine:
         """explain_occlusion's arguments with orders / rank (device int32 [M,Pn]: the shared table of permutations and the
         inverse of each row) in place of window, and ws_bytes, the cap of the curve workspace.  Returns (maps [B,Pn], stderr
         [B,Pn], answers int32 [B], logits [B,A], baseline_logits [B])."""
-        assert not self.bf16, "explain_shapley: fp32 / fp32x3 only"
-        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
+        run, answers = self._explained("explain_shapley", P, feats, ask)
+        cnull, base, column = self._occlusion_operands(P, run, answers)
         B, Pn, dev = run.img.numel(), feats.vn.shape[1], feats.vn.device
         M = orders.shape[0]
-        answers = self._picked(run.logits, ask.answers)
-        cnull, base = self._occlusion_operands(P, run)
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        one = max(1, ops._lib.load().vqa_occl_curves_orders_workspace_bytes(B, 1, Pn, self.G, self.hid))
-        per = min(M, max(1, int((self.SHAPLEY_WS_BYTES if ws_bytes is None else ws_bytes) // one)))
+        one = max(1, ops.occl_curves_workspace_bytes(B, Pn, self.G, self.hid))       # of one order: B walks
+        per = min(M, self._fits(self.SHAPLEY_WS_BYTES, ws_bytes, one))
         ws = ops.occl_curves_orders_workspace(B, per, Pn, self.G, self.hid, dev)
         curves = (new(B * per * (Pn + 1)), new(B * per * (Pn + 1)))
         state, out, baseline = (new(B, Pn), new(B, Pn)), (new(B, Pn), new(B, Pn)), new(B)
@@ -858,8 +858,8 @@ class Engine:
             for m0 in range(0, M, per):
                 n = min(per, M - m0)
                 group = tuple(c[:B * n * (Pn + 1)].view(B, n, Pn + 1) for c in curves)
-                ops.occl_curves_orders(base, U, slot, run.probs, run.score, cnull, P["classifier.lin2.weight"],
-                                       P["classifier.lin2.bias"], answers, orders[m0:m0 + n], slot0=r0, out=group, workspace=ws)
+                ops.occl_curves_orders(base, U, slot, run.probs, run.score, cnull, *column, orders[m0:m0 + n], slot0=r0, out=group,
+                                       workspace=ws)
                 ops.shapley_accumulate(*group, rank[m0:m0 + n], slot, answers, state, self.A, U.shape[0], slot0=r0, m0=m0,
                                        total=M if m0 + n == M else 0, out=out, empty=baseline)
         return out[0], out[1], answers, run.logits, baseline
@@ -921,7 +921,7 @@ class Engine:
         """How many variant rows fit WORDS_BYTES: per row hg [4H], h and c [H] per direction, the classifier input [Dc], q' [mid],
         score and probs [G, Pn] and the hidden layer [hid], fp32."""
         per_row = 4 * (self.ndir * 6 * self.H + self.Dc + self.mid + 2 * self.G * Pn + self.hid)
-        return max(1, self.WORDS_BYTES // per_row)
+        return self._fits(self.WORDS_BYTES, None, per_row)
 
     @_device_current("feats", _cache_device)
     def explain_words_occlusion(self, P: Dict[str, Tensor], feats, ask, chunks):
@@ -929,9 +929,8 @@ class Engine:
         questions, its index tensors on the device as int32 and with order / offsets / img, the chunk's variant rows (forward
         order) grouped by their question's image.  Returns (words [B,T], answers int32 [B], logits [B,A]); answers and logits
         are explain's."""
-        assert not self.bf16, "explain_words_occlusion: fp32 / fp32x3 only"
-        run = self._answer_tail(P, feats, self._asked_front(P, feats, ask))
-        txt, logits, answers = run.txt, run.logits, self._picked(run.logits, ask.answers)
+        run, answers = self._explained("explain_words_occlusion", P, feats, ask)
+        txt, logits = run.txt, run.logits
         B, T = txt.q.shape
         E, H, GC, Dc, hid, dev = self.E, self.H, self.GC, self.Dc, self.hid, feats.vn.device
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)

@@ -16,6 +16,7 @@ from __future__ import annotations
 import warnings
 import weakref
 from collections import OrderedDict
+from functools import partial
 from types import SimpleNamespace
 from typing import Dict, List, NamedTuple, Optional
 
@@ -1307,32 +1308,33 @@ class VqaNet(nn.Module):
 
     # The front door of the explain family.  Every call asks (_ask_questions / _ask_pairs: all the argument checks, on the
     # host), returns _no_result for an empty batch, uploads (_ask_upload: the index, host answers and the call's own host
-    # tensors in ONE copy), runs its engine schedule (_ask_run) and wraps what comes back.
+    # tensors in ONE copy), runs its engine schedule (_ask_run) and wraps what comes back.  A public call binds its arguments
+    # to one of the two doors and hands the door to its member, which is written once for both (_explain_member).
     def _ask_questions(self, what: str, feats, q, q_len, image_index, answers, own=None, host_first: bool = False):
         """What an explain call about (q, q_len, image_index) checks, in order: the inference check, the call's `own` check
-        (explain_occlusion's window), the type of feats, the `answers` columns, then _answer_args.  host_first (explain_words,
+        (explain_occlusion's window: own(the call's full name, B), whose value the ask keeps as .own), the type of feats, the
+        `answers` columns, then _answer_args.  host_first (explain_words,
         explain_words_occlusion): what the host alone can judge -- a bank without v', the index count -- comes before
         `answers`, in _answer_args' words.  Returns the ask: B, q / q_len as tensors, the host index tensors, the columns."""
         self._check_inference(what)
-        if own is not None:
-            own()
+        checked = None if own is None else own(f"VqaNet.{what}", len(q))
         self._need_image_features(what, feats)
         if host_first:
             self._need_vprime(what, feats)
             _check_index_count(f"VqaNet.{what}", torch.as_tensor(image_index).numel(), len(q))
         cols = self._answer_columns(what, answers, len(q))
         q, q_len, index = self._answer_args(what, feats, q, q_len, image_index)
-        return SimpleNamespace(B=q.shape[0], q=q, q_len=q_len, qfeats=None, index=index, cols=cols)
+        return SimpleNamespace(B=q.shape[0], q=q, q_len=q_len, qfeats=None, index=index, cols=cols, own=checked)
 
     def _ask_pairs(self, what: str, feats, qfeats, image_index, question_index, answers, own=None):
         """_ask_questions for (image, question) pairs from the two caches: the inference check, `own`, the `answers` columns,
         then _pairs_args.  The ask holds qfeats in place of q / q_len, and the host index has the question rows behind img."""
         self._check_inference(what)
-        if own is not None:
-            own()
-        cols = self._answer_columns(what, answers, torch.as_tensor(image_index).numel())
+        B = torch.as_tensor(image_index).numel()
+        checked = None if own is None else own(f"VqaNet.{what}", B)
+        cols = self._answer_columns(what, answers, B)
         index = self._pairs_args(what, feats, qfeats, image_index, question_index)
-        return SimpleNamespace(B=index[-1].numel(), q=None, q_len=None, qfeats=qfeats, index=index, cols=cols)
+        return SimpleNamespace(B=index[-1].numel(), q=None, q_len=None, qfeats=qfeats, index=index, cols=cols, own=checked)
 
     def _ask_upload(self, feats, ask, extra=()):
         """The ask on the device of feats, as the engine reads it: on_device, the index tensors, and answers as int32, and
@@ -1343,6 +1345,28 @@ class VqaNet(nn.Module):
         ask.on_device = index[:n]
         ask.bad_tokens = self._token_counter(ask.q) if ask.q is not None else None
         return index[n:]
+
+    def _ask_upload_asked(self, feats, ask, extra=(), grouped: bool = False):
+        """_ask_upload for the calls that explain sets of grid positions: the distinct asked images and each question's place
+        among them (compact_image_index) travel in the copy in front of `extra`.  Returns (rows, slot, *extra) on the device;
+        grouped (explain_faithfulness_probs): by_slot travels behind slot, and ask.offsets is the host list of the grouping."""
+        rows, slot, by_slot, offsets = compact_image_index(ask.index[2], feats.N)
+        ask.offsets = offsets.tolist()
+        return self._ask_upload(feats, ask, (rows, slot) + ((by_slot,) if grouped else ()) + tuple(extra))
+
+    @staticmethod
+    def _device_maps(feats, ask, maps):
+        """The caller's maps as the engine reads them: fp32 [B, P], contiguous, on the device of feats."""
+        return torch.as_tensor(maps).detach().to(device=feats.vn.device, dtype=torch.float32).reshape(ask.B, -1).contiguous()
+
+    def _explain_member(self, door, feats, kind, own, member):
+        """An explain call behind its door (_ask_questions or _ask_pairs, everything but `own` bound): the ask, judged with the
+        member's host-only check `own`; `kind` with every field empty for B == 0; else member(ask) -- the member's upload, its
+        engine schedule and its result."""
+        ask = door(own=own)
+        if ask.B == 0:
+            return self._no_result(kind, feats, 0 if ask.q is None else ask.q.shape[1])
+        return member(ask)
 
     def _ask_run(self, schedule, feats, ask, *args):
         """The engine schedule on an uploaded ask, and the token count read back where question tokens were embedded."""
@@ -1392,13 +1416,13 @@ class VqaNet(nn.Module):
         what feats.to(torch.float32) gives); B == 0 returns empty tensors.  Rows come back in the caller's order and do not
         depend on how the batch is ordered or split.  Nothing is kept for a backward: _last_ctx, the gradient buffer, p.grad
         and the dropout seed stream are left alone."""
-        return self._explain(feats, self._ask_questions("explain", feats, q, q_len, image_index, answers))
+        return self._explain(partial(self._ask_questions, "explain", feats, q, q_len, image_index, answers), feats)
 
-    def _explain(self, feats, ask) -> Attribution:
-        if ask.B == 0:
-            return self._no_result(Attribution, feats)
-        self._ask_upload(feats, ask)
-        return self._maps_result(Attribution, feats, self._ask_run(self._engine.explain, feats, ask))
+    def _explain(self, door, feats) -> Attribution:
+        def member(ask):
+            self._ask_upload(feats, ask)
+            return self._maps_result(Attribution, feats, self._ask_run(self._engine.explain, feats, ask))
+        return self._explain_member(door, feats, Attribution, None, member)
 
     @torch.no_grad()
     def explain_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
@@ -1407,7 +1431,7 @@ class VqaNet(nn.Module):
         image image_index[b] of `feats` with question question_index[b] of `qfeats`; no recurrence runs either.  maps, answers
         and the `answers` argument are explain()'s; logits are answer_pairs()'s for the same arguments, bit for bit; the index
         rules, ownership checks and errors are answer_pairs()'s, with the `answers` checks of explain() judged first."""
-        return self._explain(feats, self._ask_pairs("explain_pairs", feats, qfeats, image_index, question_index, answers))
+        return self._explain(partial(self._ask_pairs, "explain_pairs", feats, qfeats, image_index, question_index, answers), feats)
 
     # ------------------------------------------------------------------ integrated gradients from cached features
     @torch.no_grad()
@@ -1447,23 +1471,22 @@ class VqaNet(nn.Module):
         pixels, SmoothGrad, bf16 mode, train mode, data parallelism.
 
         _ig_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
-        ask = self._ask_questions("explain_integrated", feats, q, q_len, image_index, answers,
-                                  own=lambda: _check_steps("VqaNet.explain_integrated", steps))
-        return self._explain_integrated(feats, ask, steps, _ig_bytes)
+        door = partial(self._ask_questions, "explain_integrated", feats, q, q_len, image_index, answers)
+        return self._explain_integrated(door, feats, steps, _ig_bytes)
 
-    def _explain_integrated(self, feats, ask, steps, ig_bytes) -> IntegratedGradients:
-        if ask.B == 0:
-            return self._no_result(IntegratedGradients, feats)
-        # chunks cut between questions, in the caller's order; a single chunk walks the ask's own grouping
-        rows = self._engine.integrated_rows(feats.vn.shape[1], steps, ig_bytes)
-        cuts = [(b0, min(b0 + rows, ask.B)) for b0 in range(0, ask.B, rows)]
-        img = ask.index[2]
-        groups = [t for b0, b1 in cuts for t in _group(img[b0:b1], feats.N)] if len(cuts) > 1 else []
-        on_device = self._ask_upload(feats, ask, groups) or ask.on_device[:2]
-        chunks = [(b0, b1, on_device[2 * i], on_device[2 * i + 1]) for i, (b0, b1) in enumerate(cuts)]
-        alphas = integrated_alphas(steps).to(feats.vn.device)
-        maps, cols, logits, base = self._ask_run(self._engine.explain_integrated, feats, ask, alphas, chunks)
-        return IntegratedGradients(maps.view(-1, *feats.grid), cols.long(), logits, base)
+    def _explain_integrated(self, door, feats, steps, ig_bytes) -> IntegratedGradients:
+        def member(ask):
+            # chunks cut between questions, in the caller's order; a single chunk walks the ask's own grouping
+            rows = self._engine.integrated_rows(feats.vn.shape[1], ask.own, ig_bytes)
+            cuts = [(b0, min(b0 + rows, ask.B)) for b0 in range(0, ask.B, rows)]
+            img = ask.index[2]
+            groups = [t for b0, b1 in cuts for t in _group(img[b0:b1], feats.N)] if len(cuts) > 1 else []
+            on_device = self._ask_upload(feats, ask, groups) or ask.on_device[:2]
+            chunks = [(b0, b1, on_device[2 * i], on_device[2 * i + 1]) for i, (b0, b1) in enumerate(cuts)]
+            alphas = integrated_alphas(ask.own).to(feats.vn.device)
+            maps, cols, logits, base = self._ask_run(self._engine.explain_integrated, feats, ask, alphas, chunks)
+            return IntegratedGradients(maps.view(-1, *feats.grid), cols.long(), logits, base)
+        return self._explain_member(door, feats, IntegratedGradients, lambda what, B: _check_steps(what, steps), member)
 
     @torch.no_grad()
     def explain_integrated_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
@@ -1473,9 +1496,8 @@ class VqaNet(nn.Module):
         answers, baseline_logits, steps and the `answers` argument are explain_integrated()'s; logits are answer_pairs()'s for
         the same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the steps and
         `answers` checks judged first."""
-        ask = self._ask_pairs("explain_integrated_pairs", feats, qfeats, image_index, question_index, answers,
-                              own=lambda: _check_steps("VqaNet.explain_integrated_pairs", steps))
-        return self._explain_integrated(feats, ask, steps, _ig_bytes)
+        door = partial(self._ask_pairs, "explain_integrated_pairs", feats, qfeats, image_index, question_index, answers)
+        return self._explain_integrated(door, feats, steps, _ig_bytes)
 
     # ------------------------------------------------------------------ occlusion maps from cached features
     @torch.no_grad()
@@ -1512,17 +1534,15 @@ class VqaNet(nn.Module):
         alone.
 
         _u_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
-        ask = self._ask_questions("explain_occlusion", feats, q, q_len, image_index, answers,
-                                  own=lambda: _check_window("VqaNet.explain_occlusion", window))
-        return self._explain_occlusion(feats, ask, window, _u_bytes)
+        door = partial(self._ask_questions, "explain_occlusion", feats, q, q_len, image_index, answers)
+        return self._explain_occlusion(door, feats, window, _u_bytes)
 
-    def _explain_occlusion(self, feats, ask, window, u_bytes) -> Occlusion:
-        if ask.B == 0:
-            return self._no_result(Occlusion, feats)
-        # the distinct asked images and each question's place among them
-        rows, slot = self._ask_upload(feats, ask, compact_image_index(ask.index[2], feats.N)[:2])
-        out = self._ask_run(self._engine.explain_occlusion, feats, ask, rows, slot, window, u_bytes)
-        return self._maps_result(Occlusion, feats, out)
+    def _explain_occlusion(self, door, feats, window, u_bytes) -> Occlusion:
+        def member(ask):
+            rows, slot = self._ask_upload_asked(feats, ask)
+            out = self._ask_run(self._engine.explain_occlusion, feats, ask, rows, slot, ask.own, u_bytes)
+            return self._maps_result(Occlusion, feats, out)
+        return self._explain_member(door, feats, Occlusion, lambda what, B: _check_window(what, window), member)
 
     @torch.no_grad()
     def explain_occlusion_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index,
@@ -1532,9 +1552,8 @@ class VqaNet(nn.Module):
         answers, window and the `answers` argument are explain_occlusion()'s; logits are answer_pairs()'s for the same
         arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the window and
         `answers` checks judged first."""
-        ask = self._ask_pairs("explain_occlusion_pairs", feats, qfeats, image_index, question_index, answers,
-                              own=lambda: _check_window("VqaNet.explain_occlusion_pairs", window))
-        return self._explain_occlusion(feats, ask, window, _u_bytes)
+        door = partial(self._ask_pairs, "explain_occlusion_pairs", feats, qfeats, image_index, question_index, answers)
+        return self._explain_occlusion(door, feats, window, _u_bytes)
 
     # ------------------------------------------------------------------ deletion and insertion curves of an attribution map
     @torch.no_grad()
@@ -1579,19 +1598,17 @@ class VqaNet(nn.Module):
         upsampling or normalising the maps.  Probability curves and the arg-max at every step: explain_faithfulness_probs().
 
         _u_bytes (tests and tools): the workspace cap in bytes, to force several chunks at small sizes."""
-        what = "explain_faithfulness"
-        ask = self._ask_questions(what, feats, q, q_len, image_index, answers,
-                                  own=lambda: _check_maps(f"VqaNet.{what}", maps, len(q), getattr(feats, "grid", None)))
-        return self._explain_faithfulness(feats, ask, maps, _u_bytes)
+        door = partial(self._ask_questions, "explain_faithfulness", feats, q, q_len, image_index, answers)
+        return self._explain_faithfulness(door, feats, maps, _u_bytes)
 
-    def _explain_faithfulness(self, feats, ask, maps, u_bytes) -> Faithfulness:
-        if ask.B == 0:
-            return self._no_result(Faithfulness, feats)
-        rows, slot = self._ask_upload(feats, ask, compact_image_index(ask.index[2], feats.N)[:2])
-        maps = torch.as_tensor(maps).detach().to(device=feats.vn.device, dtype=torch.float32).reshape(ask.B, -1).contiguous()
-        deletion, insertion, order, cols, logits = self._ask_run(self._engine.explain_faithfulness, feats, ask, rows, slot, maps,
-                                                                 u_bytes)
-        return Faithfulness(deletion, insertion, order.long(), cols.long(), logits)
+    def _explain_faithfulness(self, door, feats, maps, u_bytes) -> Faithfulness:
+        def member(ask):
+            rows, slot = self._ask_upload_asked(feats, ask)
+            deletion, insertion, order, cols, logits = self._ask_run(self._engine.explain_faithfulness, feats, ask, rows, slot,
+                                                                     self._device_maps(feats, ask, maps), u_bytes)
+            return Faithfulness(deletion, insertion, order.long(), cols.long(), logits)
+        own = lambda what, B: _check_maps(what, maps, B, getattr(feats, "grid", None))
+        return self._explain_member(door, feats, Faithfulness, own, member)
 
     @torch.no_grad()
     def explain_faithfulness_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, maps,
@@ -1601,11 +1618,8 @@ class VqaNet(nn.Module):
         curves, order, answers, maps and the `answers` argument are explain_faithfulness()'s; logits are answer_pairs()'s for the
         same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s, with the maps and
         `answers` checks judged first."""
-        what = "explain_faithfulness_pairs"
-        ask = self._ask_pairs(what, feats, qfeats, image_index, question_index, answers,
-                              own=lambda: _check_maps(f"VqaNet.{what}", maps, torch.as_tensor(image_index).numel(),
-                                                      getattr(feats, "grid", None)))
-        return self._explain_faithfulness(feats, ask, maps, _u_bytes)
+        door = partial(self._ask_pairs, "explain_faithfulness_pairs", feats, qfeats, image_index, question_index, answers)
+        return self._explain_faithfulness(door, feats, maps, _u_bytes)
 
     # ------------------------------------------------------------------ probability curves and flip points
     @torch.no_grad()
@@ -1644,21 +1658,19 @@ class VqaNet(nn.Module):
         train mode, data parallelism.
 
         _u_bytes, _ws_bytes (tests and tools): the two workspace caps in bytes, to force several chunks at small sizes."""
-        what = "explain_faithfulness_probs"
-        ask = self._ask_questions(what, feats, q, q_len, image_index, answers,
-                                  own=lambda: _check_maps(f"VqaNet.{what}", maps, len(q), getattr(feats, "grid", None)))
-        return self._explain_faithfulness_probs(feats, ask, maps, _u_bytes, _ws_bytes)
+        door = partial(self._ask_questions, "explain_faithfulness_probs", feats, q, q_len, image_index, answers)
+        return self._explain_faithfulness_probs(door, feats, maps, _u_bytes, _ws_bytes)
 
-    def _explain_faithfulness_probs(self, feats, ask, maps, u_bytes, ws_bytes) -> ProbabilityCurves:
-        if ask.B == 0:
-            return self._no_result(ProbabilityCurves, feats)
-        *index, offsets = compact_image_index(ask.index[2], feats.N)
-        rows, slot, by_slot = self._ask_upload(feats, ask, index)
-        maps = torch.as_tensor(maps).detach().to(device=feats.vn.device, dtype=torch.float32).reshape(ask.B, -1).contiguous()
-        prob, top, top_prob, order, cols, logits = self._ask_run(self._engine.explain_faithfulness_probs, feats, ask, rows, slot,
-                                                                 by_slot, offsets.tolist(), maps, u_bytes, ws_bytes)
-        return ProbabilityCurves(prob[:, 0], prob[:, 1], top[:, 0], top[:, 1], top_prob[:, 0], top_prob[:, 1], order.long(),
-                                 cols.long(), logits)
+    def _explain_faithfulness_probs(self, door, feats, maps, u_bytes, ws_bytes) -> ProbabilityCurves:
+        def member(ask):
+            rows, slot, by_slot = self._ask_upload_asked(feats, ask, grouped=True)
+            prob, top, top_prob, order, cols, logits = self._ask_run(
+                self._engine.explain_faithfulness_probs, feats, ask, rows, slot, by_slot, ask.offsets,
+                self._device_maps(feats, ask, maps), u_bytes, ws_bytes)
+            return ProbabilityCurves(prob[:, 0], prob[:, 1], top[:, 0], top[:, 1], top_prob[:, 0], top_prob[:, 1], order.long(),
+                                     cols.long(), logits)
+        own = lambda what, B: _check_maps(what, maps, B, getattr(feats, "grid", None))
+        return self._explain_member(door, feats, ProbabilityCurves, own, member)
 
     @torch.no_grad()
     def explain_faithfulness_probs_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, maps,
@@ -1668,11 +1680,8 @@ class VqaNet(nn.Module):
         The curves, tops, order, answers, maps and the `answers` argument are explain_faithfulness_probs()'s; logits are
         answer_pairs()'s for the same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s,
         with the maps and `answers` checks judged first."""
-        what = "explain_faithfulness_probs_pairs"
-        ask = self._ask_pairs(what, feats, qfeats, image_index, question_index, answers,
-                              own=lambda: _check_maps(f"VqaNet.{what}", maps, torch.as_tensor(image_index).numel(),
-                                                      getattr(feats, "grid", None)))
-        return self._explain_faithfulness_probs(feats, ask, maps, u_bytes=_u_bytes, ws_bytes=_ws_bytes)
+        door = partial(self._ask_pairs, "explain_faithfulness_probs_pairs", feats, qfeats, image_index, question_index, answers)
+        return self._explain_faithfulness_probs(door, feats, maps, _u_bytes, _ws_bytes)
 
     # ------------------------------------------------------------------ sampled Shapley maps from cached features
     @torch.no_grad()
@@ -1727,33 +1736,32 @@ class VqaNet(nn.Module):
 
         _u_bytes, _ws_bytes (tests and tools): the caps of U and of the curve workspace in bytes, to force several chunks and
         several groups of orders at small sizes."""
-        what, table = "explain_shapley", []
-        ask = self._ask_questions(what, feats, q, q_len, image_index, answers,
-                                  own=lambda: table.append(self._shapley_table(what, feats, permutations, seed, orders)))
-        return self._explain_shapley(feats, ask, table[0], _u_bytes, _ws_bytes)
+        door = partial(self._ask_questions, "explain_shapley", feats, q, q_len, image_index, answers)
+        return self._explain_shapley(door, feats, permutations, seed, orders, _u_bytes, _ws_bytes)
 
     @staticmethod
     def _shapley_table(what: str, feats, permutations, seed, orders):
-        """The host checks of permutations / seed / orders; returns the given table, or None where it is still to be drawn."""
+        """The host checks of permutations / seed / orders in the name `what`; returns the given table, or the function of P
+        that draws it."""
         if orders is not None:
-            return _check_orders(f"VqaNet.{what}", orders, getattr(feats, "grid", None))
-        _check_permutations(f"VqaNet.{what}", permutations)
+            return _check_orders(what, orders, getattr(feats, "grid", None))
+        _check_permutations(what, permutations)
         if isinstance(seed, bool) or not isinstance(seed, int):
-            raise TypeError(f"VqaNet.{what}: seed must be an int, got {type(seed).__name__}")
+            raise TypeError(f"{what}: seed must be an int, got {type(seed).__name__}")
         return lambda P: shapley_orders(permutations, P, seed)
 
-    def _explain_shapley(self, feats, ask, table, u_bytes, ws_bytes) -> Shapley:
-        if ask.B == 0:
-            return self._no_result(Shapley, feats)
-        P = feats.grid[0] * feats.grid[1]
-        orders = table(P) if callable(table) else table
-        rank = torch.empty_like(orders)
-        rank.scatter_(1, orders, torch.arange(P).expand_as(orders))          # the inverse of every row
-        rows, slot, orders, rank = self._ask_upload(feats, ask, compact_image_index(ask.index[2], feats.N)[:2]
-                                                    + (orders.reshape(-1), rank.reshape(-1)))
-        maps, err, cols, logits, base = self._ask_run(self._engine.explain_shapley, feats, ask, rows, slot, orders.view(-1, P),
-                                                      rank.view(-1, P), u_bytes, ws_bytes)
-        return Shapley(maps.view(-1, *feats.grid), err.view(-1, *feats.grid), cols.long(), logits, base)
+    def _explain_shapley(self, door, feats, permutations, seed, orders, u_bytes, ws_bytes) -> Shapley:
+        def member(ask):
+            P = feats.grid[0] * feats.grid[1]
+            table = ask.own(P) if callable(ask.own) else ask.own
+            rank = torch.empty_like(table)
+            rank.scatter_(1, table, torch.arange(P).expand_as(table))        # the inverse of every row
+            rows, slot, table, rank = self._ask_upload_asked(feats, ask, (table.reshape(-1), rank.reshape(-1)))
+            maps, err, cols, logits, base = self._ask_run(self._engine.explain_shapley, feats, ask, rows, slot, table.view(-1, P),
+                                                          rank.view(-1, P), u_bytes, ws_bytes)
+            return Shapley(maps.view(-1, *feats.grid), err.view(-1, *feats.grid), cols.long(), logits, base)
+        own = lambda what, B: self._shapley_table(what, feats, permutations, seed, orders)
+        return self._explain_member(door, feats, Shapley, own, member)
 
     @torch.no_grad()
     def explain_shapley_pairs(self, feats: ImageFeatures, qfeats: QuestionFeatures, image_index, question_index, answers=None,
@@ -1763,10 +1771,8 @@ class VqaNet(nn.Module):
         answers, baseline_logits, permutations, seed, orders and the `answers` argument are explain_shapley()'s; logits are
         answer_pairs()'s for the same arguments, bit for bit; the index rules, ownership checks and errors are answer_pairs()'s,
         with the permutations / orders and `answers` checks judged first."""
-        what, table = "explain_shapley_pairs", []
-        ask = self._ask_pairs(what, feats, qfeats, image_index, question_index, answers,
-                              own=lambda: table.append(self._shapley_table(what, feats, permutations, seed, orders)))
-        return self._explain_shapley(feats, ask, table[0], _u_bytes, _ws_bytes)
+        door = partial(self._ask_pairs, "explain_shapley_pairs", feats, qfeats, image_index, question_index, answers)
+        return self._explain_shapley(door, feats, permutations, seed, orders, _u_bytes, _ws_bytes)
 
     # ------------------------------------------------------------------ gradient x input per question token
     @torch.no_grad()
@@ -1797,12 +1803,12 @@ class VqaNet(nn.Module):
         explained without encoding them again -- which is this call.
 
         _stages (tests and tools): a dict that receives the engine's intermediate gradients (Engine.explain_words)."""
-        ask = self._ask_questions("explain_words", feats, q, q_len, image_index, answers, host_first=True)
-        if ask.B == 0:
-            return self._no_result(WordAttribution, feats, ask.q.shape[1])
-        self._ask_upload(feats, ask)
-        words, maps, cols, logits = self._ask_run(self._engine.explain_words, feats, ask, _stages)
-        return WordAttribution(words, maps.view(-1, *feats.grid), cols.long(), logits)
+        def member(ask):
+            self._ask_upload(feats, ask)
+            words, maps, cols, logits = self._ask_run(self._engine.explain_words, feats, ask, _stages)
+            return WordAttribution(words, maps.view(-1, *feats.grid), cols.long(), logits)
+        door = partial(self._ask_questions, "explain_words", feats, q, q_len, image_index, answers, host_first=True)
+        return self._explain_member(door, feats, WordAttribution, None, member)
 
     # ------------------------------------------------------------------ exact word occlusion from cached features
     _WORD_TABLE_FIELDS = ("fwd_b", "fwd_t", "fwd_seed", "rev_b", "rev_t", "rev_seed", "rev_row", "order", "offsets", "img")
@@ -1848,23 +1854,23 @@ class VqaNet(nn.Module):
         per-step states the variant chains start from.
 
         _variant_rows (tests and tools): caps the variants per chunk, to force several chunks at small sizes."""
-        ask = self._ask_questions("explain_words_occlusion", feats, q, q_len, image_index, answers, host_first=True)
-        T = ask.q.shape[1]
-        if ask.B == 0:
-            return self._no_result(WordOcclusion, feats, T)
-        lengths = ask.q_len.detach().to(device="cpu", dtype=torch.int64).reshape(-1)  # the one copy to the host: synchronises
-        cap = self._engine.word_occlusion_rows(feats.vn.shape[1])
-        if _variant_rows is not None:
-            cap = max(1, min(cap, int(_variant_rows)))
-        img, fields = ask.index[2], self._WORD_TABLE_FIELDS
-        chunks = []
-        for b0, b1 in word_occlusion_chunks(lengths.tolist(), T, cap):
-            tab = word_occlusion_table(lengths, T, b0, b1)
-            tab.img = img[tab.fwd_b.long()]
-            tab.order, tab.offsets = _group(tab.img, feats.N)
-            chunks.append(tab)
-        on_device = self._ask_upload(feats, ask, [getattr(tab, k) for tab in chunks for k in fields])
-        for i, tab in enumerate(chunks):                                                # the tables on the device: the same copy
-            vars(tab).update(zip(fields, on_device[i * len(fields):]))
-        words, picked, logits = self._ask_run(self._engine.explain_words_occlusion, feats, ask, chunks)
-        return WordOcclusion(words, picked.long(), logits)
+        def member(ask):
+            T = ask.q.shape[1]
+            lengths = ask.q_len.detach().to(device="cpu", dtype=torch.int64).reshape(-1)  # the one copy to the host: synchronises
+            cap = self._engine.word_occlusion_rows(feats.vn.shape[1])
+            if _variant_rows is not None:
+                cap = max(1, min(cap, int(_variant_rows)))
+            img, fields = ask.index[2], self._WORD_TABLE_FIELDS
+            chunks = []
+            for b0, b1 in word_occlusion_chunks(lengths.tolist(), T, cap):
+                tab = word_occlusion_table(lengths, T, b0, b1)
+                tab.img = img[tab.fwd_b.long()]
+                tab.order, tab.offsets = _group(tab.img, feats.N)
+                chunks.append(tab)
+            on_device = self._ask_upload(feats, ask, [getattr(tab, k) for tab in chunks for k in fields])
+            for i, tab in enumerate(chunks):                                            # the tables on the device: the same copy
+                vars(tab).update(zip(fields, on_device[i * len(fields):]))
+            words, picked, logits = self._ask_run(self._engine.explain_words_occlusion, feats, ask, chunks)
+            return WordOcclusion(words, picked.long(), logits)
+        door = partial(self._ask_questions, "explain_words_occlusion", feats, q, q_len, image_index, answers, host_first=True)
+        return self._explain_member(door, feats, WordOcclusion, None, member)

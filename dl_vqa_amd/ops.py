@@ -858,10 +858,31 @@ def occl_curves_chunk() -> int:
     return _lib.load().vqa_occl_curves_chunk()
 
 
+def occl_curves_workspace_bytes(T: int, P: int, G: int, hid: int) -> int:
+    """vqa_occl_curves_workspace_bytes(T, P, G, hid): the chunk sums of T walks -- T questions, or the T = B * M (question, order)
+    pairs of vqa_occl_curves_orders, whose vqa_occl_curves_orders_workspace_bytes(B, M, ...) is the same formula."""
+    return _lib.load().vqa_occl_curves_workspace_bytes(T, P, G, hid)
+
+
 def occl_curves_workspace(B: int, P: int, G: int, hid: int, device):
     """A buffer of vqa_occl_curves_workspace_bytes(B, P, G, hid): the chunk sums of one call, freed with the call."""
-    need = _lib.load().vqa_occl_curves_workspace_bytes(B, P, G, hid)
-    return torch.empty(max(need // 4, 4), dtype=torch.float32, device=device)
+    return torch.empty(max(occl_curves_workspace_bytes(B, P, G, hid) // 4, 4), dtype=torch.float32, device=device)
+
+
+def _curves_buffers(order, rows: int, P: int, out, n_out: int, shape, workspace, walks: int, G: int, hid: int, device):
+    """What the three curve wrappers ask beside _occl_operands: order int32 [rows, P]; out, n_out fp32 tensors of `shape`, made
+    where None; workspace, a float32 buffer, made for `walks` walks where None.  Returns (out, workspace)."""
+    _chk(order, torch.int32)
+    assert order.shape == (rows, P) and order.is_contiguous()
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=torch.float32, device=device) for _ in range(n_out))
+    for t in out:
+        assert t.shape == shape and t.is_contiguous() and t.dtype == torch.float32
+    if workspace is None:
+        workspace = occl_curves_workspace(walks, P, G, hid, device)
+    _chk(workspace)
+    assert workspace.is_contiguous()
+    return out, workspace
 
 
 def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot0: int = 0, out=None, workspace=None):
@@ -870,17 +891,7 @@ def occl_curves(base, U, slot, probs, score, cnull, W2, b2, answers, order, slot
     occl_logit's without Z, window and logits, plus order int32 [B, P].  out: (deletion, insertion), written in place for the
     questions whose slot is in [slot0, slot0 + R); workspace: a float32 buffer of at least vqa_occl_curves_workspace_bytes."""
     B, G, P, R, hid, A, w2_ld = _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers)
-    _chk(order, torch.int32)
-    assert order.shape == (B, P) and order.is_contiguous()
-    if out is None:
-        out = tuple(torch.empty(B, P + 1, dtype=torch.float32, device=probs.device) for _ in range(2))
-    deletion, insertion = out
-    for t in out:
-        assert t.shape == (B, P + 1) and t.is_contiguous() and t.dtype == torch.float32
-    if workspace is None:
-        workspace = occl_curves_workspace(B, P, G, hid, probs.device)
-    _chk(workspace)
-    assert workspace.is_contiguous()
+    (deletion, insertion), workspace = _curves_buffers(order, B, P, out, 2, (B, P + 1), workspace, B, G, hid, probs.device)
     call("vqa_occl_curves", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2), w2_ld, ptr(b2),
          ptr(answers), ptr(order), ptr(workspace), workspace.numel() * 4, ptr(deletion), ptr(insertion), R, B, P, hid, G, A,
          stream())
@@ -893,15 +904,8 @@ def occl_curves_hidden(base, U, slot, probs, score, cnull, order, slot0: int = 0
     occl_curves multiplies by one row of W2, for every column at once.  The operands are occl_curves' without W2, b2 and
     answers.  out: H, written in place for the questions whose slot is in [slot0, slot0 + R); workspace: as occl_curves'."""
     B, G, P, R, hid = _occl_operands(base, U, slot, probs, score, cnull)
-    _chk(order, torch.int32)
-    assert order.shape == (B, P) and order.is_contiguous()
-    if out is None:
-        out = torch.empty(B, 2, P + 1, hid, dtype=torch.float32, device=probs.device)
-    assert out.shape == (B, 2, P + 1, hid) and out.is_contiguous() and out.dtype == torch.float32
-    if workspace is None:
-        workspace = occl_curves_workspace(B, P, G, hid, probs.device)
-    _chk(workspace)
-    assert workspace.is_contiguous()
+    (out,), workspace = _curves_buffers(order, B, P, None if out is None else (out,), 1, (B, 2, P + 1, hid), workspace, B, G, hid,
+                                        probs.device)
     call("vqa_occl_curves_hidden", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(order),
          ptr(workspace), workspace.numel() * 4, ptr(out), R, B, P, hid, G, stream())
     return out
@@ -909,8 +913,7 @@ def occl_curves_hidden(base, U, slot, probs, score, cnull, order, slot0: int = 0
 
 def occl_curves_orders_workspace(B: int, M: int, P: int, G: int, hid: int, device):
     """A buffer of vqa_occl_curves_orders_workspace_bytes(B, M, P, G, hid): the chunk sums of one launch over M orders."""
-    need = _lib.load().vqa_occl_curves_orders_workspace_bytes(B, M, P, G, hid)
-    return torch.empty(max(need // 4, 4), dtype=torch.float32, device=device)
+    return occl_curves_workspace(B * M, P, G, hid, device)
 
 
 def occl_curves_orders(base, U, slot, probs, score, cnull, W2, b2, answers, orders, slot0: int = 0, out=None, workspace=None):
@@ -919,18 +922,9 @@ def occl_curves_orders(base, U, slot, probs, score, cnull, W2, b2, answers, orde
     occl_curves' with orders int32 [M, P], one table for every question, in place of order [B, P].  out and workspace (at least
     vqa_occl_curves_orders_workspace_bytes): as occl_curves'."""
     B, G, P, R, hid, A, w2_ld = _occl_operands(base, U, slot, probs, score, cnull, W2, b2, answers)
-    _chk(orders, torch.int32)
-    assert orders.dim() == 2 and orders.shape[1] == P and orders.shape[0] >= 1 and orders.is_contiguous()
+    assert orders.dim() == 2 and orders.shape[0] >= 1
     M = orders.shape[0]
-    if out is None:
-        out = tuple(torch.empty(B, M, P + 1, dtype=torch.float32, device=probs.device) for _ in range(2))
-    deletion, insertion = out
-    for t in out:
-        assert t.shape == (B, M, P + 1) and t.is_contiguous() and t.dtype == torch.float32
-    if workspace is None:
-        workspace = occl_curves_orders_workspace(B, M, P, G, hid, probs.device)
-    _chk(workspace)
-    assert workspace.is_contiguous()
+    (deletion, insertion), workspace = _curves_buffers(orders, M, P, out, 2, (B, M, P + 1), workspace, B * M, G, hid, probs.device)
     call("vqa_occl_curves_orders", ptr(base), ptr(U), ptr(slot), slot0, ptr(probs), ptr(score), ptr(cnull), ptr(W2), w2_ld,
          ptr(b2), ptr(answers), ptr(orders), ptr(workspace), workspace.numel() * 4, ptr(deletion), ptr(insertion), R, B, M, P, hid,
          G, A, stream())

@@ -1,5 +1,6 @@
 """What the tests of the explain family share (test_attribution_*, test_word_attribution_*, test_occlusion_*,
-test_word_occlusion_*, test_explain_refusals_cpu): the tiny model and host-side caches of the CPU tests, and the model builder,
+test_word_occlusion_*, test_integrated_*, test_explain_refusals_cpu and the other refusal tests): the tiny model, host-side
+caches, the scripted call and the random float64 case of the CPU tests, and the model builder,
 groupings, error measures and given answer columns of the GPU tests.  A plain module: no fixture, no pytest setting."""
 import torch
 
@@ -27,9 +28,39 @@ def host_caches(m, N=3, M=2, vprime=True):
     return feats, qfeats
 
 
+GOOD_MAPS = torch.zeros(3, 2, 2)    # for three questions on host_caches' 2 x 2 grid: nothing about these maps is wrong
+
+
+def invoke(m, name, pairs, feats, qfeats, q, ql, index, maps=None, **kw):
+    """One explain call about three questions on host caches: the pairs forms ask the questions [0, 1, 1] of qfeats.  maps: the
+    argument the faithfulness calls take behind the index."""
+    own = () if maps is None else (maps,)
+    if pairs:
+        return getattr(m, name)(feats, qfeats, index, [0, 1, 1], *own, **kw)
+    return getattr(m, name)(feats, q, ql, index, *own, **kw)
+
+
 def columns(B, A):
     """The given answer columns of the tests."""
     return [(3 * b + 1) % A for b in range(B)]
+
+
+def _random_case(do_option, G, seed):
+    """A random attention stage + classifier in float64 (state-dict names and shapes of the model) and random inputs."""
+    g = torch.Generator().manual_seed(seed)
+    N, B, gh, gw, C, mid, Q, hid, A = 3, 7, 3, 4, 10, 12, 6, 9, 5
+    xld = 2 * mid if do_option == "|" else mid
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    sd = {"attention.v_conv.weight": rn(mid, C, 1, 1), "attention.q_lin.weight": rn(mid, Q), "attention.q_lin.bias": rn(mid),
+          "attention.x_conv.weight": rn(G, xld, 1, 1), "attention.x_conv.bias": rn(G),
+          "classifier.lin1.weight": rn(hid, G * C + Q), "classifier.lin1.bias": rn(hid),
+          "classifier.lin2.weight": rn(A, hid), "classifier.lin2.bias": rn(A)}
+    vn = rn(N, gh * gw, C)
+    vn = vn / vn.norm(dim=-1, keepdim=True)
+    qf = rn(B, Q)
+    img = torch.randint(0, N, (B,), generator=g)
+    answers = torch.randint(0, A, (B,), generator=g)
+    return sd, vn, qf, img, answers, (gh, gw)
 
 
 # ----------------------------------------------------------------------------- GPU

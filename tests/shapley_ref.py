@@ -26,7 +26,7 @@ SAMPLING_SEED = 0                             # test_shapley_cpu checks that the
 
 def case(shape, seed_offset=0):
     """Consistent synthetic operands of vqa_occl_curves_orders for shape (B, R, gh, gw, G, hid, M), built the way
-    tests/test_faithfulness_gpu.py builds vqa_occl_curves': probs = softmax(score), cnull = the row's log-sum-exp + log r with r
+    tests/curves_util.py builds vqa_occl_curves': probs = softmax(score), cnull = the row's log-sum-exp + log r with r
     drawn from [1/15, 0.6], the questions spread over the R images; orders: M random permutations."""
     import math
     B, Rr, gh, gw, G, hid, M = shape

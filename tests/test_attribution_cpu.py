@@ -10,6 +10,7 @@ import torch
 
 from dl_vqa_amd import Attribution
 from tests import attribution_ref as R
+from tests.explain_util import _random_case
 
 NEW_ENTRY_POINTS = ("vqa_att_attr_apply_gather", "vqa_att_attr_apply_gather_f16", "vqa_att_attr_score_grouped",
                     "vqa_att_attr_score_grouped_pairs", "vqa_att_attr_score_grouped_f16", "vqa_att_attr_score_grouped_pairs_f16",
@@ -17,22 +18,6 @@ NEW_ENTRY_POINTS = ("vqa_att_attr_apply_gather", "vqa_att_attr_apply_gather_f16"
 
 
 # ----------------------------------------------------------------------------- the identity, in float64
-def _random_case(do_option, G, seed):
-    """A random attention stage + classifier in float64 (state-dict names and shapes of the model) and random inputs."""
-    g = torch.Generator().manual_seed(seed)
-    N, B, gh, gw, C, mid, Q, hid, A = 3, 7, 3, 4, 10, 12, 6, 9, 5
-    xld = 2 * mid if do_option == "|" else mid
-    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
-    sd = {"attention.v_conv.weight": rn(mid, C, 1, 1), "attention.q_lin.weight": rn(mid, Q), "attention.q_lin.bias": rn(mid),
-          "attention.x_conv.weight": rn(G, xld, 1, 1), "attention.x_conv.bias": rn(G),
-          "classifier.lin1.weight": rn(hid, G * C + Q), "classifier.lin1.bias": rn(hid),
-          "classifier.lin2.weight": rn(A, hid), "classifier.lin2.bias": rn(A)}
-    vn = rn(N, gh * gw, C)
-    vn = vn / vn.norm(dim=-1, keepdim=True)
-    qf = rn(B, Q)
-    img = torch.randint(0, N, (B,), generator=g)
-    answers = torch.randint(0, A, (B,), generator=g)
-    return sd, vn, qf, img, answers, (gh, gw)
 
 
 @pytest.mark.parametrize("G", [1, 2])

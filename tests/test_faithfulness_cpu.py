@@ -7,21 +7,11 @@ import re
 import pytest
 import torch
 
-from dl_vqa_amd import Faithfulness, ImageFeatures, VqaNet
+from dl_vqa_amd import Faithfulness, ImageFeatures
 from tests import attribution_ref as R
 from tests import faithfulness_ref as FR
+from tests.curves_util import _maps, _random_case
 from tests.explain_util import columns as _columns, host_caches as _host_caches, tiny as _tiny
-from tests.golden_util import full_cfg
-from tests.test_occlusion_cpu import _random_case
-
-
-def _maps(B, P, seed, ties):
-    g = torch.Generator().manual_seed(seed)
-    if ties:                                                          # three distinct values and a signed zero
-        m = torch.randint(-1, 2, (B, P), generator=g).double()
-        m[:, 0] = -0.0
-        return m
-    return torch.randn(B, P, generator=g, dtype=torch.float64)
 
 
 def _check_identity(tag, sd, do_option, vn, qf, img, cols, grid, maps):
@@ -246,25 +236,3 @@ def test_maps_answers_and_features_are_judged_before_any_device_work():
                           "explain_faithfulness_pairs") == \
                 raised(lambda: m.explain_pairs(images, questions, [0, 1, 2], [0, 1, 1]), "explain_pairs")
     assert m._last_ctx is None and all(p.grad is None for p in m.parameters())
-
-
-@pytest.mark.parametrize("pairs", [False, True], ids=["explain_faithfulness", "explain_faithfulness_pairs"])
-def test_bf16_then_train_mode_then_device(pairs):
-    name = "explain_faithfulness_pairs" if pairs else "explain_faithfulness"
-    good = torch.zeros(3, 2, 2)
-    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
-    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
-    with pytest.raises(NotImplementedError, match="compute_dtype"):   # before the maps are looked at
-        getattr(m, name)(None, None, [0], [0], "no map") if pairs else getattr(m, name)(None, q, ql, [0], "no map")
-    g, m = _tiny()
-    m.train()
-    with pytest.raises(RuntimeError, match="training mode"):
-        getattr(m, name)(None, None, [0], [0], "no map") if pairs else getattr(m, name)(None, g.t["q"], g.t["q_len"], [0], "no map")
-    m.eval()                                                        # eval mode on the CPU: the device check speaks
-    feats, qfeats = _host_caches(m)
-    with pytest.raises(RuntimeError, match="cuda"):
-        if pairs:
-            m.explain_faithfulness_pairs(feats, qfeats, [0, 1, 2], [0, 1, 1], good)
-        else:
-            m.explain_faithfulness(feats, g.t["q"][:3], g.t["q_len"][:3], [0, 1, 2], good)
-    assert m._last_ctx is None

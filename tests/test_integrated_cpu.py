@@ -12,8 +12,7 @@ from dl_vqa_amd import IntegratedGradients
 from dl_vqa_amd.model import integrated_alphas
 from tests import attribution_ref as R
 from tests import integrated_ref as I
-from tests.explain_util import host_caches, tiny
-from tests.test_attribution_cpu import _random_case
+from tests.explain_util import _random_case, host_caches, tiny
 
 SCORE_ENTRY_POINTS = ("vqa_att_path_score_grouped", "vqa_att_path_score_grouped_pairs", "vqa_att_path_score_grouped_f16",
                       "vqa_att_path_score_grouped_pairs_f16")
@@ -39,7 +38,7 @@ def test_the_step_positions_are_the_float32_midpoints():
 @pytest.mark.parametrize("G", [1, 2])
 @pytest.mark.parametrize("do_option", ["+", "*", "|"])
 def test_closed_form_equals_autograd_in_float64(do_option, G, steps):
-    """A random attention stage + classifier (tests/test_attribution_cpu.py's), and below the three fixtures: the header's
+    """A random attention stage + classifier (tests/explain_util.py's), and below the three fixtures: the header's
     placement of alpha_s -- r1_s and dscore_s without it, r2_s with it -- against autograd on alpha_s * vn.  The bound is the one
     test_attribution_cpu.py has for the same comparison at alpha = 1."""
     sd, vn, qf, img, answers, grid = _random_case(do_option, G, seed=10 * G + R.MODES[do_option])

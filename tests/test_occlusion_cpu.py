@@ -11,6 +11,7 @@ import torch
 from dl_vqa_amd import ImageFeatures, Occlusion
 from tests import attribution_ref as R
 from tests import occlusion_ref as OR
+from tests.curves_util import _random_case
 from tests.explain_util import columns as _columns, host_caches as _host_caches, tiny as _tiny
 
 
@@ -31,26 +32,6 @@ def test_closed_form_equals_brute_force_on_the_fixtures(do_option, window):
         assert float(want.abs().max()) > 0 and err < 1e-12
         if window == 3:                                           # the whole grid: one value per question
             assert float((want - want[:, :1]).abs().max()) < 1e-12
-
-
-def _random_case(do_option, G, grid, seed):
-    """A random attention stage + classifier in float64 (state-dict names and shapes of the model) and random inputs, with
-    weights of a size that keeps the logits O(1)."""
-    g = torch.Generator().manual_seed(seed)
-    N, B, C, mid, Q, hid, A = 3, 5, 10, 12, 6, 9, 5
-    gh, gw = grid
-    xld = 2 * mid if do_option == "|" else mid
-    rn = lambda *s: 0.5 * torch.randn(*s, generator=g, dtype=torch.float64)
-    sd = {"attention.v_conv.weight": rn(mid, C, 1, 1), "attention.q_lin.weight": rn(mid, Q), "attention.q_lin.bias": rn(mid),
-          "attention.x_conv.weight": rn(G, xld, 1, 1), "attention.x_conv.bias": rn(G),
-          "classifier.lin1.weight": rn(hid, G * C + Q), "classifier.lin1.bias": rn(hid),
-          "classifier.lin2.weight": rn(A, hid), "classifier.lin2.bias": rn(A)}
-    vn = torch.randn(N, gh * gw, C, generator=g, dtype=torch.float64)
-    vn = vn / vn.norm(dim=-1, keepdim=True)
-    qf = torch.randn(B, Q, generator=g, dtype=torch.float64)
-    img = torch.randint(0, N, (B,), generator=g)
-    answers = torch.randint(0, A, (B,), generator=g)
-    return sd, vn, qf, img, answers
 
 
 @pytest.mark.parametrize("G", [1, 2])

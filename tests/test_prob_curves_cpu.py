@@ -13,9 +13,8 @@ from dl_vqa_amd import Faithfulness, ProbabilityCurves
 from tests import attribution_ref as R
 from tests import faithfulness_ref as FR
 from tests import prob_curves_ref as PR
+from tests.curves_util import _maps, _random_case
 from tests.explain_util import columns as _columns
-from tests.test_faithfulness_cpu import _maps
-from tests.test_occlusion_cpu import _random_case
 
 # The logit bound the CPU share test stands in for the one the GPU tests measure (4 x answer() on zeroed banks against
 # float64, floor 1e-7; profiles/faithfulness_parity.txt has it AT the floor on all three fixtures): ten times the floor.

@@ -12,9 +12,9 @@ from dl_vqa_amd import ProbabilityCurves, unique_questions
 from tests import attribution_ref as R
 from tests import faithfulness_ref as FR
 from tests import prob_curves_ref as PR
+from tests.curves_util import MODELS, _case, _device_brute, _fixture_run, _L, _picked, _run as _run_curves, _tied_map
 from tests.explain_util import build, columns as _columns, within
 from tests.golden_util import Golden, tiny_cfg
-from tests.test_faithfulness_gpu import MODELS, _case, _device_brute, _fixture_run, _L, _picked, _run as _run_curves, _tied_map
 from tests.test_kernels_gpu import check
 
 pytestmark = pytest.mark.gpu

@@ -1,13 +1,11 @@
-"""CPU: what VqaNet.explain_faithfulness_probs / explain_faithfulness_probs_pairs refuse before any device work, in the pattern
-of tests/test_shapley_refusals_cpu.py: bf16, train mode and the device check in that order; the maps argument (explain_faithfulness'
-own check, in this call's name); the type of feats and qfeats, a bank without v', the index count and the `answers` argument; and
-that every refusal is explain_faithfulness' refusal under the other name."""
+"""CPU: what only VqaNet.explain_faithfulness_probs / explain_faithfulness_probs_pairs assert about their refusals: the maps
+argument (explain_faithfulness' own check, in this call's name), and that every refusal is explain_faithfulness' refusal under
+the other name.  What the whole explain family refuses is in tests/test_explain_refusals_cpu.py, these two calls included."""
 import pytest
 import torch
 
-from dl_vqa_amd import ImageFeatures, VqaNet
+from dl_vqa_amd import ImageFeatures
 from tests.explain_util import host_caches, tiny
-from tests.golden_util import full_cfg
 
 # name, pairs form, the name of the logit call whose refusals these calls share
 CALLS = [("explain_faithfulness_probs", False, "explain_faithfulness"),
@@ -21,23 +19,6 @@ def invoke(m, name, pairs, feats, qfeats, q, ql, index, maps=GOOD, **kw):
     if pairs:
         return getattr(m, name)(feats, qfeats, index, [0, 1, 1], maps, **kw)
     return getattr(m, name)(feats, q, ql, index, maps, **kw)
-
-
-@pytest.mark.parametrize("name,pairs,logit_name", CALLS, ids=IDS)
-def test_bf16_then_train_mode_then_device(name, pairs, logit_name):
-    m = VqaNet(full_cfg(16), 30, compute_dtype="bf16")              # train mode, on the CPU
-    q, ql = torch.ones(1, 3, dtype=torch.int64), torch.tensor([3])
-    with pytest.raises(NotImplementedError, match="compute_dtype"):  # before the maps are looked at
-        getattr(m, name)(None, None, [0], [0], "no map") if pairs else getattr(m, name)(None, q, ql, [0], "no map")
-    g, m = tiny()
-    m.train()
-    with pytest.raises(RuntimeError, match="training mode"):
-        getattr(m, name)(None, None, [0], [0], "no map") if pairs else getattr(m, name)(None, g.t["q"], g.t["q_len"], [0], "no map")
-    m.eval()                                                        # eval mode on the CPU: the device check speaks
-    feats, qfeats = host_caches(m)
-    with pytest.raises(RuntimeError, match="cuda"):
-        invoke(m, name, pairs, feats, qfeats, g.t["q"][:3], g.t["q_len"][:3], [0, 1, 2])
-    assert m._last_ctx is None
 
 
 @pytest.mark.parametrize("name,pairs,logit_name", CALLS, ids=IDS)
@@ -69,45 +50,6 @@ def test_the_maps_are_judged_on_the_host_before_answers_and_index(name, pairs, l
         with pytest.raises(RuntimeError, match="cuda"):
             call(fine, answers=[0, A - 1, 1], _u_bytes=64, _ws_bytes=64)
     assert m._last_ctx is None
-
-
-@pytest.mark.parametrize("name,pairs,logit_name", CALLS, ids=IDS)
-def test_features_index_and_answers_are_judged_before_any_device_work(name, pairs, logit_name):
-    g, m = tiny()
-    m.eval()
-    A = m._engine.A
-    feats, qfeats = host_caches(m, N=3, M=2)
-    q, ql = g.t["q"][:3], g.t["q_len"][:3]
-    call = lambda index=(0, 1, 2), **kw: invoke(m, name, pairs, feats, qfeats, q, ql, list(index), **kw)
-    with pytest.raises(TypeError, match="encode_images"):
-        getattr(m, name)(torch.zeros(3), qfeats, [0], [0], GOOD) if pairs else getattr(m, name)(torch.zeros(3), q, ql, [0, 1, 2], GOOD)
-    if pairs:
-        with pytest.raises(TypeError, match="encode_questions"):
-            getattr(m, name)(feats, feats, [0, 1, 2], [0, 1, 1], GOOD)
-    with pytest.raises(ValueError, match="2 answers for 3"):
-        call(answers=[0, 1])
-    with pytest.raises(IndexError, match=rf"answers entry {A} out of range \[0, {A}\)"):
-        call(answers=[0, A, 1])
-    with pytest.raises(IndexError, match="answers entry -1"):
-        call(answers=torch.tensor([0, 1, -1], dtype=torch.int32))
-    with pytest.raises(TypeError, match="integer"):
-        call(answers=[0.0, 1.0, 2.0])
-    m._ensure_flat = lambda: None                                   # as on a device: the index and ownership checks speak
-    with pytest.raises(ValueError, match="2 image_index entries for 3"):
-        call(index=(0, 1), maps=GOOD if not pairs else torch.zeros(2, 2, 2))   # the pairs form counts its questions by the index
-    with pytest.raises(IndexError):
-        call(index=(0, 1, 3))
-    _, other = tiny()
-    with pytest.raises(RuntimeError, match="belong elsewhere"):
-        invoke(m, name, pairs, host_caches(other)[0], qfeats, q, ql, [0, 1, 2])
-    bank, qfeats = host_caches(m, vprime=False)                     # a bank without v' (the caches above are stale now)
-    with pytest.raises(RuntimeError, match="with_vprime=False"):
-        invoke(m, name, pairs, bank, qfeats, q, ql, [0, 1, 2])
-    del m._ensure_flat
-    feats, qfeats = host_caches(m, N=3, M=2)
-    with pytest.raises(RuntimeError, match="cuda"):                 # everything the host can judge is in order
-        call(answers=[0, A - 1, 1])
-    assert m._last_ctx is None and all(p.grad is None for p in m.parameters())
 
 
 @pytest.mark.parametrize("name,pairs,logit_name", CALLS, ids=IDS)

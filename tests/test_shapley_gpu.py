@@ -10,9 +10,9 @@ import torch
 from dl_vqa_amd import Shapley, shapley_orders, unique_questions
 from tests import attribution_ref as R
 from tests import shapley_ref as SR
+from tests.curves_util import MODELS, _bound as _curve_bound, _fixture_run
 from tests.explain_util import build, columns as _columns, within
 from tests.golden_util import Golden, tiny_cfg
-from tests.test_faithfulness_gpu import MODELS, _bound as _curve_bound, _fixture_run
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
